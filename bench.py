@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- SSIMULACRA2 scorer throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: the command starts its own N ranks, one per GPU -- oavif_amd/launch.py -- unless a launcher has announced a
      world: `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...`
      runs the same ranks)
@@ -41,7 +41,11 @@ Extra objects on the JSON line:
                   pair scoring on two contexts / one stream with the W-model fraction, the recursive cached pass, and every
                   kernel's own duration beside the stream time of a score.
   per_rank_own_ms_per_step -- N > 1 only: each rank's own work per step up to its synchronize, before the closing
-                  barrier (median block); `ms_per_step` is the max over ranks of the whole block, so a slow rank shows.
+                  barrier; `ms_per_step` is the max over ranks of the whole block, so a slow rank shows.
+  --dump-outputs DIR -- after the timed steps, rank 0 writes what the last timed step computed, as its caller receives it:
+                  DIR/score.npy (float64, shape (1,): the SSIMULACRA2 score ssimu2_wait returned) and
+                  DIR/plane_averages.npy (float64, (6, 18): ssimu2_last_averages of that score).  The inputs are seeded, so
+                  two builds run with the same arguments can be compared output for output.
   default_search_mode -- throughput of the mode the SEARCH path runs by default (the published recursion, one
                   cached-reference pass per probe), beside `value` (FIR pair scoring, two contexts); its per-kernel times
                   (recursive_blur_mode.kernels) are measured by this run: dispatch-packet timestamps of the instrumented build.
@@ -474,6 +478,8 @@ def main() -> int:
                          "uses this, so that its per-kernel averages are averages over 3840x2160 launches only")
     ap.add_argument("--width", type=int, default=W)
     ap.add_argument("--height", type=int, default=H)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's score and plane averages as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     # One command for any N (the reference's batch entry is one command, scripts/measure.py:110-158; the driver's N = 1
@@ -587,6 +593,8 @@ def main() -> int:
             dist.barrier()
         torch.cuda.synchronize()
 
+    last = {}   # context -> the score of the last step it ran (what its wait() returned)
+
     def run_steps(n, rotate=True):
         """n scores dealt round-robin over the contexts; context c walks its own pairs
         (pairs[c], pairs[c + nctx], ...) when `rotate`, else every score is pair 0."""
@@ -598,7 +606,7 @@ def main() -> int:
             used.add(c_)
         sc = None
         for j in sorted(used):
-            sc = scorers[j].wait()     # drains that context's stream
+            sc = last[j] = scorers[j].wait()     # drains that context's stream
         return sc
 
     # Setup, not measurement: a fresh MI355X needs ~50 ms of work before its clocks settle (the
@@ -611,11 +619,9 @@ def main() -> int:
     if args.warmup:
         score = run_steps(args.warmup)
 
-    # The timed region: EXACTLY `steps` steps between barrier + synchronize on both sides, max over
-    # ranks.  A short block (the driver's 20 steps are 3 ms) is one perf_counter pair around very
-    # little, so the same block is timed `repeats` times back to back -- as many as make the timed
-    # wall >= 0.25 s, the same count on every rank -- and the MEDIAN block is what is reported;
-    # min / max are printed beside it.
+    # The timed region: EXACTLY `steps` steps, one block between barrier + synchronize on both sides,
+    # max over ranks.  `--steps` is the number of steps timed, nothing more: a caller who wants a
+    # steadier figure asks for more steps (ms_per_step says how many fit in a given time).
     own = []   # this rank's own work per block (up to its synchronize, before the closing barrier): shows a slow rank
 
     def timed_block():
@@ -635,9 +641,16 @@ def main() -> int:
         return float(t_.item())
 
     blocks = [max_over_ranks(timed_block())]
-    repeats = int(min(400, max(1, -(-0.25 // blocks[0]))))
-    blocks += [max_over_ranks(timed_block()) for _ in range(repeats - 1)]
-    elapsed = sorted(blocks)[len(blocks) // 2]
+    elapsed = blocks[0]
+
+    # what the last timed step computed, read back before any later work reuses its context
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        c_last = (args.steps - 1) % nctx
+        dumped = {"score": np.array([last[c_last]], dtype=np.float64),
+                  "plane_averages": np.asarray(scorers[c_last].last_averages()[0], dtype=np.float64)}
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dumped.items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), arr)
 
     # the labelled extra: the same number of steps on ONE pair (inputs and pyramid stay in the
     # Infinity Cache) -- what round 1 reported as `value`
@@ -654,7 +667,7 @@ def main() -> int:
         gathered = [torch.zeros_like(rec) for _ in range(world)]
         dist.all_gather(gathered, rec)   # the final RCCL gather of per-rank result records
         scores = [float(g[1]) for g in gathered]
-        per_rank_ms = [round(float(g[2]) / args.steps * 1e3, 5) for g in gathered]   # each rank's OWN work per step (median block)
+        per_rank_ms = [round(float(g[2]) / args.steps * 1e3, 5) for g in gathered]   # each rank's OWN work per step
     else:
         scores = [float(score)]
         per_rank_ms = None
@@ -682,8 +695,8 @@ def main() -> int:
             "ms_per_step_min": round(min(blocks) / args.steps * 1e3, 5),
             "ms_per_step_max": round(max(blocks) / args.steps * 1e3, 5),
             "timed_region_s": round(sum(blocks), 4),
-            "timing_note": f"the {args.steps}-step block timed {len(blocks)} times back to back (barrier + synchronize "
-                           "around each, max over ranks); ms_per_step and value are the median block",
+            "timing_note": f"the {args.steps} steps timed as one block (barrier + synchronize around it, max over "
+                           "ranks); ms_per_step and value are that block",
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -703,7 +716,7 @@ def main() -> int:
         if coll is not None:
             out["collective"] = coll
         if per_rank_ms is not None:
-            # each rank's own work per step, up to its synchronize and before the closing barrier (median block): `ms_per_step`
+            # each rank's own work per step, up to its synchronize and before the closing barrier: `ms_per_step`
             # is the max over ranks of the whole block, so a rank that is slower than the others shows here
             out["per_rank_own_ms_per_step"] = per_rank_ms
         out["cache_resident"] = {
