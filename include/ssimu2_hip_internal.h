@@ -88,13 +88,6 @@ int ssimu2_time_blur_stage_rotating(ssimu2_ctx* ctx, const void* const* d_frames
 int ssimu2_time_kernels(ssimu2_ctx* ctx, const void* d_ref, const void* const* d_refs, const void* const* d_dists, int n,
                         uint32_t w, uint32_t h, int iters, float* out_ms_avg, int* out_launches, float* out_ms_wall_timed,
                         float* out_ms_wall_plain);
-/* The hipGraph experiment: with `enabled` = 1 every score of this context is submitted as ONE launch of
-   an instantiated graph -- a chain of kernel nodes, one per launch of the score, kept per context and rewritten per score with
-   hipGraphExecKernelNodeSetParams as long as the chain keeps its shape (same kernels, grids, blocks), rebuilt otherwise --
-   instead of one hipLaunchKernelGGL per kernel.  Same kernels, same arguments, same order: the bits of a score do not change.
-   `enabled` < 0 only reads the counters: graphs built / graph launches so far.  The measured outcome is in
-   profiles/r06_graph_ab.log; the product library does not have this path. */
-int ssimu2_instr_use_graph(ssimu2_ctx* ctx, int enabled, unsigned long long* out_builds, unsigned long long* out_launches);
 /* Stream placement (ssimu2_hip.hip "stream placement"): how many streams on distinct hardware queues this
    library instance holds for ctx's device -- contexts created without a caller stream borrow them in turn.
    3 with HIP's default of four hardware queues; 1 would mean every probe misread (tests/test_gpu_streams.py). */

@@ -164,8 +164,8 @@ struct ssimu2_ctx {
     float* d_rg = nullptr;
     size_t cap_rg = 0;            // floats
     double* d_rg_part = nullptr;  // [scale][18][column groups]
-    unsigned* d_rg_q = nullptr;   // job cursors of the persistent recursive-mode kernels (4 words)
-    int num_cus = 0;              // workgroups of those kernels: one per CU
+    unsigned* d_rg_q = nullptr;   // job cursor of the persistent vertical pass (RgPlan::q, 4 words)
+    int num_cus = 0;              // workgroups of that kernel: one per CU
     ssimu2_device_info dev{};     // what ctx_create saw of the device (and checked: gfx950, 160 KB of LDS per CU)
     unsigned rg_v_pad = 0;        // unused dynamic LDS of k_rg_v's launch: rg_v_pad_bytes(dev.lds_bytes_per_cu)
     size_t cap_rg_part = 0;       // doubles
@@ -185,18 +185,6 @@ struct ssimu2_ctx {
     int seg_rows_tail_override = 0;
     bool cache_ref_blur = true;
     int rg_dbg_scale = -1;  // recursive mode: keep that scale's 15 raw planes (after each pass) downloadable
-#ifdef SSIMU2_INSTRUMENTED_BUILD
-    // the hipGraph experiment of the instrumented build (ssimu2_instr_use_graph): one instantiated chain of kernel nodes
-    bool use_graph = false;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    int graph_n = 0;
-    hipGraphNode_t graph_node[8];
-    void* graph_func[8];
-    dim3 graph_grid[8], graph_block[8];
-    unsigned graph_lds[8];
-    unsigned long long graph_builds = 0, graph_launches = 0;
-#endif
 
     int fail(int code, const char* what, hipError_t e = hipSuccess) {
         char buf[256];
@@ -227,57 +215,11 @@ struct LaunchTimer {
     int n, cap;
 };
 thread_local LaunchTimer* g_launch_timer = nullptr;
-
-// The hipGraph experiment (ssimu2_instr_use_graph): while a recorder is open the launches of one score
-// are not made but noted -- function, geometry, a copy of the arguments -- and enqueue_score() hands the chain to
-// graph_flush(), which keeps one instantiated graph of kernel nodes per context, rewrites the nodes' parameters with
-// hipGraphExecKernelNodeSetParams when the chain has the shape of the last one (same functions, grids, blocks) and
-// launches the graph: one submission per score instead of one per kernel.
-struct LaunchRecorder {
-    static constexpr int kMax = 8, kArgBytes = 1024, kMaxArgs = 12;
-    int n = 0;
-    void* func[kMax];
-    dim3 grid[kMax], block[kMax];
-    unsigned lds[kMax];
-    alignas(16) unsigned char blob[kMax][kArgBytes];
-    void* argv[kMax][kMaxArgs];
-    int nargs[kMax];
-    bool overflow = false;
-};
-thread_local LaunchRecorder* g_launch_recorder = nullptr;
-
-template <typename T>
-inline void record_arg(LaunchRecorder* r, int k, size_t* off, const T& v) {
-    const size_t a = alignof(T) > 16 ? 16 : alignof(T);
-    *off = (*off + a - 1) / a * a;
-    if (*off + sizeof(T) > LaunchRecorder::kArgBytes || r->nargs[k] >= LaunchRecorder::kMaxArgs) {
-        r->overflow = true;
-        return;
-    }
-    memcpy(r->blob[k] + *off, &v, sizeof(T));
-    r->argv[k][r->nargs[k]++] = r->blob[k] + *off;
-    *off += sizeof(T);
-}
 #endif
 template <typename... KArgs>
 inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, unsigned lds, hipStream_t stream,
                    typename arg_of<KArgs>::type... args) {
 #ifdef SSIMU2_INSTRUMENTED_BUILD
-    if (LaunchRecorder* r = g_launch_recorder) {
-        if (r->n < LaunchRecorder::kMax) {
-            const int k = r->n++;
-            r->func[k] = (void*)kernel;
-            r->grid[k] = grid;
-            r->block[k] = block;
-            r->lds[k] = lds;
-            r->nargs[k] = 0;
-            size_t off = 0;
-            (record_arg<KArgs>(r, k, &off, args), ...);
-        } else {
-            r->overflow = true;
-        }
-        return;
-    }
     if (LaunchTimer* t = g_launch_timer) {
         if (t->n + 2 <= t->cap) {
             hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, t->ev[t->n], t->ev[t->n + 1], 0, args...);
@@ -573,12 +515,7 @@ void rg_build_plan(const ssimu2_ctx* c, const Pyramid& p, bool ref_frame, RgPlan
         poff += (size_t)kStats * rp->vgroups[s];
     }
     rp->dump = hbuf + 9 * ntot;
-    // jobs of the persistent kernels: horizontal = one plane of one channel over 20 rows (NK planes
-    // per channel), vertical = one channel of 64 columns; both listed largest scale first
-    const int nk = ref_frame ? 2 : 3;
-    for (int s = 0; s < p.nscales; ++s) rp->hjob_end[s] = rp->hblk_end[s] * nk;
-    rp->hjobs = hb_ * nk;
-    rp->hlong = rp->hjobs < (RG_HW / 2) * c->num_cus ? rp->hjobs : (RG_HW / 2) * c->num_cus;
+    // jobs of the persistent vertical pass: one channel of 64 columns, largest scale first
     rp->vjobs = vb_;
     rp->q = c->d_rg_q;
     *hblocks = hb_;
@@ -614,18 +551,12 @@ void rg_launch_convert(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_frame, 
     launch(k_pyramid_bands_xyb, dim3(a.bands_x * a.bands_y), dim3(PYR_THREADS), 0, c->stream, a);
 }
 
-// The horizontal pass: one workgroup per 20 rows and channel (RG_H_PERSISTENT = 1, an A/B build: one
-// workgroup per CU pulling jobs, ssimu2_recursive.h).
+// The horizontal pass: one workgroup per 20 rows and channel.
 template <bool REF>
 void rg_launch_h(ssimu2_ctx* c, bool fma, int hblocks, const RgPlan& rp) {
     if (hblocks <= 0) return;
-#if RG_H_PERSISTENT
-    if (fma) launch((k_rg_h_persistent<true, REF>), dim3(c->num_cus), dim3(64 * RG_HW), 0, c->stream, rp);
-    else launch((k_rg_h_persistent<false, REF>), dim3(c->num_cus), dim3(64 * RG_HW), 0, c->stream, rp);
-#else
     if (fma) launch((k_rg_h<true, REF>), dim3(hblocks), dim3(REF ? 128 : 192), 0, c->stream, rp);
     else launch((k_rg_h<false, REF>), dim3(hblocks), dim3(REF ? 128 : 192), 0, c->stream, rp);
-#endif
 }
 
 // What depends on the reference alone: its XYB planes and mu1 = blur(x), s11 = blur(x * x) at
@@ -681,8 +612,8 @@ int rg_enqueue_pass(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_dist) {
 
 // Enqueue the whole score of (d_ref, d_dist) on the ctx stream.  `ref_pyramid_ready`:
 // the reference's linear pyramid in d_lin_ref is already valid for this frame size.
-int enqueue_score_launches(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, uint32_t w,
-                           uint32_t h, bool ref_pyramid_ready) {
+int enqueue_score(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, uint32_t w, uint32_t h,
+                  bool ref_pyramid_ready) {
     const Pyramid p = make_pyramid(w, h);
     const bool recursive = c->blur_mode != SSIMU2_BLUR_FIR;
     if (recursive) {  // before anything is enqueued
@@ -723,75 +654,6 @@ int enqueue_score_launches(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d
     HIP_TRY(c, hipGetLastError());
     c->pending = true;
     return SSIMU2_OK;
-}
-
-#ifdef SSIMU2_INSTRUMENTED_BUILD
-void graph_drop(ssimu2_ctx* c) {
-    if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
-    if (c->graph) (void)hipGraphDestroy(c->graph);
-    c->graph_exec = nullptr;
-    c->graph = nullptr;
-    c->graph_n = 0;
-}
-
-// The recorded chain of one score as ONE graph launch (see LaunchRecorder).
-int graph_flush(ssimu2_ctx* c, LaunchRecorder& r) {
-    if (r.overflow) return c->fail(SSIMU2_ERR_INVALID_ARG, "hipGraph experiment: a score's launches do not fit the recorder");
-    if (r.n == 0) return SSIMU2_OK;
-    bool same = c->graph_exec != nullptr && c->graph_n == r.n;
-    for (int k = 0; same && k < r.n; ++k)
-        same = c->graph_func[k] == r.func[k] && c->graph_lds[k] == r.lds[k] && c->graph_grid[k].x == r.grid[k].x &&
-               c->graph_grid[k].y == r.grid[k].y && c->graph_grid[k].z == r.grid[k].z && c->graph_block[k].x == r.block[k].x &&
-               c->graph_block[k].y == r.block[k].y && c->graph_block[k].z == r.block[k].z;
-    hipKernelNodeParams kp[LaunchRecorder::kMax];
-    for (int k = 0; k < r.n; ++k) {
-        memset(&kp[k], 0, sizeof kp[k]);
-        kp[k].func = r.func[k];
-        kp[k].gridDim = r.grid[k];
-        kp[k].blockDim = r.block[k];
-        kp[k].sharedMemBytes = r.lds[k];
-        kp[k].kernelParams = r.argv[k];
-        kp[k].extra = nullptr;
-    }
-    if (!same) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));  // the old executable graph may still be running
-        graph_drop(c);
-        HIP_TRY(c, hipGraphCreate(&c->graph, 0));
-        for (int k = 0; k < r.n; ++k) {
-            HIP_TRY(c, hipGraphAddKernelNode(&c->graph_node[k], c->graph, k ? &c->graph_node[k - 1] : nullptr, k ? 1 : 0, &kp[k]));
-            c->graph_func[k] = r.func[k];
-            c->graph_grid[k] = r.grid[k];
-            c->graph_block[k] = r.block[k];
-            c->graph_lds[k] = r.lds[k];
-        }
-        HIP_TRY(c, hipGraphInstantiate(&c->graph_exec, c->graph, nullptr, nullptr, 0));
-        c->graph_n = r.n;
-        ++c->graph_builds;
-    } else {
-        for (int k = 0; k < r.n; ++k) HIP_TRY(c, hipGraphExecKernelNodeSetParams(c->graph_exec, c->graph_node[k], &kp[k]));
-    }
-    HIP_TRY(c, hipGraphLaunch(c->graph_exec, c->stream));
-    ++c->graph_launches;
-    return SSIMU2_OK;
-}
-#endif
-
-// Enqueue the whole score of (d_ref, d_dist) on the ctx stream (enqueue_score_launches above makes the launches; the
-// instrumented build's hipGraph experiment submits them as one graph instead).
-int enqueue_score(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, uint32_t w, uint32_t h, bool ref_pyramid_ready) {
-#ifdef SSIMU2_INSTRUMENTED_BUILD
-    if (c->use_graph && c->rg_dbg_scale < 0 && !g_launch_timer) {
-        LaunchRecorder* rec = new (std::nothrow) LaunchRecorder();
-        if (!rec) return c->fail(SSIMU2_ERR_OOM, "launch recorder");
-        g_launch_recorder = rec;
-        int rc = enqueue_score_launches(c, d_ref, d_dist, w, h, ref_pyramid_ready);
-        g_launch_recorder = nullptr;
-        if (rc == SSIMU2_OK) rc = graph_flush(c, *rec);
-        delete rec;
-        return rc;
-    }
-#endif
-    return enqueue_score_launches(c, d_ref, d_dist, w, h, ref_pyramid_ready);
 }
 
 int check_args(ssimu2_ctx* c, const void* a, const void* b, uint32_t w, uint32_t h) {
@@ -1203,9 +1065,6 @@ void ssimu2_ctx_destroy(ssimu2_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-#ifdef SSIMU2_INSTRUMENTED_BUILD
-    graph_drop(c);
-#endif
     free_buffers(c);
     (void)hipFree(c->d_result);
     (void)hipHostFree(c->h_result);

@@ -57,15 +57,6 @@ int ssimu2_instr_set_segment_rows(ssimu2_ctx* c, int rows_scale0, int rows_other
     return SSIMU2_OK;
 }
 
-int ssimu2_instr_use_graph(ssimu2_ctx* c, int enabled, unsigned long long* out_builds, unsigned long long* out_launches) {
-    if (!c) return SSIMU2_ERR_INVALID_ARG;
-    if (c->pending) return c->fail(SSIMU2_ERR_INVALID_ARG, "ssimu2_instr_use_graph: a score is still enqueued");
-    if (enabled >= 0) c->use_graph = enabled != 0;
-    if (out_builds) *out_builds = c->graph_builds;
-    if (out_launches) *out_launches = c->graph_launches;
-    return SSIMU2_OK;
-}
-
 int ssimu2_instr_placed_streams(ssimu2_ctx* c, int* out_n) {
     if (!c || !out_n) return SSIMU2_ERR_INVALID_ARG;
     *out_n = pool_size(c->device);

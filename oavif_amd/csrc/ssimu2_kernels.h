@@ -178,7 +178,7 @@ struct PyrBandArgs {
                            // recursive modes pad their rows to 128 floats, ssimu2_recursive.h "Row pitch")
     int nlevels;           // levels to produce: 1..5; 0 = nothing to do
     int bands_x, bands_y, nframes;
-    unsigned* zero4;       // XYB variant: four job cursors of the recursive passes that follow in the stream, zeroed here
+    unsigned* zero4;       // XYB variant: four words zeroed here, the job cursor of the recursive pass that follows (RgPlan::q)
 };
 
 constexpr int PYR_THREADS = 512;                      // (256-thread bands of 128 pixels measured the same)
@@ -389,7 +389,7 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_bands_xyb(PyrBandArgs a
     __shared__ float s_lut[256];
     __shared__ float s_tiles[PYR_BAND_LDS_FLOATS];
     if (threadIdx.x < 256) s_lut[threadIdx.x] = c_k.lut[threadIdx.x];
-    if (blockIdx.x == 0 && threadIdx.x < 4 && a.zero4) a.zero4[threadIdx.x] = 0u;  // k_rg_h / k_rg_v start after this launch has ended
+    if (blockIdx.x == 0 && threadIdx.x < 4 && a.zero4) a.zero4[threadIdx.x] = 0u;  // k_rg_v starts after this launch has ended
     __syncthreads();
     pyramid_band<true>(a, (int)blockIdx.x, s_lut, s_tiles);
 }
@@ -470,13 +470,7 @@ enum { MARCH_PAIR = 0, MARCH_REFBLUR = 1, MARCH_EMIT = 2 };
 // the pixel of this lane's column in the next output row, plus a prefetch queue (the values are
 // loaded RB_AHEAD steps before the step that consumes them; HBM latency under load is several
 // row steps).
-#ifndef MARCH_RB_AHEAD
-#define MARCH_RB_AHEAD 6   // round 4: 4 / 6 / 8 = 0.1621 / 0.1597 / 0.1636 ms per cached 4K pass (profiles/r04_refblur_ab.log)
-#endif
-#ifndef MARCH_NT_CACHED
-#define MARCH_NT_CACHED 0   // 1: streaming (nontemporal) loads of the cached reference planes, read once per pass
-#endif
-constexpr int RB_AHEAD = MARCH_RB_AHEAD;
+constexpr int RB_AHEAD = 6;  // round 4: 4 / 6 / 8 = 0.1621 / 0.1597 / 0.1636 ms per cached 4K pass (profiles/r04_refblur_ab.log)
 struct MarchRefBlur {
     float* s11;
     int pitch;       // elements per row
@@ -535,17 +529,13 @@ __device__ __forceinline__ MarchCursor march_cursor(const void* base, int w, int
 // the load is unconditional: every row issues the same number of loads and the compiler's
 // s_waitcnt vmcnt(N) can count them -- a conditional load made it fall back to vmcnt(0), which
 // shortened the prefetch distance to one row).
-template <bool U8, bool NT = false>
+template <bool U8>
 __device__ __forceinline__ void march_load(uint32_t (&raw)[3], const MarchCursor& c, int row) {
     const uint8_t* p = c.base + (size_t)(uint32_t)row * (uint32_t)c.pitch;
     if (U8) {
         uint32_t d;
         __builtin_memcpy(&d, p + c.off, 4);
         raw[0] = d;
-    } else if (NT) {
-        raw[0] = __builtin_nontemporal_load((const uint32_t*)(p + c.off));
-        raw[1] = __builtin_nontemporal_load((const uint32_t*)(p + c.plane + c.off));
-        raw[2] = __builtin_nontemporal_load((const uint32_t*)(p + 2 * c.plane + c.off));
     } else {
         raw[0] = *(const uint32_t*)(p + c.off);
         raw[1] = *(const uint32_t*)(p + c.plane + c.off);
@@ -553,24 +543,13 @@ __device__ __forceinline__ void march_load(uint32_t (&raw)[3], const MarchCursor
     }
 }
 
-// MARCH_LUT_COPIES (experiment): 4 = four interleaved copies of the table,
-// lane & 3 selects the copy.  Measured: no fewer bank conflicts and no faster (a ds_read_b32 serves
-// 32 lanes from 32 banks whichever copy a lane reads); the product uses 1.
-#ifndef MARCH_LUT_COPIES
-#define MARCH_LUT_COPIES 1
-#endif
+// One copy of the table: four interleaved copies were no faster (profiles/r03_lut_ab.log; a
+// ds_read_b32 serves 32 lanes from 32 banks whichever copy a lane reads).
 __device__ __forceinline__ void march_lut(const float* lut, uint32_t d, uint32_t shift, float (&lin)[3]) {
     d >>= shift;
-    if (MARCH_LUT_COPIES == 1) {
-        lin[0] = lut[d & 255u];
-        lin[1] = lut[(d >> 8) & 255u];
-        lin[2] = lut[(d >> 16) & 255u];
-    } else {
-        const uint32_t k = threadIdx.x & (MARCH_LUT_COPIES - 1);
-        lin[0] = lut[(d & 255u) * MARCH_LUT_COPIES + k];
-        lin[1] = lut[((d >> 8) & 255u) * MARCH_LUT_COPIES + k];
-        lin[2] = lut[((d >> 16) & 255u) * MARCH_LUT_COPIES + k];
-    }
+    lin[0] = lut[d & 255u];
+    lin[1] = lut[(d >> 8) & 255u];
+    lin[2] = lut[(d >> 16) & 255u];
 }
 
 // The converter role of one workgroup: rows 0 .. steps-1 of the segment into the ring, GROUP
@@ -612,7 +591,7 @@ __device__ __forceinline__ void march_convert_rows(f2 (*ring)[3][MRW], const flo
 #define MARCH_LOAD(J)                                                      \
     {                                                                      \
         const int lrow_ = min(max(load_row, 0), h - 1); /* uniform */      \
-        if (CACHED) march_load<false, MARCH_NT_CACHED != 0>(raw0[J], c0, lrow_); \
+        if (CACHED) march_load<false>(raw0[J], c0, lrow_);                 \
         else march_load<U8>(raw0[J], c0, lrow_);                           \
         if (TWO) march_load<U8>(raw1[J], c1, lrow_);                       \
         ++load_row;                                                        \
@@ -778,7 +757,7 @@ __device__ __forceinline__ void march_v(const lds_vu64* rp, float (&win)[5][9], 
         // consume the value loaded RB_AHEAD steps ago, then load the row RB_AHEAD steps ahead
         c_s11 = rb.ps11[P];
         if (t >= 8 - RB_AHEAD && rb.rows_left > 0) {  // uniform: that output row exists
-            rb.ps11[(P + RB_AHEAD) % 9] = ok ? (MARCH_NT_CACHED ? __builtin_nontemporal_load(rb.s11) : *rb.s11) : 0.0f;
+            rb.ps11[(P + RB_AHEAD) % 9] = ok ? *rb.s11 : 0.0f;
             rb.s11 += rb.pitch;
             --rb.rows_left;
         }
@@ -831,15 +810,12 @@ __device__ __forceinline__ void march_v(const lds_vu64* rp, float (&win)[5][9], 
 // XCD-aware tile order.  Workgroups are dealt to the eight XCDs round-robin by blockIdx (each XCD has its own
 // 4 MiB L2), while neighbouring strips of one segment share their 8 halo columns and -- strips being 120 columns,
 // not a multiple of a 128-byte line -- the cache lines their edges straddle.  With tile = blockIdx those neighbours
-// sit on DIFFERENT XCDs and every XCD fetches its own copy.  MARCH_XCD_ORDER = 1 hands each XCD a contiguous run of
-// tiles instead: among the workgroups [first, end) of a scale, the ones with blockIdx % 8 == x take the x-th run,
-// in blockIdx order.  A bijection on [0, end - first); which workgroup computes a tile does not enter the tile's
-// arithmetic, and the partial sums are stored under the TILE index: scores keep their bits.
-#ifndef MARCH_XCD_ORDER
-#define MARCH_XCD_ORDER 1
-#endif
+// sit on DIFFERENT XCDs and every XCD fetches its own copy.  So each XCD takes a contiguous run of tiles instead
+// (profiles/r04_xcd_order_ab.log: 21 % fewer fetched bytes): among the workgroups [first, end) of a scale, the ones
+// with blockIdx % 8 == x take the x-th run, in blockIdx order.  A bijection on [0, end - first); which workgroup
+// computes a tile does not enter the tile's arithmetic, and the partial sums are stored under the TILE index: scores
+// keep their bits.
 __device__ __forceinline__ int march_tile_of_block(int b, int first, int end) {
-    if (!MARCH_XCD_ORDER) return b - first;
     // cnt(n, r) = how many k in [0, n) have k % 8 == r
     const int x = b & 7;
     int before = 0;
@@ -855,7 +831,7 @@ template <int MODE>
 __device__ __forceinline__ void march_body(const MarchPlan& plan) {
     // [row slot][channel][column] of (ref, dist) pairs
     __shared__ __attribute__((aligned(16))) f2 s_ring[RING][3][MRW];
-    __shared__ float s_lut[256 * MARCH_LUT_COPIES];
+    __shared__ float s_lut[256];
     __shared__ double s_part[6][6];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -878,7 +854,7 @@ __device__ __forceinline__ void march_body(const MarchPlan& plan) {
     const int rows_out = min(seg_rows, h - y0);
     const int steps = rows_out + 2 * RAD;  // input rows y0-4 .. y0+rows_out+3
     if (u8) {
-        for (int i = tid; i < 256 * MARCH_LUT_COPIES; i += MARCH_THREADS) s_lut[i] = c_k.lut[i / MARCH_LUT_COPIES];
+        for (int i = tid; i < 256; i += MARCH_THREADS) s_lut[i] = c_k.lut[i];
     }
     __syncthreads();
 

@@ -322,16 +322,6 @@ class Ssimu2:
             self._raise(rc)
         return int(n.value)
 
-    def use_graph(self, enabled: bool | None = None):
-        """Instrumented build, the hipGraph experiment (ssimu2_instr_use_graph): submit every score of this context as one
-        graph launch.  None = only read the counters.  -> (graphs built, graph launches) so far."""
-        self._need_instr()
-        b, n = ctypes.c_ulonglong(), ctypes.c_ulonglong()
-        rc = self._L.ssimu2_instr_use_graph(self._ctx, -1 if enabled is None else int(bool(enabled)), ctypes.byref(b), ctypes.byref(n))
-        if rc != 0:
-            self._raise(rc)
-        return int(b.value), int(n.value)
-
     def rg_stop_after_scale(self, scale: int) -> None:
         """Instrumented build: the recursive mode keeps the 15 raw planes of `scale` (after the
         horizontal pass and after both passes) downloadable (debug_download what = 4 / 5);

@@ -1,6 +1,6 @@
 #!/bin/bash
-# Copy the summaries of a recorded round from gpurun_out/TAG/ (scripts/gpu_round.sh TAG + scripts/gpu_round5b.sh TAG, merged
-# back by gpurun) into profiles/ under the names they are committed under.   Usage (repo root): scripts/collect_round_records.sh r05
+# Copy the summaries of a recorded round (the TAG output directory that scripts/gpu_round.sh TAG and the round's other runs
+# fill) into profiles/ under the names they are committed under.   Usage (repo root): scripts/collect_round_records.sh r05
 set -e
 TAG=${1:-r05}
 O=gpurun_out/$TAG
