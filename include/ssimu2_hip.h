@@ -212,6 +212,33 @@ int ssimu2_enqueue_against_reference_device(ssimu2_ctx* ctx, const void* d_dist)
 int ssimu2_last_averages(ssimu2_ctx* ctx, double out[SSIMU2_NUM_SCALES * SSIMU2_STATS_PER_SCALE],
                          int* out_num_scales);
 
+/* Per-pixel error map: WHERE the frame is damaged (fssimu2's `error_map` parameter, which tq.zig:37 passes as
+   null).  fssimu2's source is not available, so the form of its map is unknown: this map is this library's own
+   (DESIGN.md section 9), exact enough for a CPU reference to be held against it.  Scale s (0 .. nscales-1) has dims
+   w_s x h_s; at each of its pixels q and channel c the three per-pixel terms of the score are d = max(0, 1 - ssim),
+   artifact and detail_lost -- the quantities whose plane means a_i (L1) and L4 norms a_i make up the 108
+   averages.  Every average has the weight w_i of the score's contiguous weight walk, and is spread over the
+   scale's pixels as a density whose mean is w_i * a_i:
+       L1 term  w_i * t(q)              L4 term  w_i * t(q)^4 / a_i^3   (0 when a_i == 0)
+   fp32, coefficient (w_i, or w_i / a_i^3 rounded to fp32) times term, the six terms of a channel summed in the order
+   d, d^4, art, art^4, det, det^4 (one multiply, five fused multiply-adds).  density_s = (X + Y) + B of the
+   channels' sums, and map(x, y) = sum over s ascending of density_s(x >> s, y >> s), fp32, w x h, row-major.
+   When w and h are multiples of 2^(nscales-1), mean(map) equals the weighted sum sum_i w_i * |a_i| (the score
+   before its 0.9562 factor and polynomial); identical frames give an all-zero map, and so does a frame too small
+   to have a scale (below 8 x 8).
+   The call is the ordinary score followed by a map pass in the context's blur mode: the score returned is
+   bit-identical to ssimu2_score_rgb8 / ssimu2_score_against_reference on the same input, and the pass leaves the
+   averages (ssimu2_last_averages) and a cached reference as the score left them.  Repeated calls give bit-identical
+   maps.  Blocking; `out_map` receives w * h floats, `out_score` the score (both required).  Errors as those two
+   calls (INVALID_ARG for a null pointer or zero size, UNSUPPORTED for channels != 3, NO_REFERENCE, the recursive
+   modes' size limit).  Device memory: 20 bytes per pixel more (density planes of every scale and channel + the
+   map), allocated by the first map call of the context only, replaced when the size changes, freed by
+   ssimu2_ctx_destroy. */
+int ssimu2_error_map_rgb8(ssimu2_ctx* ctx, const uint8_t* ref, const uint8_t* dist, uint32_t w, uint32_t h,
+                          uint32_t channels, float* out_map, double* out_score);
+/* The same against the reference of ssimu2_set_reference (kept cached). */
+int ssimu2_error_map_against_reference(ssimu2_ctx* ctx, const uint8_t* dist, float* out_map, double* out_score);
+
 /* Library/build description, e.g. "oavif_amd ssimu2 gfx950 v8 (...)". */
 const char* ssimu2_version(void);
 

@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = (
     "ssimu2_score_against_reference_strided", "ssimu2_set_reference_device",
     "ssimu2_enqueue_against_reference_device", "ssimu2_score_rgb8_device",
     "ssimu2_enqueue_rgb8_device", "ssimu2_wait", "ssimu2_last_averages",
+    "ssimu2_error_map_rgb8", "ssimu2_error_map_against_reference",
     "ssimu2_version",
     "oavif_tq_default_options", "oavif_tq_predict_q_from_score",
     "oavif_tq_interpolate_quantizer", "oavif_tq_find_target_quality", "oavif_tq_search_hip",
@@ -198,6 +199,12 @@ def _load(path: str, instrumented: bool) -> ctypes.CDLL:
     L.ssimu2_wait.restype = ci
     L.ssimu2_last_averages.argtypes = [vp, f64p, ctypes.POINTER(ci)]
     L.ssimu2_last_averages.restype = ci
+    if hasattr(L, "ssimu2_error_map_rgb8"):   # absent from builds before the error map (scripts/gpu_ab.py loads those too)
+        f32p = ctypes.POINTER(ctypes.c_float)
+        L.ssimu2_error_map_rgb8.argtypes = [vp, u8p, u8p, u32, u32, u32, f32p, f64p]
+        L.ssimu2_error_map_rgb8.restype = ci
+        L.ssimu2_error_map_against_reference.argtypes = [vp, u8p, f32p, f64p]
+        L.ssimu2_error_map_against_reference.restype = ci
     if instrumented:
         sigs = {
             "ssimu2_measure_read_stream": [vp, ctypes.c_size_t, ci, f64p],

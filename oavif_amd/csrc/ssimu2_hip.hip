@@ -11,6 +11,7 @@
 //                 (scale 0 is read straight from the u8 frames through the sRGB LUT)
 //   partials    : fp64 [scale][18 stats][workgroups] partial sums
 //   result      : fp64 [108 averages][score][nscales], written by k_finalize straight into pinned host memory
+//   error map   : first map call only: density planes [scale][3][h_s][w_s] + the fp32 map [h][w] (ssimu2_error_map_*)
 //
 //   SSIMU2_BLUR_RECURSIVE modes only (ssimu2_recursive.h), every scale packed: XYB planes of both
 //   frames, the reference's cached blur(x) / blur(x*x) planes, the horizontal pass of a pass's planes
@@ -173,6 +174,11 @@ struct ssimu2_ctx {
     size_t cap_rg_dbg = 0;
     double* d_result = nullptr;   // 110 doubles in device memory: the stage timing of the instrumented build only
     double* h_result = nullptr;   // page-locked host memory k_finalize writes the result into (110 doubles)
+    // error map (ssimu2_error_map_*), allocated by the first map call only: per-(scale, channel) density planes
+    // [scale][3][h_s][w_s] and the full-resolution map [h][w]
+    float* d_map_dens = nullptr;
+    float* d_map = nullptr;
+    size_t cap_map_dens = 0, cap_map = 0;  // floats
 
     // reference state
     bool have_ref = false;
@@ -304,7 +310,15 @@ void free_recursive(ssimu2_ctx* c) {
     c->cap_rg = c->cap_rg_part = c->cap_rg_dbg = 0;
 }
 
+void free_map(ssimu2_ctx* c) {
+    (void)hipFree(c->d_map_dens);
+    (void)hipFree(c->d_map);
+    c->d_map_dens = c->d_map = nullptr;
+    c->cap_map_dens = c->cap_map = 0;
+}
+
 void free_buffers(ssimu2_ctx* c) {
+    free_map(c);
     (void)hipFree(c->d_ref_u8);
     (void)hipFree(c->d_dist_u8);
     (void)hipFree(c->d_lin_ref);
@@ -653,6 +667,94 @@ int enqueue_score(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, ui
     launch(k_finalize, dim3(1), dim3(1024), 0, c->stream, fa, c->h_result);
     HIP_TRY(c, hipGetLastError());
     c->pending = true;
+    return SSIMU2_OK;
+}
+
+// ---- error map --------------------------------------------------------------
+// Coefficients of the map's terms from the averages of the score that just finished (h_result): the weight of
+// every average by the score's contiguous walk (k_finalize, or_score_from_averages), w for an L1 term and
+// w / a^3 for an L4 term (0 when a == 0), so that the mean of each term's density is w * a.
+void map_coefficients(const ssimu2_ctx* c, int nscales, MapCoef* mc) {
+    memset(mc, 0, sizeof *mc);
+    int j = 0;
+    for (int ch = 0; ch < 3; ++ch)
+        for (int sc = 0; sc < nscales; ++sc)
+            for (int n = 0; n < 2; ++n)
+                for (int k = 0; k < 3; ++k, ++j) {
+                    const int stat = k == 0 ? ch * 2 + n : 6 + ch * 4 + n + (k == 2 ? 2 : 0);
+                    const double a = c->h_result[sc * kStats + stat], wt = kWeightsHost[j];
+                    double v = n == 0 ? wt : (a > 0.0 ? wt / (a * a * a) : 0.0);
+                    if (v > 3.0e38) v = 3.0e38;  // a nonzero L4 average below ~1e-13 (denormal terms): stay finite
+                    mc->c[sc][stat] = (float)v;
+                }
+}
+
+// The map buffers for this frame size: allocated on first use, replaced when the size changes.
+int map_ensure(ssimu2_ctx* c, const Pyramid& p, uint32_t w, uint32_t h) {
+    const size_t need_dens = xyb_off(p, p.nscales) + 4, need_map = (size_t)w * h;
+    if (c->d_map && need_dens == c->cap_map_dens && need_map == c->cap_map) return SSIMU2_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    free_map(c);
+    hipError_t e = hipMalloc(&c->d_map_dens, need_dens * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&c->d_map, need_map * sizeof(float));
+    if (e != hipSuccess) {
+        free_map(c);
+        return c->fail(SSIMU2_ERR_OOM, "hipMalloc(error map: 20 bytes per pixel)", e);
+    }
+    c->cap_map_dens = need_dens;
+    c->cap_map = need_map;
+    return SSIMU2_OK;
+}
+
+// The map pass after a finished score of (d_ref, d_dist) (its planes still in place): densities of every scale from
+// the same per-pixel terms, composed into the w x h map, downloaded into `out_map`.  Reads the score's buffers and
+// writes only the map's own: the averages, partial sums and a cached reference are left as the score left them.
+int map_pass(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, uint32_t w, uint32_t h, float* out_map) {
+    const Pyramid p = make_pyramid(w, h);
+    int rc = map_ensure(c, p, w, h);
+    if (rc) return rc;
+    const size_t npix = (size_t)w * h;
+    if (p.nscales == 0) {  // a frame below 8 x 8 has no scale: the map is zero, as the score is 100
+        HIP_TRY(c, hipMemsetAsync(c->d_map, 0, npix * sizeof(float), c->stream));
+    } else {
+        MapCoef mc;
+        map_coefficients(c, p.nscales, &mc);
+        if (c->blur_mode == SSIMU2_BLUR_FIR) {
+            MarchPlan mp;
+            FinalizeArgs fa;
+            int blocks = 0;
+            build_plans(c, p, d_ref, d_dist, false, &mp, &fa, &blocks);
+            for (int s = 0; s < p.nscales; ++s) mp.ref_s11[s] = c->d_map_dens + xyb_off(p, s);  // the output planes
+            launch(k_march_map, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp, mc);
+        } else {
+            RgPlan rp;
+            int hblocks, vblocks;
+            rg_build_plan(c, p, false, &rp, &hblocks, &vblocks);
+            RgMapArgs ma;
+            memset(&ma, 0, sizeof ma);
+            ma.coef = mc;
+            for (int s = 0; s < p.nscales; ++s) ma.dens[s] = c->d_map_dens + xyb_off(p, s);
+            HIP_TRY(c, hipMemsetAsync(c->d_rg_q, 0, 4 * sizeof(unsigned), c->stream));  // the job cursor
+            const int vgrid = vblocks < c->num_cus ? vblocks : c->num_cus;
+            if (c->blur_mode == SSIMU2_BLUR_RECURSIVE_FMA)
+                launch((k_rg_vmap<true>), dim3(vgrid), dim3(512), c->rg_v_pad, c->stream, rp, ma);
+            else
+                launch((k_rg_vmap<false>), dim3(vgrid), dim3(512), c->rg_v_pad, c->stream, rp, ma);
+        }
+        MapComposeArgs ca;
+        memset(&ca, 0, sizeof ca);
+        ca.nscales = p.nscales;
+        for (int s = 0; s < p.nscales; ++s) {
+            ca.dens[s] = c->d_map_dens + xyb_off(p, s);
+            ca.w[s] = p.w[s];
+            ca.h[s] = p.h[s];
+        }
+        ca.out = c->d_map;
+        launch(k_map_compose, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, c->stream, ca);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out_map, c->d_map, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SSIMU2_OK;
 }
 
@@ -1271,6 +1373,23 @@ int ssimu2_score_against_reference_strided(ssimu2_ctx* c, const uint8_t* pixels,
     int rc = enqueue_score(c, c->d_ref_u8, c->d_dist_u8, w, h, true);
     if (rc) return rc;
     return ssimu2_wait(c, out_score);
+}
+
+int ssimu2_error_map_rgb8(ssimu2_ctx* c, const uint8_t* ref, const uint8_t* dist, uint32_t w, uint32_t h,
+                          uint32_t channels, float* out_map, double* out_score) {
+    if (!c) return SSIMU2_ERR_INVALID_ARG;
+    if (!out_map) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_map");
+    int rc = ssimu2_score_rgb8(c, ref, dist, w, h, channels, out_score);
+    if (rc) return rc;
+    return map_pass(c, c->d_ref_u8, c->d_dist_u8, w, h, out_map);
+}
+
+int ssimu2_error_map_against_reference(ssimu2_ctx* c, const uint8_t* dist, float* out_map, double* out_score) {
+    if (!c) return SSIMU2_ERR_INVALID_ARG;
+    if (!out_map) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_map");
+    int rc = ssimu2_score_against_reference(c, dist, out_score);
+    if (rc) return rc;
+    return map_pass(c, c->d_ref_u8, c->d_dist_u8, c->ref_w, c->ref_h, out_map);
 }
 
 int ssimu2_last_averages(ssimu2_ctx* c, double* out, int* out_num_scales) {

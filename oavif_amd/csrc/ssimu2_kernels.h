@@ -10,6 +10,8 @@
 //                  window, SSIM + edge-difference maps, fp64 partial sums
 //   k_finalize   : fixed-order fp64 reduction of the partials, 108 averages, weighted sum,
 //                  polynomial, score
+//   k_march_map, k_map_compose : the per-pixel error map (ssimu2_error_map_*): densities of every
+//                  scale, then their sum at full resolution
 //
 // Arithmetic contract: this translation unit is compiled with -ffp-contract=off;
 // every fused multiply-add is an explicit fmaf().  The sequence of IEEE operations per pixel
@@ -464,7 +466,10 @@ struct MarchPlan {
 //                  alone too, but caching it as well makes the kernel HBM-bound and slower
 //                  (measured): one cached plane is the balance point.
 //   MARCH_EMIT     writes that plane (run once by ssimu2_set_reference)
-enum { MARCH_PAIR = 0, MARCH_REFBLUR = 1, MARCH_EMIT = 2 };
+//   MARCH_MAP      both frames as MARCH_PAIR, but each lane writes its pixel's error-map density
+//                  (map_density) into the [3][h][w] plane the plan passes in
+//                  ref_s11 instead of accumulating sums (ssimu2_error_map_*)
+enum { MARCH_PAIR = 0, MARCH_REFBLUR = 1, MARCH_EMIT = 2, MARCH_MAP = 3 };
 
 // Per-lane cursor of a blur wave over the cached / emitted reference blur planes of its channel:
 // the pixel of this lane's column in the next output row, plus a prefetch queue (the values are
@@ -478,6 +483,24 @@ struct MarchRefBlur {
     bool active;     // lane owns an output column (lanes >= MHALF of a blur wave only shadow lane 0)
     float ps11[9];  // slot = phase of the consuming step; RB_AHEAD of them are live
 };
+
+// Error-map coefficients, [scale][18] in the statistic order of the averages (w, or w / a^3 for an L4
+// statistic); ssimu2_hip.hip computes them from the 108 averages of the score before the map pass.
+struct MapCoef {
+    float c[kNumScales][kStats];
+};
+
+// The six per-pixel terms whose plane means / L4 norms are the averages, and the channel's
+// density from them: sum of mc[k] * term[k] in term order (the error map's definition).
+__device__ __forceinline__ float map_density(float d, float d4, float art, float a4, float det, float t4,
+                                             const float (&mc)[6]) {
+    float v = mc[0] * d;
+    v = fmaf(mc[1], d4, v);
+    v = fmaf(mc[2], art, v);
+    v = fmaf(mc[3], a4, v);
+    v = fmaf(mc[4], det, v);
+    return fmaf(mc[5], t4, v);
+}
 
 // ---- converter waves ------------------------------------------------------------------------------
 // opsin mix and the rest of linear_to_xyb_pos as two halves (same operations in the same order),
@@ -564,7 +587,7 @@ template <bool U8, int MODE>
 __device__ __forceinline__ void march_convert_rows(f2 (*ring)[3][MRW], const float* lut,
                                                    const MarchPlan& plan, int sc, int w, int h, int x0,
                                                    int y0, int steps, int ngroups, int col) {
-    constexpr bool CACHED = MODE != MARCH_PAIR;
+    constexpr bool CACHED = MODE == MARCH_REFBLUR || MODE == MARCH_EMIT;
     constexpr bool TWO = MODE != MARCH_EMIT;
     constexpr bool LUT0 = U8 && !CACHED;  // frame 0 goes through the sRGB LUT
     const int gx = x0 - RAD + col;
@@ -751,7 +774,7 @@ __device__ __forceinline__ void march_h(const lds_vu64* rp, float (&win)[5][9], 
 template <int P, int MODE>
 __device__ __forceinline__ void march_v(const lds_vu64* rp, float (&win)[5][9], float (&acc)[6], int t,
                                         bool ok, bool edge, float w0, float w1, float w2, float w3,
-                                        float w4, MarchRefBlur& rb) {
+                                        float w4, MarchRefBlur& rb, const float (&mc)[6]) {
     float c_s11 = 0.f;
     if (MODE == MARCH_REFBLUR) {
         // consume the value loaded RB_AHEAD steps ago, then load the row RB_AHEAD steps ahead
@@ -799,6 +822,11 @@ __device__ __forceinline__ void march_v(const lds_vu64* rp, float (&win)[5][9], 
     }
     const float art = fmaxf(e, 0.0f), det = fmaxf(-e, 0.0f);
     const float d2 = d * d, a2 = art * art, t2 = det * det;
+    if (MODE == MARCH_MAP) {  // this channel's density, one row per step
+        if (ok && rb.active) *rb.s11 = map_density(d, d2 * d2, art, a2 * a2, det, t2 * t2, mc);
+        rb.s11 += rb.pitch;
+        return;
+    }
     acc[0] += d;
     acc[1] += d2 * d2;
     acc[2] += art;
@@ -828,7 +856,7 @@ __device__ __forceinline__ int march_tile_of_block(int b, int first, int end) {
 }
 
 template <int MODE>
-__device__ __forceinline__ void march_body(const MarchPlan& plan) {
+__device__ __forceinline__ void march_body(const MarchPlan& plan, const MapCoef* coef = nullptr) {
     // [row slot][channel][column] of (ref, dist) pairs
     __shared__ __attribute__((aligned(16))) f2 s_ring[RING][3][MRW];
     __shared__ float s_lut[256];
@@ -874,6 +902,15 @@ __device__ __forceinline__ void march_body(const MarchPlan& plan) {
     rb.active = hv_active;
 #pragma unroll
     for (int k = 0; k < 9; ++k) rb.ps11[k] = 0.f;
+    // MARCH_MAP: coefficients of this channel's six terms (d, d^4, art, art^4, det, det^4)
+    float mc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (MODE == MARCH_MAP) {
+        const int cc = max(ch, 0);  // statistic index as k_finalize reads it: 0..5 ssim (c*2+n), 6..17 edge (c*4+k)
+        mc[0] = coef->c[sc][cc * 2];
+        mc[1] = coef->c[sc][cc * 2 + 1];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) mc[2 + k] = coef->c[sc][6 + cc * 4 + k];
+    }
     {
         // this lane's pixel in output row y0 of its channel's planes (column clamped: lanes
         // outside the image never dereference it)
@@ -905,7 +942,7 @@ __device__ __forceinline__ void march_body(const MarchPlan& plan) {
         const int t = t0 + P;                                                                  \
         if (t < steps) march_h<P, MODE>(rp, win, t, w0, w1, w2, w3, w4);                       \
         if ((P % GROUP) == GROUP - 1 && t - (GROUP - 1) < steps) __syncthreads();              \
-        if (t < steps) march_v<P, MODE>(rp, win, acc, t, ok, edge, w0, w1, w2, w3, w4, rb);    \
+        if (t < steps) march_v<P, MODE>(rp, win, acc, t, ok, edge, w0, w1, w2, w3, w4, rb, mc);    \
     }
 #pragma unroll 1
         for (int t0 = 0; t0 < steps; t0 += 9) {
@@ -922,7 +959,7 @@ __device__ __forceinline__ void march_body(const MarchPlan& plan) {
 #undef MARCH_STEP
     }
 
-    if (MODE == MARCH_EMIT) return;  // planes written, nothing to reduce
+    if (MODE == MARCH_EMIT || MODE == MARCH_MAP) return;  // planes written, nothing to reduce
     // the two half-strip waves of a channel each publish their sums; combined in fixed order
     if (!is_conv) {
 #pragma unroll
@@ -953,6 +990,33 @@ __global__ __launch_bounds__(MARCH_THREADS, 6) void k_march_refblur(MarchPlan pl
 // once per search: blur(ref*ref) of every scale into plan.ref_s11
 __global__ __launch_bounds__(MARCH_THREADS, 6) void k_ref_blur(MarchPlan plan) {
     march_body<MARCH_EMIT>(plan);
+}
+
+// error-map pass (ssimu2_error_map_*): per-pixel densities of every scale into plan.ref_s11.  Its own entry and
+// register allocation; the score kernels above are not touched by it.
+__global__ __launch_bounds__(MARCH_THREADS, 6) void k_march_map(MarchPlan plan, MapCoef coef) {
+    march_body<MARCH_MAP>(plan, &coef);
+}
+
+// The full-resolution map: map(x, y) = sum over scales s (ascending) of
+// (dens_s[X] + dens_s[Y]) + dens_s[B] at (x >> s, y >> s).  One thread per pixel, fixed order.
+struct MapComposeArgs {
+    const float* dens[kNumScales];  // [3][h_s][w_s] per scale
+    int w[kNumScales], h[kNumScales];
+    int nscales;
+    float* out;                     // [h_0][w_0]
+};
+__global__ __launch_bounds__(256) void k_map_compose(MapComposeArgs a) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)a.w[0] * a.h[0]) return;
+    const int y = (int)(i / (unsigned)a.w[0]), x = (int)(i - (size_t)y * a.w[0]);
+    float v = 0.0f;
+    for (int s = 0; s < a.nscales; ++s) {
+        const size_t n = (size_t)a.w[s] * a.h[s];
+        const float* p = a.dens[s] + (size_t)(y >> s) * a.w[s] + (x >> s);
+        v += (p[0] + p[n]) + p[2 * n];
+    }
+    a.out[i] = v;
 }
 
 // ---- final reduction ------------------------------------------------------------------------------

@@ -405,6 +405,29 @@ __device__ __forceinline__ void rg_maps_pixel(float mu1, float mu2, float s11, f
     acc[5] += (double)(t2 * t2);
 }
 
+// The same expressions as rg_maps_pixel, the six terms returned in fp32 (the error-map pass; rg_maps_pixel is
+// left as it is so that the score kernels' code does not move).
+__device__ __forceinline__ void rg_map_terms(float mu1, float mu2, float s11, float s22, float s12, float r1,
+                                             float r2, float (&t)[6]) {
+    const float mu11 = mu1 * mu1, mu22 = mu2 * mu2, mu12 = mu1 * mu2;
+    const float dm = mu1 - mu2;
+    const float num_m = fmaf(-dm, dm, 1.0f);
+    const float num_s = fmaf(2.0f, s12 - mu12, kC2);
+    const float denom_s = ((s11 - mu11) + (s22 - mu22)) + kC2;
+    float d = 1.0f - div_rn(num_m * num_s, denom_s);
+    d = fmaxf(d, 0.0f);
+    const float ea = fabsf(r2 - mu2), eb = fabsf(r1 - mu1);
+    const float e = div_rn(ea - eb, 1.0f + eb);
+    const float art = fmaxf(e, 0.0f), det = fmaxf(-e, 0.0f);
+    const float d2 = d * d, a2 = art * art, t2 = det * det;
+    t[0] = d;
+    t[1] = d2 * d2;
+    t[2] = art;
+    t[3] = a2 * a2;
+    t[4] = det;
+    t[5] = t2 * t2;
+}
+
 // The recursion of one plane down this lane's column, PF batches of ten rows in a register queue
 // (three in flight under the one consumed).  Everything that counts in vmcnt is unconditional:
 // rows behind the image load the last row (and are replaced by the published zero padding in the
@@ -613,6 +636,105 @@ __global__ __launch_bounds__(512) void k_rg_v(RgPlan p) {
         }
         // the next job's first barrier (behind its pull) orders these reads of s_part / s_job before
         // anything overwrites them
+    }
+}
+
+// The error-map pass of the recursive modes (ssimu2_error_map_*), run after a score whose planes are still in place:
+// k_rg_v's jobs, recursion waves and barriers, but the maps waves write each pixel's density -- map_density() with the
+// coefficients of its (scale, channel) -- into the [3][h][w] plane dens[scale] instead of summing.  A kernel of its own
+// (not a template flag of k_rg_v) so that the score kernel's code stays exactly as it is.
+struct RgMapArgs {
+    MapCoef coef;
+    float* dens[kNumScales];
+};
+
+template <bool FMA>
+__global__ __launch_bounds__(512) void k_rg_vmap(RgPlan p, RgMapArgs m) {
+    constexpr int NK = 3;
+    __shared__ float s_out[2][NK][RG_VB][RG_VW];
+    __shared__ int s_job;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+#pragma unroll 1
+    for (;;) {
+        if (threadIdx.x == 0) {
+            const int j = (int)atomicAdd(p.q + 2, 1u);
+            s_job = j < p.vjobs ? j : -1;
+        }
+        __syncthreads();
+        const int job = __builtin_amdgcn_readfirstlane(s_job);
+        if (job < 0) break;
+        int sc = 0, first = 0;
+#pragma unroll
+        for (int s = 0; s < kNumScales - 1; ++s)
+            if (s + 1 < p.nscales && job >= p.vblk_end[s]) {
+                sc = s + 1;
+                first = p.vblk_end[s];
+            }
+        const int blk = job - first;
+        const int ch = blk % 3, cg = blk / 3;
+        const int w = p.w[sc], h = p.h[sc], pitch = p.pitch[sc];
+        const size_t n = (size_t)pitch * h;
+        const int x = cg * RG_VW + lane;
+        const bool ok = x < w;
+        const int xc = min(x, w - 1);
+        const int nb = rg_v_batches(h);
+
+        if (wave < NK) {
+            const int kind = wave;
+            const float* in = p.hbuf[sc] + (size_t)(ch * NK + kind) * n + xc;
+            rg_v_column<FMA>(in, pitch, h, [&](int b, const float (&o)[RG_VB]) {
+#pragma unroll
+                for (int j = 0; j < RG_VB; ++j) s_out[b & 1][kind][j][lane] = o[j];
+                __syncthreads();  // batch b is in the tile
+            });
+        } else {
+            const int j0 = 2 * (wave - NK);
+            const float* g_mu1 = p.cache[sc] + (size_t)(2 * ch) * n + xc;
+            const float* g_s11 = g_mu1 + n;
+            const float* g_r1 = p.xa[sc] + (size_t)ch * n + xc;
+            const float* g_r2 = p.xb[sc] + (size_t)ch * n + xc;
+            float mc[6];  // statistic index as k_finalize reads it: 0..5 ssim (c*2 + n), 6..17 edge (c*4 + j)
+            mc[0] = m.coef.c[sc][ch * 2];
+            mc[1] = m.coef.c[sc][ch * 2 + 1];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) mc[2 + k] = m.coef.c[sc][6 + ch * 4 + k];
+            float* dens = m.dens[sc] + (size_t)ch * w * h + xc;
+            float g[RG_PF][2][4];
+#define RG_M_LOAD(B, SLOT)                                                \
+    _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) {                    \
+        const int r_ = (B) * RG_VB + j0 + jj - (RG_N - 1);                \
+        const size_t o_ = (size_t)min(max(r_, 0), h - 1) * pitch;         \
+        g[SLOT][jj][0] = __builtin_nontemporal_load(g_mu1 + o_);          \
+        g[SLOT][jj][1] = __builtin_nontemporal_load(g_s11 + o_);          \
+        g[SLOT][jj][2] = __builtin_nontemporal_load(g_r1 + o_);           \
+        g[SLOT][jj][3] = __builtin_nontemporal_load(g_r2 + o_);           \
+    }
+#pragma unroll
+            for (int k = 0; k < RG_PF - 1; ++k) { RG_M_LOAD(k, k) }
+#pragma unroll 1
+            for (int b0 = 0; b0 < nb; b0 += RG_PF) {
+#pragma unroll
+                for (int u = 0; u < RG_PF; ++u) {
+                    const int b = b0 + u;
+                    RG_M_LOAD(b + RG_PF - 1, (u + RG_PF - 1) % RG_PF)
+                    __syncthreads();  // batch b is in the tile
+#pragma unroll
+                    for (int jj = 0; jj < 2; ++jj) {
+                        const int r = b * RG_VB + j0 + jj - (RG_N - 1);
+                        if (r >= 0 && r < h) {  // uniform
+                            float t[6];
+                            rg_map_terms(g[u][jj][0], s_out[b & 1][0][j0 + jj][lane], g[u][jj][1],
+                                         s_out[b & 1][1][j0 + jj][lane], s_out[b & 1][2][j0 + jj][lane],
+                                         g[u][jj][2], g[u][jj][3], t);
+                            if (ok) dens[(size_t)r * w] = map_density(t[0], t[1], t[2], t[3], t[4], t[5], mc);
+                        }
+                    }
+                }
+            }
+#undef RG_M_LOAD
+        }
+        __syncthreads();  // every wave is done with s_out and s_job before the next job's pull
     }
 }
 

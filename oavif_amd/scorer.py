@@ -24,6 +24,10 @@ def _u8p(a: np.ndarray):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
 
 
+def _f32p(a: np.ndarray):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
 def _check_rgb8(a, name: str) -> np.ndarray:
     a = np.ascontiguousarray(a, dtype=np.uint8)
     if a.ndim != 3 or a.shape[2] != 3:
@@ -189,6 +193,36 @@ class Ssimu2:
         if rc != 0:
             self._raise(rc)
         return out.value
+
+    def error_map(self, ref, dist, channels: int = 3):
+        """ssimu2_error_map_rgb8 -> (score, (h, w) float32 map): the score bit for bit as compute_ssimu2, and
+        where the frame is damaged (the map's definition: include/ssimu2_hip.h)."""
+        ref = _check_rgb8(ref, "ref")
+        dist = _check_rgb8(dist, "dist")
+        if ref.shape != dist.shape:
+            raise ValueError("ref and dist must have the same shape")
+        h, w, _ = ref.shape
+        out = np.empty((h, w), np.float32)
+        score = ctypes.c_double()
+        rc = self._L.ssimu2_error_map_rgb8(self._ctx, _u8p(ref), _u8p(dist), w, h, channels, _f32p(out),
+                                           ctypes.byref(score))
+        if rc != 0:
+            self._raise(rc)
+        return score.value, out
+
+    def error_map_against_reference(self, dist):
+        """ssimu2_error_map_against_reference -> (score, (h, w) float32 map) against the cached reference."""
+        dist = _check_rgb8(dist, "dist")
+        shape = getattr(self, "_ref_shape", None)
+        if shape is not None and dist.shape != shape:
+            raise ValueError("dist shape differs from the reference's")
+        h, w, _ = dist.shape
+        out = np.empty((h, w), np.float32)
+        score = ctypes.c_double()
+        rc = self._L.ssimu2_error_map_against_reference(self._ctx, _u8p(dist), _f32p(out), ctypes.byref(score))
+        if rc != 0:
+            self._raise(rc)
+        return score.value, out
 
     def set_reference(self, ref) -> None:
         ref = _check_rgb8(ref, "ref")

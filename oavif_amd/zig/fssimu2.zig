@@ -37,6 +37,8 @@ extern fn ssimu2_last_error(ctx: ?*const Ctx) [*:0]const u8;
 extern fn ssimu2_score_rgb8(ctx: ?*Ctx, ref: [*]const u8, dist: [*]const u8, w: u32, h: u32, channels: u32, out_score: *f64) c_int;
 extern fn ssimu2_set_reference(ctx: ?*Ctx, ref: [*]const u8, w: u32, h: u32) c_int;
 extern fn ssimu2_score_against_reference(ctx: ?*Ctx, dist: [*]const u8, out_score: *f64) c_int;
+extern fn ssimu2_error_map_rgb8(ctx: ?*Ctx, ref: [*]const u8, dist: [*]const u8, w: u32, h: u32, channels: u32, out_map: [*]f32, out_score: *f64) c_int;
+extern fn ssimu2_error_map_against_reference(ctx: ?*Ctx, dist: [*]const u8, out_map: [*]f32, out_score: *f64) c_int;
 extern fn ssimu2_score_against_reference_strided(ctx: ?*Ctx, pixels: [*]const u8, row_bytes: u32, channels: u32, out_score: *f64) c_int;
 extern fn ssimu2_host_alloc(ctx: ?*Ctx, bytes: usize, out_ptr: *?*anyopaque) c_int;
 extern fn ssimu2_host_free(ctx: ?*Ctx, ptr: ?*anyopaque) c_int;
@@ -195,7 +197,10 @@ pub fn deinit() void {
 }
 
 /// Same call shape as fssimu2 0.1.1 as seen from tq.zig:37.  `allocator` is unused (device
-/// scratch lives in the context); `error_map` must be null (oavif passes null).
+/// scratch lives in the context).  `error_map` is resolved at compile time: `null` (what oavif
+/// passes) scores only; a `[]f32` of at least width * height elements also receives this library's
+/// per-pixel error map (include/ssimu2_hip.h, DESIGN.md section 9 -- fssimu2's own map format is
+/// unknown); any other type is a compile error.
 pub fn computeSsimu2(
     allocator: std.mem.Allocator,
     reference: []const u8,
@@ -206,9 +211,12 @@ pub fn computeSsimu2(
     error_map: anytype,
 ) Error!f64 {
     _ = allocator;
-    _ = error_map;
+    const Map = @TypeOf(error_map);
+    if (Map != @TypeOf(null) and Map != []f32)
+        @compileError("computeSsimu2: error_map must be null or a []f32 of at least width * height elements, not " ++ @typeName(Map));
     const need: usize = @as(usize, width) * @as(usize, height) * channels;
     if (reference.len < need or distorted.len < need) return Error.InvalidArgument;
+    if (Map == []f32) return scoreWithMap(reference, distorted, width, height, channels, error_map);
     const ctx = try context();
     var score: f64 = 0;
     if (cache_reference and channels == 3) {
@@ -230,6 +238,32 @@ pub fn computeSsimu2(
     // reference must not outlive them
     g_ref_ptr = null;
     try check(ssimu2_score_rgb8(ctx, reference.ptr, distorted.ptr, width, height, channels, &score));
+    return score;
+}
+
+// computeSsimu2 with an error map: the same reference caching, through the map entry points
+// (whose score is bit-identical to the plain calls').
+fn scoreWithMap(reference: []const u8, distorted: []const u8, width: u32, height: u32, channels: u32, map: []f32) Error!f64 {
+    if (map.len < @as(usize, width) * @as(usize, height)) return Error.InvalidArgument;
+    const ctx = try context();
+    var score: f64 = 0;
+    if (cache_reference and channels == 3) {
+        if (!sameReference(reference, width, height)) {
+            try check(ssimu2_set_reference(ctx, reference.ptr, width, height));
+            rememberReference(reference, width, height);
+        }
+        const rc = ssimu2_error_map_against_reference(ctx, distorted.ptr, map.ptr, &score);
+        if (rc == -5) { // the context lost its reference: upload once more
+            try check(ssimu2_set_reference(ctx, reference.ptr, width, height));
+            rememberReference(reference, width, height);
+            try check(ssimu2_error_map_against_reference(ctx, distorted.ptr, map.ptr, &score));
+            return score;
+        }
+        try check(rc);
+        return score;
+    }
+    g_ref_ptr = null;
+    try check(ssimu2_error_map_rgb8(ctx, reference.ptr, distorted.ptr, width, height, channels, map.ptr, &score));
     return score;
 }
 
