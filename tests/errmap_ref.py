@@ -7,6 +7,9 @@ import numpy as np
 
 F32 = np.float32
 C2 = F32(0.0009)
+# a device map against reference_map: per-pixel bound relative to the map's maximum, and the bound on the
+# relative error of the mean
+PIXEL_RTOL, MEAN_RTOL = 1e-4, 1e-5
 
 
 def _fma(a, b, c):

@@ -1,5 +1,5 @@
-"""The per-pixel error map on the MI355X (ssimu2_error_map_*), in the FIR and the published-recursion modes,
-against the numpy reference of tests/errmap_ref.py."""
+"""The per-pixel error map on the MI355X (ssimu2_error_map_*), in the FIR mode and in both evaluation orders of the
+published recursion, against the numpy reference of tests/errmap_ref.py."""
 import os
 import sys
 import time
@@ -8,15 +8,17 @@ import numpy as np
 import pytest
 
 from oavif_amd import _lib, synth
+from oracle import ssimu2_oracle as orc
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import errmap_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-MODES = {"fir": (_lib.BLUR_FIR, 1), "recursive": (_lib.BLUR_RECURSIVE, 0)}   # (scorer mode, oracle BLUR_*)
+MODES = {"fir": (_lib.BLUR_FIR, orc.BLUR_FIR), "recursive": (_lib.BLUR_RECURSIVE, orc.BLUR_IIR),
+         "recursive_fma": (_lib.BLUR_RECURSIVE_FMA, orc.BLUR_IIR_FMA)}   # (scorer mode, oracle BLUR_*)
 # per-pixel bound relative to the map's maximum, and the bound on the relative error of the mean
-PIXEL_RTOL, MEAN_RTOL = 1e-4, 1e-5
+PIXEL_RTOL, MEAN_RTOL = errmap_ref.PIXEL_RTOL, errmap_ref.MEAN_RTOL
 
 
 @pytest.fixture(scope="module", params=sorted(MODES))

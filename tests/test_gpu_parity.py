@@ -10,11 +10,16 @@ The reference has no vectors for this path and its scorer source is absent: ever
 "expected" here is the repo's own oracle -- fssimu2 parity is UNPINNED.
 """
 import os
+import sys
 
 import numpy as np
 import pytest
 
 from oavif_amd import synth
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from gpu_cases import content as _content, decoded_like as _decoded_like  # noqa: E402
+from gpu_cases import pseudo_codec as _pseudo_codec  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -450,29 +455,6 @@ def test_strip_and_segment_boundaries(scorer, oracle, w, h):
     _check_pair(scorer, oracle, ref, dist)
 
 
-def _content(kind, w, h, seed):
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:h, 0:w]
-    if kind == "gradient":
-        img = np.stack([xx * 255 // max(w - 1, 1), yy * 255 // max(h - 1, 1),
-                        (xx + yy) * 255 // max(w + h - 2, 1)], -1)
-    elif kind == "primaries":      # saturated patches: exercises the opsin clamp / B-Y remap
-        cols = np.array([[255, 0, 0], [0, 255, 0], [0, 0, 255], [255, 255, 0], [0, 255, 255],
-                         [255, 0, 255], [0, 0, 0], [255, 255, 255]])
-        img = cols[((xx // 16) + (yy // 16)) % 8]
-    elif kind == "checker":        # 1-px checkerboard: maximal high-frequency energy
-        img = np.repeat((((xx + yy) & 1) * 255)[..., None], 3, -1)
-    elif kind == "text":           # thin dark strokes on light ground
-        img = np.full((h, w, 3), 235)
-        for _ in range(60):
-            x, y = int(rng.integers(0, w)), int(rng.integers(0, h))
-            img[y:y + 1 + int(rng.integers(0, 2)), x:x + int(rng.integers(3, 30))] = 20
-            img[y:y + int(rng.integers(3, 20)), x:x + 1] = 20
-    else:                          # white noise
-        img = rng.integers(0, 256, (h, w, 3))
-    return np.ascontiguousarray(img.astype(np.uint8))
-
-
 @pytest.mark.parametrize("kind", ["gradient", "primaries", "checker", "text", "noise"])
 def test_content_types(scorer, oracle, kind):
     ref = _content(kind, 250, 190, 5)
@@ -649,18 +631,6 @@ def test_any_segment_length_gives_the_same_score(hip_lib, scorer, seg, tail):
         assert s.compute_ssimu2(ref, dist) == expect
 
 
-def _decoded_like(dist, channels, pad, seed):
-    """`dist` laid out like libavif's avifRGBImage: `channels` bytes per pixel (alpha random),
-    rows `pad` bytes longer than their pixels, padding filled with noise."""
-    h, w, _ = dist.shape
-    rng = np.random.default_rng(seed)
-    pitch = w * channels + pad
-    buf = rng.integers(0, 256, (h, pitch), dtype=np.uint8)
-    view = np.lib.stride_tricks.as_strided(buf, (h, w, channels), (pitch, channels, 1))
-    view[..., :3] = dist
-    return buf, view
-
-
 @pytest.mark.parametrize("w,h,channels,pad", [
     (640, 360, 4, 0), (640, 360, 4, 64), (641, 359, 4, 0), (642, 100, 4, 2), (643, 77, 4, 3),
     (640, 360, 3, 0), (640, 360, 3, 32), (333, 217, 3, 1), (8, 8, 4, 0), (9, 9, 4, 5),
@@ -761,15 +731,6 @@ def test_maximum_size_far_corner_is_addressed_correctly(scorer):
 
 
 # ---- probes of one search fanned over contexts / HIP streams (BASELINE configs[2]) --
-
-def _pseudo_codec(ref):
-    """Deterministic stand-in for encode(q) -> decode: coarser block quantisation for lower q."""
-    def codec(q):
-        step = 1 + (100 - q) // 3
-        dec = (ref.astype(np.int32) // step) * step + step // 2
-        return np.clip(dec, 0, 255).astype(np.uint8), 1000 + 10 * q
-    return codec
-
 
 @pytest.mark.parametrize("w,h,tgt,fan", [(1920, 1080, 80.0, 4), (1920, 1080, 65.0, 6),
                                          (7680, 4320, 80.0, 4)])
