@@ -19,6 +19,16 @@ MODES = {"fir": (_lib.BLUR_FIR, orc.BLUR_FIR),
 TOL_SCORE, RTOL_AVG, ATOL_AVG = 1e-4, 2e-5, 1e-9
 TOL_FAR_BELOW_ZERO = 5e-4   # test_extreme_frames' bound for frames that score far below 0
 
+# frame sizes where the kernels change shape (tests/test_gpu_mode_matrix.py, tests/test_fp64_reference.py)
+SIZES = [
+    (1, 1), (7, 7), (7, 100), (100, 7), (8, 8),                  # at and below 8 px: no scale, one scale
+    (15, 9), (16, 16), (112, 112), (113, 113), (127, 300),       # scale-count transitions
+    (119, 40), (120, 40), (121, 40), (241, 33),                  # FIR strip edges (120 columns)
+    (64, 20), (65, 21), (128, 19), (129, 41),                    # recursive tile (64 columns) and batch edges
+    (333, 217), (513, 259), (1921, 1083),                        # ragged
+    (9, 1000), (1000, 9), (4000, 8), (8, 4000),                  # very tall, very wide
+]
+
 
 def score_tol(exp: float) -> float:
     return TOL_SCORE * max(1.0, abs(exp) / 100.0)

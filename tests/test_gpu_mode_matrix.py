@@ -23,21 +23,12 @@ import pytest
 from oavif_amd import _lib, synth
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from gpu_cases import (ATOL_AVG, MODES, RTOL_AVG, TOL_FAR_BELOW_ZERO, check_map, content,  # noqa: E402
+from gpu_cases import (ATOL_AVG, MODES, RTOL_AVG, SIZES, TOL_FAR_BELOW_ZERO, check_map, content,  # noqa: E402
                        decoded_like, pseudo_codec, score_tol)
 
 pytestmark = pytest.mark.gpu
 
 RECURSIVE_MODES = ["recursive", "recursive_fma"]
-
-SIZES = [
-    (1, 1), (7, 7), (7, 100), (100, 7), (8, 8),                  # at and below 8 px: no scale, one scale
-    (15, 9), (16, 16), (112, 112), (113, 113), (127, 300),       # scale-count transitions
-    (119, 40), (120, 40), (121, 40), (241, 33),                  # FIR strip edges (120 columns)
-    (64, 20), (65, 21), (128, 19), (129, 41),                    # recursive tile (64 columns) and batch edges
-    (333, 217), (513, 259), (1921, 1083),                        # ragged
-    (9, 1000), (1000, 9), (4000, 8), (8, 4000),                  # very tall, very wide
-]
 
 _CHECKER = {}   # (mode, case) -> the checker's (score, averages, nscales)
 
