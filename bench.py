@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- SSIMULACRA2 scorer throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: the command starts its own N ranks, one per GPU -- oavif_amd/launch.py -- unless a launcher has announced a
      world: `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...`
      runs the same ranks)
@@ -13,12 +13,17 @@ frames already resident in HBM when the timed region starts.  The steps ROTATE o
 `--pairs` distinct pairs per scorer context (default 8 per context, two contexts: 16 pairs,
 0.8 GB of frames), so every score reads its inputs from HBM, not from the 256 MiB Infinity
 Cache -- a batch never rescans one pair.  The cache-resident figure (one pair scored over and
-over, what round 1 reported) is kept as the labelled extra `cache_resident`.
+over, what round 1 reported) is kept as the labelled extra `cache_resident` (--full).
 With N ranks every rank scores its own pairs (independent images shard with no data-path
 collective: weak scaling); the only collective is the final RCCL all_gather of the per-rank
 result records.  value = megapixels (scale-0 pixels of one image) scored per second, whole job.
 
-Extra objects on the JSON line:
+A plain run does what the headline figure needs and nothing more: it sets up, warms up, times the steps, writes its
+outputs if --dump-outputs is given and prints the line (metric, value, unit, ms_per_step, ..., `scores`: the score of
+each rank's pair 0; N > 1: `collective` and per_rank_own_ms_per_step).  `--full` also measures everything else: the
+extra objects below, all of them taken after the timed steps and the dump.
+
+Extra objects on the JSON line (--full, unless said otherwise):
   roofline     -- dominant kernel (k_march: XYB + blur + maps of all six scales): algorithmic
                   bytes of SURVEY.md 8(d)'s W-model for the stages that kernel covers, divided
                   by its average launch time measured live with HIP events on the kernel's own
@@ -34,15 +39,15 @@ Extra objects on the JSON line:
                   rank the host, HIP device index, PCI bus id, NUMA node, pinned cores and the HSA_* / HIP_* / ROCR_* /
                   NCCL_* / RCCL_* variables it ran under, exchanged through the rendezvous store BEFORE any communicator
                   exists and confirmed by one all_gather over the job's process group (device tensors through RCCL when the
-                  backend is nccl; at N = 1 a process group of one rank is opened for it after the timed region).  The run
+                  backend is nccl; at N = 1, --full only, a process group of one rank is opened for it after the timed region).  The run
                   exits non-zero (rc 4, every rank, no communicator ever created) when two RCCL ranks report one GPU or the
                   host shows fewer devices than ranks; rc 5 with RCCL's message when the process group cannot be opened.
   by_resolution -- N = 1: the named resolutions (512x512, 1920x1080, 3840x2160, 7680x4320), each HBM-fed: FIR
                   pair scoring on two contexts / one stream with the W-model fraction, the recursive cached pass, and every
                   kernel's own duration beside the stream time of a score.
-  per_rank_own_ms_per_step -- N > 1 only: each rank's own work per step up to its synchronize, before the closing
+  per_rank_own_ms_per_step -- N > 1 only, every run: each rank's own work per step up to its synchronize, before the closing
                   barrier; `ms_per_step` is the max over ranks of the whole block, so a slow rank shows.
-  --dump-outputs DIR -- after the timed steps, rank 0 writes what the last timed step computed, as its caller receives it:
+  --dump-outputs DIR -- every run: after the timed steps, rank 0 writes what the last timed step computed, as its caller receives it:
                   DIR/score.npy (float64, shape (1,): the SSIMULACRA2 score ssimu2_wait returned) and
                   DIR/plane_averages.npy (float64, (6, 18): ssimu2_last_averages of that score).  The inputs are seeded, so
                   two builds run with the same arguments can be compared output for output.
@@ -480,6 +485,9 @@ def main() -> int:
     ap.add_argument("--height", type=int, default=H)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the last timed step's score and plane averages as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline figure: cache-resident rate, "
+                         "rooflines, other blur modes and sizes, search passes, the CPU baseline, the N = 1 collective record")
     args = ap.parse_args()
 
     # One command for any N (the reference's batch entry is one command, scripts/measure.py:110-158; the driver's N = 1
@@ -652,14 +660,17 @@ def main() -> int:
         for name, arr in dumped.items():
             np.save(os.path.join(args.dump_outputs, f"{name}.npy"), arr)
 
-    # the labelled extra: the same number of steps on ONE pair (inputs and pyramid stay in the
-    # Infinity Cache) -- what round 1 reported as `value`
-    run_steps(min(args.steps, 200), rotate=False)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    score = run_steps(args.steps, rotate=False)   # = the score of pair 0
-    torch.cuda.synchronize()
-    elapsed_resident = time.perf_counter() - t1
+    if args.full:
+        # the labelled extra: the same number of steps on ONE pair (inputs and pyramid stay in the
+        # Infinity Cache) -- what round 1 reported as `value`
+        run_steps(min(args.steps, 200), rotate=False)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        score = run_steps(args.steps, rotate=False)   # = the score of pair 0
+        torch.cuda.synchronize()
+        elapsed_resident = time.perf_counter() - t1
+    else:
+        score = run_steps(1, rotate=False)            # the score of pair 0, what `scores` carries in either run
 
     own_median = sorted(own)[len(own) // 2]
     rec = torch.tensor([float(rank), float(score), own_median], dtype=torch.float64, device=coll_dev)
@@ -719,12 +730,15 @@ def main() -> int:
             # each rank's own work per step, up to its synchronize and before the closing barrier: `ms_per_step`
             # is the max over ranks of the whole block, so a rank that is slower than the others shows here
             out["per_rank_own_ms_per_step"] = per_rank_ms
-        out["cache_resident"] = {
-            "value": round(args.steps * mp / elapsed_resident, 2),
-            "unit": "MP/s per GPU", "ms_per_step": round(elapsed_resident / args.steps * 1e3, 5),
-            "note": "rank 0's GPU only: every step scores the SAME pair, so inputs and pyramid are served "
-                    "by the Infinity Cache; not `value`"}
+        if args.full:
+            out["cache_resident"] = {
+                "value": round(args.steps * mp / elapsed_resident, 2),
+                "unit": "MP/s per GPU", "ms_per_step": round(elapsed_resident / args.steps * 1e3, 5),
+                "note": "rank 0's GPU only: every step scores the SAME pair, so inputs and pyramid are served "
+                        "by the Infinity Cache; not `value`"}
 
+    def measure_beside(out):
+        """--full, rank 0, every rank out of the process group: what the line carries beside the headline figure."""
         # ---- roofline of the dominant kernel, measured live with HIP events ----------------
         # (instrumented build of the same sources: the product library exports no timing hooks)
         from oavif_amd import _lib
@@ -1148,6 +1162,10 @@ def main() -> int:
                 out["cpu_baseline"] = cb
             except Exception as e:
                 out["cpu_baseline"] = {"error": str(e)[:300], "kind": "port"}
+
+    if rank == 0:
+        if args.full:
+            measure_beside(out)
         emit(out)
 
     for sc_ in scorers:

@@ -4,6 +4,7 @@
 # Outputs in gpurun_out/TAG/; the summaries to keep are then copied into profiles/ by hand
 # (kernel_stats.csv -> profiles/TAG_kernel_stats.csv, pmc_summary.txt, counters.json, bench.json).
 TAG=${1:-r02}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 export OMP_NUM_THREADS=16
 mkdir -p $OUT
@@ -13,8 +14,9 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1
 tail -4 $OUT/pytest_gpu.log
 cd /tmp && export TMPDIR=/tmp
 # per-kernel durations with the scores of one stream never overlapping (two streams stretch them); 3840x2160 launches only
-# (--no-by-resolution: the other sizes of the line's by_resolution extra would be averaged into the same kernel names)
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $GRAFT_REPO_ROOT/bench.py --steps 512 --warmup 64 --no-cpu-baseline --streams 1 --no-by-resolution > $OUT/prof.log 2>&1; echo "rocprof stats rc=$?"
+# (--full: the launches of the line's extras, as every round has traced them; --no-by-resolution: the other sizes of the
+# by_resolution extra would be averaged into the same kernel names)
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $ROOT/bench.py --full --steps 512 --warmup 64 --no-cpu-baseline --streams 1 --no-by-resolution > $OUT/prof.log 2>&1; echo "rocprof stats rc=$?"
 cd $GRAFT_REPO_ROOT
 cp $(find $OUT/prof -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv
 cut -c1-150 $OUT/kernel_stats.csv
@@ -32,5 +34,5 @@ cp $OUT/valu_rate.txt profiles/${TAG}_valu_rate.txt
 python3 scripts/make_counters_json.py profiles/${TAG}_pmc_summary.txt profiles/${TAG}_valu_rate.txt > $OUT/counters.json
 cp $OUT/counters.json profiles/counters.json
 cat $OUT/counters.json | head -12
-timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 cat $OUT/bench.json

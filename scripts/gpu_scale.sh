@@ -49,7 +49,7 @@ PY
 for N in 1 2 4 8; do
   if [ "$N" -gt "$NDEV" ]; then echo "N=$N skipped: $NDEV device(s)"; continue; fi
   echo "== bench.py --gpus $N"
-  EXTRA=""; [ "$N" -eq 1 ] && EXTRA="--no-cpu-baseline"
+  EXTRA=""; [ "$N" -eq 1 ] && EXTRA="--full --no-cpu-baseline"   # N = 1: --full carries the collective record
   timeout -k 10 900 python3 bench.py --gpus "$N" --steps "$STEPS" --warmup 50 $EXTRA > "$OUT/bench_n$N.json" 2> "$OUT/bench_n$N.err"
   echo "rc=$?" | tee "$OUT/bench_n$N.rc"
   echo "== batch of $IMAGES x 1080p on $N GPU(s)"

@@ -180,10 +180,10 @@ def test_bench_and_batch_leave_with_rc_4_before_any_rendezvous_when_devices_are_
 
 @pytest.mark.gpu
 def test_bench_line_carries_the_collective_record_through_rccl(hip_lib):
-    """the N = 1 line carries `collective` with world_size 1 gathered through RCCL (a process
-    group of one rank on backend nccl, device tensors), the rank's device as the library sees it, and the versions."""
+    """the N = 1 line of a --full run carries `collective` with world_size 1 gathered through RCCL (a
+    process group of one rank on backend nccl, device tensors), the rank's device as the library sees it, and the versions."""
     import oavif_amd
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
@@ -242,7 +242,7 @@ def test_bare_two_rank_rehearsal_over_gloo_prints_one_line_with_both_ranks(tmp_p
     env = dict(os.environ, OAVIF_BENCH_BACKEND="gloo")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads(p.stdout.splitlines()[-1])
