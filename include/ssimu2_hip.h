@@ -239,6 +239,38 @@ int ssimu2_error_map_rgb8(ssimu2_ctx* ctx, const uint8_t* ref, const uint8_t* di
 /* The same against the reference of ssimu2_set_reference (kept cached). */
 int ssimu2_error_map_against_reference(ssimu2_ctx* ctx, const uint8_t* dist, float* out_map, double* out_score);
 
+/* High-bit-depth input: 10-, 12- and 16-bit frames scored at full precision instead of
+   rounded to 8 bits first (libavif decodes into avifRGBImage at depth > 8; 16-bit PNG sources).
+   Samples: host-endian uint16_t interleaved RGB (RGBA for the strided call) with a declared `bit_depth` d,
+   8 <= d <= 16.  Sample s means s / (2^d - 1); a sample above 2^d - 1 is clamped to 2^d - 1 on the device (not an
+   error).  Its linear value is
+       (float)(v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4)),   v = (double)s / (double)(2^d - 1),
+   the 8-bit table's expression computed in fp64 and rounded once; ssimu2_linear_table returns the 2^d entries (no
+   device or context needed).  65535 = 255 * 257, so a 16-bit frame whose samples are 257 u -- or an 8-bit-depth
+   uint16_t frame holding u -- gives the 8-bit score of u bit for bit, averages included, in every blur mode.
+   From the linear values on everything is the 8-bit pipeline, same operations in the same order.
+   Each frame has its own depth: a reference set by ssimu2_set_reference (8-bit) can be scored against with the
+   _rgb16 / _strided16 calls, and one set by ssimu2_set_reference_rgb16 with ssimu2_score_against_reference /
+   _strided / _device (the cached reference is XYB planes and blur(ref*ref), which do not depend on the depth).
+   Errors: SSIMU2_ERR_UNSUPPORTED for bit_depth outside 8..16, channels other than 3 (other than 3 or 4 for the
+   strided call); SSIMU2_ERR_INVALID_ARG for a null or odd-address pointer, a zero size, row_bytes odd or below
+   w * channels * 2; SSIMU2_ERR_NO_REFERENCE as the 8-bit calls; the recursive modes' 2^28-pixel limit, checked
+   before anything is enqueued.  ssimu2_error_map_against_reference refuses a reference set from 16-bit samples
+   (SSIMU2_ERR_UNSUPPORTED).
+   Device memory of a context that never makes one of these calls is unchanged.  The first one allocates the tables
+   (512 KB, each depth uploaded by its first call) and the 16-bit frames (6 bytes per pixel each); in the FIR mode
+   also their scale-0 linear planes (12 bytes per pixel each).  All are freed by ssimu2_ctx_destroy. */
+int ssimu2_linear_table(uint32_t bit_depth, float* out);
+int ssimu2_score_rgb16(ssimu2_ctx* ctx, const uint16_t* ref, const uint16_t* dist, uint32_t w, uint32_t h,
+                       uint32_t channels, uint32_t bit_depth, double* out_score);
+int ssimu2_set_reference_rgb16(ssimu2_ctx* ctx, const uint16_t* ref, uint32_t w, uint32_t h, uint32_t bit_depth);
+int ssimu2_score_against_reference_rgb16(ssimu2_ctx* ctx, const uint16_t* dist, uint32_t bit_depth, double* out_score);
+/* libavif's avifRGBImage at depth > 8 as it is: `pixels` = rgb.pixels, `row_bytes` = rgb.rowBytes, `channels` = 3
+   or 4; row padding and alpha are skipped on the device.  Bit-identical to ssimu2_score_against_reference_rgb16 on
+   the tightly packed RGB copy. */
+int ssimu2_score_against_reference_strided16(ssimu2_ctx* ctx, const uint16_t* pixels, uint32_t row_bytes,
+                                             uint32_t channels, uint32_t bit_depth, double* out_score);
+
 /* Library/build description, e.g. "oavif_amd ssimu2 gfx950 v8 (...)". */
 const char* ssimu2_version(void);
 

@@ -39,6 +39,8 @@ EXPORTED_SYMBOLS = (
     "ssimu2_enqueue_against_reference_device", "ssimu2_score_rgb8_device",
     "ssimu2_enqueue_rgb8_device", "ssimu2_wait", "ssimu2_last_averages",
     "ssimu2_error_map_rgb8", "ssimu2_error_map_against_reference",
+    "ssimu2_linear_table", "ssimu2_score_rgb16", "ssimu2_set_reference_rgb16",
+    "ssimu2_score_against_reference_rgb16", "ssimu2_score_against_reference_strided16",
     "ssimu2_version",
     "oavif_tq_default_options", "oavif_tq_predict_q_from_score",
     "oavif_tq_interpolate_quantizer", "oavif_tq_find_target_quality", "oavif_tq_search_hip",
@@ -205,6 +207,18 @@ def _load(path: str, instrumented: bool) -> ctypes.CDLL:
         L.ssimu2_error_map_rgb8.restype = ci
         L.ssimu2_error_map_against_reference.argtypes = [vp, u8p, f32p, f64p]
         L.ssimu2_error_map_against_reference.restype = ci
+    if hasattr(L, "ssimu2_score_rgb16"):   # absent from builds before 16-bit input (scripts/gpu_ab.py loads those too)
+        u16p = ctypes.POINTER(ctypes.c_uint16)
+        L.ssimu2_linear_table.argtypes = [u32, ctypes.POINTER(ctypes.c_float)]
+        L.ssimu2_linear_table.restype = ci
+        L.ssimu2_score_rgb16.argtypes = [vp, u16p, u16p, u32, u32, u32, u32, f64p]
+        L.ssimu2_score_rgb16.restype = ci
+        L.ssimu2_set_reference_rgb16.argtypes = [vp, u16p, u32, u32, u32]
+        L.ssimu2_set_reference_rgb16.restype = ci
+        L.ssimu2_score_against_reference_rgb16.argtypes = [vp, u16p, u32, f64p]
+        L.ssimu2_score_against_reference_rgb16.restype = ci
+        L.ssimu2_score_against_reference_strided16.argtypes = [vp, u16p, u32, u32, u32, f64p]
+        L.ssimu2_score_against_reference_strided16.restype = ci
     if instrumented:
         sigs = {
             "ssimu2_measure_read_stream": [vp, ctypes.c_size_t, ci, f64p],

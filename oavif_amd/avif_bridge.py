@@ -379,19 +379,37 @@ def encode(scaled: np.ndarray, out_depth: int, o, q: int, icc: Optional[bytes] =
 
 
 class DecodedFrame:
-    """What decodeAvifCommon leaves behind (io.zig:446-482): the decoder and libavif's own 8-bit RGB(A) rows.
+    """What decodeAvifCommon leaves behind (io.zig:446-482): the decoder and libavif's own RGB(A) rows.
     `rows` is a (h, rowBytes) uint8 view of libavif's buffer, valid until close(); `channels` 3 or 4.  The
-    decoded-frame hand-off of the C ABI (`ssimu2_score_against_reference_strided`) takes exactly this."""
+    decoded-frame hand-off of the C ABI (`ssimu2_score_against_reference_strided`) takes exactly this.
+    At `rgb_depth` > 8 the samples are host-endian uint16 and `rows` is a (h, rowBytes / 2) uint16 view
+    (`ssimu2_score_against_reference_strided16`); `depth` stays the bitstream's."""
 
-    def __init__(self, L, dec, rgb, w, h, channels, depth, has_alpha):
+    def __init__(self, L, dec, rgb, w, h, channels, depth, has_alpha, rgb_depth=8):
         self._L, self._dec, self._rgb = L, dec, rgb
         self.width, self.height, self.channels, self.depth, self.has_alpha = w, h, channels, depth, has_alpha
+        self.rgb_depth = rgb_depth
         pix, row = struct.unpack_from("<QI", rgb.raw, _RGB_PIXELS)
         self.row_bytes = row
-        self.rows = np.ctypeslib.as_array((ctypes.c_uint8 * (row * h)).from_address(pix)).reshape(h, row)
+        if rgb_depth > 8:
+            self.rows = np.ctypeslib.as_array((ctypes.c_uint16 * (row // 2 * h)).from_address(pix)).reshape(h, row // 2)
+        else:
+            self.rows = np.ctypeslib.as_array((ctypes.c_uint8 * (row * h)).from_address(pix)).reshape(h, row)
+
+    def pixels(self) -> np.ndarray:
+        """(h, w, channels) view of `rows` (padding cut off, alpha kept), valid until close()."""
+        return self.rows[:, : self.width * self.channels].reshape(self.height, self.width, self.channels)
+
+    def tight_rgb16(self) -> np.ndarray:
+        """Tight (h, w, 3) uint16 copy of a decode at rgb_depth > 8, alpha dropped."""
+        if self.rgb_depth == 8:
+            raise AvifBridgeError("ConvertFailed", "tight_rgb16 of an 8-bit decode")
+        return np.array(self.pixels()[..., :3], order="C", copy=True)
 
     def tight_rgb8(self) -> np.ndarray:
         """io.decodeAvifToRgb's copy loop (io.zig:654-663): tight RGB8, alpha dropped."""
+        if self.rgb_depth != 8:
+            raise AvifBridgeError("ConvertFailed", f"tight_rgb8 of a {self.rgb_depth}-bit decode")
         a = self.rows[:, : self.width * self.channels].reshape(self.height, self.width, self.channels)
         return np.array(a[..., :3], order="C", copy=True)   # a copy: `rows` dies with close()
 
@@ -412,8 +430,11 @@ class DecodedFrame:
         self.close()
 
 
-def decode_common(data: bytes) -> DecodedFrame:
-    """decodeAvifCommon(avif_data, use_8bit = true) (io.zig:452-482)."""
+def decode_common(data: bytes, rgb_depth: int = 8) -> DecodedFrame:
+    """decodeAvifCommon(avif_data, use_8bit = true) (io.zig:452-482).  `rgb_depth` 10 / 12 / 16: libavif converts to
+    RGB samples of that many bits instead (the high-bit-depth scorer input); 8 is the reference's call exactly."""
+    if rgb_depth not in (8, 10, 12, 16):
+        raise ValueError(f"rgb_depth must be 8, 10, 12 or 16, not {rgb_depth}")
     L = _lib()
     dec = L.avifDecoderCreate()
     if not dec:
@@ -436,7 +457,7 @@ def decode_common(data: bytes) -> DecodedFrame:
         has_alpha = _ptr(img, _IMG_ALPHAPLANE) != 0
         rgb = ctypes.create_string_buffer(_RGB_SIZE)
         L.avifRGBImageSetDefaults(rgb, img)
-        struct.pack_into("<I", rgb, _RGB_DEPTH, 8)                                   # io.zig:470-471
+        struct.pack_into("<I", rgb, _RGB_DEPTH, rgb_depth)                           # io.zig:470-471 (8)
         struct.pack_into("<I", rgb, _RGB_FORMAT, _RGB_FORMAT_RGBA if has_alpha else _RGB_FORMAT_RGB)
         if L.avifRGBImageAllocatePixels(rgb) != _RESULT_OK:
             raise AvifBridgeError("AllocatePixelsFailed")
@@ -447,7 +468,7 @@ def decode_common(data: bytes) -> DecodedFrame:
     except BaseException:
         L.avifDecoderDestroy(dec)
         raise
-    return DecodedFrame(L, dec, rgb, w, h, 4 if has_alpha else 3, depth, has_alpha)
+    return DecodedFrame(L, dec, rgb, w, h, 4 if has_alpha else 3, depth, has_alpha, rgb_depth)
 
 
 def decode_rgb8(data: bytes) -> np.ndarray:

@@ -12,6 +12,8 @@
 //   partials    : fp64 [scale][18 stats][workgroups] partial sums
 //   result      : fp64 [108 averages][score][nscales], written by k_finalize straight into pinned host memory
 //   error map   : first map call only: density planes [scale][3][h_s][w_s] + the fp32 map [h][w] (ssimu2_error_map_*)
+//   16-bit input: first such call only (ssimu2_*_rgb16 / _strided16): the sRGB tables of depths 8..16, the u16
+//                 frames as uploaded, and in the FIR mode their scale-0 linear planes [3][h][w]
 //
 //   SSIMU2_BLUR_RECURSIVE modes only (ssimu2_recursive.h), every scale packed: XYB planes of both
 //   frames, the reference's cached blur(x) / blur(x*x) planes, the horizontal pass of a pass's planes
@@ -179,6 +181,17 @@ struct ssimu2_ctx {
     float* d_map_dens = nullptr;
     float* d_map = nullptr;
     size_t cap_map_dens = 0, cap_map = 0;  // floats
+    // 16-bit input (ssimu2_*_rgb16 / _strided16), allocated by the first such call only: the sRGB -> linear tables
+    // of depths 8..16 (depth d at float offset 2^d - 256, uploaded by the first call at that depth), the tight u16
+    // frames, and (FIR) the frames' scale-0 linear planes [3][h][w]
+    float* d_tab = nullptr;
+    uint32_t tab_ready = 0;  // bit d: the depth-d table is in d_tab
+    void* d_ref16 = nullptr;
+    void* d_dist16 = nullptr;
+    void* d_lin0_ref = nullptr;
+    void* d_lin0_dist = nullptr;
+    size_t cap_ref16 = 0, cap_dist16 = 0, cap_lin0_ref = 0, cap_lin0_dist = 0;  // bytes
+    bool ref_hbd = false;  // the cached reference was set from 16-bit samples (its 8-bit frame buffer is not it)
 
     // reference state
     bool have_ref = false;
@@ -317,8 +330,18 @@ void free_map(ssimu2_ctx* c) {
     c->cap_map_dens = c->cap_map = 0;
 }
 
+void free_hbd_frames(ssimu2_ctx* c) {
+    (void)hipFree(c->d_ref16);
+    (void)hipFree(c->d_dist16);
+    (void)hipFree(c->d_lin0_ref);
+    (void)hipFree(c->d_lin0_dist);
+    c->d_ref16 = c->d_dist16 = c->d_lin0_ref = c->d_lin0_dist = nullptr;
+    c->cap_ref16 = c->cap_dist16 = c->cap_lin0_ref = c->cap_lin0_dist = 0;
+}
+
 void free_buffers(ssimu2_ctx* c) {
     free_map(c);
+    free_hbd_frames(c);
     (void)hipFree(c->d_ref_u8);
     (void)hipFree(c->d_dist_u8);
     (void)hipFree(c->d_lin_ref);
@@ -393,6 +416,40 @@ void launch_pyramid(ssimu2_ctx* c, const Pyramid& p, int nframes, const uint8_t*
     if (p.nscales < 2) return;
     const PyrBandArgs a = pyramid_args(p, nframes, frames, lin);
     launch(k_pyramid_bands, dim3(a.bands_x * a.bands_y * nframes), dim3(PYR_THREADS), 0, c->stream, a);
+}
+
+// ---- 16-bit input ----------------------------------------------------------
+// One 16-bit frame on the device: rows `pitch` bytes apart, `ch` = 3 (RGB) or 4 (RGBA) samples per pixel, read through
+// the table of its depth.
+struct Src16 {
+    const void* px;
+    uint32_t pitch, ch;
+    const float* tab;
+    uint32_t maxv;
+};
+
+PyrHbdArgs hbd_args(int nframes, const Src16* const* src, float* const* lin0) {
+    PyrHbdArgs hb{};
+    for (int f = 0; f < nframes; ++f) {
+        hb.in[f] = (const uint8_t*)src[f]->px;
+        hb.pitch[f] = src[f]->pitch;
+        hb.tab[f] = src[f]->tab;
+        hb.maxv[f] = src[f]->maxv;
+        hb.lin0[f] = lin0 ? lin0[f] : nullptr;
+    }
+    return hb;
+}
+
+// FIR: levels 1..nscales-1 of up to two 16-bit frames (same channel count) into lin[i], their scale-0 linear planes
+// into lin0[i].  Launched for any frame with a scale: the marching kernel reads scale 0 from lin0.
+void launch_pyramid16(ssimu2_ctx* c, const Pyramid& p, int nframes, const Src16* const* src, float* const* lin,
+                      float* const* lin0) {
+    if (p.nscales < 1) return;
+    const uint8_t* none[2] = {nullptr, nullptr};
+    const PyrBandArgs a = pyramid_args(p, nframes, none, lin);
+    const PyrHbdArgs hb = hbd_args(nframes, src, lin0);
+    launch(src[0]->ch == 4 ? k_pyramid_bands16<4> : k_pyramid_bands16<3>, dim3(a.bands_x * a.bands_y * nframes),
+           dim3(PYR_THREADS), 0, c->stream, a, hb);
 }
 
 // float offset of scale s in the cached reference XYB buffer (scale 0 first)
@@ -554,7 +611,9 @@ void rg_debug_keep_h(ssimu2_ctx* c, const Pyramid& p, const RgPlan& rp, bool ref
 
 // Positive-XYB planes of one frame at every scale, straight from its bytes: the band pyramid with
 // XYB outputs (the recursive modes read nothing but XYB planes; no linear-light level is stored).
-void rg_launch_convert(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_frame, const RgPlan& rp) {
+// `s16`: the frame is 16-bit (d_frame unused).
+void rg_launch_convert(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_frame, const RgPlan& rp,
+                       const Src16* s16 = nullptr) {
     const uint8_t* frames[1] = {d_frame};
     float* none[1] = {nullptr};
     PyrBandArgs a = pyramid_args(p, 1, frames, none);
@@ -562,6 +621,12 @@ void rg_launch_convert(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_frame, 
     a.zero4 = rp.q;
     for (int l = 0; l < a.nlevels; ++l) a.out[0][l] = rp.xout[l + 1];
     for (int l = 0; l < p.nscales && l < 6; ++l) a.opitch[l] = rp.pitch[l];
+    if (s16) {
+        const PyrHbdArgs hb = hbd_args(1, &s16, nullptr);
+        launch(s16->ch == 4 ? k_pyramid_bands_xyb16<4> : k_pyramid_bands_xyb16<3>, dim3(a.bands_x * a.bands_y),
+               dim3(PYR_THREADS), 0, c->stream, a, hb);
+        return;
+    }
     launch(k_pyramid_bands_xyb, dim3(a.bands_x * a.bands_y), dim3(PYR_THREADS), 0, c->stream, a);
 }
 
@@ -575,14 +640,14 @@ void rg_launch_h(ssimu2_ctx* c, bool fma, int hblocks, const RgPlan& rp) {
 
 // What depends on the reference alone: its XYB planes and mu1 = blur(x), s11 = blur(x * x) at
 // every scale (the reference's linear pyramid is already enqueued).
-void rg_enqueue_reference(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_ref) {
+void rg_enqueue_reference(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_ref, const Src16* s16 = nullptr) {
     RgPlan rp;
     int hblocks, vblocks;
     rg_build_plan(c, p, true, &rp, &hblocks, &vblocks);
     if (p.nscales == 0) return;  // a frame below 8 x 8 has no scale to score
     for (int s = 0; s < p.nscales; ++s) rp.emit[s] = rp.cache[s];
     const bool fma = c->blur_mode == SSIMU2_BLUR_RECURSIVE_FMA, dbg = rg_debugging(c, p);
-    rg_launch_convert(c, p, d_ref, rp);
+    rg_launch_convert(c, p, d_ref, rp, s16);
     rg_launch_h<true>(c, fma, hblocks, rp);
     if (dbg) rg_debug_keep_h(c, p, rp, true);
     if (fma) launch((k_rg_v_emit<true, 2>), dim3(vblocks), dim3(128), 0, c->stream, rp);
@@ -591,7 +656,7 @@ void rg_enqueue_reference(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_ref)
 
 // One pass against the reference planes in place: XYB of the distorted frame, the recursion over
 // {y, y*y, x*y}, maps, final reduction (its linear pyramid is already enqueued).
-int rg_enqueue_pass(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_dist) {
+int rg_enqueue_pass(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_dist, const Src16* s16 = nullptr) {
     RgPlan rp;
     int hblocks, vblocks;
     rg_build_plan(c, p, false, &rp, &hblocks, &vblocks);
@@ -605,7 +670,7 @@ int rg_enqueue_pass(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_dist) {
         fa.inv_pixels[s] = 1.0 / ((double)p.w[s] * (double)p.h[s]);
     }
     if (p.nscales > 0) {  // a frame below 8 x 8 has no scale to score
-        rg_launch_convert(c, p, d_dist, rp);
+        rg_launch_convert(c, p, d_dist, rp, s16);
         const int vgrid = vblocks < c->num_cus ? vblocks : c->num_cus;
         rg_launch_h<false>(c, fma, hblocks, rp);
         if (fma) launch((k_rg_v<true>), dim3(vgrid), dim3(512), c->rg_v_pad, c->stream, rp);
@@ -667,6 +732,130 @@ int enqueue_score(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, ui
     launch(k_finalize, dim3(1), dim3(1024), 0, c->stream, fa, c->h_result);
     HIP_TRY(c, hipGetLastError());
     c->pending = true;
+    return SSIMU2_OK;
+}
+
+// The score of 16-bit frames: `ref` null = against the cached reference (set from 8- or 16-bit samples; its planes do
+// not depend on the depth).  Same kernels after the front end: k_pyramid_bands16 (FIR, which also writes scale 0's
+// linear planes for k_march_lin / k_march_refblur_lin) or k_pyramid_bands_xyb16 (recursive modes).
+int enqueue_score16(ssimu2_ctx* c, const Src16* ref, const Src16& dist, uint32_t w, uint32_t h) {
+    const Pyramid p = make_pyramid(w, h);
+    if (c->blur_mode != SSIMU2_BLUR_FIR) {
+        int rc = rg_check_size(c, w, h);
+        if (rc) return rc;
+        const bool had_ref = c->have_ref;
+        if ((rc = rg_ensure(c, p))) return rc;
+        if (!ref && had_ref && !c->have_ref)
+            return c->fail(SSIMU2_ERR_NO_REFERENCE, "recursive blur mode: the cached reference was dropped");
+        if (ref) rg_enqueue_reference(c, p, nullptr, ref);
+        return rg_enqueue_pass(c, p, nullptr, &dist);
+    }
+    const bool cached = !ref && c->d_xyb_ref && c->d_ref_blur && c->cap_blur;
+    if (!ref && !cached)  // 16-bit scale 0 cannot be paired with an 8-bit reference frame in one marching kernel
+        return c->fail(SSIMU2_ERR_OOM, "16-bit frames against a reference need its cached planes, which are missing");
+    {
+        const Src16* src[2];
+        float* lin[2];
+        float* lin0[2];
+        int n = 0;
+        if (ref) {
+            src[n] = ref;
+            lin[n] = c->d_lin_ref;
+            lin0[n++] = (float*)c->d_lin0_ref;
+        }
+        src[n] = &dist;
+        lin[n] = c->d_lin_dist;
+        lin0[n++] = (float*)c->d_lin0_dist;
+        launch_pyramid16(c, p, n, src, lin, lin0);
+    }
+    MarchPlan mp;
+    FinalizeArgs fa;
+    int blocks = 0;
+    build_plans(c, p, (const uint8_t*)c->d_lin0_ref, (const uint8_t*)c->d_lin0_dist, cached, &mp, &fa, &blocks);
+    if (blocks > 0) {
+        if (cached) launch(k_march_refblur_lin, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
+        else launch(k_march_lin, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
+    }
+    launch(k_finalize, dim3(1), dim3(1024), 0, c->stream, fa, c->h_result);
+    HIP_TRY(c, hipGetLastError());
+    c->pending = true;
+    return SSIMU2_OK;
+}
+
+// sRGB -> linear of a d-bit sample s, 8 <= d <= 16: the 8-bit table's expression at v = s / (2^d - 1), fp64, rounded
+// once.  65535 = 255 * 257, so the 16-bit entry 257 u is the 8-bit entry u bit for bit (v is the same double).
+// Built once per process and depth.
+const float* host_table(uint32_t d) {
+    static std::mutex mu;
+    static float* tabs[17] = {nullptr};
+    std::lock_guard<std::mutex> lock(mu);
+    if (!tabs[d]) {
+        const uint32_t n = 1u << d;
+        float* t = new (std::nothrow) float[n];
+        if (!t) return nullptr;
+        const double top = (double)(n - 1);
+        for (uint32_t i = 0; i < n; ++i) {
+            const double v = (double)i / top;
+            t[i] = (float)(v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4));
+        }
+        tabs[d] = t;
+    }
+    return tabs[d];
+}
+
+size_t table_off(uint32_t d) { return ((size_t)1 << d) - 256; }
+
+// The device table of depth d (uploaded on the context stream by the first call at that depth).
+int device_table(ssimu2_ctx* c, uint32_t d, const float** out) {
+    if (!c->d_tab) {
+        const hipError_t e = hipMalloc(&c->d_tab, table_off(17) * sizeof(float));
+        if (e != hipSuccess) {
+            c->d_tab = nullptr;
+            return c->fail(SSIMU2_ERR_OOM, "hipMalloc(16-bit sRGB tables)", e);
+        }
+        c->tab_ready = 0;
+    }
+    if (!(c->tab_ready & (1u << d))) {
+        const float* t = host_table(d);
+        if (!t) return c->fail(SSIMU2_ERR_OOM, "16-bit sRGB table");
+        HIP_TRY(c, hipMemcpyAsync(c->d_tab + table_off(d), t, ((size_t)1 << d) * sizeof(float), hipMemcpyHostToDevice,
+                                  c->stream));
+        c->tab_ready |= 1u << d;
+    }
+    *out = c->d_tab + table_off(d);
+    return SSIMU2_OK;
+}
+
+// A 16-bit buffer of at least `bytes`: grown on demand, never shrunk.
+int hbd_grow(ssimu2_ctx* c, void** p, size_t* cap, size_t bytes, const char* what) {
+    if (*p && bytes <= *cap) return SSIMU2_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) {
+        *p = nullptr;
+        return c->fail(SSIMU2_ERR_OOM, what, e);
+    }
+    *cap = bytes;
+    return SSIMU2_OK;
+}
+
+// Scale-0 linear planes for the frames of a FIR-mode 16-bit call (`ref`: the reference's too).
+int hbd_lin0(ssimu2_ctx* c, uint32_t w, uint32_t h, bool ref) {
+    if (c->blur_mode != SSIMU2_BLUR_FIR) return SSIMU2_OK;
+    const size_t bytes = (size_t)w * h * 3 * sizeof(float);
+    int rc = hbd_grow(c, &c->d_lin0_dist, &c->cap_lin0_dist, bytes, "hipMalloc(16-bit scale-0 planes)");
+    if (!rc && ref) rc = hbd_grow(c, &c->d_lin0_ref, &c->cap_lin0_ref, bytes, "hipMalloc(16-bit scale-0 planes)");
+    return rc;
+}
+
+// Argument checks of the 16-bit calls (the ctx is not null).
+int check16(ssimu2_ctx* c, const void* px, uint32_t bit_depth) {
+    if (!px) return c->fail(SSIMU2_ERR_INVALID_ARG, "null image pointer");
+    if ((uintptr_t)px & 1u) return c->fail(SSIMU2_ERR_INVALID_ARG, "16-bit image pointer not 2-byte aligned");
+    if (bit_depth < 8 || bit_depth > 16) return c->fail(SSIMU2_ERR_UNSUPPORTED, "bit_depth must be 8..16");
     return SSIMU2_OK;
 }
 
@@ -1168,6 +1357,7 @@ void ssimu2_ctx_destroy(ssimu2_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     free_buffers(c);
+    (void)hipFree(c->d_tab);
     (void)hipFree(c->d_result);
     (void)hipHostFree(c->h_result);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1221,34 +1411,10 @@ int ssimu2_score_rgb8(ssimu2_ctx* c, const uint8_t* ref, const uint8_t* dist, ui
     return ssimu2_wait(c, out_score);
 }
 
-static int set_reference_impl(ssimu2_ctx* c, const void* ref, uint32_t w, uint32_t h,
-                              hipMemcpyKind kind) {
-    int rc = check_args(c, ref, ref, w, h);
-    if (rc) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if ((rc = ensure_capacity(c, w, h))) return rc;
-    const Pyramid p = make_pyramid(w, h);
-    if (c->blur_mode != SSIMU2_BLUR_FIR) {  // size limit and planes of the recursive modes, before any launch
-        if ((rc = rg_check_size(c, w, h))) return rc;
-        if ((rc = rg_ensure(c, p))) return rc;
-    }
-    c->have_ref = false;
-    const size_t bytes = (size_t)w * h * 3;
-    HIP_TRY(c, hipMemcpyAsync(c->d_ref_u8, ref, bytes, kind, c->stream));
-    if (p.nscales > 1 && c->blur_mode == SSIMU2_BLUR_FIR) {  // the reference's linear pyramid, once per search
-        const uint8_t* frames[1] = {c->d_ref_u8};
-        float* lin[1] = {c->d_lin_ref};
-        launch_pyramid(c, p, 1, frames, lin);
-    }
-    if (c->blur_mode != SSIMU2_BLUR_FIR) {  // XYB planes, blur(x) and blur(x*x) by the published recursion
-        rg_enqueue_reference(c, p, c->d_ref_u8);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipStreamSynchronize(c->stream));  // caller may free `ref` after return
-        c->have_ref = true;
-        c->ref_w = w;
-        c->ref_h = h;
-        return SSIMU2_OK;
-    }
+// FIR mode: the reference's positive-XYB planes and blur(ref*ref) at every scale from its scale 0 (`scale0`: the 8-bit
+// frame, or with !scale0_u8 the linear planes of a 16-bit one) and its linear pyramid in d_lin_ref, already enqueued.
+// `required` (16-bit references): a failed allocation is an error instead of a reference converted on every pass.
+static int cache_reference_fir(ssimu2_ctx* c, const Pyramid& p, const void* scale0, bool scale0_u8, bool required) {
     // ... and its positive-XYB planes at every scale, so that the per-pass kernel skips the
     // LUT / opsin / cube-root work for the reference frame (same values, bit-identical scores)
     const size_t need_xyb = xyb_off(p, p.nscales) + 4;
@@ -1268,9 +1434,9 @@ static int set_reference_impl(ssimu2_ctx* c, const void* ref, uint32_t w, uint32
     if (c->d_xyb_ref) {
         for (int sc = 0; sc < p.nscales; ++sc) {
             const size_t n = (size_t)p.w[sc] * p.h[sc];
-            const void* in = sc == 0 ? (const void*)c->d_ref_u8 : (const void*)(c->d_lin_ref + p.lin_off[sc]);
+            const void* in = sc == 0 ? scale0 : (const void*)(c->d_lin_ref + p.lin_off[sc]);
             launch(k_ref_xyb, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, in,
-                               sc == 0, p.w[sc], p.h[sc], c->d_xyb_ref + xyb_off(p, sc));
+                               sc == 0 && scale0_u8, p.w[sc], p.h[sc], c->d_xyb_ref + xyb_off(p, sc));
         }
     }
     // ... and blur(ref*ref) at every scale, which depends on the reference alone: the per-pass
@@ -1292,7 +1458,7 @@ static int set_reference_impl(ssimu2_ctx* c, const void* ref, uint32_t w, uint32
             MarchPlan mp;
             FinalizeArgs fa;
             int blocks = 0;
-            build_plans(c, p, c->d_ref_u8, c->d_ref_u8, true, &mp, &fa, &blocks);
+            build_plans(c, p, (const uint8_t*)scale0, (const uint8_t*)scale0, true, &mp, &fa, &blocks);
             for (int sc = 0; sc < p.nscales; ++sc) mp.dist[sc] = mp.ref[sc];  // second frame unused
             if (blocks > 0)
                 launch(k_ref_blur, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
@@ -1302,6 +1468,41 @@ static int set_reference_impl(ssimu2_ctx* c, const void* ref, uint32_t w, uint32
         c->d_ref_blur = nullptr;
         c->cap_blur = 0;
     }
+    if (required && !(c->d_xyb_ref && c->d_ref_blur && c->cap_blur))
+        return c->fail(SSIMU2_ERR_OOM, "hipMalloc(cached planes of a 16-bit reference)");
+    return SSIMU2_OK;
+}
+
+static int set_reference_impl(ssimu2_ctx* c, const void* ref, uint32_t w, uint32_t h,
+                              hipMemcpyKind kind) {
+    int rc = check_args(c, ref, ref, w, h);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = ensure_capacity(c, w, h))) return rc;
+    const Pyramid p = make_pyramid(w, h);
+    if (c->blur_mode != SSIMU2_BLUR_FIR) {  // size limit and planes of the recursive modes, before any launch
+        if ((rc = rg_check_size(c, w, h))) return rc;
+        if ((rc = rg_ensure(c, p))) return rc;
+    }
+    c->have_ref = false;
+    c->ref_hbd = false;
+    const size_t bytes = (size_t)w * h * 3;
+    HIP_TRY(c, hipMemcpyAsync(c->d_ref_u8, ref, bytes, kind, c->stream));
+    if (p.nscales > 1 && c->blur_mode == SSIMU2_BLUR_FIR) {  // the reference's linear pyramid, once per search
+        const uint8_t* frames[1] = {c->d_ref_u8};
+        float* lin[1] = {c->d_lin_ref};
+        launch_pyramid(c, p, 1, frames, lin);
+    }
+    if (c->blur_mode != SSIMU2_BLUR_FIR) {  // XYB planes, blur(x) and blur(x*x) by the published recursion
+        rg_enqueue_reference(c, p, c->d_ref_u8);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));  // caller may free `ref` after return
+        c->have_ref = true;
+        c->ref_w = w;
+        c->ref_h = h;
+        return SSIMU2_OK;
+    }
+    (void)cache_reference_fir(c, p, c->d_ref_u8, true, false);  // not required: an 8-bit pass can convert the reference
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // caller may free `ref` after return
     c->have_ref = true;
@@ -1387,9 +1588,136 @@ int ssimu2_error_map_rgb8(ssimu2_ctx* c, const uint8_t* ref, const uint8_t* dist
 int ssimu2_error_map_against_reference(ssimu2_ctx* c, const uint8_t* dist, float* out_map, double* out_score) {
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     if (!out_map) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_map");
+    if (c->have_ref && c->ref_hbd)  // the map pass reads the reference's 8-bit frame
+        return c->fail(SSIMU2_ERR_UNSUPPORTED, "no error map against a reference set from 16-bit samples");
     int rc = ssimu2_score_against_reference(c, dist, out_score);
     if (rc) return rc;
     return map_pass(c, c->d_ref_u8, c->d_dist_u8, c->ref_w, c->ref_h, out_map);
+}
+
+// ---- 16-bit input ----------------------------------------------------------
+int ssimu2_linear_table(uint32_t bit_depth, float* out) {
+    if (!out) return SSIMU2_ERR_INVALID_ARG;
+    if (bit_depth < 8 || bit_depth > 16) return SSIMU2_ERR_UNSUPPORTED;
+    const float* t = host_table(bit_depth);
+    if (!t) return SSIMU2_ERR_OOM;
+    memcpy(out, t, ((size_t)1 << bit_depth) * sizeof(float));
+    return SSIMU2_OK;
+}
+
+int ssimu2_score_rgb16(ssimu2_ctx* c, const uint16_t* ref, const uint16_t* dist, uint32_t w, uint32_t h,
+                       uint32_t channels, uint32_t bit_depth, double* out_score) {
+    int rc = check_args(c, ref, dist, w, h);
+    if (rc) return rc;
+    if ((rc = check16(c, ref, bit_depth)) || (rc = check16(c, dist, bit_depth))) return rc;
+    if (channels != 3) return c->fail(SSIMU2_ERR_UNSUPPORTED, "channels must be 3");
+    if (!out_score) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_score");
+    if (c->blur_mode != SSIMU2_BLUR_FIR && (rc = rg_check_size(c, w, h))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = ensure_capacity(c, w, h))) return rc;
+    c->have_ref = false;  // the lin_ref pyramid is overwritten
+    const size_t bytes = (size_t)w * h * 3 * sizeof(uint16_t);
+    const float* tab = nullptr;
+    if ((rc = hbd_grow(c, &c->d_ref16, &c->cap_ref16, bytes, "hipMalloc(16-bit frames)")) ||
+        (rc = hbd_grow(c, &c->d_dist16, &c->cap_dist16, bytes, "hipMalloc(16-bit frames)")) ||
+        (rc = hbd_lin0(c, w, h, true)) || (rc = device_table(c, bit_depth, &tab)))
+        return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->d_ref16, ref, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_dist16, dist, bytes, hipMemcpyHostToDevice, c->stream));
+    const uint32_t maxv = (1u << bit_depth) - 1u;
+    const Src16 r{c->d_ref16, w * 6u, 3u, tab, maxv}, d{c->d_dist16, w * 6u, 3u, tab, maxv};
+    if ((rc = enqueue_score16(c, &r, d, w, h))) return rc;
+    return ssimu2_wait(c, out_score);
+}
+
+int ssimu2_set_reference_rgb16(ssimu2_ctx* c, const uint16_t* ref, uint32_t w, uint32_t h, uint32_t bit_depth) {
+    int rc = check_args(c, ref, ref, w, h);
+    if (rc) return rc;
+    if ((rc = check16(c, ref, bit_depth))) return rc;
+    const bool fir = c->blur_mode == SSIMU2_BLUR_FIR;
+    if (!fir && (rc = rg_check_size(c, w, h))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = ensure_capacity(c, w, h))) return rc;
+    const Pyramid p = make_pyramid(w, h);
+    if (!fir && (rc = rg_ensure(c, p))) return rc;
+    c->have_ref = false;
+    const size_t bytes = (size_t)w * h * 3 * sizeof(uint16_t);
+    const float* tab = nullptr;
+    if ((rc = hbd_grow(c, &c->d_ref16, &c->cap_ref16, bytes, "hipMalloc(16-bit frames)")) ||
+        (rc = hbd_lin0(c, w, h, true)) || (rc = device_table(c, bit_depth, &tab)))
+        return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->d_ref16, ref, bytes, hipMemcpyHostToDevice, c->stream));
+    const Src16 r{c->d_ref16, w * 6u, 3u, tab, (1u << bit_depth) - 1u};
+    if (fir) {  // linear pyramid and scale-0 planes, then the same caches as an 8-bit reference's (required here)
+        const Src16* src[1] = {&r};
+        float* lin[1] = {c->d_lin_ref};
+        float* lin0[1] = {(float*)c->d_lin0_ref};
+        launch_pyramid16(c, p, 1, src, lin, lin0);
+        if ((rc = cache_reference_fir(c, p, c->d_lin0_ref, false, true))) return rc;
+    } else {
+        rg_enqueue_reference(c, p, nullptr, &r);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // caller may free `ref` after return
+    c->have_ref = true;
+    c->ref_hbd = true;
+    c->ref_w = w;
+    c->ref_h = h;
+    return SSIMU2_OK;
+}
+
+// Score the 16-bit frame at `src.px` (already on the device) against the cached reference.
+static int score_against_reference16(ssimu2_ctx* c, const Src16& src, double* out_score) {
+    int rc = enqueue_score16(c, nullptr, src, c->ref_w, c->ref_h);
+    if (rc) return rc;
+    return ssimu2_wait(c, out_score);
+}
+
+int ssimu2_score_against_reference_rgb16(ssimu2_ctx* c, const uint16_t* dist, uint32_t bit_depth, double* out_score) {
+    if (!c) return SSIMU2_ERR_INVALID_ARG;
+    if (!c->have_ref) return c->fail(SSIMU2_ERR_NO_REFERENCE, "no reference set");
+    if (!out_score) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
+    int rc = check16(c, dist, bit_depth);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t w = c->ref_w, h = c->ref_h;
+    const size_t bytes = (size_t)w * h * 3 * sizeof(uint16_t);
+    const float* tab = nullptr;
+    if ((rc = hbd_grow(c, &c->d_dist16, &c->cap_dist16, bytes, "hipMalloc(16-bit frames)")) ||
+        (rc = hbd_lin0(c, w, h, false)) || (rc = device_table(c, bit_depth, &tab)))
+        return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->d_dist16, dist, bytes, hipMemcpyHostToDevice, c->stream));
+    return score_against_reference16(c, Src16{c->d_dist16, w * 6u, 3u, tab, (1u << bit_depth) - 1u}, out_score);
+}
+
+int ssimu2_score_against_reference_strided16(ssimu2_ctx* c, const uint16_t* pixels, uint32_t row_bytes,
+                                             uint32_t channels, uint32_t bit_depth, double* out_score) {
+    if (!c) return SSIMU2_ERR_INVALID_ARG;
+    if (!c->have_ref) return c->fail(SSIMU2_ERR_NO_REFERENCE, "no reference set");
+    if (!out_score) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
+    int rc = check16(c, pixels, bit_depth);
+    if (rc) return rc;
+    if (channels != 3 && channels != 4)
+        return c->fail(SSIMU2_ERR_UNSUPPORTED, "channels must be 3 (RGB) or 4 (RGBA)");
+    const uint32_t w = c->ref_w, h = c->ref_h;
+    if ((row_bytes & 1u) || (uint64_t)row_bytes < (uint64_t)w * channels * 2)
+        return c->fail(SSIMU2_ERR_INVALID_ARG, "row_bytes odd or smaller than one row of 16-bit pixels");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // rows are read where they are, padding and alpha skipped by the front end; the last row needs only its pixels
+    const size_t bytes = (size_t)row_bytes * (h - 1) + (size_t)w * channels * 2;
+    const float* tab = nullptr;
+    if ((rc = hbd_lin0(c, w, h, false)) || (rc = device_table(c, bit_depth, &tab))) return rc;
+    if (bytes > c->cap_stage) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(c->d_stage);
+        c->d_stage = nullptr;
+        c->cap_stage = 0;
+        hipError_t e = hipMalloc(&c->d_stage, bytes + 16);
+        if (e != hipSuccess) return c->fail(SSIMU2_ERR_OOM, "hipMalloc(staging frame)", e);
+        c->cap_stage = bytes;
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->d_stage, pixels, bytes, hipMemcpyHostToDevice, c->stream));
+    return score_against_reference16(c, Src16{c->d_stage, row_bytes, channels, tab, (1u << bit_depth) - 1u}, out_score);
 }
 
 int ssimu2_last_averages(ssimu2_ctx* c, double* out, int* out_num_scales) {

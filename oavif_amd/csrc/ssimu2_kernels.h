@@ -12,6 +12,8 @@
 //                  polynomial, score
 //   k_march_map, k_map_compose : the per-pixel error map (ssimu2_error_map_*): densities of every
 //                  scale, then their sum at full resolution
+//   k_pyramid_bands16, k_pyramid_bands_xyb16, k_march_lin, k_march_refblur_lin : 16-bit input
+//                  (ssimu2_*_rgb16 / _strided16)
 //
 // Arithmetic contract: this translation unit is compiled with -ffp-contract=off;
 // every fused multiply-add is an explicit fmaf().  The sequence of IEEE operations per pixel
@@ -183,6 +185,20 @@ struct PyrBandArgs {
     unsigned* zero4;       // XYB variant: four words zeroed here, the job cursor of the recursive pass that follows (RgPlan::q)
 };
 
+// High-bit-depth front end (ssimu2_*_rgb16 / _strided16): the frames are
+// host-endian uint16_t RGB (CH = 3) or RGBA (CH = 4, alpha ignored) rows `pitch` bytes apart, and a
+// sample s becomes tab[min(s, maxv)], the 2^d-entry table of its frame's depth d (device memory:
+// 256 KB at d = 16, too big for __constant__ or beside the kernels' LDS).  The FIR modes also get the
+// frame's scale-0 linear planes [3][h][w] (lin0), which the marching kernels read as they read the
+// planes of the smaller scales.
+struct PyrHbdArgs {
+    const uint8_t* in[2];  // first byte of each frame's rows
+    uint32_t pitch[2];     // bytes per row
+    const float* tab[2];   // sRGB -> linear table of each frame's depth, maxv + 1 entries
+    uint32_t maxv[2];      // 2^d - 1: larger samples are clamped to it
+    float* lin0[2];        // FIR: scale-0 linear planes of each frame (null in the XYB variant)
+};
+
 constexpr int PYR_THREADS = 512;                      // (256-thread bands of 128 pixels measured the same)
 constexpr int PYR_TX = PYR_THREADS / 8;               // threads across a band (8 thread rows of 4 pixel rows)
 constexpr int PYR_BAND_W = 4 * PYR_TX, PYR_BAND_H = 32;
@@ -233,10 +249,59 @@ __device__ __forceinline__ void pyr_lds_level(const float* src, int sw, int sh, 
     }
 }
 
+// Linear values of one thread's 4 x 4 block of a 16-bit frame: per row 2 * CH contiguous dwords
+// (24 / 32 bytes, unaligned dword loads), all four rows in flight before the table gathers; at the
+// frame border clamped coordinates, one 16-bit load per sample.
+template <int CH>
+__device__ __forceinline__ void pyr_load16(const PyrHbdArgs& hb, int f, int w0, int h0, int X0, int Y0, bool inside,
+                                           float (&lin)[4][4][3]) {
+    const uint8_t* base = hb.in[f];
+    const uint32_t pitch = hb.pitch[f], maxv = hb.maxv[f];
+    const float* tab = hb.tab[f];
+    uint32_t s[4][4][3];
+    if (inside) {
+        uint32_t raw[4][2 * CH];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint8_t* p = base + (size_t)(Y0 + j) * pitch + (size_t)X0 * (2 * CH);
+#pragma unroll
+            for (int k = 0; k < 2 * CH; ++k) __builtin_memcpy(&raw[j][k], p + 4 * k, 4);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int e = CH * i + c;  // 16-bit element of the row's run
+                    s[j][i][c] = (raw[j][e >> 1] >> (16 * (e & 1))) & 0xFFFFu;
+                }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint8_t* row = base + (size_t)min(Y0 + j, h0 - 1) * pitch;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const uint16_t* p = (const uint16_t*)(row + (size_t)min(X0 + i, w0 - 1) * (2 * CH));
+#pragma unroll
+                for (int c = 0; c < 3; ++c) s[j][i][c] = p[c];
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) lin[j][i][c] = tab[min(s[j][i][c], maxv)];
+}
+
 // `lut`: the sRGB table in LDS; `lds`: PYR_BAND_LDS_FLOATS floats of scratch; 512 threads, all of
 // which must call (barriers inside).  `band` < bands_x * bands_y * nframes.
-template <bool XYB>
-__device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, const float* lut, float* lds) {
+// CH16 = 0: 8-bit frames through the LDS table `lut`; 3 / 4: 16-bit RGB / RGBA frames of `hb`.
+template <bool XYB, int CH16 = 0>
+__device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, const float* lut, float* lds,
+                                             const PyrHbdArgs* hb = nullptr) {
     const int t = threadIdx.x;
     const int per_frame = a.bands_x * a.bands_y;
     const int f = band / per_frame;
@@ -260,8 +325,11 @@ __device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, con
     if (X0 < w0 && Y0 < h0) {
         const uint8_t* base = a.in[f];
         uint32_t raw[4][3];
+        float lin16[4][4][3];  // CH16: linear values of this thread's 4 x 4 pixels
         const bool inside = X0 + 3 < w0 && Y0 + 3 < h0;
-        if (inside) {  // four rows of 12 contiguous bytes
+        if constexpr (CH16 != 0) {
+            pyr_load16<CH16>(*hb, f, w0, h0, X0, Y0, inside, lin16);
+        } else if (inside) {  // four rows of 12 contiguous bytes
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const uint8_t* p = base + ((size_t)(Y0 + j) * w0 + X0) * 3;
@@ -287,7 +355,8 @@ __device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, con
             }
         }
         // byte 3*i + c of a row = channel c of pixel i
-#define PYR_LIN(j, i, c) lut[(raw[j][(3 * (i) + (c)) >> 2] >> (8 * ((3 * (i) + (c)) & 3))) & 255u]
+#define PYR_LIN(j, i, c) \
+    (CH16 ? lin16[j][i][c] : lut[(raw[j][(3 * (i) + (c)) >> 2] >> (8 * ((3 * (i) + (c)) & 3))) & 255u])
         const int p1 = a.opitch[1];
         const size_t n1 = (size_t)p1 * h1;
 #pragma unroll
@@ -307,6 +376,28 @@ __device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, con
 #pragma unroll
                         for (int c = 0; c < 3; ++c) o[c * n1 + (size_t)oy * p1 + ox] = l1[j][i][c];
                     }
+                }
+            }
+        }
+        if constexpr (CH16 != 0 && !XYB) {  // FIR: the frame's scale-0 linear planes, a row of four pixels at a time
+            const size_t n0 = (size_t)w0 * h0;
+            float* o = hb->lin0[f];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (inside) {
+                    const size_t at = (size_t)(Y0 + j) * w0 + X0;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const float px[4] = {lin16[j][0][c], lin16[j][1][c], lin16[j][2][c], lin16[j][3][c]};
+                        __builtin_memcpy(o + c * n0 + at, px, 16);
+                    }
+                } else if (Y0 + j < h0) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (X0 + i < w0) {
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) o[c * n0 + (size_t)(Y0 + j) * w0 + X0 + i] = lin16[j][i][c];
+                        }
                 }
             }
         }
@@ -394,6 +485,23 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_bands_xyb(PyrBandArgs a
     if (blockIdx.x == 0 && threadIdx.x < 4 && a.zero4) a.zero4[threadIdx.x] = 0u;  // k_rg_v starts after this launch has ended
     __syncthreads();
     pyramid_band<true>(a, (int)blockIdx.x, s_lut, s_tiles);
+}
+
+// The 16-bit counterparts (CH = 3: tight or padded RGB rows; 4: RGBA rows, alpha dropped here).
+// FIR: levels 1..5 as k_pyramid_bands and the frame's scale-0 linear planes.
+template <int CH>
+__global__ __launch_bounds__(PYR_THREADS) void k_pyramid_bands16(PyrBandArgs a, PyrHbdArgs hb) {
+    __shared__ float s_tiles[PYR_BAND_LDS_FLOATS];
+    pyramid_band<false, CH>(a, (int)blockIdx.x, nullptr, s_tiles, &hb);
+}
+
+// Recursive modes: XYB planes of every level, as k_pyramid_bands_xyb.
+template <int CH>
+__global__ __launch_bounds__(PYR_THREADS) void k_pyramid_bands_xyb16(PyrBandArgs a, PyrHbdArgs hb) {
+    __shared__ float s_tiles[PYR_BAND_LDS_FLOATS];
+    if (blockIdx.x == 0 && threadIdx.x < 4 && a.zero4) a.zero4[threadIdx.x] = 0u;  // k_rg_v starts after this launch has ended
+    __syncthreads();
+    pyramid_band<true, CH>(a, (int)blockIdx.x, nullptr, s_tiles, &hb);
 }
 
 // ---- fused per-scale kernel, marching form, all scales in one launch ----------------------------
@@ -583,7 +691,9 @@ __device__ __forceinline__ void march_lut(const float* lut, uint32_t d, uint32_t
 // Per row and lane: [LUT values of this row, requested one row earlier] -> opsin mix of both
 // frames -> request the LUT values of the next row -> cube roots, XYB, one ds_write_b64 per
 // channel.  The LUT reads therefore land under ~100 arithmetic instructions.
-template <bool U8, int MODE>
+// LIN0: instantiated for the kernels of march_body<MODE, true> (same code; an instantiation of their own leaves the
+// code generated for the 8-bit kernels as it was).
+template <bool U8, int MODE, bool LIN0 = false>
 __device__ __forceinline__ void march_convert_rows(f2 (*ring)[3][MRW], const float* lut,
                                                    const MarchPlan& plan, int sc, int w, int h, int x0,
                                                    int y0, int steps, int ngroups, int col) {
@@ -855,7 +965,8 @@ __device__ __forceinline__ int march_tile_of_block(int b, int first, int end) {
     return before + (b >> 3) - ((first + 7 - x) >> 3);  // + its rank among those of phase x
 }
 
-template <int MODE>
+// LIN0: scale 0 is fp32 linear planes [3][h][w] like the smaller scales (the 16-bit front end's), not 8-bit frames.
+template <int MODE, bool LIN0 = false>
 __device__ __forceinline__ void march_body(const MarchPlan& plan, const MapCoef* coef = nullptr) {
     // [row slot][channel][column] of (ref, dist) pairs
     __shared__ __attribute__((aligned(16))) f2 s_ring[RING][3][MRW];
@@ -876,7 +987,7 @@ __device__ __forceinline__ void march_body(const MarchPlan& plan, const MapCoef*
     const int w = plan.w[sc], h = plan.h[sc], seg_rows = plan.seg[sc];
     const int nstrips = plan.nstrips[sc];
     const int by = blk / nstrips, bx = blk - by * nstrips;
-    const bool u8 = sc == 0;
+    const bool u8 = !LIN0 && sc == 0;
     const int x0 = bx * MW;
     const int y0 = by * seg_rows;
     const int rows_out = min(seg_rows, h - y0);
@@ -928,8 +1039,8 @@ __device__ __forceinline__ void march_body(const MarchPlan& plan, const MapCoef*
         // issue-priority bump lets them keep pace (measured: -7 %).
         __builtin_amdgcn_s_setprio(1);
         const int col = (wave << 6) + lane;  // staged column; this lane converts both frames
-        if (u8) march_convert_rows<true, MODE>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col);
-        else march_convert_rows<false, MODE>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col);
+        if (u8) march_convert_rows<true, MODE, LIN0>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col);
+        else march_convert_rows<false, MODE, LIN0>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col);
     } else {
         float win[5][9];
         const lds_vu64* rp = (const lds_vu64*)&s_ring[0][ch][o];  // staged columns o .. o+8, centre o+4
@@ -990,6 +1101,16 @@ __global__ __launch_bounds__(MARCH_THREADS, 6) void k_march_refblur(MarchPlan pl
 // once per search: blur(ref*ref) of every scale into plan.ref_s11
 __global__ __launch_bounds__(MARCH_THREADS, 6) void k_ref_blur(MarchPlan plan) {
     march_body<MARCH_EMIT>(plan);
+}
+
+// The same two kernels for 16-bit frames: scale 0 comes from the linear planes k_pyramid_bands16 wrote
+// (ssimu2_score_rgb16, ssimu2_score_against_reference_rgb16 / _strided16).
+__global__ __launch_bounds__(MARCH_THREADS, 6) void k_march_lin(MarchPlan plan) {
+    march_body<MARCH_PAIR, true>(plan);
+}
+
+__global__ __launch_bounds__(MARCH_THREADS, 6) void k_march_refblur_lin(MarchPlan plan) {
+    march_body<MARCH_REFBLUR, true>(plan);
 }
 
 // error-map pass (ssimu2_error_map_*): per-pixel densities of every scale into plan.ref_s11.  Its own entry and

@@ -35,6 +35,30 @@ def _check_rgb8(a, name: str) -> np.ndarray:
     return a
 
 
+def _u16p(a: np.ndarray):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16))
+
+
+def _check_rgb16(a, name: str) -> np.ndarray:
+    """An (h, w, 3) uint16 array as the 16-bit calls take it (no silent conversion from another dtype)."""
+    a = np.asarray(a)
+    if a.dtype != np.uint16:
+        raise TypeError(f"{name} must be uint16 (16-bit samples), got {a.dtype}")
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"{name} must be (h, w, 3) uint16, got {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def linear_table(bit_depth: int) -> np.ndarray:
+    """ssimu2_linear_table: the 2^bit_depth-entry sRGB -> linear table the 16-bit calls read (host only, no device)."""
+    L = _lib.lib()
+    out = np.empty(1 << max(0, min(int(bit_depth), 16)), np.float32)
+    rc = L.ssimu2_linear_table(int(bit_depth), _f32p(out))
+    if rc != 0:
+        raise Ssimu2Error(rc, f"bit_depth {bit_depth} outside 8..16" if rc == _lib.ERR_UNSUPPORTED else "ssimu2_linear_table failed")
+    return out
+
+
 def query_device(device: int = 0, instrumented: bool = False) -> dict:
     """ssimu2_query_device: what the library reads off HIP device `device` without creating a context
     (`usable` False = ssimu2_ctx_create would refuse it: not gfx950, or less than 160 KB of LDS per CU)."""
@@ -265,6 +289,65 @@ class Ssimu2:
         ptr = ctypes.cast(ctypes.c_void_p(a.ctypes.data), ctypes.POINTER(ctypes.c_uint8))
         rc = self._L.ssimu2_score_against_reference_strided(self._ctx, ptr, int(row_bytes),
                                                             int(channels), ctypes.byref(out))
+        if rc != 0:
+            self._raise(rc)
+        return out.value
+
+    # -- 16-bit input (include/ssimu2_hip.h) --------------------------------
+    def compute_ssimu2_hbd(self, ref, dist, bit_depth: int) -> float:
+        """ssimu2_score_rgb16: (h, w, 3) uint16 frames of `bit_depth` (8..16) bits; samples above 2^d - 1 are clamped."""
+        ref = _check_rgb16(ref, "ref")
+        dist = _check_rgb16(dist, "dist")
+        if ref.shape != dist.shape:
+            raise ValueError("ref and dist must have the same shape")
+        h, w, _ = ref.shape
+        out = ctypes.c_double()
+        rc = self._L.ssimu2_score_rgb16(self._ctx, _u16p(ref), _u16p(dist), w, h, 3, int(bit_depth), ctypes.byref(out))
+        if rc != 0:
+            self._raise(rc)
+        return out.value
+
+    def set_reference_hbd(self, ref, bit_depth: int) -> None:
+        """ssimu2_set_reference_rgb16; later 8-bit and 16-bit frames can both be scored against it."""
+        ref = _check_rgb16(ref, "ref")
+        h, w, _ = ref.shape
+        rc = self._L.ssimu2_set_reference_rgb16(self._ctx, _u16p(ref), w, h, int(bit_depth))
+        if rc != 0:
+            self._raise(rc)
+        self._ref_shape = ref.shape
+
+    def score_against_reference_hbd(self, dist, bit_depth: int) -> float:
+        """ssimu2_score_against_reference_rgb16 against the reference of set_reference or set_reference_hbd."""
+        dist = _check_rgb16(dist, "dist")
+        if getattr(self, "_ref_shape", None) is not None and dist.shape != self._ref_shape:
+            raise ValueError("dist shape differs from the reference's")
+        out = ctypes.c_double()
+        rc = self._L.ssimu2_score_against_reference_rgb16(self._ctx, _u16p(dist), int(bit_depth), ctypes.byref(out))
+        if rc != 0:
+            self._raise(rc)
+        return out.value
+
+    def score_decoded_against_reference_hbd(self, rows, row_bytes: int | None = None, channels: int | None = None,
+                                            bit_depth: int = 16) -> float:
+        """ssimu2_score_against_reference_strided16: libavif's avifRGBImage at depth > 8 as it is -- an (h, w, 3|4)
+        uint16 array whose rows may be padded (pixels tightly packed within a row), or a flat uint16 buffer with
+        explicit `row_bytes` / `channels`.  Alpha and padding are skipped on the device."""
+        a = np.asarray(rows)
+        if a.dtype != np.uint16:
+            raise TypeError(f"rows must be uint16, got {a.dtype}")
+        if a.ndim == 3:
+            if a.strides[2] != 2 or a.strides[1] != 2 * a.shape[2]:
+                raise ValueError("pixels of a row must be tightly packed")
+            if getattr(self, "_ref_shape", None) is not None and a.shape[:2] != self._ref_shape[:2]:
+                raise ValueError("frame size differs from the reference's")
+            row_bytes = a.strides[0] if row_bytes is None else row_bytes
+            channels = a.shape[2] if channels is None else channels
+        elif row_bytes is None or channels is None:
+            raise ValueError("flat buffers need row_bytes and channels")
+        out = ctypes.c_double()
+        ptr = ctypes.cast(ctypes.c_void_p(a.ctypes.data), ctypes.POINTER(ctypes.c_uint16))
+        rc = self._L.ssimu2_score_against_reference_strided16(self._ctx, ptr, int(row_bytes), int(channels),
+                                                              int(bit_depth), ctypes.byref(out))
         if rc != 0:
             self._raise(rc)
         return out.value

@@ -202,15 +202,24 @@ def search_hip(scorer: Ssimu2, ref_rgb: np.ndarray,
 
 
 def search_hip_frames(scorer: Ssimu2, ref_rgb: np.ndarray, codec_frame, score_tgt: float = 80.0,
-                      tolerance: float = 2.0, max_pass: int = 6) -> TQResult:
+                      tolerance: float = 2.0, max_pass: int = 6, ref_bit_depth: int | None = None) -> TQResult:
     """The search with the decoded-frame hand-off: codec_frame(q) -> (frame, avif size)
     where `frame` is what decodeAvifCommon leaves behind (oavif_amd.avif_bridge.DecodedFrame: libavif's own
     8-bit RGB or RGBA rows, `rows` / `row_bytes` / `channels`, closed here after the score).  The rows go to
     the device as they are (`ssimu2_score_against_reference_strided`); the alpha-dropping copy loop of
     io.decodeAvifToRgb (io.zig:654-663) never runs on the host.  Same control flow, q and scores as
-    search_hip (the device unpacks to the same tight RGB8)."""
-    ref = np.ascontiguousarray(ref_rgb, dtype=np.uint8)
-    scorer.set_reference(ref)
+    search_hip (the device unpacks to the same tight RGB8).
+    A frame decoded at rgb_depth > 8 (avif_bridge.decode_common(data, rgb_depth)) is scored at that depth
+    (`ssimu2_score_against_reference_strided16`).  A uint16 `ref_rgb` is a high-bit-depth source and needs its
+    `ref_bit_depth` (8..16); the default, a uint8 source, is the reference's search exactly."""
+    if ref_bit_depth is None:
+        if np.asarray(ref_rgb).dtype == np.uint16:
+            raise ValueError("a uint16 ref_rgb needs ref_bit_depth")
+        ref = np.ascontiguousarray(ref_rgb, dtype=np.uint8)
+        scorer.set_reference(ref)
+    else:
+        ref = np.asarray(ref_rgb)
+        scorer.set_reference_hbd(ref, int(ref_bit_depth))
     last = {"size": 0}
 
     def probe(q: int) -> float:
@@ -218,7 +227,12 @@ def search_hip_frames(scorer: Ssimu2, ref_rgb: np.ndarray, codec_frame, score_tg
         try:
             if (frame.height, frame.width) != ref.shape[:2]:
                 raise ValueError(f"codec returned {frame.width}x{frame.height}, expected {ref.shape[1]}x{ref.shape[0]}")
-            score = scorer.score_decoded_against_reference(frame.rows.reshape(-1), frame.row_bytes, frame.channels)
+            depth = getattr(frame, "rgb_depth", 8)
+            if depth > 8:
+                score = scorer.score_decoded_against_reference_hbd(frame.rows.reshape(-1), frame.row_bytes,
+                                                                   frame.channels, depth)
+            else:
+                score = scorer.score_decoded_against_reference(frame.rows.reshape(-1), frame.row_bytes, frame.channels)
         finally:
             frame.close()
         last["size"] = int(size)

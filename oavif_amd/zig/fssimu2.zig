@@ -40,6 +40,8 @@ extern fn ssimu2_score_against_reference(ctx: ?*Ctx, dist: [*]const u8, out_scor
 extern fn ssimu2_error_map_rgb8(ctx: ?*Ctx, ref: [*]const u8, dist: [*]const u8, w: u32, h: u32, channels: u32, out_map: [*]f32, out_score: *f64) c_int;
 extern fn ssimu2_error_map_against_reference(ctx: ?*Ctx, dist: [*]const u8, out_map: [*]f32, out_score: *f64) c_int;
 extern fn ssimu2_score_against_reference_strided(ctx: ?*Ctx, pixels: [*]const u8, row_bytes: u32, channels: u32, out_score: *f64) c_int;
+extern fn ssimu2_score_rgb16(ctx: ?*Ctx, ref: [*]const u16, dist: [*]const u16, w: u32, h: u32, channels: u32, bit_depth: u32, out_score: *f64) c_int;
+extern fn ssimu2_score_against_reference_strided16(ctx: ?*Ctx, pixels: [*]const u16, row_bytes: u32, channels: u32, bit_depth: u32, out_score: *f64) c_int;
 extern fn ssimu2_host_alloc(ctx: ?*Ctx, bytes: usize, out_ptr: *?*anyopaque) c_int;
 extern fn ssimu2_host_free(ctx: ?*Ctx, ptr: ?*anyopaque) c_int;
 
@@ -290,5 +292,50 @@ pub fn computeSsimu2Decoded(
     }
     var score: f64 = 0;
     try check(ssimu2_score_against_reference_strided(ctx, pixels, row_bytes, src_channels, &score));
+    return score;
+}
+
+/// High-bit-depth pair score (include/ssimu2_hip.h, DESIGN.md section 10): `reference` and `distorted` are
+/// interleaved RGB u16 samples of `bit_depth` bits (8..16), as libavif's avifRGBImage holds them at depth > 8 and as
+/// a 16-bit PNG decodes.  Scored at full precision; a 16-bit frame of 257 * u gives the 8-bit score of u bit for bit.
+/// Not reference-cached (a pair call replaces the context's cached reference, so the next cached call re-uploads).
+pub fn computeSsimu2Hbd(
+    reference: []const u16,
+    distorted: []const u16,
+    width: u32,
+    height: u32,
+    bit_depth: u32,
+) Error!f64 {
+    const need: usize = @as(usize, width) * @as(usize, height) * 3;
+    if (reference.len < need or distorted.len < need) return Error.InvalidArgument;
+    const ctx = try context();
+    invalidateReference();
+    var score: f64 = 0;
+    try check(ssimu2_score_rgb16(ctx, reference.ptr, distorted.ptr, width, height, 3, bit_depth, &score));
+    return score;
+}
+
+/// The `--tenbit 1` hand-off (INTEGRATION.md section 2f): an 8-bit source `reference` against libavif's decode of a
+/// probe at rgb.depth = 16 (`pixels` = rgb.pixels as u16, `row_bytes` = rgb.rowBytes, `src_channels` = 3 or 4,
+/// `bit_depth` = rgb.depth), so that a 10-bit encode is judged at full precision instead of on an 8-bit rounding of
+/// itself.  The reference is cached as in computeSsimu2Decoded; alpha and row padding are skipped on the device.
+pub fn computeSsimu2DecodedHbd(
+    reference: []const u8,
+    pixels: [*]const u16,
+    row_bytes: u32,
+    src_channels: u32,
+    bit_depth: u32,
+    width: u32,
+    height: u32,
+) Error!f64 {
+    const need: usize = @as(usize, width) * @as(usize, height) * 3;
+    if (reference.len < need) return Error.InvalidArgument;
+    const ctx = try context();
+    if (!cache_reference or !sameReference(reference, width, height)) {
+        try check(ssimu2_set_reference(ctx, reference.ptr, width, height));
+        rememberReference(reference, width, height);
+    }
+    var score: f64 = 0;
+    try check(ssimu2_score_against_reference_strided16(ctx, pixels, row_bytes, src_channels, bit_depth, &score));
     return score;
 }
