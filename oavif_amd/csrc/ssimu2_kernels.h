@@ -660,17 +660,25 @@ __device__ __forceinline__ MarchCursor march_cursor(const void* base, int w, int
 // the load is unconditional: every row issues the same number of loads and the compiler's
 // s_waitcnt vmcnt(N) can count them -- a conditional load made it fall back to vmcnt(0), which
 // shortened the prefetch distance to one row).
+// Addressing: the row's address is uniform (scalar arithmetic) and the lane's 32-bit offset is added by
+// the load itself (global_load_dword v, v_off, s[base:base+1]): no VALU for the address.  The compiler
+// only selects that form when it sees the offset's zero extension in the load's own basic block; the
+// offset is loop-invariant, so without the empty asm it would hoist the extension out of the loop and
+// form every address with a 64-bit VALU add (v_lshl_add_u64 / v_mad_u64_u32).  The asm rewrites the
+// cursor's own offset (not a copy), so the register carried round the loop is its output: no v_mov.
 template <bool U8>
-__device__ __forceinline__ void march_load(uint32_t (&raw)[3], const MarchCursor& c, int row) {
+__device__ __forceinline__ void march_load(uint32_t (&raw)[3], MarchCursor& c, int row) {
     const uint8_t* p = c.base + (size_t)(uint32_t)row * (uint32_t)c.pitch;
+    asm volatile("" : "+v"(c.off));
+    const uint32_t off = c.off;
     if (U8) {
         uint32_t d;
-        __builtin_memcpy(&d, p + c.off, 4);
+        __builtin_memcpy(&d, p + off, 4);
         raw[0] = d;
     } else {
-        raw[0] = *(const uint32_t*)(p + c.off);
-        raw[1] = *(const uint32_t*)(p + c.plane + c.off);
-        raw[2] = *(const uint32_t*)(p + 2 * c.plane + c.off);
+        raw[0] = *(const uint32_t*)(p + off);
+        raw[1] = *(const uint32_t*)((p + c.plane) + off);
+        raw[2] = *(const uint32_t*)((p + 2 * c.plane) + off);
     }
 }
 
@@ -704,9 +712,9 @@ __device__ __forceinline__ void march_convert_rows(f2 (*ring)[3][MRW], const flo
     const bool col_ok = gx >= 0 && gx < w;
     const bool all_cols = x0 - RAD >= 0 && x0 - RAD + MRW <= w;  // uniform: no lane outside the image
     const int gxc = min(max(gx, 0), w - 1);  // clamped: the value is discarded when gx is outside
-    const MarchCursor c0 = CACHED ? march_cursor<false>(plan.ref_xyb[sc], w, h, gxc)
-                                  : march_cursor<U8>(plan.ref[sc], w, h, gxc);
-    const MarchCursor c1 = march_cursor<U8>(plan.dist[sc], w, h, gxc);
+    MarchCursor c0 = CACHED ? march_cursor<false>(plan.ref_xyb[sc], w, h, gxc)
+                            : march_cursor<U8>(plan.ref[sc], w, h, gxc);
+    MarchCursor c1 = march_cursor<U8>(plan.dist[sc], w, h, gxc);
     int load_row = y0 - RAD;  // image row of the next load
     // raw[f][j]: loaded, not yet converted row of frame f.  The queue is QD = 2 * GROUP rows deep
     // (the LUT reads of a row are requested one row before it is converted, so its pixels must
@@ -924,7 +932,9 @@ __device__ __forceinline__ void march_v(const lds_vu64* rp, float (&win)[5][9], 
     float d = 1.0f - div_rn(num_m * num_s, denom_s);
     d = fmaxf(d, 0.0f);
     const float ea = fabsf(r2 - mu2), eb = fabsf(r1 - mu1);
-    float e = div_rn(ea - eb, 1.0f + eb);  // == (1+ea)/(1+eb) - 1, no cancellation
+    // == (1+ea)/(1+eb) - 1, no cancellation.  One reciprocal times the difference (<= 1.5 ulp): the checker
+    // evaluates this map in fp64, so the correctly rounded fp32 quotient of div_rn bought no agreement.
+    float e = (ea - eb) * __builtin_amdgcn_rcpf(1.0f + eb);
     if (edge) {  // uniform; the asm keeps it a branch
         asm volatile("; right image edge");
         d = ok ? d : 0.0f;  // column inside the image?
@@ -1035,9 +1045,10 @@ __device__ __forceinline__ void march_body(const MarchPlan& plan, const MapCoef*
     // gets its own register allocation instead of carrying the other role's state.
     const int ngroups = (steps + GROUP - 1) / GROUP;
     if (is_conv) {
-        // The converter waves carry the heavier per-row stream on their SIMDs; a static
-        // issue-priority bump lets them keep pace (measured: -7 %).
-        __builtin_amdgcn_s_setprio(1);
+        // No issue-priority bump for the converter waves: s_setprio(1) once took 7 % off, but with the
+        // 64-bit address arithmetic gone from their rows it makes k_march 4 % slower
+        // (profiles/r07_march_ab.txt).  Waves 0-1 of the three workgroups of a CU already sit 2/2/1/1
+        // on its SIMDs (profiles/r07_placement.txt), so which wave converts is left as it is.
         const int col = (wave << 6) + lane;  // staged column; this lane converts both frames
         if (u8) march_convert_rows<true, MODE, LIN0>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col);
         else march_convert_rows<false, MODE, LIN0>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col);
