@@ -20,7 +20,11 @@ extern "C" {
 
 /* Parity hook: download one intermediate plane set of the last score / reference.
    `what`: SSIMU2_DEBUG_LIN_REF / _LIN_DIST = linear-light pyramid level `scale` (1..5) of the
-   reference / distorted frame, SSIMU2_DEBUG_XYB_REF = cached positive-XYB planes of the
+   reference / distorted frame; scale 0 of them only after a 16-bit call (ssimu2_*_rgb16 /
+   _strided16) in SSIMU2_BLUR_FIR: the frame's scale-0 linear planes, as the 16-bit front end
+   wrote them for the marching kernel, refused when the last score or reference did not write
+   them at this frame size (an 8-bit score, a recursive mode, a cached pass's reference set from
+   8-bit samples); SSIMU2_DEBUG_XYB_REF = cached positive-XYB planes of the
    reference at `scale` (0..5; needs ssimu2_set_reference), SSIMU2_DEBUG_REF_BLUR = the cached
    blur(ref*ref) planes of that reference (written by the marching body in emit mode: the blur
    waves' arithmetic, downloadable).  `out` receives 3 planes of w_s*h_s floats; returns

@@ -204,6 +204,11 @@ struct ssimu2_ctx {
     int seg_rows_tail_override = 0;
     bool cache_ref_blur = true;
     int rg_dbg_scale = -1;  // recursive mode: keep that scale's 15 raw planes (after each pass) downloadable
+#ifdef SSIMU2_INSTRUMENTED_BUILD
+    // the frame size whose scale-0 planes d_lin0_ref / d_lin0_dist hold for the last score or reference (0: none;
+    // for ssimu2_debug_download at scale 0)
+    uint32_t lin0_ref_w = 0, lin0_ref_h = 0, lin0_dist_w = 0, lin0_dist_h = 0;
+#endif
 
     int fail(int code, const char* what, hipError_t e = hipSuccess) {
         char buf[256];
@@ -248,6 +253,23 @@ inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, unsigned lds
     }
 #endif
     hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+}
+
+// Instrumented build: record whether d_lin0_ref / d_lin0_dist hold the w x h scale-0 planes of the last score or
+// reference (1: they do from now on, 0: they do not, -1: unchanged).  Nothing in the product library.
+inline void note_lin0(ssimu2_ctx* c, int ref, int dist, uint32_t w, uint32_t h) {
+#ifdef SSIMU2_INSTRUMENTED_BUILD
+    if (ref >= 0) {
+        c->lin0_ref_w = ref ? w : 0;
+        c->lin0_ref_h = ref ? h : 0;
+    }
+    if (dist >= 0) {
+        c->lin0_dist_w = dist ? w : 0;
+        c->lin0_dist_h = dist ? h : 0;
+    }
+#else
+    (void)c, (void)ref, (void)dist, (void)w, (void)h;
+#endif
 }
 
 struct Pyramid {
@@ -695,6 +717,7 @@ int enqueue_score(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, ui
                   bool ref_pyramid_ready) {
     const Pyramid p = make_pyramid(w, h);
     const bool recursive = c->blur_mode != SSIMU2_BLUR_FIR;
+    note_lin0(c, 0, 0, w, h);  // an 8-bit score: the 16-bit scale-0 planes are older than it
     if (recursive) {  // before anything is enqueued
         int rc = rg_check_size(c, w, h);
         if (rc) return rc;
@@ -767,6 +790,7 @@ int enqueue_score16(ssimu2_ctx* c, const Src16* ref, const Src16& dist, uint32_t
         lin[n] = c->d_lin_dist;
         lin0[n++] = (float*)c->d_lin0_dist;
         launch_pyramid16(c, p, n, src, lin, lin0);
+        if (p.nscales >= 1) note_lin0(c, ref ? 1 : -1, 1, w, h);
     }
     MarchPlan mp;
     FinalizeArgs fa;
@@ -844,6 +868,7 @@ int hbd_grow(ssimu2_ctx* c, void** p, size_t* cap, size_t bytes, const char* wha
 
 // Scale-0 linear planes for the frames of a FIR-mode 16-bit call (`ref`: the reference's too).
 int hbd_lin0(ssimu2_ctx* c, uint32_t w, uint32_t h, bool ref) {
+    note_lin0(c, ref ? 0 : -1, 0, w, h);  // the call may regrow or rewrite them: valid again once launched
     if (c->blur_mode != SSIMU2_BLUR_FIR) return SSIMU2_OK;
     const size_t bytes = (size_t)w * h * 3 * sizeof(float);
     int rc = hbd_grow(c, &c->d_lin0_dist, &c->cap_lin0_dist, bytes, "hipMalloc(16-bit scale-0 planes)");
@@ -1486,6 +1511,7 @@ static int set_reference_impl(ssimu2_ctx* c, const void* ref, uint32_t w, uint32
     }
     c->have_ref = false;
     c->ref_hbd = false;
+    note_lin0(c, 0, 0, w, h);
     const size_t bytes = (size_t)w * h * 3;
     HIP_TRY(c, hipMemcpyAsync(c->d_ref_u8, ref, bytes, kind, c->stream));
     if (p.nscales > 1 && c->blur_mode == SSIMU2_BLUR_FIR) {  // the reference's linear pyramid, once per search
@@ -1653,6 +1679,7 @@ int ssimu2_set_reference_rgb16(ssimu2_ctx* c, const uint16_t* ref, uint32_t w, u
         float* lin[1] = {c->d_lin_ref};
         float* lin0[1] = {(float*)c->d_lin0_ref};
         launch_pyramid16(c, p, 1, src, lin, lin0);
+        if (p.nscales >= 1) note_lin0(c, 1, -1, w, h);
         if ((rc = cache_reference_fir(c, p, c->d_lin0_ref, false, true))) return rc;
     } else {
         rg_enqueue_reference(c, p, nullptr, &r);

@@ -82,7 +82,15 @@ int ssimu2_debug_download(ssimu2_ctx* c, int what, int scale, uint32_t w, uint32
     if (w == 0 || h == 0) return c->fail(SSIMU2_ERR_INVALID_ARG, "zero image dimension");
     const Pyramid p = make_pyramid(w, h);
     const float* src = nullptr;
-    if (what == SSIMU2_DEBUG_LIN_REF || what == SSIMU2_DEBUG_LIN_DIST) {
+    if ((what == SSIMU2_DEBUG_LIN_REF || what == SSIMU2_DEBUG_LIN_DIST) && scale == 0) {
+        // a 16-bit FIR call's scale-0 linear planes (what k_march_lin reads), while they are the last score's
+        const bool r = what == SSIMU2_DEBUG_LIN_REF;
+        const void* planes = r ? c->d_lin0_ref : c->d_lin0_dist;
+        if (!planes || p.nscales < 1 || (r ? c->lin0_ref_w : c->lin0_dist_w) != w ||
+            (r ? c->lin0_ref_h : c->lin0_dist_h) != h)
+            return c->fail(SSIMU2_ERR_INVALID_ARG, "no 16-bit scale-0 planes of that frame from the last score");
+        src = (const float*)planes;
+    } else if (what == SSIMU2_DEBUG_LIN_REF || what == SSIMU2_DEBUG_LIN_DIST) {
         if (scale < 1 || scale >= p.nscales || !c->d_lin_ref) return c->fail(SSIMU2_ERR_INVALID_ARG, "no such level");
         src = (what == SSIMU2_DEBUG_LIN_REF ? c->d_lin_ref : c->d_lin_dist) + p.lin_off[scale];
     } else if (what == SSIMU2_DEBUG_XYB_REF) {

@@ -3,7 +3,9 @@
 `table(d)` restates the library's sRGB -> linear table of d-bit samples.  `compute` builds the scale-0 linear planes
 of two uint16 frames from it and follows tests/errmap_ref.py's route through the oracle's public helpers
 (downsample2, linear_to_xyb, the blur helpers, score_from_averages): the checker's arithmetic, fed 16-bit planes.
-`compute_fp64` is the counterpart in fp64 (tests/ssimu2_fp64.py's stages, linear values never rounded to fp32)."""
+`compute_fp64` is the counterpart in fp64 (tests/ssimu2_fp64.py's stages, linear values never rounded to fp32).
+`levels` / `reference_levels` are the per-scale planes of both routes, for the instrumented build's plane downloads, and
+`every_code_frame` is a frame that holds every 16-bit code once per channel."""
 from __future__ import annotations
 
 import numpy as np
@@ -29,6 +31,15 @@ def linear_planes(img: np.ndarray, d: int) -> np.ndarray:
     return table(d)[_clamped(img, d)].transpose(2, 0, 1).copy()
 
 
+def every_code_frame() -> np.ndarray:
+    """(256, 256, 3) uint16: each channel holds all 65,536 codes once, each channel in its own order (R in raster
+    order, G and B two fixed permutations), so that a pixel's three samples differ and no channel repeats another."""
+    v = np.arange(1 << 16, dtype=np.uint32)
+    g = (v * 40503 + 12345) & 0xFFFF                      # odd multiplier: a bijection of Z / 2^16
+    b = np.random.default_rng(1016).permutation(1 << 16)
+    return np.ascontiguousarray(np.stack([v, g, b], -1).astype(np.uint16).reshape(256, 256, 3))
+
+
 def _scales(orc, lin):
     out = []
     for s in range(6):
@@ -39,6 +50,12 @@ def _scales(orc, lin):
             lin = orc.downsample2(lin)
         out.append(lin)
     return out
+
+
+def levels(orc, img: np.ndarray, d: int) -> list:
+    """The checker's planes of a d-bit frame at every scale: [(linear (3, h_s, w_s), positive XYB)] (scale 0's linear
+    planes from `linear_planes`, then the checker's downsample2 and linear_to_xyb)."""
+    return [(lin, orc.linear_to_xyb(lin)) for lin in _scales(orc, linear_planes(img, d))]
 
 
 def terms(orc, lin1, lin2, blur):
@@ -81,11 +98,26 @@ def linear_planes_fp64(img: np.ndarray, d: int) -> np.ndarray:
                     ((v + ref64.SRGB_A) / (1.0 + ref64.SRGB_A)) ** ref64.SRGB_GAMMA)
 
 
-def compute_fp64(ref: np.ndarray, dist: np.ndarray, d: int) -> dict:
-    """ssimu2_fp64.evaluate for uint16 frames of d bits: {"score", "averages", "nscales", "weighted_sum"}."""
+def reference_levels(ref: np.ndarray, dist: np.ndarray, d: int, scales, d_dist: int | None = None) -> dict:
+    """fp64_checks.reference_levels for uint16 frames of d bits (`d_dist`: the distorted frame's own depth):
+    -> {scale: (lin1, lin2, xyb1, xyb2)} fp64 (3, h_s, w_s) planes at the scales asked for."""
+    out = {}
+    lin1 = linear_planes_fp64(ref, d)
+    lin2 = linear_planes_fp64(dist, d if d_dist is None else d_dist)
+    for s in range(max(scales) + 1):
+        if s:
+            lin1, lin2 = ref64.downsample2(lin1), ref64.downsample2(lin2)
+        if s in scales:
+            out[s] = (lin1, lin2, ref64.to_xyb(lin1), ref64.to_xyb(lin2))
+    return out
+
+
+def compute_fp64(ref: np.ndarray, dist: np.ndarray, d: int, d_dist: int | None = None) -> dict:
+    """ssimu2_fp64.evaluate for uint16 frames of d bits (`d_dist`: the distorted frame's own depth):
+    {"score", "averages", "nscales", "weighted_sum"}."""
     h, w, _ = ref.shape
     avg = np.zeros((ref64.NUM_SCALES, 18))
-    lin1, lin2 = linear_planes_fp64(ref, d), linear_planes_fp64(dist, d)
+    lin1, lin2 = linear_planes_fp64(ref, d), linear_planes_fp64(dist, d if d_dist is None else d_dist)
     ns = ref64.nscales_of(w, h)
     for s in range(ns):
         if s:

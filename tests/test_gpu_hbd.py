@@ -124,7 +124,7 @@ def test_genuine_high_bit_depth_content_against_the_checker(ctxs, oracle, mode):
 
 
 @pytest.mark.parametrize("mode", MODES)
-def test_mixed_depths(ctxs, mode):
+def test_mixed_depths(ctxs, oracle, mode):
     s = ctxs[mode]
     w, h = 333, 217
     ref8 = gpu_cases.content("text", w, h, seed=3)
@@ -144,13 +144,16 @@ def test_mixed_depths(ctxs, mode):
     for ch, pad in ((3, 0), (4, 8)):
         buf8, view8 = gpu_cases.decoded_like(d8, ch, pad, seed=2)
         assert_same(s, s.score_decoded_against_reference(view8), exp, (mode, "16-bit ref, 8-bit strided", ch))
-    # a 10-bit frame against a 12-bit reference equals the pair of both lifted to 16 bits only when the codes
-    # coincide; here just the pair call on the same depths through the cached path
+    # a 10-bit frame against a 12-bit reference: the checker and the fp64 counterpart read each frame at its own depth
     r12 = hbd_content("text", w, h, 12, seed=7)
     d10 = hbd_distort(hbd_content("text", w, h, 10, seed=7), 10, seed=8)
     s.set_reference_hbd(r12, 12)
     got = s.score_against_reference_hbd(d10, 10)
-    assert np.isfinite(got) and got < 100.0
+    avg, ns = s.last_averages()
+    exp, avg_r, ns_r = hbd_ref.compute(oracle, r12, d10, 12, gpu_cases.MODES[mode][1], d_dist=10)
+    assert ns == ns_r and abs(got - exp) <= gpu_cases.score_tol(exp), (mode, got, exp)
+    assert np.allclose(avg, avg_r, rtol=gpu_cases.RTOL_AVG, atol=gpu_cases.ATOL_AVG), mode
+    fp64_checks.check(got, avg, ns, hbd_ref.compute_fp64(r12, d10, 12, d_dist=10), mode, (mode, "12/10"), "synthetic")
     with pytest.raises(Ssimu2Error) as ei:
         s.error_map_against_reference(d8)
     assert ei.value.code == _lib.ERR_UNSUPPORTED

@@ -85,6 +85,61 @@ def test_fp64_counterpart_on_257u_frames():
     assert abs(got["score"] - exp["score"]) <= 1e-9
 
 
+def test_fp64_counterpart_with_the_frames_own_depth():
+    """compute_fp64(d_dist=d) is the call without it; another d_dist reads the frame, and only the frame, at that
+    depth."""
+    rng = np.random.default_rng(11)
+    ref = rng.integers(0, 1 << 12, (40, 56, 3)).astype(np.uint16)
+    dist = np.clip(ref.astype(np.int64) + rng.integers(-40, 41, ref.shape), 0, 4095).astype(np.uint16)
+    for d in (10, 12, 16):
+        a, b = hbd_ref.compute_fp64(ref, dist, d), hbd_ref.compute_fp64(ref, dist, d, d_dist=d)
+        assert a["score"] == b["score"] and a["nscales"] == b["nscales"]
+        assert np.array_equal(a["averages"], b["averages"]) and a["weighted_sum"] == b["weighted_sum"]
+    # an 8-bit reference u is the 16-bit reference 257 u (the same doubles), whatever the frame's own depth
+    r8 = (ref >> 4).astype(np.uint16)
+    mixed = hbd_ref.compute_fp64(r8, dist, 8, d_dist=12)
+    lifted = hbd_ref.compute_fp64(r8 * np.uint16(257), dist, 16, d_dist=12)
+    assert mixed["score"] == lifted["score"] and np.array_equal(mixed["averages"], lifted["averages"])
+    assert mixed["score"] != hbd_ref.compute_fp64(r8 * np.uint16(257), dist, 16)["score"]
+
+
+def test_uint16_levels_on_257u_frames_are_the_8bit_levels():
+    """hbd_ref.reference_levels of 257*u frames (and of depth-8 uint16 frames of u) = fp64_checks.reference_levels
+    of u, bit for bit; the checker-route levels equal the 8-bit pyramid of the oracle's table."""
+    import fp64_checks
+    from oracle import ssimu2_oracle as orc
+    ref, dist = _frames(67, 45, 3)
+    scales = list(range(ref64.nscales_of(67, 45)))
+    exp = fp64_checks.reference_levels(ref, dist, scales)
+    r16, d16 = ref.astype(np.uint16) * 257, dist.astype(np.uint16) * 257
+    for got in (hbd_ref.reference_levels(r16, d16, 16, scales),
+                hbd_ref.reference_levels(ref.astype(np.uint16), dist.astype(np.uint16), 8, scales),
+                hbd_ref.reference_levels(r16, dist.astype(np.uint16), 16, scales, d_dist=8)):
+        assert sorted(got) == scales
+        for s in scales:
+            for k in range(4):
+                assert got[s][k].dtype == np.float64 and np.array_equal(got[s][k], exp[s][k]), (s, k)
+    lin = np.ascontiguousarray(orc.srgb_lut()[ref].transpose(2, 0, 1))
+    lv = hbd_ref.levels(orc, r16, 16)
+    assert len(lv) == len(scales)
+    for s, (lin16, xyb16) in enumerate(lv):
+        if s:
+            lin = orc.downsample2(lin)
+        assert np.array_equal(lin16.view(np.uint32), lin.view(np.uint32)), s
+        assert np.array_equal(xyb16.view(np.uint32), orc.linear_to_xyb(lin).view(np.uint32)), s
+
+
+def test_every_code_frame_holds_each_code_once_per_channel():
+    f = hbd_ref.every_code_frame()
+    assert f.shape == (256, 256, 3) and f.dtype == np.uint16 and f.flags.c_contiguous
+    codes = np.arange(1 << 16)
+    for c in range(3):
+        assert np.array_equal(np.sort(f[..., c].reshape(-1)), codes), c
+    for a, b in ((0, 1), (0, 2), (1, 2)):   # three different orders
+        assert np.count_nonzero(f[..., a] == f[..., b]) < 64, (a, b)
+    assert np.array_equal(f, hbd_ref.every_code_frame())
+
+
 def test_clamping_in_the_reference():
     rng = np.random.default_rng(0)
     a = rng.integers(0, 65536, (16, 16, 3)).astype(np.uint16)
