@@ -1,6 +1,6 @@
 """Test-side helpers shared by the GPU modules: the blur-mode table (scorer mode -> the checker's mode of the same
-blur), synthetic content kinds, libavif-like padded RGB(A) layouts and the error-map check against
-tests/errmap_ref.py."""
+blur), synthetic content kinds, libavif-like padded RGB(A) layouts, the hold of a score's averages and of k_finalize
+to the kernel-order terms (check_against_terms) and the error-map check against tests/errmap_ref.py (check_map)."""
 from __future__ import annotations
 
 import numpy as np
@@ -70,17 +70,142 @@ def decoded_like(dist, channels, pad, seed):
     return buf, view
 
 
+# ---- the averages and k_finalize against the kernel-order terms (DESIGN.md sections 2.3 and 9) --------------------
+#
+# errmap_ref.kernel_averages(...) are the means, in fp64, of the very fp32 terms the score kernels sum: the terms are
+# computed from the checker's planes (which the kernels match bit for bit) by the kernels' expressions in their order.
+# What separates a device average from it is then only how the kernels add the terms up:
+#
+# * k_finalize: score = the published polynomial of sum_j w_j |avg_j| (oavif_amd/csrc/ssimu2_kernels.h).  Given the
+#   device's own averages, oracle.score_from_averages differs from it only in the order of that fp64 sum (a shuffle
+#   tree against a running sum: ~1e-16 relative) and in device against host pow(): FINALIZE_TOL.  No scale: 100 exactly.
+# * Recursive modes: k_rg_v sums each fp32 term converted to fp64 (rg_maps_pixel, ssimu2_recursive.h), per lane,
+#   then over lanes, waves and column groups, and k_finalize over the groups' partials, all in fp64; the reference
+#   takes the mean in extended precision.  A sum of n non-negative values in fp64, in any order, is within (n - 1) *
+#   2^-53 of the exact sum, relatively; the division by the pixel count and the two square roots of an L4 norm add a
+#   few units of 2^-53 (a 4th root divides a relative error by 4).  n <= 3840 * 2160 = 8.3 M terms per average gives
+#   8.3e6 * 2^-53 = 9.2e-10 < RTOL_RECURSIVE = 1e-9.  An average is 0 exactly where all its terms are.
+# * FIR: k_march sums each term in fp32 per lane down the rows of its segment (at most march_seg_rows rows), then in
+#   fp64 (march_body).  A sum of `seg` non-negative fp32 values is within (seg - 1) * 2^-24 of the exact one.  The
+#   edge quotient is (ea - eb) * rcp(1 + eb) (march_v): rcp within 1 ulp (2^-23 relative) and the product rounded
+#   (2^-24), against the correctly rounded quotient of the reference (2^-24): art and det within 4 * 2^-24, their 4th
+#   powers within 4 * 4 + 3 + 3 = 22 units (two squarings on each side), 22 / 4 = 5.5 units after an L4 norm's 4th
+#   root.  d and d^4 are the reference's bits.  Per average: (seg - 1 + 4) * 2^-24 for an L1 statistic,
+#   (seg - 1 + 22) / 4 * 2^-24 <= (seg + 3) * 2^-24 for an L4 one (seg >= 8); plus the fp64 part, n * 2^-53.
+FINALIZE_TOL = 1e-11
+RTOL_RECURSIVE = 1e-9
+MAX_TERMS = 3840 * 2160
+MW = 120   # output columns per k_march strip (ssimu2_kernels.h)
+
+
+def march_seg_rows(w: int, h: int, scale: int) -> int:
+    """Rows per k_march workgroup at `scale` of a w x h frame: march_seg_rows in oavif_amd/csrc/ssimu2_hip.hip (no
+    ssimu2_instr_set_segment_rows override): ~512 workgroups at full resolution, 8..160 rows, at most 48 below it."""
+    nstrips = (w + MW - 1) // MW
+    nsegs = max(1, (512 + nstrips // 2) // nstrips)
+    seg = min(max((h + nsegs - 1) // nsegs, 8), 160)
+    return min(seg, 48) if scale > 0 else seg
+
+
+def fir_rtol(w: int, h: int, scale: int) -> float:
+    """The bound of a FIR average at `scale` against the kernel-order terms (derivation above)."""
+    sw, sh = w, h
+    for _ in range(scale):
+        sw, sh = (sw + 1) // 2, (sh + 1) // 2
+    return (march_seg_rows(w, h, scale) + 3) * 2.0 ** -24 + sw * sh * 2.0 ** -53
+
+
+def check_against_terms(oracle, score, avg, ns, ref, dist, mode, what, kavg=None):
+    """A device score of (ref, dist) in scorer mode `mode` (a key of MODES), its averages `avg` over `ns` scales:
+    k_finalize against oracle.score_from_averages(avg) to FINALIZE_TOL, and every average against
+    errmap_ref.kernel_averages (or `kavg`, the same computed by the caller) to RTOL_RECURSIVE in the recursive modes,
+    fir_rtol in FIR, exactly 0 where the reference is 0.  -> the largest deviation of an average in units of its bound
+    (0 without a scale)."""
+    h, w, _ = ref.shape
+    assert w * h <= MAX_TERMS, what
+    if ns == 0:
+        assert score == 100.0 and not avg.any(), what
+        return 0.0
+    host = oracle.score_from_averages(avg, ns)
+    assert abs(score - host) <= FINALIZE_TOL, (what, score, host)
+    if kavg is None:
+        kavg, ns_r = errmap_ref.kernel_averages(oracle, ref, dist, MODES[mode][1])
+        assert ns_r == ns, what
+    assert avg.shape == kavg.shape == (6, 18), what
+    worst = 0.0
+    for s in range(6):
+        got, exp = avg[s], kavg[s]
+        assert np.array_equal(got == 0, exp == 0), (what, s, got, exp)
+        if s >= ns:
+            continue
+        rtol = RTOL_RECURSIVE if mode != "fir" else fir_rtol(w, h, s)
+        dev = np.abs(got - exp) / np.where(exp == 0, 1.0, exp)
+        assert (dev <= rtol).all(), (what, s, int(np.argmax(dev)), float(dev.max()), rtol)
+        worst = max(worst, float(dev.max()) / rtol)
+    print(f"measured: {what}: averages {worst:.3e} of the bound, finalize "
+          f"{abs(score - host):.1e}")
+    return worst
+
+
+# ---- the error map -----------------------------------------------------------------------------------------------
+#
+# Recursive modes: k_rg_vmap forms the reference's terms (rg_map_terms: div_rn for both quotients), map_density and
+# k_map_compose restate compose()'s order, and the coefficients are the host's: the map equals the reference bit for
+# bit.  FIR: k_march_map shares march_v's edge quotient, (ea - eb) * rcp(1 + eb).  All terms and coefficients are
+# non-negative, so relative errors add without cancellation, per pixel, in units of 2^-24:
+#   art, det            4   (rcp 1 ulp = 2 units, the product 1, the reference's quotient 1)
+#   art^4, det^4       22   (4 * 4, and two squarings on each side)
+#   density chain      12   (one product and five FMAs, 6 roundings on each side)
+#   channel sum         4   ((X + Y) + B: 2 roundings on each side)
+#   sum over scales    10   (up to 6 scales: 5 roundings on each side)
+# K = 48: every FIR pixel within K * 2^-24 of the reference's value (2^-126 below the normal range), and 0 exactly
+# where the reference is 0.
+MAP_K = 48
+
+
 def check_map(oracle, m, avg, ns, ref, dist, blur, what):
     """The device map `m` of (ref, dist), whose score left averages `avg` over `ns` scales, against the numpy
-    reference in the checker's mode `blur`: per pixel to PIXEL_RTOL of the map's peak, the mean to MEAN_RTOL."""
-    exp, _own, ns_r = errmap_ref.reference_map(oracle, ref, dist, blur, avg=avg)
+    reference in the checker's mode `blur`: bit for bit in the recursive modes; in FIR per pixel within
+    MAP_K * 2^-24 of the reference pixel, and 0 where it is 0; the mean to MEAN_RTOL.  -> the FIR map's largest
+    relative deviation in units of 2^-24 (0 in the recursive modes) and the averages of the reference's terms (those
+    of errmap_ref.kernel_averages, for check_against_terms)."""
+    exp, own, ns_r = errmap_ref.reference_map(oracle, ref, dist, blur, avg=avg)
     assert ns == ns_r and m.shape == exp.shape and m.dtype == np.float32, what
-    peak = float(exp.max())
-    err = float(np.abs(m.astype(np.float64) - exp).max())
     mean_e = exp.mean(dtype=np.float64)
     rel_mean = abs(m.mean(dtype=np.float64) - mean_e) / max(mean_e, 1e-30)
-    assert err <= errmap_ref.PIXEL_RTOL * peak, (what, err, peak)
     assert rel_mean <= errmap_ref.MEAN_RTOL, (what, rel_mean)
+    if blur != oracle.BLUR_FIR:
+        bad = m.view(np.uint32) != exp.view(np.uint32)
+        assert not bad.any(), (what, int(bad.sum()), np.argwhere(bad)[:4].tolist())
+        return 0.0, own
+    assert np.array_equal(m == 0, exp == 0), (what, int(np.sum((m == 0) != (exp == 0))))
+    units = np.abs(m.astype(np.float64) - exp) / np.maximum(exp.astype(np.float64), 2.0 ** -126) * 2.0 ** 24
+    worst = float(units.max()) if units.size else 0.0
+    assert worst <= MAP_K, (what, worst, np.unravel_index(int(np.argmax(units)), units.shape))
+    print(f"measured: {what}: FIR map {worst:.2f} units of 2^-24 (K = {MAP_K})")
+    return worst, own
+
+
+def same_bits(got, exp, what):
+    assert got.shape == exp.shape and got.dtype == exp.dtype == np.float32, (what, got.shape, exp.shape)
+    assert np.array_equal(got.view(np.uint32), exp.view(np.uint32)), what
+
+
+def rg_planes(oracle, blur, xa, xb):
+    """The 15 planes (5 * channel + {x, y, xx, yy, xy}) of the checker's recursion over two XYB plane sets."""
+    out = []
+    for c in range(3):
+        a, b = xa[c], xb[c]
+        out += [oracle.blur_plane(src, blur) for src in (a, b, a * a, b * b, a * b)]
+    return out
+
+
+def check_rg(s, oracle, blur, scale, w, h, xa, xb, what):
+    """The instrumented build's planes after both recursive passes at `scale` (ssimu2_debug_download RG_V = 5) against
+    the checker's recursion in mode `blur` over the XYB planes xa (reference) and xb, bit for bit."""
+    got = s.debug_download(5, scale, w, h)
+    for k, exp in enumerate(rg_planes(oracle, blur, xa, xb)):
+        same_bits(got[k], exp, what + (scale, k))
 
 
 def pseudo_codec(ref):

@@ -60,27 +60,9 @@ def levels(orc, img: np.ndarray, d: int) -> list:
 
 def terms(orc, lin1, lin2, blur):
     """errmap_ref.terms from linear planes instead of 8-bit frames."""
-    res = []
-    for l1, l2 in zip(_scales(orc, lin1), _scales(orc, lin2)):
-        x1, x2 = orc.linear_to_xyb(l1), orc.linear_to_xyb(l2)
-        t = np.zeros((3, 6) + x1.shape[1:], np.float32)
-        for c in range(3):
-            a, b = x1[c], x2[c]
-            mu1, mu2 = orc.blur_plane(a, blur), orc.blur_plane(b, blur)
-            s11, s22, s12 = orc.blur_product(a, a, blur), orc.blur_product(b, b, blur), orc.blur_product(a, b, blur)
-            mu11, mu22, mu12 = mu1 * mu1, mu2 * mu2, mu1 * mu2
-            dm = mu1 - mu2
-            num_m = errmap_ref._fma(-dm, dm, 1.0)
-            num_s = errmap_ref._fma(np.float32(2.0), s12 - mu12, errmap_ref.C2)
-            denom_s = ((s11 - mu11) + (s22 - mu22)) + errmap_ref.C2
-            d = np.maximum(np.float32(1.0) - (num_m * num_s) / denom_s, np.float32(0.0))
-            ea, eb = np.abs(b - mu2), np.abs(a - mu1)
-            e = (ea - eb) / (np.float32(1.0) + eb)
-            art, det = np.maximum(e, np.float32(0.0)), np.maximum(-e, np.float32(0.0))
-            d2, a2, t2 = d * d, art * art, det * det
-            t[c] = np.stack([d, d2 * d2, art, a2 * a2, det, t2 * t2])
-        res.append(t)
-    return res
+    return [np.stack([errmap_ref.channel_terms(orc, x1[c], x2[c], blur) for c in range(3)])
+            for x1, x2 in ((orc.linear_to_xyb(l1), orc.linear_to_xyb(l2))
+                           for l1, l2 in zip(_scales(orc, lin1), _scales(orc, lin2)))]
 
 
 def compute(orc, ref: np.ndarray, dist: np.ndarray, d: int, blur: int, d_dist: int | None = None):

@@ -5,6 +5,7 @@ import os
 import re
 import subprocess
 import sys
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -37,6 +38,94 @@ def test_reference_map_of_identical_frames_is_zero(oracle):
     ref = synth.make_ref(40, 24, seed=3)
     m, _own, ns = errmap_ref.reference_map(oracle, ref, ref, oracle.BLUR_FIR)
     assert ns == 3 and not m.any()
+
+
+def _rn32(x: Fraction) -> np.float32:
+    """x correctly rounded to fp32 (to nearest, ties to even), by exact comparison with the neighbours of a value
+    at most one fp32 ulp from it."""
+    f = np.float32(float(x))
+    cands = [np.nextafter(f, np.float32(-np.inf)), f, np.nextafter(f, np.float32(np.inf))]
+    return min(cands, key=lambda v: (abs(Fraction(float(v)) - x), int(np.array(v).view(np.uint32)) & 1))
+
+
+def _exact_fma(a, b, c) -> np.float32:
+    return _rn32(Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c)))
+
+
+def test_fma_is_correctly_rounded_on_random_operands():
+    """errmap_ref._fma against exact rational arithmetic: operands over 2^-30..2^30 of both signs, and sums that
+    cancel (c near -a * b), where most of the product's bits decide the result."""
+    rng = np.random.default_rng(2024)
+    n = 3000
+
+    def f32(k, lo, hi):
+        m = rng.uniform(1.0, 2.0, k) * rng.choice([-1.0, 1.0], k)
+        return (m * np.exp2(rng.integers(lo, hi, k).astype(np.float64))).astype(np.float32)
+
+    a, b, c = f32(n, -15, 15), f32(n, -15, 15), f32(n, -30, 30)
+    c[: n // 3] = -(a[: n // 3].astype(np.float64) * b[: n // 3]).astype(np.float32)   # cancellation
+    c[n // 3: n // 2] = np.nextafter(c[: n // 6], np.float32(np.inf))
+    got = errmap_ref._fma(a, b, c)
+    exp = np.array([_exact_fma(x, y, z) for x, y, z in zip(a, b, c)], np.float32)
+    assert np.array_equal(got, exp), int(np.sum(got != exp))
+    assert errmap_ref._fma(np.float32(-0.75), np.float32(0.75), 1.0) == np.float32(0.4375)
+
+
+def _double_rounding_cases():
+    """(a, b, c = 1) with a * b = t (1 + r), t = 2^-24 or 3 * 2^-24 and 0 < |r| * t < 2^-53: the exact sum lies within
+    half an fp64 ulp of the fp32 halfway point 1 + t, so rounding it to fp64 lands on that point and the tie then goes
+    to the even neighbour, which is the wrong one when r has the sign that moves the sum away from it."""
+    out = []
+    for t, sign in ((2.0 ** -24, 1), (3 * 2.0 ** -24, -1)):
+        for k in range(1, 1 << 16):
+            a = np.float32(1.0 + k * 2.0 ** -23)
+            b = np.float32(t / float(a))
+            r = Fraction(float(a)) * Fraction(float(b)) / Fraction(t) - 1
+            if r != 0 and (r > 0) == (sign > 0) and abs(r) * Fraction(t) < Fraction(1, 2 ** 53):
+                out.append((a, b, np.float32(1.0)))
+                if len(out) % 8 == 0:
+                    break
+    return out
+
+
+def test_fma_rounds_once_where_rounding_through_fp64_rounds_twice():
+    cases = _double_rounding_cases()
+    assert len(cases) == 16
+    for a, b, c in cases:
+        twice = np.float32(float(a) * float(b) + float(c))   # the fp64 sum, then fp32: two roundings
+        exact = _exact_fma(a, b, c)
+        assert twice != exact, (a, b)
+        assert errmap_ref._fma(a, b, c) == exact, (a, b)
+        assert errmap_ref._fma(np.array([a]), np.array([b]), np.array([c]))[0] == exact
+
+
+def test_coefficients_restate_the_hosts_expression(oracle):
+    """map_coefficients (ssimu2_hip.hip): w, or w / (a * a * a) in fp64 clamped at 3e38 and rounded once to fp32,
+    0 when a == 0 -- against exact rationals of the same fp64 steps, at a == 0, around the clamp and where the cube
+    underflows (the quotient is inf there, then 3e38)."""
+    wts = oracle.weights()
+    walk, _ = errmap_ref.weighted_terms(oracle, np.zeros((6, 18)), 6)
+    w = max(wt for wt, _s, st in walk if st % 2 == 1 and wt > 0)
+    clamp_a = (w / 3.0e38) ** (1.0 / 3.0)          # the L4 average whose coefficient is the clamp
+    for a in [0.0, 1e-200, 1e-110, 1e-105, clamp_a * (1 - 1e-9), clamp_a, clamp_a * (1 + 1e-9), clamp_a * 1.01,
+              1e-3, 0.0123456789, 0.5, 1.0]:
+        got = errmap_ref.coefficient(w, a, True)
+        if a == 0.0:
+            exp = np.float32(0.0)
+        else:
+            a3 = Fraction(float(Fraction(a) * Fraction(a))) * Fraction(a)
+            a3 = float(a3) if a3 else 0.0
+            q = float(Fraction(w) / Fraction(a3)) if a3 and Fraction(w) / Fraction(a3) < 2 ** 1024 else np.inf
+            exp = _rn32(Fraction(min(q, 3.0e38)))
+        assert got == exp and got.dtype == np.float32, (a, got, exp)
+        assert errmap_ref.coefficient(w, a, False) == np.float32(w)
+    assert errmap_ref.coefficient(w, 1e-110, True) == np.float32(3.0e38)
+    (w0, s0, st0), (w1, s1, st1) = [(wt, sc, st) for wt, sc, st in walk if st % 2 == 1 and wt > 0][:2]
+    avg = np.full((6, 18), 0.25)
+    avg[s0, st0], avg[s1, st1] = 0.0, 1e-110
+    coef = errmap_ref.coefficients(oracle, avg, 6)
+    assert coef.dtype == np.float32 and coef[s0, st0] == 0.0 and coef[s1, st1] == np.float32(3.0e38)
+    assert coef[0, 0] == np.float32(wts[0]) and coef[0, 1] == np.float32(wts[3] / (0.25 * 0.25 * 0.25))
 
 
 def test_header_declares_both_entry_points():

@@ -12,13 +12,12 @@ from oracle import ssimu2_oracle as orc
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import errmap_ref  # noqa: E402
+import gpu_cases  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 MODES = {"fir": (_lib.BLUR_FIR, orc.BLUR_FIR), "recursive": (_lib.BLUR_RECURSIVE, orc.BLUR_IIR),
          "recursive_fma": (_lib.BLUR_RECURSIVE_FMA, orc.BLUR_IIR_FMA)}   # (scorer mode, oracle BLUR_*)
-# per-pixel bound relative to the map's maximum, and the bound on the relative error of the mean
-PIXEL_RTOL, MEAN_RTOL = errmap_ref.PIXEL_RTOL, errmap_ref.MEAN_RTOL
 
 
 @pytest.fixture(scope="module", params=sorted(MODES))
@@ -30,16 +29,13 @@ def mode(request, hip_lib):
 
 
 def _check_against_reference(oracle, s, blur, ref, dist, what):
+    """The map pixel by pixel (gpu_cases.check_map: bit for bit in the recursive modes, within MAP_K * 2^-24 in FIR),
+    its mean, and the score's averages and k_finalize against the same terms (gpu_cases.check_against_terms)."""
     score, m = s.error_map(ref, dist)
     avg, ns = s.last_averages()
-    exp, _own, ns_r = errmap_ref.reference_map(oracle, ref, dist, blur, avg=avg)
-    assert ns == ns_r and m.shape == exp.shape and m.dtype == np.float32
-    peak = float(exp.max())
-    err = float(np.abs(m.astype(np.float64) - exp).max())
-    rel_mean = abs(m.mean(dtype=np.float64) - exp.mean(dtype=np.float64)) / max(exp.mean(dtype=np.float64), 1e-30)
-    print(f"{what}: max|d| / max(map) = {err / max(peak, 1e-30):.3e}, mean rel = {rel_mean:.3e}")
-    assert err <= PIXEL_RTOL * peak, (what, err, peak)
-    assert rel_mean <= MEAN_RTOL, (what, rel_mean)
+    mode = next(k for k, v in MODES.items() if v[1] == blur)
+    _worst, own = gpu_cases.check_map(oracle, m, avg, ns, ref, dist, blur, what)
+    gpu_cases.check_against_terms(oracle, score, avg, ns, ref, dist, mode, what, kavg=own)
     return score, m
 
 

@@ -14,6 +14,7 @@ import fp64_checks as fc
 import gpu_cases
 import hbd_ref
 import ssimu2_fp64 as R
+from gpu_cases import check_rg, same_bits
 from oavif_amd import Ssimu2, Ssimu2Error, _lib, synth
 
 pytestmark = pytest.mark.gpu
@@ -49,11 +50,6 @@ def ctxs(hip_lib):
         s.close()
 
 
-def same_bits(got, exp, what):
-    assert got.shape == exp.shape and got.dtype == exp.dtype == np.float32, (what, got.shape, exp.shape)
-    assert np.array_equal(got.view(np.uint32), exp.view(np.uint32)), what
-
-
 def lift(u8):
     """8-bit samples u as the 16-bit samples 257 u (the same normalised values), one allocation."""
     return np.multiply(u8, np.uint16(257), dtype=np.uint16)
@@ -81,21 +77,6 @@ def rows16(img, channels, pad, fill):
     view = np.lib.stride_tricks.as_strided(buf, (h, w, channels), (pitch * 2, channels * 2, 2))
     view[..., :3] = img
     return buf, view
-
-
-def rg_planes(orc, blur, xa, xb):
-    """The 15 planes (5 * channel + {x, y, xx, yy, xy}) of the checker's recursion over two XYB plane sets."""
-    out = []
-    for c in range(3):
-        a, b = xa[c], xb[c]
-        out += [orc.blur_plane(src, blur) for src in (a, b, a * a, b * b, a * b)]
-    return out
-
-
-def check_rg(s, orc, blur, scale, w, h, xa, xb, what):
-    got = s.debug_download(RG_V, scale, w, h)
-    for k, exp in enumerate(rg_planes(orc, blur, xa, xb)):
-        same_bits(got[k], exp, what + (scale, k))
 
 
 def scrub(s, ref, bits=None):

@@ -9,8 +9,11 @@ score's bits.  Then extreme frames and content kinds, production-sized frames th
 fan-out over contexts, and one long-lived context driven through sizes, modes and entry points against fresh
 contexts.
 
-Tolerances are those of tests/test_gpu_recursive.py (score 1e-4, relative beyond 100 points; averages rtol 2e-5),
-5e-4 for frames that score far below 0 (test_extreme_frames), and the error map's PIXEL_RTOL / MEAN_RTOL.
+Tolerances against the checker are those of tests/test_gpu_recursive.py (score 1e-4, relative beyond 100 points;
+averages rtol 2e-5) and 5e-4 for frames that score far below 0 (test_extreme_frames).  Beyond them the pair scores are
+held to the kernel-order terms (gpu_cases.check_against_terms: k_finalize to 1e-11, the averages to 1e-9 in the
+recursive modes and to the FIR sums' derived bound), at production size too, and the error map pixel by pixel
+(gpu_cases.check_map: bit for bit in the recursive modes, MAP_K * 2^-24 in FIR).
 """
 import json
 import os
@@ -23,8 +26,8 @@ import pytest
 from oavif_amd import _lib, synth
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from gpu_cases import (ATOL_AVG, MODES, RTOL_AVG, SIZES, TOL_FAR_BELOW_ZERO, check_map, content,  # noqa: E402
-                       decoded_like, pseudo_codec, score_tol)
+from gpu_cases import (ATOL_AVG, MODES, RTOL_AVG, SIZES, TOL_FAR_BELOW_ZERO, check_against_terms,  # noqa: E402
+                       check_map, content, decoded_like, pseudo_codec, score_tol)
 
 pytestmark = pytest.mark.gpu
 
@@ -111,7 +114,8 @@ def test_every_entry_point_matches_the_checker(ctxs, oracle, mode, w, h):
     ref_score, ref_map = s.error_map_against_reference(dist)
     same("error_map_against_reference", ref_score)
     assert np.array_equal(ref_map.view(np.uint32), pair_map.view(np.uint32))
-    check_map(oracle, pair_map, avg, ns, ref, dist, MODES[mode][1], f"{mode} {w}x{h}")
+    _worst, own = check_map(oracle, pair_map, avg, ns, ref, dist, MODES[mode][1], f"{mode} {w}x{h}")
+    check_against_terms(oracle, got, avg, ns, ref, dist, mode, f"{mode} {w}x{h}", kavg=own)
     if min(w, h) < 8:   # no scale to score
         assert got == 100.0 and not pair_map.any()
 
@@ -155,10 +159,25 @@ def test_extreme_frames_and_content_in_the_recursive_modes(ctxs, oracle, mode, g
         exp, avg_o, ns_o = _checker(oracle, mode, (group, i), ref, dist)
         tol = TOL_FAR_BELOW_ZERO if exp < 0 else score_tol(exp)
         _check_score(got, avg, ns, exp, avg_o, ns_o, f"{mode} {group} {i}", tol)
+        check_against_terms(oracle, got, avg, ns, ref, dist, mode, f"{mode} {group} {i}")
         if np.array_equal(ref, dist):
             assert got == 100.0
         s.set_reference(ref)
         assert _bits(s.score_against_reference(dist)) == _bits(got)
+
+
+@pytest.mark.parametrize("mode", ["recursive", "fir"])
+def test_a_4k_pair_against_the_kernel_order_terms(ctxs, oracle, mode):
+    """One 3840 x 2160 pair in the search default and in FIR: the averages over 8.3 M terms per statistic within
+    RTOL_RECURSIVE (the whole fp64 summation bound) or the FIR sums' bound at a 135-row segment, k_finalize to
+    FINALIZE_TOL."""
+    s = ctxs[mode]
+    ref = synth.make_ref(3840, 2160, seed=21)
+    dist = synth.distort(ref, "blockq", 2, seed=22)
+    got = s.compute_ssimu2(ref, dist)
+    avg, ns = s.last_averages()
+    assert ns == 6
+    check_against_terms(oracle, got, avg, ns, ref, dist, mode, f"{mode} 3840x2160")
 
 
 # ---- 3. frames shaped like production: RGBA rows against a cached reference --------------------------------------
