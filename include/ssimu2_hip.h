@@ -271,6 +271,48 @@ int ssimu2_score_against_reference_rgb16(ssimu2_ctx* ctx, const uint16_t* dist, 
 int ssimu2_score_against_reference_strided16(ssimu2_ctx* ctx, const uint16_t* pixels, uint32_t row_bytes,
                                              uint32_t channels, uint32_t bit_depth, double* out_score);
 
+/* Batch scoring: n pairs of ONE size w x h in one launch set -- one pyramid launch, one marching
+   launch and one finalize launch whatever n is, on one context, one stream and one set of scratch.  Meant for corpora
+   of small frames (thumbnails, tiles, video frames), where a single score cannot fill the GPU, and for several probes
+   of one image against one cached reference.  8-bit RGB, SSIMU2_BLUR_FIR only.
+     ssimu2_score_batch_rgb8                 refs[i] / dists[i]: n host frames each (tight RGB8, as ssimu2_score_rgb8);
+     ssimu2_score_batch_against_reference    dists[i] against the reference of ssimu2_set_reference (kept cached);
+     ..._device                              the frames already on the context's device: item i at
+                                             d_refs + i * item_stride_bytes and d_dists + i * item_stride_bytes.
+   out_scores receives n doubles in input order; ssimu2_last_batch_averages returns the 108 averages of one item of the
+   last finished batch (layout of ssimu2_last_averages).  Blocking: the uploads of the host-pointer forms go through
+   the context's stream, the three launches follow, one synchronise per batch.
+   What an item scores does not depend on the batch: n, the item's place and its neighbours never enter its arithmetic.
+   The marching kernel's segment length -- which fixes how the fp32 partial sums of an average are grouped -- is a
+   function of (w, h, scale) alone: 96 rows at full resolution, 48 below it, where a single score cuts full
+   resolution into about 512 workgroups.  So a batch score has the bits of a single score taken at the same segment
+   rows, and differs from the default ssimu2_score_rgb8 of the same pair only by that regrouping: each average within
+   (rows + 3) * 2^-24 relative of the exact mean of its terms, as the single score is with its own rows (so at most
+   1.6e-5 relative between the two; measured below 1e-6 score points on the test pairs).  The pair form and the cached-reference form give the
+   same bits.
+   Contract: n == 0 is SSIMU2_OK and touches nothing (no pointer is read, no state changes).  SSIMU2_ERR_INVALID_ARG:
+   a null array, a null item, null out_scores, a zero dimension, item_stride_bytes < 3 * w * h, n > SSIMU2_MAX_BATCH
+   (split the work), or a frame so large that n items exceed one launch's grid.  SSIMU2_ERR_UNSUPPORTED with the
+   context in SSIMU2_BLUR_RECURSIVE / _FMA (the message names ssimu2_ctx_set_blur; those modes score pair by pair).
+   SSIMU2_ERR_NO_REFERENCE for ..._against_reference without a reference.  SSIMU2_ERR_OOM when the batch's scratch
+   cannot grow: the context stays usable, a smaller batch may fit.  Frames too small for any scale (below 8 x 8) score
+   100.0 with zero averages.  A batch call leaves the blur mode, a cached reference (the pair form too: it has scratch
+   of its own, unlike ssimu2_score_rgb8), the result of ssimu2_last_averages and the bits of every later single score
+   and error map of the context as they were.
+   Device memory, allocated by the first batch call and grown on demand, freed by ssimu2_ctx_destroy: per item
+   8 bytes per pixel of linear pyramids (4 in the cached-reference form), the partial sums, and in the host-pointer
+   forms the staged frames (6 bytes per pixel; 3 against a reference); 880 bytes of page-locked host memory per item. */
+#define SSIMU2_MAX_BATCH 4096
+int ssimu2_score_batch_rgb8(ssimu2_ctx* ctx, const uint8_t* const* refs, const uint8_t* const* dists, uint32_t n,
+                            uint32_t w, uint32_t h, double* out_scores);
+int ssimu2_score_batch_against_reference(ssimu2_ctx* ctx, const uint8_t* const* dists, uint32_t n, double* out_scores);
+int ssimu2_score_batch_rgb8_device(ssimu2_ctx* ctx, const void* d_refs, const void* d_dists, size_t item_stride_bytes,
+                                   uint32_t n, uint32_t w, uint32_t h, double* out_scores);
+int ssimu2_score_batch_against_reference_device(ssimu2_ctx* ctx, const void* d_dists, size_t item_stride_bytes,
+                                                uint32_t n, double* out_scores);
+int ssimu2_last_batch_averages(ssimu2_ctx* ctx, uint32_t item, double out[SSIMU2_NUM_SCALES * SSIMU2_STATS_PER_SCALE],
+                               int* out_num_scales);
+
 /* Library/build description, e.g. "oavif_amd ssimu2 gfx950 v8 (...)". */
 const char* ssimu2_version(void);
 

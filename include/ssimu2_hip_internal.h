@@ -72,6 +72,13 @@ int ssimu2_measure_read_stream(ssimu2_ctx* ctx, size_t bytes, int iters, double*
    ssimu2_set_reference also caches blur(ref*ref). */
 int ssimu2_instr_set_segment_rows(ssimu2_ctx* ctx, int rows_scale0, int rows_other_scales);
 int ssimu2_instr_cache_reference_blur(ssimu2_ctx* ctx, int enabled);
+/* Batch scoring (ssimu2_score_batch_*): the scale-0 segment rows of a batch item.  0 = the library's rule (96 rows),
+   -1 = the single-score rule of the frame size (~512 workgroups), 8..160 = that many rows; the other scales follow
+   with at most 48.  For the tiling A/B of scripts/gpu_batch_bench.py.  ssimu2_instr_batch_segment_rows returns the
+   rows the context's batch calls use at `scale` of a w x h frame (with no override: the product's rule), so that a test
+   can take a single score at the same rows with ssimu2_instr_set_segment_rows. */
+int ssimu2_instr_set_batch_segment_rows(ssimu2_ctx* ctx, int rows_scale0);
+int ssimu2_instr_batch_segment_rows(ssimu2_ctx* ctx, uint32_t w, uint32_t h, int scale, int* out_rows);
 /* The marching body as a plain blur stage (k_ref_blur: XYB planes of one frame in, one blurred
    plane per channel out, all scales in one launch) timed over `iters` launches rotating over the
    plane sets of `nframes` device-resident RGB8 frames (HBM-fed).  *out_bytes_per_launch: the

@@ -25,6 +25,7 @@ STAGE_PYRAMID, STAGE_MARCH, STAGE_FINALIZE = 0, 1, 2
 NUM_SCALES = 6
 STATS_PER_SCALE = 18
 TQ_MAX_PASS = 12
+MAX_BATCH = 4096   # SSIMU2_MAX_BATCH (include/ssimu2_hip.h): items of one ssimu2_score_batch_* call
 
 # every symbol the public headers declare; tests/test_abi.py checks that liboavif_hip.so exports
 # exactly these (and that the Zig shim / INTEGRATION.md bind nothing else)
@@ -41,6 +42,8 @@ EXPORTED_SYMBOLS = (
     "ssimu2_error_map_rgb8", "ssimu2_error_map_against_reference",
     "ssimu2_linear_table", "ssimu2_score_rgb16", "ssimu2_set_reference_rgb16",
     "ssimu2_score_against_reference_rgb16", "ssimu2_score_against_reference_strided16",
+    "ssimu2_score_batch_rgb8", "ssimu2_score_batch_against_reference", "ssimu2_score_batch_rgb8_device",
+    "ssimu2_score_batch_against_reference_device", "ssimu2_last_batch_averages",
     "ssimu2_version",
     "oavif_tq_default_options", "oavif_tq_predict_q_from_score",
     "oavif_tq_interpolate_quantizer", "oavif_tq_find_target_quality", "oavif_tq_search_hip",
@@ -111,7 +114,8 @@ INSTR_SYMBOLS = ("ssimu2_debug_download", "ssimu2_time_device", "ssimu2_time_sta
                  "ssimu2_time_march_rotating", "ssimu2_measure_read_stream",
                  "ssimu2_instr_set_segment_rows", "ssimu2_instr_cache_reference_blur",
                  "ssimu2_instr_rg_stop_after_scale", "ssimu2_time_blur_stage_rotating",
-                 "ssimu2_instr_placed_streams", "ssimu2_time_kernels")
+                 "ssimu2_instr_placed_streams", "ssimu2_time_kernels",
+                 "ssimu2_instr_set_batch_segment_rows", "ssimu2_instr_batch_segment_rows")
 
 TQ_MAX_FANOUT = 16
 BATCH_PROBE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
@@ -219,8 +223,22 @@ def _load(path: str, instrumented: bool) -> ctypes.CDLL:
         L.ssimu2_score_against_reference_rgb16.restype = ci
         L.ssimu2_score_against_reference_strided16.argtypes = [vp, u16p, u32, u32, u32, f64p]
         L.ssimu2_score_against_reference_strided16.restype = ci
+    if hasattr(L, "ssimu2_score_batch_rgb8"):   # absent from builds before batch scoring (scripts/gpu_ab.py loads those too)
+        u8pp = ctypes.POINTER(u8p)
+        L.ssimu2_score_batch_rgb8.argtypes = [vp, u8pp, u8pp, u32, u32, u32, f64p]
+        L.ssimu2_score_batch_rgb8.restype = ci
+        L.ssimu2_score_batch_against_reference.argtypes = [vp, u8pp, u32, f64p]
+        L.ssimu2_score_batch_against_reference.restype = ci
+        L.ssimu2_score_batch_rgb8_device.argtypes = [vp, vp, vp, ctypes.c_size_t, u32, u32, u32, f64p]
+        L.ssimu2_score_batch_rgb8_device.restype = ci
+        L.ssimu2_score_batch_against_reference_device.argtypes = [vp, vp, ctypes.c_size_t, u32, f64p]
+        L.ssimu2_score_batch_against_reference_device.restype = ci
+        L.ssimu2_last_batch_averages.argtypes = [vp, u32, f64p, ctypes.POINTER(ci)]
+        L.ssimu2_last_batch_averages.restype = ci
     if instrumented:
         sigs = {
+            "ssimu2_instr_set_batch_segment_rows": [vp, ci],
+            "ssimu2_instr_batch_segment_rows": [vp, u32, u32, ci, ctypes.POINTER(ci)],
             "ssimu2_measure_read_stream": [vp, ctypes.c_size_t, ci, f64p],
             "ssimu2_debug_download": [vp, ci, ci, u32, u32, ctypes.POINTER(ctypes.c_float),
                                       ctypes.POINTER(u32), ctypes.POINTER(u32)],

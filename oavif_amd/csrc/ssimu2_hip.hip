@@ -192,6 +192,19 @@ struct ssimu2_ctx {
     void* d_lin0_dist = nullptr;
     size_t cap_ref16 = 0, cap_dist16 = 0, cap_lin0_ref = 0, cap_lin0_dist = 0;  // bytes
     bool ref_hbd = false;  // the cached reference was set from 16-bit samples (its 8-bit frame buffer is not it)
+    // batch scoring (ssimu2_score_batch_*), allocated by the first batch call only and grown on demand: the staged 8-bit
+    // frames of the host-pointer forms, the linear pyramids (scales 1..5) and partial sums of every item -- scratch of
+    // its own, so a batch leaves the single-score buffers and a cached reference alone -- and the page-locked result
+    // block k_finalize_batch writes (110 doubles per item)
+    void* b_u8_ref = nullptr;
+    void* b_u8_dist = nullptr;
+    void* b_lin_ref = nullptr;
+    void* b_lin_dist = nullptr;
+    void* b_part = nullptr;
+    size_t cap_b_u8_ref = 0, cap_b_u8_dist = 0, cap_b_lin_ref = 0, cap_b_lin_dist = 0, cap_b_part = 0;  // bytes
+    double* bh_result = nullptr;
+    size_t cap_bh_result = 0;  // items
+    uint32_t batch_n = 0;      // items of the last finished batch (ssimu2_last_batch_averages)
 
     // reference state
     bool have_ref = false;
@@ -202,6 +215,7 @@ struct ssimu2_ctx {
     // measurement builds only (ssimu2_instrument.hip); always 0 / true in the product library
     int seg_rows_override = 0;
     int seg_rows_tail_override = 0;
+    int batch_seg_override = 0;  // scale-0 rows of a batch item: 0 = the rule, -1 = the single-score rule, 8..160 fixed
     bool cache_ref_blur = true;
     int rg_dbg_scale = -1;  // recursive mode: keep that scale's 15 raw planes (after each pass) downloadable
 #ifdef SSIMU2_INSTRUMENTED_BUILD
@@ -308,9 +322,7 @@ Pyramid make_pyramid(uint32_t w, uint32_t h) {
 // best at ~512 workgroups (two thirds of the 768 resident slots, 6 % halo), the smaller scales
 // at ~48 rows -- their few, long workgroups overlap the tail of scale 0 and, with two
 // streams, the next score.  Bounds: >= 8 rows, <= 160 rows (fp32 partial sums per lane).
-int march_seg_rows(const ssimu2_ctx* c, const Pyramid& p, int scale) {
-    if (scale > 0 && c->seg_rows_tail_override > 0) return c->seg_rows_tail_override;
-    if (scale == 0 && c->seg_rows_override > 0) return c->seg_rows_override;
+int march_seg_rule(const Pyramid& p, int scale) {
     const int nstrips = (p.w[0] + MW - 1) / MW;
     int nsegs = (512 + nstrips / 2) / nstrips;
     if (nsegs < 1) nsegs = 1;
@@ -319,6 +331,26 @@ int march_seg_rows(const ssimu2_ctx* c, const Pyramid& p, int scale) {
     if (seg > 160) seg = 160;
     // smaller scales: 48 rows, but never longer than the full-resolution segments, or their
     // workgroups would outlast scale 0's on small frames
+    if (scale > 0 && seg > 48) seg = 48;
+    return seg;
+}
+
+int march_seg_rows(const ssimu2_ctx* c, const Pyramid& p, int scale) {
+    if (scale > 0 && c->seg_rows_tail_override > 0) return c->seg_rows_tail_override;
+    if (scale == 0 && c->seg_rows_override > 0) return c->seg_rows_override;
+    return march_seg_rule(p, scale);
+}
+
+// Segment rows of a BATCH item (ssimu2_score_batch_*): a function of the frame size and the scale ONLY -- never of
+// the number of items or of an item's place among them -- so that an item's score is a property of its pair and not
+// of the batch it travelled in.  A batch does not need scale 0 cut into ~512 workgroups to fill the GPU (the other
+// items do that), so its segments are long: kBatchSegRows rows at scale 0 (a workgroup converts and blurs R + 8 rows
+// for R rows scored), at most 48 below it as in a single score.  The choice among the single-score rule and 48, 96
+// and 160 fixed rows is measured: scripts/gpu_batch_bench.py, profiles/batch_score.json, DESIGN.md section 11.
+constexpr int kBatchSegRows = 96;
+int batch_seg_rows(const ssimu2_ctx* c, const Pyramid& p, int scale) {
+    int seg = c->batch_seg_override > 0 ? c->batch_seg_override
+              : c->batch_seg_override < 0 ? march_seg_rule(p, 0) : kBatchSegRows;
     if (scale > 0 && seg > 48) seg = 48;
     return seg;
 }
@@ -359,6 +391,19 @@ void free_hbd_frames(ssimu2_ctx* c) {
     (void)hipFree(c->d_lin0_dist);
     c->d_ref16 = c->d_dist16 = c->d_lin0_ref = c->d_lin0_dist = nullptr;
     c->cap_ref16 = c->cap_dist16 = c->cap_lin0_ref = c->cap_lin0_dist = 0;
+}
+
+void free_batch(ssimu2_ctx* c) {
+    (void)hipFree(c->b_u8_ref);
+    (void)hipFree(c->b_u8_dist);
+    (void)hipFree(c->b_lin_ref);
+    (void)hipFree(c->b_lin_dist);
+    (void)hipFree(c->b_part);
+    (void)hipHostFree(c->bh_result);
+    c->b_u8_ref = c->b_u8_dist = c->b_lin_ref = c->b_lin_dist = c->b_part = nullptr;
+    c->bh_result = nullptr;
+    c->cap_b_u8_ref = c->cap_b_u8_dist = c->cap_b_lin_ref = c->cap_b_lin_dist = c->cap_b_part = c->cap_bh_result = 0;
+    c->batch_n = 0;
 }
 
 void free_buffers(ssimu2_ctx* c) {
@@ -981,6 +1026,131 @@ int check_args(ssimu2_ctx* c, const void* a, const void* b, uint32_t w, uint32_t
     return SSIMU2_OK;
 }
 
+// ---- batch scoring (include/ssimu2_hip.h "Batch scoring") -------------------
+constexpr size_t kResultDoubles = kNumScales * kStats + 2;  // one item's block of the result mirror
+
+// The page-locked result block for n items (k_finalize_batch writes it over the bus itself, as k_finalize does).
+int batch_result_grow(ssimu2_ctx* c, uint32_t n) {
+    if (c->bh_result && n <= c->cap_bh_result) return SSIMU2_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    (void)hipHostFree(c->bh_result);
+    c->bh_result = nullptr;
+    c->cap_bh_result = 0;
+    c->batch_n = 0;
+    const hipError_t e = hipHostMalloc(&c->bh_result, (size_t)n * kResultDoubles * sizeof(double), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        c->bh_result = nullptr;
+        (void)hipGetLastError();
+        return c->fail(SSIMU2_ERR_OOM, "hipHostMalloc(batch results)", e);
+    }
+    c->cap_bh_result = n;
+    return SSIMU2_OK;
+}
+
+// What every batch call checks first (the ctx is not null, n > 0).
+int batch_check(ssimu2_ctx* c, uint32_t n, bool against_reference) {
+    if (c->blur_mode != SSIMU2_BLUR_FIR)
+        return c->fail(SSIMU2_ERR_UNSUPPORTED, "batch scoring runs in SSIMU2_BLUR_FIR only: switch the context with "
+                                               "ssimu2_ctx_set_blur, or score the pairs one by one");
+    if (against_reference && !c->have_ref) return c->fail(SSIMU2_ERR_NO_REFERENCE, "no reference set");
+    if (n > SSIMU2_MAX_BATCH) return c->fail(SSIMU2_ERR_INVALID_ARG, "batch larger than SSIMU2_MAX_BATCH items");
+    return SSIMU2_OK;
+}
+
+// Score n device-resident items of w x h: d_dists + i * dist_stride0 against d_refs + i * ref_stride0, or (d_refs
+// null) against the context's cached reference.  ONE k_pyramid_bands_batch, ONE k_march_batch / k_march_refblur_batch,
+// ONE k_finalize_batch, one synchronise; whatever was enqueued on the stream before (uploads) comes first.
+int batch_run(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dists, size_t stride0, uint32_t n, uint32_t w,
+              uint32_t h, double* out_scores) {
+    const bool against_ref = d_refs == nullptr;
+    const Pyramid p = make_pyramid(w, h);
+    MarchBatchPlan bp;
+    FinalizeArgs fa;
+    memset(&bp, 0, sizeof bp);
+    memset(&fa, 0, sizeof fa);
+    MarchPlan& mp = bp.item;
+    mp.nscales = fa.nscales = p.nscales;
+    size_t poff[kNumScales] = {0}, part_stride = 0;
+    long long blocks = 0;
+    for (int s = 0; s < p.nscales; ++s) {
+        const int seg = batch_seg_rows(c, p, s);
+        const int nstrips = (p.w[s] + MW - 1) / MW;
+        const int nb = nstrips * ((p.h[s] + seg - 1) / seg);
+        blocks += nb;
+        mp.blk_end[s] = (int)blocks;
+        mp.w[s] = p.w[s];
+        mp.h[s] = p.h[s];
+        mp.seg[s] = seg;
+        mp.nstrips[s] = nstrips;
+        mp.nblocks[s] = nb;
+        fa.nblocks[s] = nb;
+        fa.inv_pixels[s] = 1.0 / ((double)p.w[s] * (double)p.h[s]);
+        poff[s] = part_stride;
+        part_stride += (size_t)nb * kStats;
+    }
+    const int nframes = against_ref ? 1 : 2;
+    const long long bands = (long long)((p.w[0] + PYR_BAND_W - 1) / PYR_BAND_W) * ((p.h[0] + PYR_BAND_H - 1) / PYR_BAND_H);
+    if (blocks * n > 0x7fffffffLL || bands * nframes * n > 0x7fffffffLL)
+        return c->fail(SSIMU2_ERR_INVALID_ARG, "batch too large for one launch: fewer items per call");
+    const bool cached = against_ref && c->d_xyb_ref && c->d_ref_blur && c->cap_blur;
+    if (against_ref && !cached && c->ref_hbd)  // as ssimu2_score_against_reference_rgb16: no 8-bit frame of that reference
+        return c->fail(SSIMU2_ERR_OOM, "a batch against a 16-bit reference needs its cached planes, which are missing");
+    const size_t lin_stride = (p.lin_total + 3) & ~(size_t)3;  // floats between items' pyramids
+    int rc;
+    if ((rc = hbd_grow(c, &c->b_lin_dist, &c->cap_b_lin_dist, (size_t)n * lin_stride * sizeof(float) + 16,
+                       "hipMalloc(batch pyramids)")) ||
+        (!against_ref && (rc = hbd_grow(c, &c->b_lin_ref, &c->cap_b_lin_ref, (size_t)n * lin_stride * sizeof(float) + 16,
+                                        "hipMalloc(batch pyramids)"))) ||
+        (rc = hbd_grow(c, &c->b_part, &c->cap_b_part, ((size_t)n * part_stride + 8) * sizeof(double),
+                       "hipMalloc(batch partial sums)")) ||
+        (rc = batch_result_grow(c, n)))
+        return rc;
+    const float* lin_ref = against_ref ? c->d_lin_ref : (const float*)c->b_lin_ref;
+    for (int s = 0; s < p.nscales; ++s) {
+        mp.ref[s] = s == 0 ? (const void*)(against_ref ? c->d_ref_u8 : d_refs) : (const void*)(lin_ref + p.lin_off[s]);
+        mp.dist[s] = s == 0 ? (const void*)d_dists : (const void*)((const float*)c->b_lin_dist + p.lin_off[s]);
+        mp.ref_xyb[s] = cached ? c->d_xyb_ref + xyb_off(p, s) : nullptr;
+        mp.ref_s11[s] = cached ? c->d_ref_blur + xyb_off(p, s) : nullptr;
+        mp.part[s] = (double*)c->b_part + poff[s];
+        fa.part[s] = mp.part[s];
+        bp.blk_end[s] = (int)(mp.blk_end[s] * (long long)n);
+    }
+    bp.n_items = (int)n;
+    bp.ref_stride0 = against_ref ? 0 : stride0;  // one reference for all items
+    bp.dist_stride0 = stride0;
+    bp.ref_stride = against_ref ? 0 : lin_stride * sizeof(float);
+    bp.dist_stride = lin_stride * sizeof(float);
+    bp.part_stride = part_stride;
+    if (p.nscales > 1) {
+        const uint8_t* frames[2] = {against_ref ? d_dists : d_refs, d_dists};
+        float* lin[2] = {against_ref ? (float*)c->b_lin_dist : (float*)c->b_lin_ref, (float*)c->b_lin_dist};
+        PyrBatchArgs pb;
+        pb.a = pyramid_args(p, nframes, frames, lin);
+        pb.in_stride = stride0;
+        pb.out_stride = lin_stride;
+        launch(k_pyramid_bands_batch, dim3((unsigned)(bands * nframes * n)), dim3(PYR_THREADS), 0, c->stream, pb);
+    }
+    if (blocks > 0) {
+        if (cached) launch(k_march_refblur_batch, dim3((unsigned)(blocks * n)), dim3(MARCH_THREADS), 0, c->stream, bp);
+        else launch(k_march_batch, dim3((unsigned)(blocks * n)), dim3(MARCH_THREADS), 0, c->stream, bp);
+    }
+    launch(k_finalize_batch, dim3(n), dim3(1024), 0, c->stream, fa, part_stride, c->bh_result);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->batch_n = n;
+    for (uint32_t i = 0; i < n; ++i) out_scores[i] = c->bh_result[(size_t)i * kResultDoubles + 108];
+    return SSIMU2_OK;
+}
+
+// Upload n host frames into a staging buffer of the context, `stride` bytes apart, on the context stream.
+int batch_stage(ssimu2_ctx* c, void** buf, size_t* cap, const uint8_t* const* frames, uint32_t n, size_t bytes, size_t stride) {
+    int rc = hbd_grow(c, buf, cap, (size_t)n * stride + 16, "hipMalloc(batch frames)");
+    if (rc) return rc;
+    for (uint32_t i = 0; i < n; ++i)
+        HIP_TRY(c, hipMemcpyAsync((uint8_t*)*buf + (size_t)i * stride, frames[i], bytes, hipMemcpyHostToDevice, c->stream));
+    return SSIMU2_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1382,6 +1552,7 @@ void ssimu2_ctx_destroy(ssimu2_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     free_buffers(c);
+    free_batch(c);
     (void)hipFree(c->d_tab);
     (void)hipFree(c->d_result);
     (void)hipHostFree(c->h_result);
@@ -1755,6 +1926,84 @@ int ssimu2_last_averages(ssimu2_ctx* c, double* out, int* out_num_scales) {
     }
     memcpy(out, c->h_result, 108 * sizeof(double));
     if (out_num_scales) *out_num_scales = (int)c->h_result[109];
+    return SSIMU2_OK;
+}
+
+// ---- batch scoring ---------------------------------------------------------
+int ssimu2_score_batch_rgb8_device(ssimu2_ctx* c, const void* d_refs, const void* d_dists, size_t item_stride_bytes,
+                                   uint32_t n, uint32_t w, uint32_t h, double* out_scores) {
+    if (!c) return SSIMU2_ERR_INVALID_ARG;
+    if (n == 0) return SSIMU2_OK;
+    int rc = batch_check(c, n, false);
+    if (rc) return rc;
+    if ((rc = check_args(c, d_refs, d_dists, w, h))) return rc;
+    if (!out_scores) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_scores");
+    if ((uint64_t)item_stride_bytes < (uint64_t)w * h * 3)
+        return c->fail(SSIMU2_ERR_INVALID_ARG, "item_stride_bytes smaller than one frame");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_run(c, (const uint8_t*)d_refs, (const uint8_t*)d_dists, item_stride_bytes, n, w, h, out_scores);
+}
+
+int ssimu2_score_batch_against_reference_device(ssimu2_ctx* c, const void* d_dists, size_t item_stride_bytes, uint32_t n,
+                                                double* out_scores) {
+    if (!c) return SSIMU2_ERR_INVALID_ARG;
+    if (n == 0) return SSIMU2_OK;
+    int rc = batch_check(c, n, true);
+    if (rc) return rc;
+    if (!d_dists || !out_scores) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
+    if ((uint64_t)item_stride_bytes < (uint64_t)c->ref_w * c->ref_h * 3)
+        return c->fail(SSIMU2_ERR_INVALID_ARG, "item_stride_bytes smaller than one frame");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_run(c, nullptr, (const uint8_t*)d_dists, item_stride_bytes, n, c->ref_w, c->ref_h, out_scores);
+}
+
+int ssimu2_score_batch_rgb8(ssimu2_ctx* c, const uint8_t* const* refs, const uint8_t* const* dists, uint32_t n, uint32_t w,
+                            uint32_t h, double* out_scores) {
+    if (!c) return SSIMU2_ERR_INVALID_ARG;
+    if (n == 0) return SSIMU2_OK;
+    int rc = batch_check(c, n, false);
+    if (rc) return rc;
+    if ((rc = check_args(c, refs, dists, w, h))) return rc;
+    if (!out_scores) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_scores");
+    for (uint32_t i = 0; i < n; ++i)
+        if (!refs[i] || !dists[i]) return c->fail(SSIMU2_ERR_INVALID_ARG, "null image pointer in the batch");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)w * h * 3, stride = (bytes + 15) & ~(size_t)15;
+    if ((rc = batch_stage(c, &c->b_u8_ref, &c->cap_b_u8_ref, refs, n, bytes, stride)) ||
+        (rc = batch_stage(c, &c->b_u8_dist, &c->cap_b_u8_dist, dists, n, bytes, stride))) {
+        (void)hipStreamSynchronize(c->stream);  // the caller may free its frames after any return
+        return rc;
+    }
+    rc = batch_run(c, (const uint8_t*)c->b_u8_ref, (const uint8_t*)c->b_u8_dist, stride, n, w, h, out_scores);
+    if (rc) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+int ssimu2_score_batch_against_reference(ssimu2_ctx* c, const uint8_t* const* dists, uint32_t n, double* out_scores) {
+    if (!c) return SSIMU2_ERR_INVALID_ARG;
+    if (n == 0) return SSIMU2_OK;
+    int rc = batch_check(c, n, true);
+    if (rc) return rc;
+    if (!dists || !out_scores) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
+    for (uint32_t i = 0; i < n; ++i)
+        if (!dists[i]) return c->fail(SSIMU2_ERR_INVALID_ARG, "null image pointer in the batch");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->ref_w * c->ref_h * 3, stride = (bytes + 15) & ~(size_t)15;
+    if ((rc = batch_stage(c, &c->b_u8_dist, &c->cap_b_u8_dist, dists, n, bytes, stride))) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    rc = batch_run(c, nullptr, (const uint8_t*)c->b_u8_dist, stride, n, c->ref_w, c->ref_h, out_scores);
+    if (rc) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+int ssimu2_last_batch_averages(ssimu2_ctx* c, uint32_t item, double* out, int* out_num_scales) {
+    if (!c || !out) return SSIMU2_ERR_INVALID_ARG;
+    if (item >= c->batch_n) return c->fail(SSIMU2_ERR_INVALID_ARG, "ssimu2_last_batch_averages: no such item in the last batch");
+    const double* r = c->bh_result + (size_t)item * kResultDoubles;
+    memcpy(out, r, 108 * sizeof(double));
+    if (out_num_scales) *out_num_scales = (int)r[109];
     return SSIMU2_OK;
 }
 

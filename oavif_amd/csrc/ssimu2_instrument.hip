@@ -57,6 +57,22 @@ int ssimu2_instr_set_segment_rows(ssimu2_ctx* c, int rows_scale0, int rows_other
     return SSIMU2_OK;
 }
 
+int ssimu2_instr_set_batch_segment_rows(ssimu2_ctx* c, int rows_scale0) {
+    if (!c) return SSIMU2_ERR_INVALID_ARG;
+    if (rows_scale0 != 0 && rows_scale0 != -1 && (rows_scale0 < 8 || rows_scale0 > 160))
+        return c->fail(SSIMU2_ERR_INVALID_ARG, "batch segment rows must be 0 (the rule), -1 (the single-score rule) or 8..160");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->batch_seg_override = rows_scale0;
+    return SSIMU2_OK;  // the batch's partial-sum buffer is sized per call
+}
+
+int ssimu2_instr_batch_segment_rows(ssimu2_ctx* c, uint32_t w, uint32_t h, int scale, int* out_rows) {
+    if (!c || !out_rows || scale < 0 || scale >= kNumScales || w == 0 || h == 0) return SSIMU2_ERR_INVALID_ARG;
+    *out_rows = batch_seg_rows(c, make_pyramid(w, h), scale);
+    return SSIMU2_OK;
+}
+
 int ssimu2_instr_placed_streams(ssimu2_ctx* c, int* out_n) {
     if (!c || !out_n) return SSIMU2_ERR_INVALID_ARG;
     *out_n = pool_size(c->device);

@@ -299,9 +299,11 @@ __device__ __forceinline__ void pyr_load16(const PyrHbdArgs& hb, int f, int w0, 
 // `lut`: the sRGB table in LDS; `lds`: PYR_BAND_LDS_FLOATS floats of scratch; 512 threads, all of
 // which must call (barriers inside).  `band` < bands_x * bands_y * nframes.
 // CH16 = 0: 8-bit frames through the LDS table `lut`; 3 / 4: 16-bit RGB / RGBA frames of `hb`.
-template <bool XYB, int CH16 = 0>
+// BATCH (k_pyramid_bands_batch): `in_off` (bytes) / `out_off` (floats) are added to the frame's input and to each of
+// its output levels -- item i of a batch.  An instantiation of its own: the code of the other kernels is as it was.
+template <bool XYB, int CH16 = 0, bool BATCH = false>
 __device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, const float* lut, float* lds,
-                                             const PyrHbdArgs* hb = nullptr) {
+                                             const PyrHbdArgs* hb = nullptr, size_t in_off = 0, size_t out_off = 0) {
     const int t = threadIdx.x;
     const int per_frame = a.bands_x * a.bands_y;
     const int f = band / per_frame;
@@ -324,6 +326,7 @@ __device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, con
             for (int c = 0; c < 3; ++c) l1[j][i][c] = 0.f;
     if (X0 < w0 && Y0 < h0) {
         const uint8_t* base = a.in[f];
+        if constexpr (BATCH) base += in_off;
         uint32_t raw[4][3];
         float lin16[4][4][3];  // CH16: linear values of this thread's 4 x 4 pixels
         const bool inside = X0 + 3 < w0 && Y0 + 3 < h0;
@@ -370,6 +373,7 @@ __device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, con
                                        PYR_LIN(2 * j + 1, 2 * i, c), PYR_LIN(2 * j + 1, 2 * i + 1, c));
                 if (ox < w1 && oy < h1 && (!XYB || a.nlevels >= 1)) {
                     float* o = a.out[f][0];
+                    if constexpr (BATCH) o += out_off;
                     if (XYB) {
                         pyr_store_xyb(o, n1, (size_t)oy * p1 + ox, l1[j][i]);
                     } else {
@@ -439,6 +443,7 @@ __device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, con
             const int p2 = a.opitch[2];
             const size_t n2 = (size_t)p2 * h2;
             float* o = a.out[f][1];
+            if constexpr (BATCH) o += out_off;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float p01 = ib ? l1[0][1][c] : l1[0][0][c];
@@ -455,17 +460,17 @@ __device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, con
     if (a.nlevels < 3) return;
     __syncthreads();
     if (t < 4 * (TX / 2))
-        pyr_lds_level<XYB>(s2, TX, 8, a.w[2], a.h[2], s3, TX / 2, 4, a.out[f][2], a.w[3], a.h[3], a.opitch[3], bx * (TX / 2), by * 4,
+        pyr_lds_level<XYB>(s2, TX, 8, a.w[2], a.h[2], s3, TX / 2, 4, BATCH ? a.out[f][2] + out_off : a.out[f][2], a.w[3], a.h[3], a.opitch[3], bx * (TX / 2), by * 4,
                       t % (TX / 2), t / (TX / 2));
     if (a.nlevels < 4) return;
     __syncthreads();
     if (t < 2 * (TX / 4))
-        pyr_lds_level<XYB>(s3, TX / 2, 4, a.w[3], a.h[3], s4, TX / 4, 2, a.out[f][3], a.w[4], a.h[4], a.opitch[4], bx * (TX / 4), by * 2,
+        pyr_lds_level<XYB>(s3, TX / 2, 4, a.w[3], a.h[3], s4, TX / 4, 2, BATCH ? a.out[f][3] + out_off : a.out[f][3], a.w[4], a.h[4], a.opitch[4], bx * (TX / 4), by * 2,
                       t % (TX / 4), t / (TX / 4));
     if (a.nlevels < 5) return;
     __syncthreads();
     if (t < TX / 8)
-        pyr_lds_level<XYB>(s4, TX / 4, 2, a.w[4], a.h[4], nullptr, 0, 0, a.out[f][4], a.w[5], a.h[5], a.opitch[5], bx * (TX / 8), by, t, 0);
+        pyr_lds_level<XYB>(s4, TX / 4, 2, a.w[4], a.h[4], nullptr, 0, 0, BATCH ? a.out[f][4] + out_off : a.out[f][4], a.w[5], a.h[5], a.opitch[5], bx * (TX / 8), by, t, 0);
 }
 
 __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_bands(PyrBandArgs a) {
@@ -474,6 +479,25 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_bands(PyrBandArgs a) {
     if (threadIdx.x < 256) s_lut[threadIdx.x] = c_k.lut[threadIdx.x];
     __syncthreads();
     pyramid_band<false>(a, (int)blockIdx.x, s_lut, s_tiles);
+}
+
+// The band pyramid of a BATCH (ssimu2_score_batch_*): `a` describes item 0 -- a.nframes (2: reference and distorted,
+// 1: distorted only) frames of one size -- and item i's frames and levels lie i * stride further on.  Grid:
+// [item][frame][band]; per frame the arithmetic of k_pyramid_bands, so an item's planes do not depend on the batch.
+struct PyrBatchArgs {
+    PyrBandArgs a;
+    size_t in_stride;   // bytes between the 8-bit frames of consecutive items
+    size_t out_stride;  // floats between their linear pyramids
+};
+__global__ __launch_bounds__(PYR_THREADS) void k_pyramid_bands_batch(PyrBatchArgs b) {
+    __shared__ float s_lut[256];
+    __shared__ float s_tiles[PYR_BAND_LDS_FLOATS];
+    if (threadIdx.x < 256) s_lut[threadIdx.x] = c_k.lut[threadIdx.x];
+    __syncthreads();
+    const int per_item = b.a.bands_x * b.a.bands_y * b.a.nframes;
+    const int item = (int)blockIdx.x / per_item;
+    pyramid_band<false, 0, true>(b.a, (int)blockIdx.x - item * per_item, s_lut, s_tiles, nullptr, (size_t)item * b.in_stride,
+                        (size_t)item * b.out_stride);
 }
 
 // The same bands with positive-XYB planes of every level -- the frame's own included -- as the
@@ -701,10 +725,13 @@ __device__ __forceinline__ void march_lut(const float* lut, uint32_t d, uint32_t
 // channel.  The LUT reads therefore land under ~100 arithmetic instructions.
 // LIN0: instantiated for the kernels of march_body<MODE, true> (same code; an instantiation of their own leaves the
 // code generated for the 8-bit kernels as it was).
-template <bool U8, int MODE, bool LIN0 = false>
+template <bool U8, int MODE, bool LIN0 = false, bool BATCH = false>
 __device__ __forceinline__ void march_convert_rows(f2 (*ring)[3][MRW], const float* lut,
                                                    const MarchPlan& plan, int sc, int w, int h, int x0,
-                                                   int y0, int steps, int ngroups, int col) {
+                                                   int y0, int steps, int ngroups, int col, size_t off0 = 0,
+                                                   size_t off1 = 0) {
+    // BATCH: off0 / off1 are the uniform byte offsets of this workgroup's item from plan.ref[sc] / plan.dist[sc]
+    // (the cached reference planes are shared by every item).
     constexpr bool CACHED = MODE == MARCH_REFBLUR || MODE == MARCH_EMIT;
     constexpr bool TWO = MODE != MARCH_EMIT;
     constexpr bool LUT0 = U8 && !CACHED;  // frame 0 goes through the sRGB LUT
@@ -715,6 +742,10 @@ __device__ __forceinline__ void march_convert_rows(f2 (*ring)[3][MRW], const flo
     MarchCursor c0 = CACHED ? march_cursor<false>(plan.ref_xyb[sc], w, h, gxc)
                             : march_cursor<U8>(plan.ref[sc], w, h, gxc);
     MarchCursor c1 = march_cursor<U8>(plan.dist[sc], w, h, gxc);
+    if constexpr (BATCH) {
+        if (!CACHED) c0.base += off0;
+        c1.base += off1;
+    }
     int load_row = y0 - RAD;  // image row of the next load
     // raw[f][j]: loaded, not yet converted row of frame f.  The queue is QD = 2 * GROUP rows deep
     // (the LUT reads of a row are requested one row before it is converted, so its pixels must
@@ -975,9 +1006,19 @@ __device__ __forceinline__ int march_tile_of_block(int b, int first, int end) {
     return before + (b >> 3) - ((first + 7 - x) >> 3);  // + its rank among those of phase x
 }
 
+// Where a workgroup of a BATCH launch works (march_batch_body): its scale and tile come from the batch grid instead
+// of blockIdx.x, and its item's frames and partial sums lie at uniform offsets from the plan's (item 0's) pointers.
+struct MarchItem {
+    int sc, tile;
+    size_t off_ref, off_dist;  // bytes: the item's frame at scale `sc` from plan.ref[sc] / plan.dist[sc]
+    size_t off_part;           // doubles: the item's partial sums from plan.part[sc]
+};
+
 // LIN0: scale 0 is fp32 linear planes [3][h][w] like the smaller scales (the 16-bit front end's), not 8-bit frames.
-template <int MODE, bool LIN0 = false>
-__device__ __forceinline__ void march_body(const MarchPlan& plan, const MapCoef* coef = nullptr) {
+// BATCH: `it` says where the workgroup works; otherwise blockIdx.x does and `it` is not read.
+template <int MODE, bool LIN0 = false, bool BATCH = false>
+__device__ __forceinline__ void march_body(const MarchPlan& plan, const MapCoef* coef = nullptr,
+                                           const MarchItem* it = nullptr) {
     // [row slot][channel][column] of (ref, dist) pairs
     __shared__ __attribute__((aligned(16))) f2 s_ring[RING][3][MRW];
     __shared__ float s_lut[256];
@@ -989,11 +1030,12 @@ __device__ __forceinline__ void march_body(const MarchPlan& plan, const MapCoef*
     int sc = 0, first = 0;
 #pragma unroll
     for (int s = 0; s < kNumScales - 1; ++s)
-        if (s + 1 < plan.nscales && (int)blockIdx.x >= plan.blk_end[s]) {
+        if (!BATCH && s + 1 < plan.nscales && (int)blockIdx.x >= plan.blk_end[s]) {
             sc = s + 1;
             first = plan.blk_end[s];
         }
-    const int blk = march_tile_of_block((int)blockIdx.x, first, plan.blk_end[sc]);
+    if constexpr (BATCH) sc = it->sc;
+    const int blk = BATCH ? it->tile : march_tile_of_block((int)blockIdx.x, first, plan.blk_end[sc]);
     const int w = plan.w[sc], h = plan.h[sc], seg_rows = plan.seg[sc];
     const int nstrips = plan.nstrips[sc];
     const int by = blk / nstrips, bx = blk - by * nstrips;
@@ -1050,8 +1092,13 @@ __device__ __forceinline__ void march_body(const MarchPlan& plan, const MapCoef*
         // (profiles/r07_march_ab.txt).  Waves 0-1 of the three workgroups of a CU already sit 2/2/1/1
         // on its SIMDs (profiles/r07_placement.txt), so which wave converts is left as it is.
         const int col = (wave << 6) + lane;  // staged column; this lane converts both frames
-        if (u8) march_convert_rows<true, MODE, LIN0>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col);
-        else march_convert_rows<false, MODE, LIN0>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col);
+        if constexpr (BATCH) {
+            if (u8) march_convert_rows<true, MODE, LIN0, true>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col, it->off_ref, it->off_dist);
+            else march_convert_rows<false, MODE, LIN0, true>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col, it->off_ref, it->off_dist);
+        } else {
+            if (u8) march_convert_rows<true, MODE, LIN0>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col);
+            else march_convert_rows<false, MODE, LIN0>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col);
+        }
     } else {
         float win[5][9];
         const lds_vu64* rp = (const lds_vu64*)&s_ring[0][ch][o];  // staged columns o .. o+8, centre o+4
@@ -1095,8 +1142,65 @@ __device__ __forceinline__ void march_body(const MarchPlan& plan, const MapCoef*
         // tid = stat index: 0..5 ssim (c*2+n), 6..17 edge (c*4+k)
         const int c = tid < 6 ? tid >> 1 : (tid - 6) >> 2;
         const int k = tid < 6 ? (tid & 1) : 2 + ((tid - 6) & 3);
-        plan.part[sc][(size_t)tid * plan.nblocks[sc] + blk] = s_part[2 * c][k] + s_part[2 * c + 1][k];
+        if constexpr (BATCH)
+            plan.part[sc][it->off_part + (size_t)tid * plan.nblocks[sc] + blk] = s_part[2 * c][k] + s_part[2 * c + 1][k];
+        else
+            plan.part[sc][(size_t)tid * plan.nblocks[sc] + blk] = s_part[2 * c][k] + s_part[2 * c + 1][k];
     }
+}
+
+// ---- batch form: N pairs of one size in ONE marching launch (ssimu2_score_batch_*) ----------------
+// `item` is the MarchPlan of item 0 (geometry, and the pointers of its frames, pyramids and partial sums); item i's
+// buffers lie i * stride further on.  The cached reference planes (ref_xyb, ref_s11) are one set for the whole batch.
+struct MarchBatchPlan {
+    MarchPlan item;
+    int n_items;
+    int blk_end[kNumScales];          // exclusive end of each scale's range in the batch grid: n_items * item.blk_end[s]
+    size_t ref_stride0, dist_stride0;  // bytes between items' 8-bit frames (a reference shared by all items: 0)
+    size_t ref_stride, dist_stride;    // bytes between items' linear pyramids (scales >= 1)
+    size_t part_stride;                // doubles between items' partial sums
+};
+
+// Workgroup -> (scale, item, tile).  The grid is ordered largest scale first ACROSS all items, so the short workgroups
+// of the small scales fill the tail of the whole batch, as they fill the tail of scale 0 in a single score.  Within
+// a scale, march_tile_of_block deals each XCD (own L2) a contiguous run of the scale's n_items * nblocks virtual
+// indices, and
+//   ITEMS_FASTEST = false (pairs): index = item * nblocks + tile -- an XCD's run is neighbouring tiles of one item,
+//       which share their halo columns and the cache lines their strip edges straddle, as in a single score;
+//   ITEMS_FASTEST = true (cached reference): index = tile * n_items + item -- an XCD's run is the SAME tile of
+//       consecutive items, which all read that tile of the reference's XYB and blur planes: fetched from HBM once
+//       per XCD and batch instead of once per item (the reference is 24 of the 27 bytes per pixel such a pass reads).
+// Which workgroup computes a tile does not enter its arithmetic and sums are stored under (item, tile): bits unmoved.
+template <int MODE, bool ITEMS_FASTEST>
+__device__ __forceinline__ void march_batch_body(const MarchBatchPlan& bp) {
+    const int b = (int)blockIdx.x;
+    int sc = 0, first = 0;
+#pragma unroll
+    for (int s = 0; s < kNumScales - 1; ++s)
+        if (s + 1 < bp.item.nscales && b >= bp.blk_end[s]) {
+            sc = s + 1;
+            first = bp.blk_end[s];
+        }
+    const int v = march_tile_of_block(b, first, bp.blk_end[sc]);
+    const int nb = bp.item.nblocks[sc];
+    int item, tile;
+    if (ITEMS_FASTEST) {
+        tile = v / bp.n_items;
+        item = v - tile * bp.n_items;
+    } else {
+        item = v / nb;
+        tile = v - item * nb;
+    }
+    // blockIdx arithmetic over kernel arguments: uniform, but say so (the converters' loads take their base from SGPRs)
+    item = __builtin_amdgcn_readfirstlane(item);
+    tile = __builtin_amdgcn_readfirstlane(tile);
+    MarchItem it;
+    it.sc = sc;
+    it.tile = tile;
+    it.off_ref = (size_t)item * (sc == 0 ? bp.ref_stride0 : bp.ref_stride);
+    it.off_dist = (size_t)item * (sc == 0 ? bp.dist_stride0 : bp.dist_stride);
+    it.off_part = (size_t)item * bp.part_stride;
+    march_body<MODE, false, true>(bp.item, nullptr, &it);
 }
 
 // launch bound: 3 workgroups of 8 waves per CU = 6 waves per SIMD (<= 80 VGPRs)
@@ -1122,6 +1226,16 @@ __global__ __launch_bounds__(MARCH_THREADS, 6) void k_march_lin(MarchPlan plan) 
 
 __global__ __launch_bounds__(MARCH_THREADS, 6) void k_march_refblur_lin(MarchPlan plan) {
     march_body<MARCH_REFBLUR, true>(plan);
+}
+
+// The batch forms of k_march and k_march_refblur: entries of their own (own register allocation; the single-score
+// kernels above are not touched by them).
+__global__ __launch_bounds__(MARCH_THREADS, 6) void k_march_batch(MarchBatchPlan bp) {
+    march_batch_body<MARCH_PAIR, false>(bp);
+}
+
+__global__ __launch_bounds__(MARCH_THREADS, 6) void k_march_refblur_batch(MarchBatchPlan bp) {
+    march_batch_body<MARCH_REFBLUR, true>(bp);
 }
 
 // error-map pass (ssimu2_error_map_*): per-pixel densities of every scale into plan.ref_s11.  Its own entry and
@@ -1177,6 +1291,73 @@ __global__ __launch_bounds__(1024) void k_finalize(FinalizeArgs fa, double* __re
         // each lane sums runs of 8 consecutive partials: the 8 loads of a run are independent,
         // so the loop is 8x shorter than one dependent load + add per partial
         const double* p = fa.part[scale] + (size_t)stat * fa.nblocks[scale];
+        const int nb = fa.nblocks[scale];
+        for (int b = sub * 8; b < nb; b += 64) {
+            double t[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) t[k] = b + k < nb ? p[b + k] : 0.0;
+            v += ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
+        }
+    }
+    v += __shfl_down(v, 4, 8);
+    v += __shfl_down(v, 2, 8);
+    v += __shfl_down(v, 1, 8);
+    if (sub == 0 && item < kNumScales * kStats) {
+        if (live) {
+            v *= fa.inv_pixels[scale];
+            if (stat & 1) v = sqrt(sqrt(v));  // odd stats are L4 norms
+        }
+        s_avg[item] = v;
+    }
+    __syncthreads();
+    // published Score(): weights are consumed with a running index over (channel, scale present,
+    // norm, {ssim, artifact, detail}); term j of that walk is evaluated by thread j and the
+    // terms are summed with a fixed shuffle tree (two waves), then by thread 0.
+    __shared__ double s_red[2];
+    if (threadIdx.x < 128) {
+        const int j = threadIdx.x;
+        const int nterms = 3 * fa.nscales * 2 * 3;
+        double term = 0.0;
+        if (j < nterms) {
+            const int k = j % 3, n = (j / 3) & 1, cs = j / 6;
+            const int sc = cs % fa.nscales, c = cs / fa.nscales;
+            const double* a = s_avg + sc * kStats;
+            const double val = k == 0 ? a[c * 2 + n] : a[6 + c * 4 + n + (k == 2 ? 2 : 0)];
+            term = c_k.weights[j] * fabs(val);
+        }
+        term = wave_sum(term);
+        if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = term;
+    }
+    __syncthreads();
+    // the averages leave as two full-wave stores of consecutive doubles (they cross PCIe: not 108 scattered ones)
+    if (threadIdx.x < kNumScales * kStats) result[threadIdx.x] = s_avg[threadIdx.x];
+    if (threadIdx.x == 0) {
+        double ssim = s_red[0] + s_red[1];
+        ssim = ssim * 0.9562382616834844;
+        ssim = 2.326765642916932 * ssim - 0.020884521182843837 * ssim * ssim +
+               6.248496625763138e-05 * ssim * ssim * ssim;
+        if (ssim > 0.0) ssim = 100.0 - 10.0 * pow(ssim, 0.6276336467831387);
+        else ssim = 100.0;
+        result[108] = ssim;
+        result[109] = (double)fa.nscales;
+    }
+}
+
+// One workgroup per item of a batch: k_finalize's reduction, statement for statement (a copy, not a shared body: as an
+// inlined function with the offsets as arguments it moved k_finalize's register allocation), over the item's partial
+// sums -- `part_stride` doubles per item behind fa.part[scale] -- with its 110 doubles going to result + 110 * item of the
+// context's page-locked batch mirror.  An item's result depends on its own sums alone.
+__global__ __launch_bounds__(1024) void k_finalize_batch(FinalizeArgs fa, size_t part_stride, double* __restrict__ results) {
+    double* __restrict__ result = results + (size_t)blockIdx.x * (kNumScales * kStats + 2);
+    __shared__ double s_avg[kNumScales * kStats];
+    const int item = threadIdx.x >> 3, sub = threadIdx.x & 7;
+    double v = 0.0;
+    const int scale = item / kStats, stat = item - scale * kStats;
+    const bool live = item < kNumScales * kStats && scale < fa.nscales;
+    if (live) {
+        // each lane sums runs of 8 consecutive partials: the 8 loads of a run are independent,
+        // so the loop is 8x shorter than one dependent load + add per partial
+        const double* p = fa.part[scale] + (size_t)blockIdx.x * part_stride + (size_t)stat * fa.nblocks[scale];
         const int nb = fa.nblocks[scale];
         for (int b = sub * 8; b < nb; b += 64) {
             double t[8];

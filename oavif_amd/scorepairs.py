@@ -1,0 +1,154 @@
+"""Score a list of image pairs with the batch scorer.
+
+    python -m oavif_amd.scorepairs PAIRS.tsv OUT.csv [--batch B] [--device D]
+
+PAIRS.tsv holds one `ref<TAB>dist` path pair per line (PNG or PAM, through the project's own loaders; relative paths are
+taken from the list's directory; blank lines and lines starting with '#' are skipped).  Pairs are grouped by frame
+size, every group is scored with Ssimu2.score_batch in batches of at most B pairs (one launch set each), and OUT.csv
+gets one row per pair in input order: line, ref, dist, width, height, score.  8-bit RGB in SSIMU2_BLUR_FIR (what the
+batch calls score); 16-bit PNGs are truncated to 8 bits and alpha is dropped, as the search's reference is.
+"""
+from __future__ import annotations
+
+import csv
+import os
+import sys
+from typing import Callable, List, Sequence, Tuple
+
+import numpy as np
+
+DEFAULT_BATCH = 64
+
+
+class PairListError(Exception):
+    """A line of the pair list that cannot be scored; carries the 1-based line number."""
+
+    def __init__(self, line: int, msg: str):
+        super().__init__(f"line {line}: {msg}")
+        self.line = line
+
+
+def load_rgb8(path: str) -> np.ndarray:
+    """A PNG or PAM file as the scorer's (h, w, 3) uint8 frame: gray replicated, alpha dropped, 16 bits >> 8."""
+    ext = os.path.splitext(path)[1].lower()
+    data = open(path, "rb").read()
+    if ext == ".pam":
+        from .pam import load_pam
+        raster, w, h, ch = load_pam(data)
+        arr = np.frombuffer(raster, np.uint8).reshape(h, w, ch)
+    elif ext == ".png":
+        from .png import load_png
+        arr, _ch, _hbd, _icc = load_png(data)
+        if arr.dtype == np.uint16:
+            arr = (arr >> 8).astype(np.uint8)
+    else:
+        raise ValueError(f"unsupported image format {ext or path!r} (PNG or PAM)")
+    rgb = np.repeat(arr[..., :1], 3, axis=2) if arr.shape[2] < 3 else arr[..., :3]
+    return np.ascontiguousarray(rgb)
+
+
+def parse_pairs(text: str, base_dir: str = "") -> List[Tuple[int, str, str]]:
+    """-> [(line number, ref path, dist path)] of a pair list."""
+    out = []
+    for no, raw in enumerate(text.splitlines(), 1):
+        line = raw.strip("\r\n")
+        if not line.strip() or line.lstrip().startswith("#"):
+            continue
+        parts = line.split("\t")
+        if len(parts) != 2 or not parts[0].strip() or not parts[1].strip():
+            raise PairListError(no, "expected `ref<TAB>dist`")
+        out.append((no, os.path.join(base_dir, parts[0].strip()), os.path.join(base_dir, parts[1].strip())))
+    return out
+
+
+def score_pairs(scorer, pairs: Sequence[Tuple[int, str, str]], batch: int = DEFAULT_BATCH,
+                load: Callable[[str], np.ndarray] = load_rgb8):
+    """Score `pairs` ([(line, ref path, dist path)]) with `scorer.score_batch(refs, dists)`: pairs grouped by frame
+    size in order of first appearance, each group in batches of at most `batch`, frames loaded one batch at a time.
+    -> [(line, ref, dist, w, h, score)] in input order.  A file that is missing or unreadable, or a pair whose frames
+    differ in size, raises PairListError with the pair's line before anything is scored."""
+    if batch < 1:
+        raise ValueError("batch must be at least 1")
+    sizes = []
+    for line, rp, dp in pairs:   # sizes first: a bad line is reported before any GPU work
+        shapes = []
+        for path in (rp, dp):
+            if not os.path.isfile(path):
+                raise PairListError(line, f"no such file: {path}")
+            try:
+                shapes.append(load(path).shape)
+            except Exception as e:   # a decoder's own error, with the line that names the file
+                raise PairListError(line, f"cannot read {path}: {e}") from e
+        if shapes[0] != shapes[1]:
+            raise PairListError(line, f"ref is {shapes[0][1]}x{shapes[0][0]}, dist is {shapes[1][1]}x{shapes[1][0]}")
+        sizes.append(shapes[0])
+    groups = {}
+    for i, shape in enumerate(sizes):
+        groups.setdefault(shape, []).append(i)
+    scores = [None] * len(pairs)
+    for shape, members in groups.items():
+        for at in range(0, len(members), batch):
+            chunk = members[at:at + batch]
+            refs = [load(pairs[i][1]) for i in chunk]
+            dists = [load(pairs[i][2]) for i in chunk]
+            got = scorer.score_batch(refs, dists)
+            if len(got) != len(chunk):
+                raise RuntimeError("score_batch returned the wrong number of scores")
+            for i, s in zip(chunk, got):
+                scores[i] = float(s)
+    return [(line, rp, dp, sizes[i][1], sizes[i][0], scores[i]) for i, (line, rp, dp) in enumerate(pairs)]
+
+
+def write_csv(rows, f) -> None:
+    wr = csv.writer(f, lineterminator="\n")
+    wr.writerow(["line", "ref", "dist", "width", "height", "score"])
+    for line, rp, dp, w, h, score in rows:
+        wr.writerow([line, rp, dp, w, h, repr(score)])
+
+
+def main(argv=None, scorer=None) -> int:
+    args = list(sys.argv[1:] if argv is None else argv)
+    batch, device, pos = DEFAULT_BATCH, 0, []
+    i = 0
+    while i < len(args):
+        if args[i] in ("--batch", "--device"):
+            if i + 1 >= len(args) or not args[i + 1].lstrip("-").isdigit():
+                print(f"{args[i]} needs an integer", file=sys.stderr)
+                return 2
+            if args[i] == "--batch":
+                batch = int(args[i + 1])
+            else:
+                device = int(args[i + 1])
+            i += 2
+        else:
+            pos.append(args[i])
+            i += 1
+    if len(pos) != 2 or batch < 1:
+        print("usage: python -m oavif_amd.scorepairs PAIRS.tsv OUT.csv [--batch B] [--device D]", file=sys.stderr)
+        return 2
+    from . import _lib
+    batch = min(batch, _lib.MAX_BATCH)
+    try:
+        pairs = parse_pairs(open(pos[0]).read(), os.path.dirname(os.path.abspath(pos[0])))
+    except (OSError, PairListError) as e:
+        print(f"{pos[0]}: {e}", file=sys.stderr)
+        return 1
+    own = scorer is None
+    if own:
+        from .scorer import Ssimu2
+        scorer = Ssimu2(device)
+    try:
+        rows = score_pairs(scorer, pairs, batch)
+    except PairListError as e:
+        print(f"{pos[0]}: {e}", file=sys.stderr)
+        return 1
+    finally:
+        if own:
+            scorer.close()
+    with open(pos[1], "w", newline="") as f:
+        write_csv(rows, f)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -385,6 +385,96 @@ class Ssimu2:
             self._raise(rc)
         return out.value
 
+    # -- batch scoring (include/ssimu2_hip.h "Batch scoring", DESIGN.md section 11) -----------------
+    @staticmethod
+    def _check_batch(frames, name: str):
+        """[N, h, w, 3] uint8 or a sequence of (h, w, 3) uint8 -> list of contiguous frames of one size."""
+        out = [_check_rgb8(f, f"{name}[{i}]") for i, f in enumerate(frames)]
+        if any(f.shape != out[0].shape for f in out):
+            raise ValueError(f"{name}: the frames of a batch must have one size")
+        return out
+
+    @staticmethod
+    def _ptr_array(frames):
+        return (ctypes.POINTER(ctypes.c_uint8) * len(frames))(*[_u8p(f) for f in frames])
+
+    def score_batch(self, refs, dists) -> np.ndarray:
+        """ssimu2_score_batch_rgb8: N pairs of one size in one launch set -> float64 scores in input order.
+        A cached reference is kept."""
+        refs, dists = self._check_batch(refs, "refs"), self._check_batch(dists, "dists")
+        if len(refs) != len(dists):
+            raise ValueError("refs and dists must hold the same number of frames")
+        out = np.zeros(len(refs), np.float64)
+        if not refs:
+            return out
+        if refs[0].shape != dists[0].shape:
+            raise ValueError("refs and dists must have the same shape")
+        h, w, _ = refs[0].shape
+        rc = self._L.ssimu2_score_batch_rgb8(self._ctx, self._ptr_array(refs), self._ptr_array(dists), len(refs), w, h,
+                                             out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        if rc != 0:
+            self._raise(rc)
+        return out
+
+    def score_batch_against_reference(self, dists) -> np.ndarray:
+        """ssimu2_score_batch_against_reference: N distorted frames against the cached reference (kept)."""
+        dists = self._check_batch(dists, "dists")
+        out = np.zeros(len(dists), np.float64)
+        if not dists:
+            return out
+        if getattr(self, "_ref_shape", None) is not None and dists[0].shape != self._ref_shape:
+            raise ValueError("dist shape differs from the reference's")
+        rc = self._L.ssimu2_score_batch_against_reference(self._ctx, self._ptr_array(dists), len(dists),
+                                                          out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        if rc != 0:
+            self._raise(rc)
+        return out
+
+    def score_batch_device(self, d_refs: int, d_dists: int, item_stride_bytes: int, n: int, w: int, h: int) -> np.ndarray:
+        """ssimu2_score_batch_rgb8_device: item i at d_refs + i * item_stride_bytes / d_dists + i * item_stride_bytes."""
+        out = np.zeros(int(n), np.float64)
+        rc = self._L.ssimu2_score_batch_rgb8_device(self._ctx, ctypes.c_void_p(d_refs), ctypes.c_void_p(d_dists),
+                                                    int(item_stride_bytes), int(n), w, h,
+                                                    out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        if rc != 0:
+            self._raise(rc)
+        return out
+
+    def score_batch_against_reference_device(self, d_dists: int, item_stride_bytes: int, n: int) -> np.ndarray:
+        """ssimu2_score_batch_against_reference_device against the reference of set_reference / set_reference_device."""
+        out = np.zeros(int(n), np.float64)
+        rc = self._L.ssimu2_score_batch_against_reference_device(self._ctx, ctypes.c_void_p(d_dists), int(item_stride_bytes),
+                                                                 int(n), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        if rc != 0:
+            self._raise(rc)
+        return out
+
+    def last_batch_averages(self, item: int):
+        """-> ((6, 18) float64 plane averages of `item` of the last batch, number of scales)."""
+        avg = np.zeros(_lib.NUM_SCALES * _lib.STATS_PER_SCALE, np.float64)
+        ns = ctypes.c_int()
+        rc = self._L.ssimu2_last_batch_averages(self._ctx, int(item), avg.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                ctypes.byref(ns))
+        if rc != 0:
+            self._raise(rc)
+        return avg.reshape(_lib.NUM_SCALES, _lib.STATS_PER_SCALE), ns.value
+
+    def set_batch_segment_rows(self, rows_scale0: int) -> None:
+        """Instrumented build: scale-0 rows of a batch item (0 = the rule, -1 = the single-score rule, 8..160)."""
+        self._need_instr()
+        rc = self._L.ssimu2_instr_set_batch_segment_rows(self._ctx, int(rows_scale0))
+        if rc != 0:
+            self._raise(rc)
+
+    def batch_segment_rows(self, w: int, h: int, scale: int) -> int:
+        """Instrumented build: rows per workgroup a batch item of w x h gets at `scale` (ssimu2_instr_batch_segment_rows)."""
+        self._need_instr()
+        rows = ctypes.c_int()
+        rc = self._L.ssimu2_instr_batch_segment_rows(self._ctx, int(w), int(h), int(scale), ctypes.byref(rows))
+        if rc != 0:
+            self._raise(rc)
+        return int(rows.value)
+
     # -- measurement / parity hooks: instrumented build only ------------------------------------
     def _need_instr(self):
         if not self.instrumented:

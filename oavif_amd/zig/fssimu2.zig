@@ -42,6 +42,8 @@ extern fn ssimu2_error_map_against_reference(ctx: ?*Ctx, dist: [*]const u8, out_
 extern fn ssimu2_score_against_reference_strided(ctx: ?*Ctx, pixels: [*]const u8, row_bytes: u32, channels: u32, out_score: *f64) c_int;
 extern fn ssimu2_score_rgb16(ctx: ?*Ctx, ref: [*]const u16, dist: [*]const u16, w: u32, h: u32, channels: u32, bit_depth: u32, out_score: *f64) c_int;
 extern fn ssimu2_score_against_reference_strided16(ctx: ?*Ctx, pixels: [*]const u16, row_bytes: u32, channels: u32, bit_depth: u32, out_score: *f64) c_int;
+extern fn ssimu2_score_batch_rgb8(ctx: ?*Ctx, refs: [*]const [*]const u8, dists: [*]const [*]const u8, n: u32, w: u32, h: u32, out_scores: [*]f64) c_int;
+extern fn ssimu2_score_batch_against_reference(ctx: ?*Ctx, dists: [*]const [*]const u8, n: u32, out_scores: [*]f64) c_int;
 extern fn ssimu2_host_alloc(ctx: ?*Ctx, bytes: usize, out_ptr: *?*anyopaque) c_int;
 extern fn ssimu2_host_free(ctx: ?*Ctx, ptr: ?*anyopaque) c_int;
 
@@ -338,4 +340,76 @@ pub fn computeSsimu2DecodedHbd(
     var score: f64 = 0;
     try check(ssimu2_score_against_reference_strided16(ctx, pixels, row_bytes, src_channels, bit_depth, &score));
     return score;
+}
+
+var g_batch_ctx: ?*Ctx = null;
+
+// Batches run in the FIR mode only (include/ssimu2_hip.h "Batch scoring"), whatever `blur` the search path uses:
+// they get a context of their own, which a bare ssimu2_ctx_create leaves in SSIMU2_BLUR_FIR.
+fn batchContext() Error!*Ctx {
+    if (g_batch_ctx) |c| return c;
+    var c: ?*Ctx = null;
+    try check(ssimu2_ctx_create(device, null, &c));
+    g_batch_ctx = c;
+    return c.?;
+}
+
+/// Release the batch context (optional, as deinit()).
+pub fn deinitBatch() void {
+    if (g_batch_ctx) |c| ssimu2_ctx_destroy(c);
+    g_batch_ctx = null;
+}
+
+/// Score `references.len` pairs of ONE size in one launch set (ssimu2_score_batch_rgb8): a corpus of thumbnails, tiles
+/// or video frames, where a single small score cannot fill the GPU.  `scores` receives one score per pair in input
+/// order, each independent of the batch it travelled in.  8-bit RGB, SSIMU2_BLUR_FIR; at most 4096 pairs per call
+/// (SSIMU2_MAX_BATCH).  `allocator` holds the two pointer arrays for the duration of the call.
+pub fn computeSsimu2Batch(
+    allocator: std.mem.Allocator,
+    references: []const []const u8,
+    distorted: []const []const u8,
+    width: u32,
+    height: u32,
+    scores: []f64,
+) Error!void {
+    const n = references.len;
+    if (distorted.len != n or scores.len < n or n > 4096) return Error.InvalidArgument;
+    if (n == 0) return;
+    const need: usize = @as(usize, width) * @as(usize, height) * 3;
+    const refs = allocator.alloc([*]const u8, n) catch return Error.OutOfMemory;
+    defer allocator.free(refs);
+    const dists = allocator.alloc([*]const u8, n) catch return Error.OutOfMemory;
+    defer allocator.free(dists);
+    for (references, distorted, 0..) |r, d, i| {
+        if (r.len < need or d.len < need) return Error.InvalidArgument;
+        refs[i] = r.ptr;
+        dists[i] = d.ptr;
+    }
+    const ctx = try batchContext();
+    try check(ssimu2_score_batch_rgb8(ctx, refs.ptr, dists.ptr, @intCast(n), width, height, scores.ptr));
+}
+
+/// Several probes of one image in one launch set (ssimu2_score_batch_against_reference): `reference` is uploaded and
+/// cached on the batch context as computeSsimu2 caches it, every frame of `distorted` is scored against it.
+pub fn computeSsimu2BatchAgainst(
+    allocator: std.mem.Allocator,
+    reference: []const u8,
+    distorted: []const []const u8,
+    width: u32,
+    height: u32,
+    scores: []f64,
+) Error!void {
+    const n = distorted.len;
+    const need: usize = @as(usize, width) * @as(usize, height) * 3;
+    if (reference.len < need or scores.len < n or n > 4096) return Error.InvalidArgument;
+    if (n == 0) return;
+    const dists = allocator.alloc([*]const u8, n) catch return Error.OutOfMemory;
+    defer allocator.free(dists);
+    for (distorted, 0..) |d, i| {
+        if (d.len < need) return Error.InvalidArgument;
+        dists[i] = d.ptr;
+    }
+    const ctx = try batchContext();
+    try check(ssimu2_set_reference(ctx, reference.ptr, width, height));
+    try check(ssimu2_score_batch_against_reference(ctx, dists.ptr, @intCast(n), scores.ptr));
 }
