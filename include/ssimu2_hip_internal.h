@@ -72,6 +72,19 @@ int ssimu2_measure_read_stream(ssimu2_ctx* ctx, size_t bytes, int iters, double*
    ssimu2_set_reference also caches blur(ref*ref). */
 int ssimu2_instr_set_segment_rows(ssimu2_ctx* ctx, int rows_scale0, int rows_other_scales);
 int ssimu2_instr_cache_reference_blur(ssimu2_ctx* ctx, int enabled);
+/* Which marching kernel the context's last score or batch launched (read-only; a frame below 8 x 8 launches none).
+   With the reference's blur cache off (above), or when its allocation failed, a pass against the reference runs
+   k_march / k_march_batch instead of k_march_refblur / k_march_refblur_batch: this is how a test sees which ran. */
+enum {
+    SSIMU2_MARCH_NONE = 0,
+    SSIMU2_MARCH_PAIR_U8 = 1,          /* k_march */
+    SSIMU2_MARCH_REFBLUR_U8 = 2,       /* k_march_refblur */
+    SSIMU2_MARCH_PAIR_LIN = 3,         /* k_march_lin */
+    SSIMU2_MARCH_REFBLUR_LIN = 4,      /* k_march_refblur_lin */
+    SSIMU2_MARCH_PAIR_BATCH = 5,       /* k_march_batch */
+    SSIMU2_MARCH_REFBLUR_BATCH = 6     /* k_march_refblur_batch */
+};
+int ssimu2_instr_last_march(ssimu2_ctx* ctx, int* out_kind);
 /* Batch scoring (ssimu2_score_batch_*): the scale-0 segment rows of a batch item.  0 = the library's rule (96 rows),
    -1 = the single-score rule of the frame size (~512 workgroups), 8..160 = that many rows; the other scales follow
    with at most 48.  For the tiling A/B of scripts/gpu_batch_bench.py.  ssimu2_instr_batch_segment_rows returns the

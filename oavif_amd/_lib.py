@@ -115,7 +115,8 @@ INSTR_SYMBOLS = ("ssimu2_debug_download", "ssimu2_time_device", "ssimu2_time_sta
                  "ssimu2_instr_set_segment_rows", "ssimu2_instr_cache_reference_blur",
                  "ssimu2_instr_rg_stop_after_scale", "ssimu2_time_blur_stage_rotating",
                  "ssimu2_instr_placed_streams", "ssimu2_time_kernels",
-                 "ssimu2_instr_set_batch_segment_rows", "ssimu2_instr_batch_segment_rows")
+                 "ssimu2_instr_set_batch_segment_rows", "ssimu2_instr_batch_segment_rows",
+                 "ssimu2_instr_last_march")
 
 TQ_MAX_FANOUT = 16
 BATCH_PROBE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
@@ -248,6 +249,7 @@ def _load(path: str, instrumented: bool) -> ctypes.CDLL:
                                            ctypes.POINTER(ctypes.c_float)],
             "ssimu2_instr_set_segment_rows": [vp, ci, ci],
             "ssimu2_instr_cache_reference_blur": [vp, ci],
+            "ssimu2_instr_last_march": [vp, ctypes.POINTER(ci)],
             "ssimu2_instr_rg_stop_after_scale": [vp, ci],
             "ssimu2_instr_placed_streams": [vp, ctypes.POINTER(ci)],
             "ssimu2_time_blur_stage_rotating": [vp, ctypes.POINTER(vp), ci, u32, u32, ci,

@@ -222,6 +222,7 @@ struct ssimu2_ctx {
     // the frame size whose scale-0 planes d_lin0_ref / d_lin0_dist hold for the last score or reference (0: none;
     // for ssimu2_debug_download at scale 0)
     uint32_t lin0_ref_w = 0, lin0_ref_h = 0, lin0_dist_w = 0, lin0_dist_h = 0;
+    int last_march = 0;  // SSIMU2_MARCH_* of the last score or batch (ssimu2_instr_last_march)
 #endif
 
     int fail(int code, const char* what, hipError_t e = hipSuccess) {
@@ -283,6 +284,16 @@ inline void note_lin0(ssimu2_ctx* c, int ref, int dist, uint32_t w, uint32_t h) 
     }
 #else
     (void)c, (void)ref, (void)dist, (void)w, (void)h;
+#endif
+}
+
+// Instrumented build: which marching kernel the score or batch being enqueued launches (SSIMU2_MARCH_* of
+// include/ssimu2_hip_internal.h, 0 = none).  Nothing in the product library.
+inline void note_march(ssimu2_ctx* c, int kind) {
+#ifdef SSIMU2_INSTRUMENTED_BUILD
+    c->last_march = kind;
+#else
+    (void)c, (void)kind;
 #endif
 }
 
@@ -790,6 +801,7 @@ int enqueue_score(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, ui
     FinalizeArgs fa;
     int blocks = 0;
     build_plans(c, p, d_ref, d_dist, ref_pyramid_ready && c->d_xyb_ref != nullptr, &mp, &fa, &blocks);
+    note_march(c, blocks <= 0 ? 0 : mp.ref_s11[0] ? 2 : 1);
     if (blocks > 0) {
         if (mp.ref_s11[0])  // reference XYB and blur(ref*ref) cached: the search's per-pass kernel
             launch(k_march_refblur, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
@@ -841,6 +853,7 @@ int enqueue_score16(ssimu2_ctx* c, const Src16* ref, const Src16& dist, uint32_t
     FinalizeArgs fa;
     int blocks = 0;
     build_plans(c, p, (const uint8_t*)c->d_lin0_ref, (const uint8_t*)c->d_lin0_dist, cached, &mp, &fa, &blocks);
+    note_march(c, blocks <= 0 ? 0 : cached ? 4 : 3);
     if (blocks > 0) {
         if (cached) launch(k_march_refblur_lin, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
         else launch(k_march_lin, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
@@ -1130,6 +1143,7 @@ int batch_run(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dists, size
         pb.out_stride = lin_stride;
         launch(k_pyramid_bands_batch, dim3((unsigned)(bands * nframes * n)), dim3(PYR_THREADS), 0, c->stream, pb);
     }
+    note_march(c, blocks <= 0 ? 0 : cached ? 6 : 5);
     if (blocks > 0) {
         if (cached) launch(k_march_refblur_batch, dim3((unsigned)(blocks * n)), dim3(MARCH_THREADS), 0, c->stream, bp);
         else launch(k_march_batch, dim3((unsigned)(blocks * n)), dim3(MARCH_THREADS), 0, c->stream, bp);

@@ -92,6 +92,12 @@ int ssimu2_instr_cache_reference_blur(ssimu2_ctx* c, int enabled) {
     return SSIMU2_OK;
 }
 
+int ssimu2_instr_last_march(ssimu2_ctx* c, int* out_kind) {
+    if (!c || !out_kind) return SSIMU2_ERR_INVALID_ARG;
+    *out_kind = c->last_march;
+    return SSIMU2_OK;
+}
+
 int ssimu2_debug_download(ssimu2_ctx* c, int what, int scale, uint32_t w, uint32_t h, float* out,
                           uint32_t* out_w, uint32_t* out_h) {
     if (!c || !out) return SSIMU2_ERR_INVALID_ARG;

@@ -620,6 +620,19 @@ class Ssimu2:
         if rc != 0:
             self._raise(rc)
 
+    MARCH_KERNELS = (None, "k_march", "k_march_refblur", "k_march_lin", "k_march_refblur_lin", "k_march_batch",
+                     "k_march_refblur_batch")
+
+    def last_march(self):
+        """Instrumented build: the marching kernel the last score or batch launched (ssimu2_instr_last_march), by name;
+        None when it launched none (a frame below 8 x 8)."""
+        self._need_instr()
+        kind = ctypes.c_int()
+        rc = self._L.ssimu2_instr_last_march(self._ctx, ctypes.byref(kind))
+        if rc != 0:
+            self._raise(rc)
+        return self.MARCH_KERNELS[kind.value]
+
     def last_averages(self):
         """-> ((6, 18) float64 plane averages of the last score, number of scales)."""
         avg = np.zeros(_lib.NUM_SCALES * _lib.STATS_PER_SCALE, np.float64)

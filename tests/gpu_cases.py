@@ -1,11 +1,13 @@
 """Test-side helpers shared by the GPU modules: the blur-mode table (scorer mode -> the checker's mode of the same
 blur), synthetic content kinds, libavif-like padded RGB(A) layouts, the hold of a score's averages and of k_finalize
-to the kernel-order terms (check_against_terms) and the error-map check against tests/errmap_ref.py (check_map)."""
+to the kernel-order terms (check_against_terms), the error-map check against tests/errmap_ref.py (check_map), and
+what the batch modules share: the batch rule's rows and bound, seeded neighbours and the comparison of score and
+averages for bits."""
 from __future__ import annotations
 
 import numpy as np
 
-from oavif_amd import _lib
+from oavif_amd import _lib, synth
 from oracle import ssimu2_oracle as orc
 
 import errmap_ref
@@ -189,6 +191,71 @@ def check_map(oracle, m, avg, ns, ref, dist, blur, what):
 def same_bits(got, exp, what):
     assert got.shape == exp.shape and got.dtype == exp.dtype == np.float32, (what, got.shape, exp.shape)
     assert np.array_equal(got.view(np.uint32), exp.view(np.uint32)), what
+
+
+# ---- batch scoring (tests/test_gpu_score_batch.py, tests/test_gpu_batch_items.py) --------------------------------
+KINDS = ("gradient", "primaries", "checker", "text", "noise")
+
+
+def batch_seg_rows(w, h, scale):
+    """batch_seg_rows of oavif_amd/csrc/ssimu2_hip.hip: a function of the scale alone."""
+    return 96 if scale == 0 else 48
+
+
+def batch_rtol(w, h, scale):
+    """fir_rtol's formula at the batch rule's rows (derivation: tests/test_gpu_score_batch.py's docstring)."""
+    sw, sh = w, h
+    for _ in range(scale):
+        sw, sh = (sw + 1) // 2, (sh + 1) // 2
+    return (min(batch_seg_rows(w, h, scale), sh) + 3) * 2.0 ** -24 + sw * sh * 2.0 ** -53
+
+
+def bits_equal(score_a, avg_a, score_b, avg_b, what):
+    """Score and all 108 averages: the same bits (same_bits over the doubles' 32-bit halves)."""
+    a = np.concatenate([[score_a], np.asarray(avg_a, np.float64).ravel()])
+    b = np.concatenate([[score_b], np.asarray(avg_b, np.float64).ravel()])
+    same_bits(np.ascontiguousarray(a).view(np.float32), np.ascontiguousarray(b).view(np.float32), what)
+
+
+def damaged(ref, seed):
+    kind, strength = (("blockq", 4), ("noise", 3), ("blur", 2), ("blockq", 1))[seed % 4]
+    return synth.distort(ref, kind, strength, seed=seed)
+
+
+def neighbours(w, h, n, seed):
+    """n seeded pairs of every content kind, some identical, some heavily damaged."""
+    refs, dists = [], []
+    for k in range(n):
+        r = content(KINDS[(k + seed) % len(KINDS)], w, h, seed * 100 + k)
+        refs.append(r)
+        dists.append(r.copy() if k % 5 == 4 else damaged(r, seed + k))
+    if n >= 8:
+        dists[0] = 255 - refs[0]   # as damaged as a frame gets
+    return refs, dists
+
+
+def check_item_against_kavg(oracle, score, avg, ns, w, h, kavg, what):
+    """A batch item's score and averages over `ns` scales of a w x h frame: k_finalize_batch against
+    oracle.score_from_averages(avg) to FINALIZE_TOL, every average against the kernel-order averages `kavg` to
+    batch_rtol, exactly 0 where the reference is 0.  -> the largest deviation in units of its bound."""
+    if ns == 0:
+        assert score == 100.0 and not avg.any(), what
+        return 0.0
+    host = oracle.score_from_averages(avg, ns)
+    print(f"measured: {what}: finalize {abs(score - host):.1e}")
+    assert abs(score - host) <= FINALIZE_TOL, (what, score, host)
+    assert avg.shape == kavg.shape == (6, 18), what
+    worst = 0.0
+    for s in range(6):
+        got, exp = avg[s], kavg[s]
+        assert np.array_equal(got == 0, exp == 0), (what, s, got, exp)
+        if s >= ns:
+            continue
+        dev = np.abs(got - exp) / np.where(exp == 0, 1.0, exp)
+        print(f"measured: {what} scale {s}: {float(dev.max()):.3e} (bound {batch_rtol(w, h, s):.3e})")
+        assert (dev <= batch_rtol(w, h, s)).all(), (what, s, int(np.argmax(dev)), float(dev.max()), batch_rtol(w, h, s))
+        worst = max(worst, float(dev.max()) / batch_rtol(w, h, s))
+    return worst
 
 
 def rg_planes(oracle, blur, xa, xb):

@@ -67,7 +67,9 @@ def terms(orc, lin1, lin2, blur):
 
 def compute(orc, ref: np.ndarray, dist: np.ndarray, d: int, blur: int, d_dist: int | None = None):
     """-> (score, (6, 18) averages, nscales) of two uint16 frames of d bits (`d_dist`: the distorted frame's own
-    depth) in the checker's blur mode `blur`."""
+    depth) in the checker's blur mode `blur`.  The averages are errmap_ref.averages(terms(...)): the fp64 means (sums
+    in extended precision) of the fp32 terms in the kernels' order, i.e. the `kavg` gpu_cases.check_against_terms
+    holds a device score's averages to -- a caller needs no second pass over the terms for them."""
     tm = terms(orc, linear_planes(ref, d), linear_planes(dist, d if d_dist is None else d_dist), blur)
     avg = errmap_ref.averages(tm)
     ns = len(tm)

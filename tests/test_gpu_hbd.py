@@ -1,6 +1,11 @@
 """16-bit scorer input on the MI355X (ssimu2_*_rgb16 / _strided16), in all three blur modes:
 bit identity with the 8-bit path on 257*u frames, mixed depths against a cached reference, the strided hand-off,
-clamping, genuine 10/12/16-bit content against tests/hbd_ref.py and the fp64 counterpart, and the context lifecycle."""
+clamping, genuine 10/12/16-bit content against tests/hbd_ref.py and the fp64 counterpart, and the context lifecycle.
+
+Genuine 16-bit content is also held to the kernel-order terms (gpu_cases.check_against_terms): hbd_ref.compute's
+averages ARE errmap_ref.averages(hbd_ref.terms(...)), the fp64 means of the fp32 terms k_march_lin /
+k_march_refblur_lin sum, so the derived bounds of tests/gpu_cases.py apply unchanged -- RTOL_RECURSIVE in the recursive
+modes, fir_rtol in FIR (k_march_lin shares march_v and the segment rule with k_march), FINALIZE_TOL for k_finalize."""
 import numpy as np
 import pytest
 
@@ -104,7 +109,7 @@ def hbd_distort(img, depth, seed):
 def test_genuine_high_bit_depth_content_against_the_checker(ctxs, oracle, mode):
     s = ctxs[mode]
     blur = gpu_cases.MODES[mode][1]
-    k = 0
+    k, worst = 0, 0.0
     for depth in (10, 12, 16):
         for kind in ["hgradient", "hnoise"] + KINDS:
             w, h = [(256, 192), (333, 217), (129, 41)][k % 3]
@@ -120,7 +125,10 @@ def test_genuine_high_bit_depth_content_against_the_checker(ctxs, oracle, mode):
             # white noise and flat or saturated content: fp32 cancellation noise is as large as the averages there,
             # so fp64_checks' "synthetic" bounds (every weighted average absolutely, the score loosely) apply
             fp64_checks.check(got, avg, ns, exp64, mode, (mode, depth, kind), "synthetic")
+            worst = max(worst, gpu_cases.check_against_terms(oracle, got, avg, ns, ref, dist, mode,
+                                                             f"{mode} {depth}-bit {kind} {w}x{h}", kavg=avg_r))
             k += 1
+    print(f"measured: genuine 16-bit content, {mode}: worst average {worst:.3e} of its bound")
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -154,19 +162,25 @@ def test_mixed_depths(ctxs, oracle, mode):
     assert ns == ns_r and abs(got - exp) <= gpu_cases.score_tol(exp), (mode, got, exp)
     assert np.allclose(avg, avg_r, rtol=gpu_cases.RTOL_AVG, atol=gpu_cases.ATOL_AVG), mode
     fp64_checks.check(got, avg, ns, hbd_ref.compute_fp64(r12, d10, 12, d_dist=10), mode, (mode, "12/10"), "synthetic")
+    gpu_cases.check_against_terms(oracle, got, avg, ns, r12, d10, mode, f"{mode} 10-bit frame, 12-bit reference", kavg=avg_r)
     with pytest.raises(Ssimu2Error) as ei:
         s.error_map_against_reference(d8)
     assert ei.value.code == _lib.ERR_UNSUPPORTED
 
 
 @pytest.mark.parametrize("mode", MODES)
-def test_strided_hand_off_equals_the_tight_call(ctxs, mode):
+def test_strided_hand_off_equals_the_tight_call(ctxs, oracle, mode):
     s = ctxs[mode]
     for k, (w, h) in enumerate([(333, 217), (120, 40), (121, 41), (1921, 1083), (8, 8)]):
         ref = hbd_content("text", w, h, 10, seed=k)
         dist = hbd_distort(ref, 10, seed=k + 1)
         s.set_reference_hbd(ref, 10)
         exp = (s.score_against_reference_hbd(dist, 10), s.last_averages())
+        if k == 0:   # the hand-offs below equal the tight call in bits: one value check anchors them all
+            _score, kavg, ns_r = hbd_ref.compute(oracle, ref, dist, 10, gpu_cases.MODES[mode][1])
+            assert ns_r == exp[1][1]
+            gpu_cases.check_against_terms(oracle, exp[0], exp[1][0], ns_r, ref, dist, mode,
+                                          f"{mode} tight 10-bit call {w}x{h}", kavg=kavg)
         for ch, pad in ((3, 0), (3, 7), (4, 0), (4, 12)):
             buf, view = decoded_like16(dist, ch, pad, seed=k + ch)
             assert_same(s, s.score_decoded_against_reference_hbd(view, bit_depth=10), exp, (mode, w, h, ch, pad))

@@ -26,43 +26,7 @@ import gpu_cases  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-KINDS = ("gradient", "primaries", "checker", "text", "noise")
-
-
-def batch_seg_rows(w, h, scale):
-    """batch_seg_rows of oavif_amd/csrc/ssimu2_hip.hip: a function of the scale alone."""
-    return 96 if scale == 0 else 48
-
-
-def batch_rtol(w, h, scale):
-    sw, sh = w, h
-    for _ in range(scale):
-        sw, sh = (sw + 1) // 2, (sh + 1) // 2
-    return (min(batch_seg_rows(w, h, scale), sh) + 3) * 2.0 ** -24 + sw * sh * 2.0 ** -53
-
-
-def bits_equal(score_a, avg_a, score_b, avg_b, what):
-    """Score and all 108 averages: the same bits (gpu_cases.same_bits over the doubles' 32-bit halves)."""
-    a = np.concatenate([[score_a], np.asarray(avg_a, np.float64).ravel()])
-    b = np.concatenate([[score_b], np.asarray(avg_b, np.float64).ravel()])
-    gpu_cases.same_bits(np.ascontiguousarray(a).view(np.float32), np.ascontiguousarray(b).view(np.float32), what)
-
-
-def damaged(ref, seed):
-    kind, strength = (("blockq", 4), ("noise", 3), ("blur", 2), ("blockq", 1))[seed % 4]
-    return synth.distort(ref, kind, strength, seed=seed)
-
-
-def neighbours(w, h, n, seed):
-    """n seeded pairs of every content kind, some identical, some heavily damaged."""
-    refs, dists = [], []
-    for k in range(n):
-        r = gpu_cases.content(KINDS[(k + seed) % len(KINDS)], w, h, seed * 100 + k)
-        refs.append(r)
-        dists.append(r.copy() if k % 5 == 4 else damaged(r, seed + k))
-    if n >= 8:
-        dists[0] = 255 - refs[0]   # as damaged as a frame gets
-    return refs, dists
+from gpu_cases import KINDS, batch_rtol, batch_seg_rows, bits_equal, damaged, neighbours  # noqa: E402
 
 
 def check_item_against_terms(oracle, score, avg, ns, ref, dist, what):
@@ -71,19 +35,9 @@ def check_item_against_terms(oracle, score, avg, ns, ref, dist, what):
     if ns == 0:
         assert score == 100.0 and not avg.any(), what
         return
-    host = oracle.score_from_averages(avg, ns)
-    print(f"measured: {what}: finalize {abs(score - host):.1e}")
-    assert abs(score - host) <= gpu_cases.FINALIZE_TOL, (what, score, host)
     kavg, ns_r = errmap_ref.kernel_averages(oracle, ref, dist, gpu_cases.MODES["fir"][1])
-    assert ns_r == ns and avg.shape == kavg.shape == (6, 18), what
-    for s in range(6):
-        got, exp = avg[s], kavg[s]
-        assert np.array_equal(got == 0, exp == 0), (what, s, got, exp)
-        if s >= ns:
-            continue
-        dev = np.abs(got - exp) / np.where(exp == 0, 1.0, exp)
-        print(f"measured: {what} scale {s}: {float(dev.max()):.3e} (bound {batch_rtol(w, h, s):.3e})")
-        assert (dev <= batch_rtol(w, h, s)).all(), (what, s, int(np.argmax(dev)), float(dev.max()), batch_rtol(w, h, s))
+    assert ns_r == ns, what
+    gpu_cases.check_item_against_kavg(oracle, score, avg, ns, w, h, kavg, what)
 
 
 def item_in_batches(s, ref, dist, cached, placements=((0, 1), (3, 7), (31, 32), (5, 64))):

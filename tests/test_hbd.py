@@ -76,6 +76,26 @@ def test_cpu_reference_on_257u_frames_is_the_checker(oracle, blur):
         assert got8 == got and np.array_equal(avg8, avg)
 
 
+@pytest.mark.parametrize("blur", ["fir", "iir"])
+def test_cpu_reference_averages_are_the_kernel_order_terms_averages(oracle, blur):
+    """hbd_ref.compute's averages are errmap_ref.averages(hbd_ref.terms(...)) bit for bit (what the GPU tests pass to
+    gpu_cases.check_against_terms as kavg), at the frames' own depths; on 257 u frames they are the 8-bit path's
+    errmap_ref.kernel_averages."""
+    import errmap_ref
+    mode = oracle.BLUR_FIR if blur == "fir" else oracle.BLUR_IIR
+    rng = np.random.default_rng(5)
+    r12 = rng.integers(0, 4096, (41, 67, 3)).astype(np.uint16)
+    d10 = np.minimum(r12 // 4 + rng.integers(0, 9, r12.shape), 1023).astype(np.uint16)
+    score, avg, ns = hbd_ref.compute(oracle, r12, d10, 12, mode, d_dist=10)
+    tm = hbd_ref.terms(oracle, hbd_ref.linear_planes(r12, 12), hbd_ref.linear_planes(d10, 10), mode)
+    assert ns == len(tm) == 4 and np.array_equal(avg, errmap_ref.averages(tm))
+    assert score == oracle.score_from_averages(avg, ns) and avg[:ns].any() and not avg[ns:].any()
+    ref, dist = _frames(67, 41, 3)
+    _, avg16, ns16 = hbd_ref.compute(oracle, ref.astype(np.uint16) * 257, dist.astype(np.uint16) * 257, 16, mode)
+    kavg, ns8 = errmap_ref.kernel_averages(oracle, ref, dist, mode)
+    assert ns16 == ns8 and np.array_equal(avg16, kavg)
+
+
 def test_fp64_counterpart_on_257u_frames():
     ref, dist = _frames(80, 56, 7)
     exp = ref64.evaluate(ref, dist)
