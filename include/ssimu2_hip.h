@@ -192,7 +192,10 @@ int ssimu2_score_against_reference_strided(ssimu2_ctx* ctx, const uint8_t* pixel
    valid on the ctx's device.  _enqueue only enqueues on the ctx stream and returns;
    ssimu2_wait blocks until the enqueued score is done and returns it.  Used by the
    batch driver and bench.py (inputs already in HBM), and for fanning speculative
-   quantizer probes over several ctxs/streams. */
+   quantizer probes over several ctxs/streams.
+   ssimu2_wait with nothing enqueued on the ctx returns SSIMU2_ERR_INVALID_ARG.
+   Between an _enqueue and its ssimu2_wait, ssimu2_ctx_set_blur returns SSIMU2_ERR_INVALID_ARG and changes
+   nothing (mode and cached reference stay; the ssimu2_wait that follows returns the score). */
 int ssimu2_score_rgb8_device(ssimu2_ctx* ctx, const void* d_ref, const void* d_dist,
                              uint32_t w, uint32_t h, double* out_score);
 int ssimu2_enqueue_rgb8_device(ssimu2_ctx* ctx, const void* d_ref, const void* d_dist,
