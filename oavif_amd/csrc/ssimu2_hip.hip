@@ -5,18 +5,21 @@
 // (fssimu2 0.1.1 source is absent from the reference tree; the arithmetic follows the
 // published SSIMULACRA2 v2.1 definition, see DESIGN.md "Oracle").
 //
-// Data layout in HBM (all per ctx, allocated once for the largest frame seen):
-//   u8  frames  : ref, dist, interleaved RGB8, w*h*3 bytes each (the reference's layout)
-//   lin pyramid : scales 1..5 of both frames, planar fp32 linear RGB [3][h_s][w_s]
-//                 (scale 0 is read straight from the u8 frames through the sRGB LUT)
-//   partials    : fp64 [scale][18 stats][workgroups] partial sums
+// Data layout in HBM, per ctx.  Every buffer is a DevBuf member of ssimu2_ctx, allocated by the first call that needs
+// it and grouped there by the call that releases it ("Which call touches which buffer"):
+//   frame       : ref and dist u8 frames, interleaved RGB8, w*h*3 bytes each (the reference's layout); the linear
+//                 pyramids, scales 1..5 of both frames, planar fp32 linear RGB [3][h_s][w_s] (scale 0 is read straight
+//                 from the u8 frames through the sRGB LUT); the fp64 [scale][18 stats][workgroups] partial sums
+//   cache       : FIR mode, the cached reference: its positive-XYB planes and blur(ref*ref) planes, every scale
+//   stage       : a decoded frame as uploaded (ssimu2_*_strided / _strided16)
+//   rg          : SSIMU2_BLUR_RECURSIVE modes only (ssimu2_recursive.h), every scale packed: XYB planes of both frames,
+//                 the reference's cached blur(x) / blur(x*x) planes, the horizontal pass of a pass's planes
+//   map         : first map call only: density planes [scale][3][h_s][w_s] + the fp32 map [h][w] (ssimu2_error_map_*)
+//   hbd, tab    : first 16-bit call only (ssimu2_*_rgb16 / _strided16): the u16 frames as uploaded and in the FIR mode
+//                 their scale-0 linear planes [3][h][w]; the sRGB tables of depths 8..16
+//   batch       : first batch call only (ssimu2_score_batch_*): staged frames, pyramids, partial sums and results of
+//                 every item
 //   result      : fp64 [108 averages][score][nscales], written by k_finalize straight into pinned host memory
-//   error map   : first map call only: density planes [scale][3][h_s][w_s] + the fp32 map [h][w] (ssimu2_error_map_*)
-//   16-bit input: first such call only (ssimu2_*_rgb16 / _strided16): the sRGB tables of depths 8..16, the u16
-//                 frames as uploaded, and in the FIR mode their scale-0 linear planes [3][h][w]
-//
-//   SSIMU2_BLUR_RECURSIVE modes only (ssimu2_recursive.h), every scale packed: XYB planes of both
-//   frames, the reference's cached blur(x) / blur(x*x) planes, the horizontal pass of a pass's planes
 //
 // One score = ONE k_pyramid_bands launch (all five levels), ONE k_march launch covering all six scales, one
 // k_finalize launch that writes its 880 bytes into the host mirror itself (recursive modes: conversion, horizontal
@@ -39,6 +42,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 
 #include "../../include/ssimu2_hip.h"
 #include "ssimu2_kernels.h"
@@ -139,6 +143,21 @@ float cbrt_repro_host(float x) {
 
 thread_local std::string g_create_error;
 
+// One buffer of a context: device memory, or (`host`) page-locked host memory that a kernel writes.  `cap` is in
+// bytes, always; p is null exactly when cap is 0.  grow() is the one place that allocates.
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    bool host = false;
+    template <class T>
+    T* as() const { return (T*)p; }
+    void release() {
+        (void)(host ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+};
+
 }  // namespace
 
 struct ssimu2_ctx {
@@ -148,67 +167,66 @@ struct ssimu2_ctx {
     bool pool_stream = false;  // borrowed from the process-wide set of streams on distinct hardware queues
     std::string err;
 
-    // capacity (bytes / floats / doubles currently allocated)
-    size_t cap_u8 = 0, cap_lin = 0, cap_part = 0;
-    uint8_t* d_ref_u8 = nullptr;
-    uint8_t* d_dist_u8 = nullptr;
-    float* d_lin_ref = nullptr;   // scales 1..5 packed
-    float* d_lin_dist = nullptr;
-    float* d_xyb_ref = nullptr;   // cached positive-XYB planes of the reference, all scales
-    float* d_ref_blur = nullptr;  // cached blur(ref*ref) planes, all scales
-    size_t cap_blur = 0;          // floats allocated (0 = not cached)
-    uint8_t* d_stage = nullptr;   // decoded avifRGBImage as uploaded (RGBA / padded rows)
-    size_t cap_stage = 0;
-    size_t cap_xyb = 0;
-    double* d_partials = nullptr;
-    // SSIMU2_BLUR_RECURSIVE only (ssimu2_recursive.h), every scale packed: XYB planes of both frames
-    // [3], the reference's cached mu1 / s11 planes [6], the horizontal pass of a pass's planes [9]
     int blur_mode = SSIMU2_BLUR_FIR;
-    float* d_rg = nullptr;
-    size_t cap_rg = 0;            // floats
-    double* d_rg_part = nullptr;  // [scale][18][column groups]
-    unsigned* d_rg_q = nullptr;   // job cursor of the persistent vertical pass (RgPlan::q, 4 words)
-    int num_cus = 0;              // workgroups of that kernel: one per CU
-    ssimu2_device_info dev{};     // what ctx_create saw of the device (and checked: gfx950, 160 KB of LDS per CU)
-    unsigned rg_v_pad = 0;        // unused dynamic LDS of k_rg_v's launch: rg_v_pad_bytes(dev.lds_bytes_per_cu)
-    size_t cap_rg_part = 0;       // doubles
-    float* d_rg_dbg = nullptr;    // instrumented builds: 15 + 15 raw planes of scale rg_dbg_scale
-    size_t cap_rg_dbg = 0;
-    double* d_result = nullptr;   // 110 doubles in device memory: the stage timing of the instrumented build only
-    double* h_result = nullptr;   // page-locked host memory k_finalize writes the result into (110 doubles)
-    // error map (ssimu2_error_map_*), allocated by the first map call only: per-(scale, channel) density planes
-    // [scale][3][h_s][w_s] and the full-resolution map [h][w]
-    float* d_map_dens = nullptr;
-    float* d_map = nullptr;
-    size_t cap_map_dens = 0, cap_map = 0;  // floats
-    // 16-bit input (ssimu2_*_rgb16 / _strided16), allocated by the first such call only: the sRGB -> linear tables
-    // of depths 8..16 (depth d at float offset 2^d - 256, uploaded by the first call at that depth), the tight u16
-    // frames, and (FIR) the frames' scale-0 linear planes [3][h][w]
-    float* d_tab = nullptr;
-    uint32_t tab_ready = 0;  // bit d: the depth-d table is in d_tab
-    void* d_ref16 = nullptr;
-    void* d_dist16 = nullptr;
-    void* d_lin0_ref = nullptr;
-    void* d_lin0_dist = nullptr;
-    size_t cap_ref16 = 0, cap_dist16 = 0, cap_lin0_ref = 0, cap_lin0_dist = 0;  // bytes
-    bool ref_hbd = false;  // the cached reference was set from 16-bit samples (its 8-bit frame buffer is not it)
-    // batch scoring (ssimu2_score_batch_*), allocated by the first batch call only and grown on demand: the staged 8-bit
-    // frames of the host-pointer forms, the linear pyramids (scales 1..5) and partial sums of every item -- scratch of
-    // its own, so a batch leaves the single-score buffers and a cached reference alone -- and the page-locked result
-    // block k_finalize_batch writes (110 doubles per item)
-    void* b_u8_ref = nullptr;
-    void* b_u8_dist = nullptr;
-    void* b_lin_ref = nullptr;
-    void* b_lin_dist = nullptr;
-    void* b_part = nullptr;
-    size_t cap_b_u8_ref = 0, cap_b_u8_dist = 0, cap_b_lin_ref = 0, cap_b_lin_dist = 0, cap_b_part = 0;  // bytes
-    double* bh_result = nullptr;
-    size_t cap_bh_result = 0;  // items
-    uint32_t batch_n = 0;      // items of the last finished batch (ssimu2_last_batch_averages)
+    ssimu2_device_info dev{};  // what ctx_create saw of the device (and checked: gfx950, 160 KB of LDS per CU)
+
+    // The buffers, grouped by who releases them: the rows of DESIGN.md section 3, "Which call touches which buffer".
+    // A group is a struct of DevBuf members and nothing else, so that release(group) finds every one of them.
+    // Every group from `frame` to `hbd` is released when the frame buffers regrow (release_frame_groups).
+    // frame: ensure_capacity grows all five or none
+    struct {
+        DevBuf ref_u8, dist_u8;    // interleaved RGB8
+        DevBuf lin_ref, lin_dist;  // fp32, scales 1..5 packed
+        DevBuf partials;           // fp64 [scale][18][workgroups]
+    } frame;
+    // cache: cache_reference_fir, for a reference set in FIR mode
+    struct {
+        DevBuf xyb;   // positive-XYB planes of the reference, all scales
+        DevBuf blur;  // blur(ref*ref) planes, all scales (null = not cached)
+    } cache;
+    // stage: stage_upload, for the _strided and _strided16 calls
+    DevBuf stage;  // decoded avifRGBImage as uploaded (RGBA / padded rows)
+    // rg: rg_ensure, SSIMU2_BLUR_RECURSIVE modes only (ssimu2_recursive.h); also released by ssimu2_ctx_set_blur(FIR)
+    struct {
+        DevBuf planes;  // fp32, every scale packed: XYB planes of both frames [3], the reference's cached mu1 / s11
+                        // planes [6], the horizontal pass of a pass's planes [9]
+        DevBuf part;    // fp64 [scale][18][column groups]
+        DevBuf dbg;     // instrumented builds: 15 + 15 raw fp32 planes of scale rg_dbg_scale
+    } rg;
+    unsigned* d_rg_q = nullptr;  // job cursor of the persistent vertical pass (RgPlan::q, 4 words); released with `rg`
+    int num_cus = 0;             // workgroups of that kernel: one per CU
+    unsigned rg_v_pad = 0;       // unused dynamic LDS of k_rg_v's launch: rg_v_pad_bytes(dev.lds_bytes_per_cu)
+    // map: map_ensure, by the first ssimu2_error_map_* call
+    struct {
+        DevBuf dens;  // fp32 per-(scale, channel) density planes [scale][3][h_s][w_s]
+        DevBuf out;   // the full-resolution fp32 map [h][w]
+    } map;
+    // hbd: the first 16-bit call (ssimu2_*_rgb16 / _strided16)
+    struct {
+        DevBuf ref16, dist16;        // the tight u16 frames
+        DevBuf lin0_ref, lin0_dist;  // FIR: the frames' scale-0 linear planes, fp32 [3][h][w]
+    } hbd;
+    // tab: device_table; released by ssimu2_ctx_destroy only.  The sRGB -> linear tables of depths 8..16: depth d at
+    // float offset 2^d - 256, uploaded by the first call at that depth
+    DevBuf tab;
+    uint32_t tab_ready = 0;  // bit d: the depth-d table is in `tab`
+    // batch: batch_run / batch_stage (ssimu2_score_batch_*), each buffer when too small; released by ssimu2_ctx_destroy
+    // only.  Scratch of its own, so a batch leaves the single-score buffers and a cached reference alone: the staged
+    // 8-bit frames of the host-pointer forms, the linear pyramids (scales 1..5) and partial sums of every item, and the
+    // page-locked result block k_finalize_batch writes (110 doubles per item)
+    struct {
+        DevBuf u8_ref, u8_dist, lin_ref, lin_dist, part;
+        DevBuf result{nullptr, 0, true};
+    } batch;
+    uint32_t batch_n = 0;  // items of the last finished batch (ssimu2_last_batch_averages)
+    // result: ssimu2_ctx_create; ssimu2_ctx_destroy
+    double* d_result = nullptr;         // 110 doubles in device memory: the stage timing of the instrumented build only
+    DevBuf h_result{nullptr, 0, true};  // page-locked host memory k_finalize writes the result into (110 doubles)
 
     // reference state
     bool have_ref = false;
     uint32_t ref_w = 0, ref_h = 0;
+    bool ref_hbd = false;  // the cached reference was set from 16-bit samples (its 8-bit frame buffer is not it)
     bool pending = false;
 
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -219,7 +237,7 @@ struct ssimu2_ctx {
     bool cache_ref_blur = true;
     int rg_dbg_scale = -1;  // recursive mode: keep that scale's 15 raw planes (after each pass) downloadable
 #ifdef SSIMU2_INSTRUMENTED_BUILD
-    // the frame size whose scale-0 planes d_lin0_ref / d_lin0_dist hold for the last score or reference (0: none;
+    // the frame size whose scale-0 planes hbd.lin0_ref / hbd.lin0_dist hold for the last score or reference (0: none;
     // for ssimu2_debug_download at scale 0)
     uint32_t lin0_ref_w = 0, lin0_ref_h = 0, lin0_dist_w = 0, lin0_dist_h = 0;
     int last_march = 0;  // SSIMU2_MARCH_* of the last score or batch (ssimu2_instr_last_march)
@@ -270,7 +288,7 @@ inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, unsigned lds
     hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
 }
 
-// Instrumented build: record whether d_lin0_ref / d_lin0_dist hold the w x h scale-0 planes of the last score or
+// Instrumented build: record whether hbd.lin0_ref / hbd.lin0_dist hold the w x h scale-0 planes of the last score or
 // reference (1: they do from now on, 0: they do not, -1: unchanged).  Nothing in the product library.
 inline void note_lin0(ssimu2_ctx* c, int ref, int dist, uint32_t w, uint32_t h) {
 #ifdef SSIMU2_INSTRUMENTED_BUILD
@@ -366,106 +384,121 @@ int batch_seg_rows(const ssimu2_ctx* c, const Pyramid& p, int scale) {
     return seg;
 }
 
-int scale_blocks(const ssimu2_ctx* c, const Pyramid& p, int s) {
-    const int seg = march_seg_rows(c, p, s);
-    return ((p.w[s] + MW - 1) / MW) * ((p.h[s] + seg - 1) / seg);
+using SegRows = int (*)(const ssimu2_ctx*, const Pyramid&, int);
+
+// What the final reduction needs of the frame size alone; `part` and `nblocks` are the caller's.
+FinalizeArgs finalize_args(const Pyramid& p) {
+    FinalizeArgs fa;
+    memset(&fa, 0, sizeof fa);
+    fa.nscales = p.nscales;
+    for (int s = 0; s < p.nscales; ++s) fa.inv_pixels[s] = 1.0 / ((double)p.w[s] * (double)p.h[s]);
+    return fa;
 }
 
-size_t partial_doubles(const ssimu2_ctx* c, const Pyramid& p) {
-    size_t t = 0;
-    for (int s = 0; s < p.nscales; ++s) t += (size_t)scale_blocks(c, p, s) * kStats;
-    return t;
+// The size-only fields of a marching plan and its final reduction under a segment-rows rule (march_seg_rows or
+// batch_seg_rows): per scale w, h, segment rows, strips, workgroups and their running total, 1 / pixels, and in
+// poff[s] the offset (doubles) of scale s in one pair's partial sums.  Every pointer of *mp and *fa is left null for
+// the caller.  Returns the doubles of partial sums of one pair; its workgroups are mp->blk_end[nscales - 1].
+size_t plan_geometry(const ssimu2_ctx* c, const Pyramid& p, SegRows seg_rows, MarchPlan* mp, FinalizeArgs* fa,
+                     size_t poff[kNumScales]) {
+    memset(mp, 0, sizeof *mp);
+    *fa = finalize_args(p);
+    mp->nscales = p.nscales;
+    size_t doubles = 0;
+    int blocks = 0;
+    for (int s = 0; s < p.nscales; ++s) {
+        const int seg = seg_rows(c, p, s);
+        const int nstrips = (p.w[s] + MW - 1) / MW;
+        const int nb = nstrips * ((p.h[s] + seg - 1) / seg);
+        blocks += nb;
+        mp->blk_end[s] = blocks;
+        mp->w[s] = p.w[s];
+        mp->h[s] = p.h[s];
+        mp->seg[s] = seg;
+        mp->nstrips[s] = nstrips;
+        mp->nblocks[s] = fa->nblocks[s] = nb;
+        poff[s] = doubles;
+        doubles += (size_t)nb * kStats;
+    }
+    return doubles;
 }
 
-void free_recursive(ssimu2_ctx* c) {
-    (void)hipFree(c->d_rg);
-    (void)hipFree(c->d_rg_part);
-    (void)hipFree(c->d_rg_dbg);
+// ---- the buffers: one grow, one release ---------------------------------------------------------
+bool fits(const DevBuf& b, size_t bytes) { return b.p && bytes <= b.cap; }
+
+// `b` holds at least `bytes` afterwards: grown on demand, never shrunk, the old content is not kept.  The stream is
+// drained before the old block is freed.  Any failure leaves `b` released; a failed allocation is SSIMU2_ERR_OOM with
+// `what` and leaves no sticky HIP error behind.
+int grow(ssimu2_ctx* c, DevBuf& b, size_t bytes, const char* what) {
+    if (fits(b, bytes)) return SSIMU2_OK;
+    hipError_t e = hipStreamSynchronize(c->stream);
+    b.release();
+    if (e != hipSuccess) return c->fail(SSIMU2_ERR_HIP, "hipStreamSynchronize(c->stream)", e);
+    e = b.host ? hipHostMalloc(&b.p, bytes, hipHostMallocDefault) : hipMalloc(&b.p, bytes);
+    if (e != hipSuccess) {
+        b.p = nullptr;
+        (void)hipGetLastError();
+        return c->fail(SSIMU2_ERR_OOM, what, e);
+    }
+    b.cap = bytes;
+    return SSIMU2_OK;
+}
+
+// Release every buffer of a group (a struct of DevBuf members, or one DevBuf).
+template <class G>
+void release(G& group) {
+    static_assert(std::is_standard_layout<G>::value && sizeof(G) % sizeof(DevBuf) == 0, "a group holds DevBufs only");
+    for (DevBuf* b = (DevBuf*)&group; b != (DevBuf*)(&group + 1); ++b) b->release();
+}
+
+void release_recursive(ssimu2_ctx* c) {
+    release(c->rg);
     (void)hipFree(c->d_rg_q);
     c->d_rg_q = nullptr;
-    c->d_rg = c->d_rg_dbg = nullptr;
-    c->d_rg_part = nullptr;
-    c->cap_rg = c->cap_rg_part = c->cap_rg_dbg = 0;
 }
 
-void free_map(ssimu2_ctx* c) {
-    (void)hipFree(c->d_map_dens);
-    (void)hipFree(c->d_map);
-    c->d_map_dens = c->d_map = nullptr;
-    c->cap_map_dens = c->cap_map = 0;
+// Everything sized by the frame or holding content of the frame buffers: every group except the batch scratch, the
+// 16-bit tables and the result.  The caller has drained the stream and drops the reference.
+void release_frame_groups(ssimu2_ctx* c) {
+    release(c->frame);
+    release(c->cache);
+    release(c->stage);
+    release_recursive(c);
+    release(c->map);
+    release(c->hbd);
 }
 
-void free_hbd_frames(ssimu2_ctx* c) {
-    (void)hipFree(c->d_ref16);
-    (void)hipFree(c->d_dist16);
-    (void)hipFree(c->d_lin0_ref);
-    (void)hipFree(c->d_lin0_dist);
-    c->d_ref16 = c->d_dist16 = c->d_lin0_ref = c->d_lin0_dist = nullptr;
-    c->cap_ref16 = c->cap_dist16 = c->cap_lin0_ref = c->cap_lin0_dist = 0;
-}
-
-void free_batch(ssimu2_ctx* c) {
-    (void)hipFree(c->b_u8_ref);
-    (void)hipFree(c->b_u8_dist);
-    (void)hipFree(c->b_lin_ref);
-    (void)hipFree(c->b_lin_dist);
-    (void)hipFree(c->b_part);
-    (void)hipHostFree(c->bh_result);
-    c->b_u8_ref = c->b_u8_dist = c->b_lin_ref = c->b_lin_dist = c->b_part = nullptr;
-    c->bh_result = nullptr;
-    c->cap_b_u8_ref = c->cap_b_u8_dist = c->cap_b_lin_ref = c->cap_b_lin_dist = c->cap_b_part = c->cap_bh_result = 0;
-    c->batch_n = 0;
-}
-
-void free_buffers(ssimu2_ctx* c) {
-    free_map(c);
-    free_hbd_frames(c);
-    (void)hipFree(c->d_ref_u8);
-    (void)hipFree(c->d_dist_u8);
-    (void)hipFree(c->d_lin_ref);
-    (void)hipFree(c->d_lin_dist);
-    (void)hipFree(c->d_partials);
-    (void)hipFree(c->d_xyb_ref);
-    c->d_xyb_ref = nullptr;
-    c->cap_xyb = 0;
-    (void)hipFree(c->d_stage);
-    c->d_stage = nullptr;
-    c->cap_stage = 0;
-    (void)hipFree(c->d_ref_blur);
-    c->d_ref_blur = nullptr;
-    c->cap_blur = 0;
-    free_recursive(c);
-    c->d_ref_u8 = c->d_dist_u8 = nullptr;
-    c->d_lin_ref = c->d_lin_dist = nullptr;
-    c->d_partials = nullptr;
-    c->cap_u8 = c->cap_lin = c->cap_part = 0;
-}
-
+// The u8 frames, linear pyramids and partial sums for a w x h frame: all five or none.  Each grows to max(need,
+// current); growing any of them releases every group release_frame_groups names and drops the reference.  On failure
+// everything is released.
 int ensure_capacity(ssimu2_ctx* c, uint32_t w, uint32_t h) {
     const Pyramid p = make_pyramid(w, h);
-    const size_t need_u8 = (size_t)w * h * 3, need_lin = p.lin_total + 4,
-                 need_part = partial_doubles(c, p) + 8;
-    if (c->d_ref_u8 && need_u8 <= c->cap_u8 && need_lin <= c->cap_lin && need_part <= c->cap_part)
-        return SSIMU2_OK;
-    // growing frees everything, which also drops a cached reference
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const size_t nu8 = need_u8 > c->cap_u8 ? need_u8 : c->cap_u8;
-    const size_t nlin = need_lin > c->cap_lin ? need_lin : c->cap_lin;
-    const size_t npart = need_part > c->cap_part ? need_part : c->cap_part;
-    free_buffers(c);
-    c->have_ref = false;
-    hipError_t e;
-    if ((e = hipMalloc(&c->d_ref_u8, nu8)) != hipSuccess ||
-        (e = hipMalloc(&c->d_dist_u8, nu8)) != hipSuccess ||
-        (e = hipMalloc(&c->d_lin_ref, nlin * sizeof(float))) != hipSuccess ||
-        (e = hipMalloc(&c->d_lin_dist, nlin * sizeof(float))) != hipSuccess ||
-        (e = hipMalloc(&c->d_partials, npart * sizeof(double))) != hipSuccess) {
-        free_buffers(c);
-        return c->fail(SSIMU2_ERR_OOM, "hipMalloc(frame buffers)", e);
+    MarchPlan mp;
+    FinalizeArgs fa;
+    size_t poff[kNumScales];
+    const size_t need_u8 = (size_t)w * h * 3, need_lin = (p.lin_total + 4) * sizeof(float),
+                 need_part = (plan_geometry(c, p, march_seg_rows, &mp, &fa, poff) + 8) * sizeof(double);
+    struct {
+        DevBuf& b;
+        size_t bytes;
+    } want[5] = {{c->frame.ref_u8, need_u8}, {c->frame.dist_u8, need_u8}, {c->frame.lin_ref, need_lin},
+                 {c->frame.lin_dist, need_lin}, {c->frame.partials, need_part}};
+    bool ok = true;
+    for (auto& x : want) {
+        ok = ok && fits(x.b, x.bytes);
+        if (x.bytes < x.b.cap) x.bytes = x.b.cap;
     }
-    c->cap_u8 = nu8;
-    c->cap_lin = nlin;
-    c->cap_part = npart;
+    if (ok) return SSIMU2_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    release_frame_groups(c);
+    c->have_ref = false;
+    for (auto& x : want) {
+        const int rc = grow(c, x.b, x.bytes, "hipMalloc(frame buffers)");
+        if (rc) {
+            release_frame_groups(c);
+            return rc;
+        }
+    }
     return SSIMU2_OK;
 }
 
@@ -537,36 +570,24 @@ size_t xyb_off(const Pyramid& p, int s) {
     return off;
 }
 
+// The reference's cached planes, both sets (FIR mode): what the refblur kernels and every 16-bit pass need.
+bool ref_cached(const ssimu2_ctx* c) { return c->cache.xyb.p && c->cache.blur.p; }
+
+// The plans of a single score's marching launch and final reduction: scale 0 read from d_ref / d_dist, the scales
+// below it from the context's linear pyramids.
 void build_plans(const ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_ref, const uint8_t* d_dist,
                  bool ref_xyb_cached, MarchPlan* mp, FinalizeArgs* fa, int* total_blocks) {
-    memset(mp, 0, sizeof *mp);
-    memset(fa, 0, sizeof *fa);
-    mp->nscales = fa->nscales = p.nscales;
-    size_t poff = 0;
-    int blocks = 0;
+    size_t poff[kNumScales];
+    plan_geometry(c, p, march_seg_rows, mp, fa, poff);
+    const bool blur_cached = ref_xyb_cached && ref_cached(c);
     for (int s = 0; s < p.nscales; ++s) {
-        const int seg = march_seg_rows(c, p, s);
-        const int nstrips = (p.w[s] + MW - 1) / MW;
-        const int nb = nstrips * ((p.h[s] + seg - 1) / seg);
-        blocks += nb;
-        mp->blk_end[s] = blocks;
-        mp->w[s] = p.w[s];
-        mp->h[s] = p.h[s];
-        mp->seg[s] = seg;
-        mp->nstrips[s] = nstrips;
-        mp->nblocks[s] = nb;
-        mp->ref[s] = s == 0 ? (const void*)d_ref : (const void*)(c->d_lin_ref + p.lin_off[s]);
-        mp->dist[s] = s == 0 ? (const void*)d_dist : (const void*)(c->d_lin_dist + p.lin_off[s]);
-        mp->ref_xyb[s] = ref_xyb_cached ? c->d_xyb_ref + xyb_off(p, s) : nullptr;
-        const bool blur_cached = ref_xyb_cached && c->d_ref_blur && c->cap_blur;
-        mp->ref_s11[s] = blur_cached ? c->d_ref_blur + xyb_off(p, s) : nullptr;
-        mp->part[s] = c->d_partials + poff;
-        fa->part[s] = mp->part[s];
-        fa->nblocks[s] = nb;
-        fa->inv_pixels[s] = 1.0 / ((double)p.w[s] * (double)p.h[s]);
-        poff += (size_t)nb * kStats;
+        mp->ref[s] = s == 0 ? (const void*)d_ref : (const void*)(c->frame.lin_ref.as<float>() + p.lin_off[s]);
+        mp->dist[s] = s == 0 ? (const void*)d_dist : (const void*)(c->frame.lin_dist.as<float>() + p.lin_off[s]);
+        mp->ref_xyb[s] = ref_xyb_cached ? c->cache.xyb.as<float>() + xyb_off(p, s) : nullptr;
+        mp->ref_s11[s] = blur_cached ? c->cache.blur.as<float>() + xyb_off(p, s) : nullptr;
+        fa->part[s] = mp->part[s] = c->frame.partials.as<double>() + poff[s];
     }
-    *total_blocks = blocks;
+    *total_blocks = p.nscales > 0 ? mp->blk_end[p.nscales - 1] : 0;
 }
 
 // ---- the published-recursion modes (ssimu2_recursive.h) ------------------------------------------
@@ -585,50 +606,33 @@ int rg_check_size(ssimu2_ctx* c, uint32_t w, uint32_t h) {
     return SSIMU2_OK;
 }
 
-// Scratch + cache of the recursive modes for this frame size.  Growing drops a cached reference
-// (its planes live here).
+// Scratch + cache of the recursive modes for this frame size.  The planes and their partial sums are replaced
+// together when either is too small, which drops a cached reference (its planes live here); a failure leaves both
+// released.  The debug planes follow rg_dbg_scale.
 int rg_ensure(ssimu2_ctx* c, const Pyramid& p) {
     const size_t ntot = rg_plane_off(p, p.nscales);
-    const size_t need = 21 * ntot + (size_t)rg_pitch(p.w[0]) + 16;  // + the dump row of k_rg_v_emit
-    size_t need_part = 8;
-    for (int s = 0; s < p.nscales; ++s) need_part += (size_t)kStats * ((p.w[s] + RG_VW - 1) / RG_VW);
-    if (need > c->cap_rg || need_part > c->cap_rg_part) {
+    const size_t need = (21 * ntot + (size_t)rg_pitch(p.w[0]) + 16) * sizeof(float);  // + the dump row of k_rg_v_emit
+    size_t need_part = 8 * sizeof(double);
+    for (int s = 0; s < p.nscales; ++s) need_part += (size_t)kStats * ((p.w[s] + RG_VW - 1) / RG_VW) * sizeof(double);
+    const char* what = "hipMalloc(recursive-blur planes: 84 bytes per pixel and scale)";
+    if (!fits(c->rg.planes, need) || !fits(c->rg.part, need_part)) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_rg);
-        (void)hipFree(c->d_rg_part);
-        c->d_rg = nullptr;
-        c->d_rg_part = nullptr;
-        c->cap_rg = c->cap_rg_part = 0;
+        c->rg.planes.release();
+        c->rg.part.release();
         c->have_ref = false;
-        hipError_t e = hipMalloc(&c->d_rg, need * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc(&c->d_rg_part, need_part * sizeof(double));
-        if (e != hipSuccess) {
-            (void)hipFree(c->d_rg);
-            c->d_rg = nullptr;
-            c->d_rg_part = nullptr;
-            return c->fail(SSIMU2_ERR_OOM, "hipMalloc(recursive-blur planes: 84 bytes per pixel and scale)", e);
+        int rc;
+        if ((rc = grow(c, c->rg.planes, need, what)) || (rc = grow(c, c->rg.part, need_part, what))) {
+            c->rg.planes.release();
+            return rc;
         }
-        c->cap_rg = need;
-        c->cap_rg_part = need_part;
     }
     if (!c->d_rg_q) {
         HIP_TRY(c, hipMalloc(&c->d_rg_q, 4 * sizeof(unsigned)));
         c->num_cus = c->dev.compute_units > 0 ? (int)c->dev.compute_units : 256;
     }
-    if (c->rg_dbg_scale >= 0 && c->rg_dbg_scale < p.nscales) {
-        const size_t nd = (size_t)24 * rg_pitch(p.w[c->rg_dbg_scale]) * p.h[c->rg_dbg_scale] + 16;  // 15 h planes + 9 v planes
-        if (nd > c->cap_rg_dbg) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            (void)hipFree(c->d_rg_dbg);
-            c->d_rg_dbg = nullptr;
-            c->cap_rg_dbg = 0;
-            const hipError_t e = hipMalloc(&c->d_rg_dbg, nd * sizeof(float));
-            if (e != hipSuccess) {
-                c->d_rg_dbg = nullptr;
-                return c->fail(SSIMU2_ERR_OOM, "hipMalloc(recursive-blur debug planes)", e);
-            }
-            c->cap_rg_dbg = nd;
-        }
+    if (c->rg_dbg_scale >= 0 && c->rg_dbg_scale < p.nscales) {  // 15 h planes + 9 v planes
+        const size_t nd = (size_t)24 * rg_pitch(p.w[c->rg_dbg_scale]) * p.h[c->rg_dbg_scale] + 16;
+        return grow(c, c->rg.dbg, nd * sizeof(float), "hipMalloc(recursive-blur debug planes)");
     }
     return SSIMU2_OK;
 }
@@ -638,7 +642,7 @@ int rg_ensure(ssimu2_ctx* c, const Pyramid& p) {
 void rg_build_plan(const ssimu2_ctx* c, const Pyramid& p, bool ref_frame, RgPlan* rp, int* hblocks, int* vblocks) {
     memset(rp, 0, sizeof *rp);
     const size_t ntot = rg_plane_off(p, p.nscales);
-    float* xa = c->d_rg;
+    float* xa = c->rg.planes.as<float>();
     float* xb = xa + 3 * ntot;
     float* cache = xb + 3 * ntot;
     float* hbuf = cache + 6 * ntot;
@@ -660,7 +664,7 @@ void rg_build_plan(const ssimu2_ctx* c, const Pyramid& p, bool ref_frame, RgPlan
         rp->xout[s] = (ref_frame ? xa : xb) + 3 * off;
         rp->cache[s] = cache + 6 * off;
         rp->hbuf[s] = hbuf + 9 * off;
-        rp->part[s] = c->d_rg_part + poff;
+        rp->part[s] = c->rg.part.as<double>() + poff;
         poff += (size_t)kStats * rp->vgroups[s];
     }
     rp->dump = hbuf + 9 * ntot;
@@ -675,7 +679,7 @@ void rg_build_plan(const ssimu2_ctx* c, const Pyramid& p, bool ref_frame, RgPlan
 // parity tests.  After a horizontal pass its planes are copied out of hbuf; the per-pass planes of
 // the vertical pass exist only in LDS, so k_rg_v_emit recomputes them into the debug buffer.
 bool rg_debugging(const ssimu2_ctx* c, const Pyramid& p) {
-    return c->d_rg_dbg && c->rg_dbg_scale >= 0 && c->rg_dbg_scale < p.nscales;
+    return c->rg.dbg.p && c->rg_dbg_scale >= 0 && c->rg_dbg_scale < p.nscales;
 }
 
 void rg_debug_keep_h(ssimu2_ctx* c, const Pyramid& p, const RgPlan& rp, bool ref) {
@@ -683,7 +687,7 @@ void rg_debug_keep_h(ssimu2_ctx* c, const Pyramid& p, const RgPlan& rp, bool ref
     const size_t n = (size_t)rg_pitch(p.w[s]) * p.h[s];
     for (int ch = 0; ch < 3; ++ch)
         for (int k = 0; k < nk; ++k)
-            (void)hipMemcpyAsync(c->d_rg_dbg + (size_t)rg_plane15(ref, ch, k) * n, rp.hbuf[s] + (size_t)(ch * nk + k) * n,
+            (void)hipMemcpyAsync(c->rg.dbg.as<float>() + (size_t)rg_plane15(ref, ch, k) * n, rp.hbuf[s] + (size_t)(ch * nk + k) * n,
                                  n * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
 }
 
@@ -732,6 +736,15 @@ void rg_enqueue_reference(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_ref,
     else launch((k_rg_v_emit<false, 2>), dim3(vblocks), dim3(128), 0, c->stream, rp);
 }
 
+// The tail of every single score: the final reduction, which writes its 880 bytes straight into the context's
+// page-locked mirror (no D2H copy command per score); ssimu2_wait collects it.
+int finish_score(ssimu2_ctx* c, const FinalizeArgs& fa) {
+    launch(k_finalize, dim3(1), dim3(1024), 0, c->stream, fa, c->h_result.as<double>());
+    HIP_TRY(c, hipGetLastError());
+    c->pending = true;
+    return SSIMU2_OK;
+}
+
 // One pass against the reference planes in place: XYB of the distorted frame, the recursion over
 // {y, y*y, x*y}, maps, final reduction (its linear pyramid is already enqueued).
 int rg_enqueue_pass(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_dist, const Src16* s16 = nullptr) {
@@ -739,13 +752,10 @@ int rg_enqueue_pass(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_dist, cons
     int hblocks, vblocks;
     rg_build_plan(c, p, false, &rp, &hblocks, &vblocks);
     const bool fma = c->blur_mode == SSIMU2_BLUR_RECURSIVE_FMA, dbg = rg_debugging(c, p);
-    FinalizeArgs fa;
-    memset(&fa, 0, sizeof fa);
-    fa.nscales = p.nscales;
+    FinalizeArgs fa = finalize_args(p);
     for (int s = 0; s < p.nscales; ++s) {
         fa.part[s] = rp.part[s];
-        fa.nblocks[s] = rp.vgroups[s];
-        fa.inv_pixels[s] = 1.0 / ((double)p.w[s] * (double)p.h[s]);
+        fa.nblocks[s] = rp.vgroups[s];  // one partial sum per column group
     }
     if (p.nscales > 0) {  // a frame below 8 x 8 has no scale to score
         rg_launch_convert(c, p, d_dist, rp, s16);
@@ -756,14 +766,23 @@ int rg_enqueue_pass(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_dist, cons
         if (dbg) {
             rg_debug_keep_h(c, p, rp, false);
             const int s = c->rg_dbg_scale;
-            rp.emit[s] = c->d_rg_dbg + (size_t)15 * rg_pitch(p.w[s]) * p.h[s];  // [channel][{y, yy, xy}][n]
+            rp.emit[s] = c->rg.dbg.as<float>() + (size_t)15 * rg_pitch(p.w[s]) * p.h[s];  // [channel][{y, yy, xy}][n]
             if (fma) launch((k_rg_v_emit<true, 3>), dim3(vblocks), dim3(192), 0, c->stream, rp);
             else launch((k_rg_v_emit<false, 3>), dim3(vblocks), dim3(192), 0, c->stream, rp);
         }
     }
-    launch(k_finalize, dim3(1), dim3(1024), 0, c->stream, fa, c->h_result);  // result: see enqueue_score
-    HIP_TRY(c, hipGetLastError());
-    c->pending = true;
+    return finish_score(c, fa);
+}
+
+// Recursive modes, before anything of a score or reference is enqueued: the size limit and the planes.  `needs_ref`:
+// the call scores against the cached reference, which growing the planes drops.
+int rg_prepare(ssimu2_ctx* c, const Pyramid& p, uint32_t w, uint32_t h, bool needs_ref) {
+    int rc = rg_check_size(c, w, h);
+    if (rc) return rc;
+    const bool had_ref = c->have_ref;
+    if ((rc = rg_ensure(c, p))) return rc;
+    if (needs_ref && had_ref && !c->have_ref)
+        return c->fail(SSIMU2_ERR_NO_REFERENCE, "recursive blur mode: the cached reference was dropped");
     return SSIMU2_OK;
 }
 
@@ -774,22 +793,18 @@ int enqueue_score(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, ui
     const Pyramid p = make_pyramid(w, h);
     const bool recursive = c->blur_mode != SSIMU2_BLUR_FIR;
     note_lin0(c, 0, 0, w, h);  // an 8-bit score: the 16-bit scale-0 planes are older than it
-    if (recursive) {  // before anything is enqueued
-        int rc = rg_check_size(c, w, h);
+    if (recursive) {
+        const int rc = rg_prepare(c, p, w, h, ref_pyramid_ready);
         if (rc) return rc;
-        const bool had_ref = c->have_ref;
-        if ((rc = rg_ensure(c, p))) return rc;
-        if (ref_pyramid_ready && had_ref && !c->have_ref)
-            return c->fail(SSIMU2_ERR_NO_REFERENCE, "recursive blur mode: the cached reference was dropped");
     }
     if (p.nscales > 1 && !recursive) {  // the recursive modes convert straight to XYB planes
         if (ref_pyramid_ready) {
             const uint8_t* frames[1] = {d_dist};
-            float* lin[1] = {c->d_lin_dist};
+            float* lin[1] = {c->frame.lin_dist.as<float>()};
             launch_pyramid(c, p, 1, frames, lin);
         } else {
             const uint8_t* frames[2] = {d_ref, d_dist};
-            float* lin[2] = {c->d_lin_ref, c->d_lin_dist};
+            float* lin[2] = {c->frame.lin_ref.as<float>(), c->frame.lin_dist.as<float>()};
             launch_pyramid(c, p, 2, frames, lin);
         }
     }
@@ -800,7 +815,7 @@ int enqueue_score(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, ui
     MarchPlan mp;
     FinalizeArgs fa;
     int blocks = 0;
-    build_plans(c, p, d_ref, d_dist, ref_pyramid_ready && c->d_xyb_ref != nullptr, &mp, &fa, &blocks);
+    build_plans(c, p, d_ref, d_dist, ref_pyramid_ready && c->cache.xyb.p != nullptr, &mp, &fa, &blocks);
     note_march(c, blocks <= 0 ? 0 : mp.ref_s11[0] ? 2 : 1);
     if (blocks > 0) {
         if (mp.ref_s11[0])  // reference XYB and blur(ref*ref) cached: the search's per-pass kernel
@@ -808,11 +823,7 @@ int enqueue_score(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, ui
         else
             launch(k_march, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
     }
-    // the 880-byte result goes straight into the context's page-locked mirror: no D2H copy command per score
-    launch(k_finalize, dim3(1), dim3(1024), 0, c->stream, fa, c->h_result);
-    HIP_TRY(c, hipGetLastError());
-    c->pending = true;
-    return SSIMU2_OK;
+    return finish_score(c, fa);
 }
 
 // The score of 16-bit frames: `ref` null = against the cached reference (set from 8- or 16-bit samples; its planes do
@@ -821,16 +832,12 @@ int enqueue_score(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, ui
 int enqueue_score16(ssimu2_ctx* c, const Src16* ref, const Src16& dist, uint32_t w, uint32_t h) {
     const Pyramid p = make_pyramid(w, h);
     if (c->blur_mode != SSIMU2_BLUR_FIR) {
-        int rc = rg_check_size(c, w, h);
+        const int rc = rg_prepare(c, p, w, h, !ref);
         if (rc) return rc;
-        const bool had_ref = c->have_ref;
-        if ((rc = rg_ensure(c, p))) return rc;
-        if (!ref && had_ref && !c->have_ref)
-            return c->fail(SSIMU2_ERR_NO_REFERENCE, "recursive blur mode: the cached reference was dropped");
         if (ref) rg_enqueue_reference(c, p, nullptr, ref);
         return rg_enqueue_pass(c, p, nullptr, &dist);
     }
-    const bool cached = !ref && c->d_xyb_ref && c->d_ref_blur && c->cap_blur;
+    const bool cached = !ref && ref_cached(c);
     if (!ref && !cached)  // 16-bit scale 0 cannot be paired with an 8-bit reference frame in one marching kernel
         return c->fail(SSIMU2_ERR_OOM, "16-bit frames against a reference need its cached planes, which are missing");
     {
@@ -840,28 +847,25 @@ int enqueue_score16(ssimu2_ctx* c, const Src16* ref, const Src16& dist, uint32_t
         int n = 0;
         if (ref) {
             src[n] = ref;
-            lin[n] = c->d_lin_ref;
-            lin0[n++] = (float*)c->d_lin0_ref;
+            lin[n] = c->frame.lin_ref.as<float>();
+            lin0[n++] = c->hbd.lin0_ref.as<float>();
         }
         src[n] = &dist;
-        lin[n] = c->d_lin_dist;
-        lin0[n++] = (float*)c->d_lin0_dist;
+        lin[n] = c->frame.lin_dist.as<float>();
+        lin0[n++] = c->hbd.lin0_dist.as<float>();
         launch_pyramid16(c, p, n, src, lin, lin0);
         if (p.nscales >= 1) note_lin0(c, ref ? 1 : -1, 1, w, h);
     }
     MarchPlan mp;
     FinalizeArgs fa;
     int blocks = 0;
-    build_plans(c, p, (const uint8_t*)c->d_lin0_ref, (const uint8_t*)c->d_lin0_dist, cached, &mp, &fa, &blocks);
+    build_plans(c, p, c->hbd.lin0_ref.as<uint8_t>(), c->hbd.lin0_dist.as<uint8_t>(), cached, &mp, &fa, &blocks);
     note_march(c, blocks <= 0 ? 0 : cached ? 4 : 3);
     if (blocks > 0) {
         if (cached) launch(k_march_refblur_lin, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
         else launch(k_march_lin, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
     }
-    launch(k_finalize, dim3(1), dim3(1024), 0, c->stream, fa, c->h_result);
-    HIP_TRY(c, hipGetLastError());
-    c->pending = true;
-    return SSIMU2_OK;
+    return finish_score(c, fa);
 }
 
 // sRGB -> linear of a d-bit sample s, 8 <= d <= 16: the 8-bit table's expression at v = s / (2^d - 1), fp64, rounded
@@ -889,38 +893,16 @@ size_t table_off(uint32_t d) { return ((size_t)1 << d) - 256; }
 
 // The device table of depth d (uploaded on the context stream by the first call at that depth).
 int device_table(ssimu2_ctx* c, uint32_t d, const float** out) {
-    if (!c->d_tab) {
-        const hipError_t e = hipMalloc(&c->d_tab, table_off(17) * sizeof(float));
-        if (e != hipSuccess) {
-            c->d_tab = nullptr;
-            return c->fail(SSIMU2_ERR_OOM, "hipMalloc(16-bit sRGB tables)", e);
-        }
-        c->tab_ready = 0;
-    }
+    const int rc = grow(c, c->tab, table_off(17) * sizeof(float), "hipMalloc(16-bit sRGB tables)");  // once per context
+    if (rc) return rc;
     if (!(c->tab_ready & (1u << d))) {
         const float* t = host_table(d);
         if (!t) return c->fail(SSIMU2_ERR_OOM, "16-bit sRGB table");
-        HIP_TRY(c, hipMemcpyAsync(c->d_tab + table_off(d), t, ((size_t)1 << d) * sizeof(float), hipMemcpyHostToDevice,
-                                  c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->tab.as<float>() + table_off(d), t, ((size_t)1 << d) * sizeof(float),
+                                  hipMemcpyHostToDevice, c->stream));
         c->tab_ready |= 1u << d;
     }
-    *out = c->d_tab + table_off(d);
-    return SSIMU2_OK;
-}
-
-// A 16-bit buffer of at least `bytes`: grown on demand, never shrunk.
-int hbd_grow(ssimu2_ctx* c, void** p, size_t* cap, size_t bytes, const char* what) {
-    if (*p && bytes <= *cap) return SSIMU2_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        return c->fail(SSIMU2_ERR_OOM, what, e);
-    }
-    *cap = bytes;
+    *out = c->tab.as<float>() + table_off(d);
     return SSIMU2_OK;
 }
 
@@ -929,8 +911,8 @@ int hbd_lin0(ssimu2_ctx* c, uint32_t w, uint32_t h, bool ref) {
     note_lin0(c, ref ? 0 : -1, 0, w, h);  // the call may regrow or rewrite them: valid again once launched
     if (c->blur_mode != SSIMU2_BLUR_FIR) return SSIMU2_OK;
     const size_t bytes = (size_t)w * h * 3 * sizeof(float);
-    int rc = hbd_grow(c, &c->d_lin0_dist, &c->cap_lin0_dist, bytes, "hipMalloc(16-bit scale-0 planes)");
-    if (!rc && ref) rc = hbd_grow(c, &c->d_lin0_ref, &c->cap_lin0_ref, bytes, "hipMalloc(16-bit scale-0 planes)");
+    int rc = grow(c, c->hbd.lin0_dist, bytes, "hipMalloc(16-bit scale-0 planes)");
+    if (!rc && ref) rc = grow(c, c->hbd.lin0_ref, bytes, "hipMalloc(16-bit scale-0 planes)");
     return rc;
 }
 
@@ -954,28 +936,24 @@ void map_coefficients(const ssimu2_ctx* c, int nscales, MapCoef* mc) {
             for (int n = 0; n < 2; ++n)
                 for (int k = 0; k < 3; ++k, ++j) {
                     const int stat = k == 0 ? ch * 2 + n : 6 + ch * 4 + n + (k == 2 ? 2 : 0);
-                    const double a = c->h_result[sc * kStats + stat], wt = kWeightsHost[j];
+                    const double a = c->h_result.as<double>()[sc * kStats + stat], wt = kWeightsHost[j];
                     double v = n == 0 ? wt : (a > 0.0 ? wt / (a * a * a) : 0.0);
                     if (v > 3.0e38) v = 3.0e38;  // a nonzero L4 average below ~1e-13 (denormal terms): stay finite
                     mc->c[sc][stat] = (float)v;
                 }
 }
 
-// The map buffers for this frame size: allocated on first use, replaced when the size changes.
+// The map buffers for this frame size: allocated on first use, replaced when the size DIFFERS (not only when it is
+// larger: a map of a small frame does not sit on a large frame's planes); a failure leaves both released.
 int map_ensure(ssimu2_ctx* c, const Pyramid& p, uint32_t w, uint32_t h) {
-    const size_t need_dens = xyb_off(p, p.nscales) + 4, need_map = (size_t)w * h;
-    if (c->d_map && need_dens == c->cap_map_dens && need_map == c->cap_map) return SSIMU2_OK;
+    const size_t need_dens = (xyb_off(p, p.nscales) + 4) * sizeof(float), need_map = (size_t)w * h * sizeof(float);
+    if (c->map.out.p && need_dens == c->map.dens.cap && need_map == c->map.out.cap) return SSIMU2_OK;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    free_map(c);
-    hipError_t e = hipMalloc(&c->d_map_dens, need_dens * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&c->d_map, need_map * sizeof(float));
-    if (e != hipSuccess) {
-        free_map(c);
-        return c->fail(SSIMU2_ERR_OOM, "hipMalloc(error map: 20 bytes per pixel)", e);
-    }
-    c->cap_map_dens = need_dens;
-    c->cap_map = need_map;
-    return SSIMU2_OK;
+    release(c->map);
+    const char* what = "hipMalloc(error map: 20 bytes per pixel)";
+    int rc;
+    if ((rc = grow(c, c->map.dens, need_dens, what)) || (rc = grow(c, c->map.out, need_map, what))) release(c->map);
+    return rc;
 }
 
 // The map pass after a finished score of (d_ref, d_dist) (its planes still in place): densities of every scale from
@@ -986,8 +964,9 @@ int map_pass(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, uint32_
     int rc = map_ensure(c, p, w, h);
     if (rc) return rc;
     const size_t npix = (size_t)w * h;
+    float* const dens = c->map.dens.as<float>();
     if (p.nscales == 0) {  // a frame below 8 x 8 has no scale: the map is zero, as the score is 100
-        HIP_TRY(c, hipMemsetAsync(c->d_map, 0, npix * sizeof(float), c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->map.out.p, 0, npix * sizeof(float), c->stream));
     } else {
         MapCoef mc;
         map_coefficients(c, p.nscales, &mc);
@@ -996,7 +975,7 @@ int map_pass(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, uint32_
             FinalizeArgs fa;
             int blocks = 0;
             build_plans(c, p, d_ref, d_dist, false, &mp, &fa, &blocks);
-            for (int s = 0; s < p.nscales; ++s) mp.ref_s11[s] = c->d_map_dens + xyb_off(p, s);  // the output planes
+            for (int s = 0; s < p.nscales; ++s) mp.ref_s11[s] = dens + xyb_off(p, s);  // the output planes
             launch(k_march_map, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp, mc);
         } else {
             RgPlan rp;
@@ -1005,7 +984,7 @@ int map_pass(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, uint32_
             RgMapArgs ma;
             memset(&ma, 0, sizeof ma);
             ma.coef = mc;
-            for (int s = 0; s < p.nscales; ++s) ma.dens[s] = c->d_map_dens + xyb_off(p, s);
+            for (int s = 0; s < p.nscales; ++s) ma.dens[s] = dens + xyb_off(p, s);
             HIP_TRY(c, hipMemsetAsync(c->d_rg_q, 0, 4 * sizeof(unsigned), c->stream));  // the job cursor
             const int vgrid = vblocks < c->num_cus ? vblocks : c->num_cus;
             if (c->blur_mode == SSIMU2_BLUR_RECURSIVE_FMA)
@@ -1017,15 +996,15 @@ int map_pass(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, uint32_
         memset(&ca, 0, sizeof ca);
         ca.nscales = p.nscales;
         for (int s = 0; s < p.nscales; ++s) {
-            ca.dens[s] = c->d_map_dens + xyb_off(p, s);
+            ca.dens[s] = dens + xyb_off(p, s);
             ca.w[s] = p.w[s];
             ca.h[s] = p.h[s];
         }
-        ca.out = c->d_map;
+        ca.out = c->map.out.as<float>();
         launch(k_map_compose, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, c->stream, ca);
     }
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(out_map, c->d_map, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out_map, c->map.out.p, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SSIMU2_OK;
 }
@@ -1042,26 +1021,11 @@ int check_args(ssimu2_ctx* c, const void* a, const void* b, uint32_t w, uint32_t
 // ---- batch scoring (include/ssimu2_hip.h "Batch scoring") -------------------
 constexpr size_t kResultDoubles = kNumScales * kStats + 2;  // one item's block of the result mirror
 
-// The page-locked result block for n items (k_finalize_batch writes it over the bus itself, as k_finalize does).
-int batch_result_grow(ssimu2_ctx* c, uint32_t n) {
-    if (c->bh_result && n <= c->cap_bh_result) return SSIMU2_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    (void)hipHostFree(c->bh_result);
-    c->bh_result = nullptr;
-    c->cap_bh_result = 0;
-    c->batch_n = 0;
-    const hipError_t e = hipHostMalloc(&c->bh_result, (size_t)n * kResultDoubles * sizeof(double), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        c->bh_result = nullptr;
-        (void)hipGetLastError();
-        return c->fail(SSIMU2_ERR_OOM, "hipHostMalloc(batch results)", e);
-    }
-    c->cap_bh_result = n;
-    return SSIMU2_OK;
-}
-
-// What every batch call checks first (the ctx is not null, n > 0).
-int batch_check(ssimu2_ctx* c, uint32_t n, bool against_reference) {
+// The opening of the four batch entry points, used as `if (rc || n == 0) return rc;`: a null context, an empty batch
+// (SSIMU2_OK, nothing else is looked at), then what every batch call refuses.
+int batch_open(ssimu2_ctx* c, uint32_t n, bool against_reference) {
+    if (!c) return SSIMU2_ERR_INVALID_ARG;
+    if (n == 0) return SSIMU2_OK;
     if (c->blur_mode != SSIMU2_BLUR_FIR)
         return c->fail(SSIMU2_ERR_UNSUPPORTED, "batch scoring runs in SSIMU2_BLUR_FIR only: switch the context with "
                                                "ssimu2_ctx_set_blur, or score the pairs one by one");
@@ -1080,52 +1044,37 @@ int batch_run(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dists, size
     MarchBatchPlan bp;
     FinalizeArgs fa;
     memset(&bp, 0, sizeof bp);
-    memset(&fa, 0, sizeof fa);
     MarchPlan& mp = bp.item;
-    mp.nscales = fa.nscales = p.nscales;
-    size_t poff[kNumScales] = {0}, part_stride = 0;
-    long long blocks = 0;
-    for (int s = 0; s < p.nscales; ++s) {
-        const int seg = batch_seg_rows(c, p, s);
-        const int nstrips = (p.w[s] + MW - 1) / MW;
-        const int nb = nstrips * ((p.h[s] + seg - 1) / seg);
-        blocks += nb;
-        mp.blk_end[s] = (int)blocks;
-        mp.w[s] = p.w[s];
-        mp.h[s] = p.h[s];
-        mp.seg[s] = seg;
-        mp.nstrips[s] = nstrips;
-        mp.nblocks[s] = nb;
-        fa.nblocks[s] = nb;
-        fa.inv_pixels[s] = 1.0 / ((double)p.w[s] * (double)p.h[s]);
-        poff[s] = part_stride;
-        part_stride += (size_t)nb * kStats;
-    }
+    size_t poff[kNumScales];
+    const size_t part_stride = plan_geometry(c, p, batch_seg_rows, &mp, &fa, poff);  // doubles between items' partial sums
+    const long long blocks = p.nscales > 0 ? mp.blk_end[p.nscales - 1] : 0;
     const int nframes = against_ref ? 1 : 2;
     const long long bands = (long long)((p.w[0] + PYR_BAND_W - 1) / PYR_BAND_W) * ((p.h[0] + PYR_BAND_H - 1) / PYR_BAND_H);
     if (blocks * n > 0x7fffffffLL || bands * nframes * n > 0x7fffffffLL)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "batch too large for one launch: fewer items per call");
-    const bool cached = against_ref && c->d_xyb_ref && c->d_ref_blur && c->cap_blur;
+    const bool cached = against_ref && ref_cached(c);
     if (against_ref && !cached && c->ref_hbd)  // as ssimu2_score_against_reference_rgb16: no 8-bit frame of that reference
         return c->fail(SSIMU2_ERR_OOM, "a batch against a 16-bit reference needs its cached planes, which are missing");
     const size_t lin_stride = (p.lin_total + 3) & ~(size_t)3;  // floats between items' pyramids
+    auto& b = c->batch;
+    const size_t lin_bytes = (size_t)n * lin_stride * sizeof(float) + 16, res_bytes = (size_t)n * kResultDoubles * sizeof(double);
     int rc;
-    if ((rc = hbd_grow(c, &c->b_lin_dist, &c->cap_b_lin_dist, (size_t)n * lin_stride * sizeof(float) + 16,
-                       "hipMalloc(batch pyramids)")) ||
-        (!against_ref && (rc = hbd_grow(c, &c->b_lin_ref, &c->cap_b_lin_ref, (size_t)n * lin_stride * sizeof(float) + 16,
-                                        "hipMalloc(batch pyramids)"))) ||
-        (rc = hbd_grow(c, &c->b_part, &c->cap_b_part, ((size_t)n * part_stride + 8) * sizeof(double),
-                       "hipMalloc(batch partial sums)")) ||
-        (rc = batch_result_grow(c, n)))
+    if ((rc = grow(c, b.lin_dist, lin_bytes, "hipMalloc(batch pyramids)")) ||
+        (!against_ref && (rc = grow(c, b.lin_ref, lin_bytes, "hipMalloc(batch pyramids)"))) ||
+        (rc = grow(c, b.part, ((size_t)n * part_stride + 8) * sizeof(double), "hipMalloc(batch partial sums)")))
         return rc;
-    const float* lin_ref = against_ref ? c->d_lin_ref : (const float*)c->b_lin_ref;
+    // the page-locked result block (k_finalize_batch writes it over the bus itself, as k_finalize does); regrowing it
+    // takes the last batch's averages with it
+    if (!fits(b.result, res_bytes)) c->batch_n = 0;
+    if ((rc = grow(c, b.result, res_bytes, "hipHostMalloc(batch results)"))) return rc;
+    const float* lin_ref = against_ref ? c->frame.lin_ref.as<float>() : b.lin_ref.as<float>();
+    const uint8_t* ref0 = against_ref ? c->frame.ref_u8.as<uint8_t>() : d_refs;
     for (int s = 0; s < p.nscales; ++s) {
-        mp.ref[s] = s == 0 ? (const void*)(against_ref ? c->d_ref_u8 : d_refs) : (const void*)(lin_ref + p.lin_off[s]);
-        mp.dist[s] = s == 0 ? (const void*)d_dists : (const void*)((const float*)c->b_lin_dist + p.lin_off[s]);
-        mp.ref_xyb[s] = cached ? c->d_xyb_ref + xyb_off(p, s) : nullptr;
-        mp.ref_s11[s] = cached ? c->d_ref_blur + xyb_off(p, s) : nullptr;
-        mp.part[s] = (double*)c->b_part + poff[s];
-        fa.part[s] = mp.part[s];
+        mp.ref[s] = s == 0 ? (const void*)ref0 : (const void*)(lin_ref + p.lin_off[s]);
+        mp.dist[s] = s == 0 ? (const void*)d_dists : (const void*)(b.lin_dist.as<float>() + p.lin_off[s]);
+        mp.ref_xyb[s] = cached ? c->cache.xyb.as<float>() + xyb_off(p, s) : nullptr;
+        mp.ref_s11[s] = cached ? c->cache.blur.as<float>() + xyb_off(p, s) : nullptr;
+        fa.part[s] = mp.part[s] = b.part.as<double>() + poff[s];
         bp.blk_end[s] = (int)(mp.blk_end[s] * (long long)n);
     }
     bp.n_items = (int)n;
@@ -1136,7 +1085,7 @@ int batch_run(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dists, size
     bp.part_stride = part_stride;
     if (p.nscales > 1) {
         const uint8_t* frames[2] = {against_ref ? d_dists : d_refs, d_dists};
-        float* lin[2] = {against_ref ? (float*)c->b_lin_dist : (float*)c->b_lin_ref, (float*)c->b_lin_dist};
+        float* lin[2] = {against_ref ? b.lin_dist.as<float>() : b.lin_ref.as<float>(), b.lin_dist.as<float>()};
         PyrBatchArgs pb;
         pb.a = pyramid_args(p, nframes, frames, lin);
         pb.in_stride = stride0;
@@ -1148,20 +1097,20 @@ int batch_run(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dists, size
         if (cached) launch(k_march_refblur_batch, dim3((unsigned)(blocks * n)), dim3(MARCH_THREADS), 0, c->stream, bp);
         else launch(k_march_batch, dim3((unsigned)(blocks * n)), dim3(MARCH_THREADS), 0, c->stream, bp);
     }
-    launch(k_finalize_batch, dim3(n), dim3(1024), 0, c->stream, fa, part_stride, c->bh_result);
+    launch(k_finalize_batch, dim3(n), dim3(1024), 0, c->stream, fa, part_stride, b.result.as<double>());
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->batch_n = n;
-    for (uint32_t i = 0; i < n; ++i) out_scores[i] = c->bh_result[(size_t)i * kResultDoubles + 108];
+    for (uint32_t i = 0; i < n; ++i) out_scores[i] = b.result.as<double>()[(size_t)i * kResultDoubles + 108];
     return SSIMU2_OK;
 }
 
 // Upload n host frames into a staging buffer of the context, `stride` bytes apart, on the context stream.
-int batch_stage(ssimu2_ctx* c, void** buf, size_t* cap, const uint8_t* const* frames, uint32_t n, size_t bytes, size_t stride) {
-    int rc = hbd_grow(c, buf, cap, (size_t)n * stride + 16, "hipMalloc(batch frames)");
+int batch_stage(ssimu2_ctx* c, DevBuf& buf, const uint8_t* const* frames, uint32_t n, size_t bytes, size_t stride) {
+    int rc = grow(c, buf, (size_t)n * stride + 16, "hipMalloc(batch frames)");
     if (rc) return rc;
     for (uint32_t i = 0; i < n; ++i)
-        HIP_TRY(c, hipMemcpyAsync((uint8_t*)*buf + (size_t)i * stride, frames[i], bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(buf.as<uint8_t>() + (size_t)i * stride, frames[i], bytes, hipMemcpyHostToDevice, c->stream));
     return SSIMU2_OK;
 }
 
@@ -1176,10 +1125,10 @@ int ssimu2_ctx_set_blur(ssimu2_ctx* c, int mode) {
     if (mode != SSIMU2_BLUR_FIR && mode != SSIMU2_BLUR_RECURSIVE && mode != SSIMU2_BLUR_RECURSIVE_FMA)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "unknown blur mode");
     if (c->pending) return c->fail(SSIMU2_ERR_INVALID_ARG, "ssimu2_ctx_set_blur: a score is still enqueued");
-    if (mode == SSIMU2_BLUR_FIR && c->d_rg) {  // the recursive modes' planes are of no use to the default mode
+    if (mode == SSIMU2_BLUR_FIR && c->rg.planes.p) {  // the recursive modes' planes are of no use to the default mode
         HIP_TRY(c, hipSetDevice(c->device));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        free_recursive(c);
+        release_recursive(c);
     }
     c->blur_mode = mode;
     c->have_ref = false;
@@ -1529,7 +1478,8 @@ static int ctx_create_impl(int device, void* hip_stream, ssimu2_ctx** out_ctx) {
     CREATE_TRY(hipEventCreate(&c->ev0));
     CREATE_TRY(hipEventCreate(&c->ev1));
     CREATE_TRY(hipMalloc(&c->d_result, 110 * sizeof(double)));
-    CREATE_TRY(hipHostMalloc(&c->h_result, 110 * sizeof(double), hipHostMallocDefault));
+    CREATE_TRY(hipHostMalloc(&c->h_result.p, 110 * sizeof(double), hipHostMallocDefault));
+    c->h_result.cap = 110 * sizeof(double);
     {
         // The constant table lives in device memory of this module, one copy per device, shared
         // by every context on that device: upload it once per device (contexts may be created
@@ -1565,11 +1515,11 @@ void ssimu2_ctx_destroy(ssimu2_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    free_buffers(c);
-    free_batch(c);
-    (void)hipFree(c->d_tab);
+    release_frame_groups(c);
+    release(c->batch);
+    release(c->tab);
     (void)hipFree(c->d_result);
-    (void)hipHostFree(c->h_result);
+    release(c->h_result);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -1582,7 +1532,7 @@ int ssimu2_wait(ssimu2_ctx* c, double* out_score) {
     if (!c->pending) return c->fail(SSIMU2_ERR_INVALID_ARG, "ssimu2_wait: nothing enqueued");
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->pending = false;
-    if (out_score) *out_score = c->h_result[108];
+    if (out_score) *out_score = c->h_result.as<double>()[108];
     return SSIMU2_OK;
 }
 
@@ -1615,9 +1565,10 @@ int ssimu2_score_rgb8(ssimu2_ctx* c, const uint8_t* ref, const uint8_t* dist, ui
     if ((rc = ensure_capacity(c, w, h))) return rc;
     c->have_ref = false;
     const size_t bytes = (size_t)w * h * 3;
-    HIP_TRY(c, hipMemcpyAsync(c->d_ref_u8, ref, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_dist_u8, dist, bytes, hipMemcpyHostToDevice, c->stream));
-    if ((rc = enqueue_score(c, c->d_ref_u8, c->d_dist_u8, w, h, false))) return rc;
+    uint8_t *d_ref = c->frame.ref_u8.as<uint8_t>(), *d_dist = c->frame.dist_u8.as<uint8_t>();
+    HIP_TRY(c, hipMemcpyAsync(d_ref, ref, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_dist, dist, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = enqueue_score(c, d_ref, d_dist, w, h, false))) return rc;
     return ssimu2_wait(c, out_score);
 }
 
@@ -1626,45 +1577,27 @@ int ssimu2_score_rgb8(ssimu2_ctx* c, const uint8_t* ref, const uint8_t* dist, ui
 // `required` (16-bit references): a failed allocation is an error instead of a reference converted on every pass.
 static int cache_reference_fir(ssimu2_ctx* c, const Pyramid& p, const void* scale0, bool scale0_u8, bool required) {
     // ... and its positive-XYB planes at every scale, so that the per-pass kernel skips the
-    // LUT / opsin / cube-root work for the reference frame (same values, bit-identical scores)
-    const size_t need_xyb = xyb_off(p, p.nscales) + 4;
-    if (need_xyb > c->cap_xyb) {
-        (void)hipFree(c->d_xyb_ref);
-        c->d_xyb_ref = nullptr;
-        c->cap_xyb = 0;
-        hipError_t e = hipMalloc(&c->d_xyb_ref, need_xyb * sizeof(float));
-        if (e != hipSuccess) {
-            // not fatal: the search still works, the reference is just converted on every pass
-            c->d_xyb_ref = nullptr;
-            (void)hipGetLastError();
-        } else {
-            c->cap_xyb = need_xyb;
-        }
-    }
-    if (c->d_xyb_ref) {
+    // LUT / opsin / cube-root work for the reference frame (same values, bit-identical scores).
+    // A failed allocation of either plane set is not an error unless `required`: the search still works, the
+    // reference is just converted (and all five planes blurred) on every pass.  A grow() that fails leaves the
+    // buffer released and no sticky HIP error.
+    const size_t bytes = (xyb_off(p, p.nscales) + 4) * sizeof(float);
+    const char* what = "hipMalloc(cached reference planes)";
+    (void)grow(c, c->cache.xyb, bytes, what);
+    float* const xyb = c->cache.xyb.as<float>();
+    if (xyb) {
         for (int sc = 0; sc < p.nscales; ++sc) {
             const size_t n = (size_t)p.w[sc] * p.h[sc];
-            const void* in = sc == 0 ? scale0 : (const void*)(c->d_lin_ref + p.lin_off[sc]);
+            const void* in = sc == 0 ? scale0 : (const void*)(c->frame.lin_ref.as<float>() + p.lin_off[sc]);
             launch(k_ref_xyb, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, in,
-                               sc == 0 && scale0_u8, p.w[sc], p.h[sc], c->d_xyb_ref + xyb_off(p, sc));
+                               sc == 0 && scale0_u8, p.w[sc], p.h[sc], xyb + xyb_off(p, sc));
         }
     }
     // ... and blur(ref*ref) at every scale, which depends on the reference alone: the per-pass
     // kernel then blurs four planes instead of five (caching blur(ref) too was measured slower)
-    if (c->d_xyb_ref && c->cache_ref_blur) {
-        if (need_xyb > c->cap_blur) {
-            (void)hipFree(c->d_ref_blur);
-            c->d_ref_blur = nullptr;
-            c->cap_blur = 0;
-            hipError_t e = hipMalloc(&c->d_ref_blur, need_xyb * sizeof(float));
-            if (e != hipSuccess) {  // not fatal either: the pass blurs all five planes
-                c->d_ref_blur = nullptr;
-                (void)hipGetLastError();
-            } else {
-                c->cap_blur = need_xyb;
-            }
-        }
-        if (c->d_ref_blur) {
+    if (xyb && c->cache_ref_blur) {
+        (void)grow(c, c->cache.blur, bytes, what);
+        if (c->cache.blur.p) {
             MarchPlan mp;
             FinalizeArgs fa;
             int blocks = 0;
@@ -1673,13 +1606,22 @@ static int cache_reference_fir(ssimu2_ctx* c, const Pyramid& p, const void* scal
             if (blocks > 0)
                 launch(k_ref_blur, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
         }
-    } else if (c->d_ref_blur) {
-        (void)hipFree(c->d_ref_blur);
-        c->d_ref_blur = nullptr;
-        c->cap_blur = 0;
+    } else if (c->cache.blur.p) {  // the instrumented build's cache flag is off
+        c->cache.blur.release();
     }
-    if (required && !(c->d_xyb_ref && c->d_ref_blur && c->cap_blur))
+    if (required && !ref_cached(c))
         return c->fail(SSIMU2_ERR_OOM, "hipMalloc(cached planes of a 16-bit reference)");
+    return SSIMU2_OK;
+}
+
+// The end of every ssimu2_set_reference*: everything of the reference is enqueued.
+static int reference_set(ssimu2_ctx* c, uint32_t w, uint32_t h, bool hbd) {
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // caller may free `ref` after return
+    c->have_ref = true;
+    c->ref_hbd = hbd;
+    c->ref_w = w;
+    c->ref_h = h;
     return SSIMU2_OK;
 }
 
@@ -1690,36 +1632,23 @@ static int set_reference_impl(ssimu2_ctx* c, const void* ref, uint32_t w, uint32
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = ensure_capacity(c, w, h))) return rc;
     const Pyramid p = make_pyramid(w, h);
-    if (c->blur_mode != SSIMU2_BLUR_FIR) {  // size limit and planes of the recursive modes, before any launch
-        if ((rc = rg_check_size(c, w, h))) return rc;
-        if ((rc = rg_ensure(c, p))) return rc;
-    }
+    const bool fir = c->blur_mode == SSIMU2_BLUR_FIR;
+    if (!fir && (rc = rg_prepare(c, p, w, h, false))) return rc;  // before any launch
     c->have_ref = false;
-    c->ref_hbd = false;
     note_lin0(c, 0, 0, w, h);
-    const size_t bytes = (size_t)w * h * 3;
-    HIP_TRY(c, hipMemcpyAsync(c->d_ref_u8, ref, bytes, kind, c->stream));
-    if (p.nscales > 1 && c->blur_mode == SSIMU2_BLUR_FIR) {  // the reference's linear pyramid, once per search
-        const uint8_t* frames[1] = {c->d_ref_u8};
-        float* lin[1] = {c->d_lin_ref};
+    uint8_t* const d_ref = c->frame.ref_u8.as<uint8_t>();
+    HIP_TRY(c, hipMemcpyAsync(d_ref, ref, (size_t)w * h * 3, kind, c->stream));
+    if (!fir) {  // XYB planes, blur(x) and blur(x*x) by the published recursion
+        rg_enqueue_reference(c, p, d_ref);
+        return reference_set(c, w, h, false);
+    }
+    if (p.nscales > 1) {  // the reference's linear pyramid, once per search
+        const uint8_t* frames[1] = {d_ref};
+        float* lin[1] = {c->frame.lin_ref.as<float>()};
         launch_pyramid(c, p, 1, frames, lin);
     }
-    if (c->blur_mode != SSIMU2_BLUR_FIR) {  // XYB planes, blur(x) and blur(x*x) by the published recursion
-        rg_enqueue_reference(c, p, c->d_ref_u8);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipStreamSynchronize(c->stream));  // caller may free `ref` after return
-        c->have_ref = true;
-        c->ref_w = w;
-        c->ref_h = h;
-        return SSIMU2_OK;
-    }
-    (void)cache_reference_fir(c, p, c->d_ref_u8, true, false);  // not required: an 8-bit pass can convert the reference
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // caller may free `ref` after return
-    c->have_ref = true;
-    c->ref_w = w;
-    c->ref_h = h;
-    return SSIMU2_OK;
+    (void)cache_reference_fir(c, p, d_ref, true, false);  // not required: an 8-bit pass can convert the reference
+    return reference_set(c, w, h, false);
 }
 
 int ssimu2_set_reference(ssimu2_ctx* c, const uint8_t* ref, uint32_t w, uint32_t h) {
@@ -1730,31 +1659,50 @@ int ssimu2_set_reference_device(ssimu2_ctx* c, const void* d_ref, uint32_t w, ui
     return set_reference_impl(c, d_ref, w, h, hipMemcpyDeviceToDevice);
 }
 
-int ssimu2_enqueue_against_reference_device(ssimu2_ctx* c, const void* d_dist) {
+// What every against-reference call checks first, in this order; `pointers`: none of the call's pointers is null.
+static int check_against(ssimu2_ctx* c, bool pointers) {
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     if (!c->have_ref) return c->fail(SSIMU2_ERR_NO_REFERENCE, "no reference set");
-    if (!d_dist) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
-    HIP_TRY(c, hipSetDevice(c->device));
-    return enqueue_score(c, c->d_ref_u8, (const uint8_t*)d_dist, c->ref_w, c->ref_h, true);
+    if (!pointers) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
+    return SSIMU2_OK;
 }
 
-int ssimu2_score_against_reference(ssimu2_ctx* c, const uint8_t* dist, double* out_score) {
-    if (!c) return SSIMU2_ERR_INVALID_ARG;
-    if (!c->have_ref) return c->fail(SSIMU2_ERR_NO_REFERENCE, "no reference set");
-    if (!dist || !out_score) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
+int ssimu2_enqueue_against_reference_device(ssimu2_ctx* c, const void* d_dist) {
+    int rc = check_against(c, d_dist != nullptr);
+    if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)c->ref_w * c->ref_h * 3;
-    HIP_TRY(c, hipMemcpyAsync(c->d_dist_u8, dist, bytes, hipMemcpyHostToDevice, c->stream));
-    int rc = enqueue_score(c, c->d_ref_u8, c->d_dist_u8, c->ref_w, c->ref_h, true);
+    return enqueue_score(c, c->frame.ref_u8.as<uint8_t>(), (const uint8_t*)d_dist, c->ref_w, c->ref_h, true);
+}
+
+// The 8-bit frame now in frame.dist_u8 against the cached reference.
+static int score_against_reference8(ssimu2_ctx* c, double* out_score) {
+    int rc = enqueue_score(c, c->frame.ref_u8.as<uint8_t>(), c->frame.dist_u8.as<uint8_t>(), c->ref_w, c->ref_h, true);
     if (rc) return rc;
     return ssimu2_wait(c, out_score);
 }
 
+// One decoded frame into the staging buffer: one buffer for the 8-bit and the 16-bit strided call, with 16 bytes of
+// slack behind the frame.
+static int stage_upload(ssimu2_ctx* c, const void* pixels, size_t bytes) {
+    int rc = grow(c, c->stage, bytes + 16, "hipMalloc(staging frame)");
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->stage.p, pixels, bytes, hipMemcpyHostToDevice, c->stream));
+    return SSIMU2_OK;
+}
+
+int ssimu2_score_against_reference(ssimu2_ctx* c, const uint8_t* dist, double* out_score) {
+    int rc = check_against(c, dist && out_score);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->ref_w * c->ref_h * 3;
+    HIP_TRY(c, hipMemcpyAsync(c->frame.dist_u8.p, dist, bytes, hipMemcpyHostToDevice, c->stream));
+    return score_against_reference8(c, out_score);
+}
+
 int ssimu2_score_against_reference_strided(ssimu2_ctx* c, const uint8_t* pixels, uint32_t row_bytes,
                                            uint32_t channels, double* out_score) {
-    if (!c) return SSIMU2_ERR_INVALID_ARG;
-    if (!c->have_ref) return c->fail(SSIMU2_ERR_NO_REFERENCE, "no reference set");
-    if (!pixels || !out_score) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
+    int rc = check_against(c, pixels && out_score);
+    if (rc) return rc;
     if (channels != 3 && channels != 4)
         return c->fail(SSIMU2_ERR_UNSUPPORTED, "channels must be 3 (RGB) or 4 (RGBA)");
     const uint32_t w = c->ref_w, h = c->ref_h;
@@ -1766,25 +1714,14 @@ int ssimu2_score_against_reference_strided(ssimu2_ctx* c, const uint8_t* pixels,
     // the last row needs only its pixels, not its padding (libavif allocates rowBytes * height,
     // a cropped view of a larger buffer may not)
     const size_t bytes = (size_t)row_bytes * (h - 1) + (size_t)w * channels;
-    if (bytes > c->cap_stage) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_stage);
-        c->d_stage = nullptr;
-        c->cap_stage = 0;
-        hipError_t e = hipMalloc(&c->d_stage, bytes + 16);
-        if (e != hipSuccess) return c->fail(SSIMU2_ERR_OOM, "hipMalloc(staging frame)", e);
-        c->cap_stage = bytes;
-    }
-    HIP_TRY(c, hipMemcpyAsync(c->d_stage, pixels, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = stage_upload(c, pixels, bytes))) return rc;
     if (channels == 4 && w % 4 == 0 && row_bytes % 4 == 0)
         launch(k_unpack_rgb<true>, dim3((w / 4 + 255) / 256, h), dim3(256), 0, c->stream,
-                           c->d_stage, row_bytes, channels, w, h, c->d_dist_u8);
+                           c->stage.as<uint8_t>(), row_bytes, channels, w, h, c->frame.dist_u8.as<uint8_t>());
     else
         launch(k_unpack_rgb<false>, dim3((w + 255) / 256, h), dim3(256), 0, c->stream,
-                           c->d_stage, row_bytes, channels, w, h, c->d_dist_u8);
-    int rc = enqueue_score(c, c->d_ref_u8, c->d_dist_u8, w, h, true);
-    if (rc) return rc;
-    return ssimu2_wait(c, out_score);
+                           c->stage.as<uint8_t>(), row_bytes, channels, w, h, c->frame.dist_u8.as<uint8_t>());
+    return score_against_reference8(c, out_score);
 }
 
 int ssimu2_error_map_rgb8(ssimu2_ctx* c, const uint8_t* ref, const uint8_t* dist, uint32_t w, uint32_t h,
@@ -1793,7 +1730,7 @@ int ssimu2_error_map_rgb8(ssimu2_ctx* c, const uint8_t* ref, const uint8_t* dist
     if (!out_map) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_map");
     int rc = ssimu2_score_rgb8(c, ref, dist, w, h, channels, out_score);
     if (rc) return rc;
-    return map_pass(c, c->d_ref_u8, c->d_dist_u8, w, h, out_map);
+    return map_pass(c, c->frame.ref_u8.as<uint8_t>(), c->frame.dist_u8.as<uint8_t>(), w, h, out_map);
 }
 
 int ssimu2_error_map_against_reference(ssimu2_ctx* c, const uint8_t* dist, float* out_map, double* out_score) {
@@ -1803,7 +1740,7 @@ int ssimu2_error_map_against_reference(ssimu2_ctx* c, const uint8_t* dist, float
         return c->fail(SSIMU2_ERR_UNSUPPORTED, "no error map against a reference set from 16-bit samples");
     int rc = ssimu2_score_against_reference(c, dist, out_score);
     if (rc) return rc;
-    return map_pass(c, c->d_ref_u8, c->d_dist_u8, c->ref_w, c->ref_h, out_map);
+    return map_pass(c, c->frame.ref_u8.as<uint8_t>(), c->frame.dist_u8.as<uint8_t>(), c->ref_w, c->ref_h, out_map);
 }
 
 // ---- 16-bit input ----------------------------------------------------------
@@ -1829,14 +1766,14 @@ int ssimu2_score_rgb16(ssimu2_ctx* c, const uint16_t* ref, const uint16_t* dist,
     c->have_ref = false;  // the lin_ref pyramid is overwritten
     const size_t bytes = (size_t)w * h * 3 * sizeof(uint16_t);
     const float* tab = nullptr;
-    if ((rc = hbd_grow(c, &c->d_ref16, &c->cap_ref16, bytes, "hipMalloc(16-bit frames)")) ||
-        (rc = hbd_grow(c, &c->d_dist16, &c->cap_dist16, bytes, "hipMalloc(16-bit frames)")) ||
+    if ((rc = grow(c, c->hbd.ref16, bytes, "hipMalloc(16-bit frames)")) ||
+        (rc = grow(c, c->hbd.dist16, bytes, "hipMalloc(16-bit frames)")) ||
         (rc = hbd_lin0(c, w, h, true)) || (rc = device_table(c, bit_depth, &tab)))
         return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->d_ref16, ref, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_dist16, dist, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->hbd.ref16.p, ref, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->hbd.dist16.p, dist, bytes, hipMemcpyHostToDevice, c->stream));
     const uint32_t maxv = (1u << bit_depth) - 1u;
-    const Src16 r{c->d_ref16, w * 6u, 3u, tab, maxv}, d{c->d_dist16, w * 6u, 3u, tab, maxv};
+    const Src16 r{c->hbd.ref16.p, w * 6u, 3u, tab, maxv}, d{c->hbd.dist16.p, w * 6u, 3u, tab, maxv};
     if ((rc = enqueue_score16(c, &r, d, w, h))) return rc;
     return ssimu2_wait(c, out_score);
 }
@@ -1854,28 +1791,22 @@ int ssimu2_set_reference_rgb16(ssimu2_ctx* c, const uint16_t* ref, uint32_t w, u
     c->have_ref = false;
     const size_t bytes = (size_t)w * h * 3 * sizeof(uint16_t);
     const float* tab = nullptr;
-    if ((rc = hbd_grow(c, &c->d_ref16, &c->cap_ref16, bytes, "hipMalloc(16-bit frames)")) ||
+    if ((rc = grow(c, c->hbd.ref16, bytes, "hipMalloc(16-bit frames)")) ||
         (rc = hbd_lin0(c, w, h, true)) || (rc = device_table(c, bit_depth, &tab)))
         return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->d_ref16, ref, bytes, hipMemcpyHostToDevice, c->stream));
-    const Src16 r{c->d_ref16, w * 6u, 3u, tab, (1u << bit_depth) - 1u};
+    HIP_TRY(c, hipMemcpyAsync(c->hbd.ref16.p, ref, bytes, hipMemcpyHostToDevice, c->stream));
+    const Src16 r{c->hbd.ref16.p, w * 6u, 3u, tab, (1u << bit_depth) - 1u};
     if (fir) {  // linear pyramid and scale-0 planes, then the same caches as an 8-bit reference's (required here)
         const Src16* src[1] = {&r};
-        float* lin[1] = {c->d_lin_ref};
-        float* lin0[1] = {(float*)c->d_lin0_ref};
+        float* lin[1] = {c->frame.lin_ref.as<float>()};
+        float* lin0[1] = {c->hbd.lin0_ref.as<float>()};
         launch_pyramid16(c, p, 1, src, lin, lin0);
         if (p.nscales >= 1) note_lin0(c, 1, -1, w, h);
-        if ((rc = cache_reference_fir(c, p, c->d_lin0_ref, false, true))) return rc;
+        if ((rc = cache_reference_fir(c, p, c->hbd.lin0_ref.p, false, true))) return rc;
     } else {
         rg_enqueue_reference(c, p, nullptr, &r);
     }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // caller may free `ref` after return
-    c->have_ref = true;
-    c->ref_hbd = true;
-    c->ref_w = w;
-    c->ref_h = h;
-    return SSIMU2_OK;
+    return reference_set(c, w, h, true);
 }
 
 // Score the 16-bit frame at `src.px` (already on the device) against the cached reference.
@@ -1886,29 +1817,23 @@ static int score_against_reference16(ssimu2_ctx* c, const Src16& src, double* ou
 }
 
 int ssimu2_score_against_reference_rgb16(ssimu2_ctx* c, const uint16_t* dist, uint32_t bit_depth, double* out_score) {
-    if (!c) return SSIMU2_ERR_INVALID_ARG;
-    if (!c->have_ref) return c->fail(SSIMU2_ERR_NO_REFERENCE, "no reference set");
-    if (!out_score) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
-    int rc = check16(c, dist, bit_depth);
-    if (rc) return rc;
+    int rc = check_against(c, out_score != nullptr);
+    if (rc || (rc = check16(c, dist, bit_depth))) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const uint32_t w = c->ref_w, h = c->ref_h;
     const size_t bytes = (size_t)w * h * 3 * sizeof(uint16_t);
     const float* tab = nullptr;
-    if ((rc = hbd_grow(c, &c->d_dist16, &c->cap_dist16, bytes, "hipMalloc(16-bit frames)")) ||
+    if ((rc = grow(c, c->hbd.dist16, bytes, "hipMalloc(16-bit frames)")) ||
         (rc = hbd_lin0(c, w, h, false)) || (rc = device_table(c, bit_depth, &tab)))
         return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->d_dist16, dist, bytes, hipMemcpyHostToDevice, c->stream));
-    return score_against_reference16(c, Src16{c->d_dist16, w * 6u, 3u, tab, (1u << bit_depth) - 1u}, out_score);
+    HIP_TRY(c, hipMemcpyAsync(c->hbd.dist16.p, dist, bytes, hipMemcpyHostToDevice, c->stream));
+    return score_against_reference16(c, Src16{c->hbd.dist16.p, w * 6u, 3u, tab, (1u << bit_depth) - 1u}, out_score);
 }
 
 int ssimu2_score_against_reference_strided16(ssimu2_ctx* c, const uint16_t* pixels, uint32_t row_bytes,
                                              uint32_t channels, uint32_t bit_depth, double* out_score) {
-    if (!c) return SSIMU2_ERR_INVALID_ARG;
-    if (!c->have_ref) return c->fail(SSIMU2_ERR_NO_REFERENCE, "no reference set");
-    if (!out_score) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
-    int rc = check16(c, pixels, bit_depth);
-    if (rc) return rc;
+    int rc = check_against(c, out_score != nullptr);
+    if (rc || (rc = check16(c, pixels, bit_depth))) return rc;
     if (channels != 3 && channels != 4)
         return c->fail(SSIMU2_ERR_UNSUPPORTED, "channels must be 3 (RGB) or 4 (RGBA)");
     const uint32_t w = c->ref_w, h = c->ref_h;
@@ -1919,17 +1844,8 @@ int ssimu2_score_against_reference_strided16(ssimu2_ctx* c, const uint16_t* pixe
     const size_t bytes = (size_t)row_bytes * (h - 1) + (size_t)w * channels * 2;
     const float* tab = nullptr;
     if ((rc = hbd_lin0(c, w, h, false)) || (rc = device_table(c, bit_depth, &tab))) return rc;
-    if (bytes > c->cap_stage) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_stage);
-        c->d_stage = nullptr;
-        c->cap_stage = 0;
-        hipError_t e = hipMalloc(&c->d_stage, bytes + 16);
-        if (e != hipSuccess) return c->fail(SSIMU2_ERR_OOM, "hipMalloc(staging frame)", e);
-        c->cap_stage = bytes;
-    }
-    HIP_TRY(c, hipMemcpyAsync(c->d_stage, pixels, bytes, hipMemcpyHostToDevice, c->stream));
-    return score_against_reference16(c, Src16{c->d_stage, row_bytes, channels, tab, (1u << bit_depth) - 1u}, out_score);
+    if ((rc = stage_upload(c, pixels, bytes))) return rc;
+    return score_against_reference16(c, Src16{c->stage.p, row_bytes, channels, tab, (1u << bit_depth) - 1u}, out_score);
 }
 
 int ssimu2_last_averages(ssimu2_ctx* c, double* out, int* out_num_scales) {
@@ -1938,18 +1854,16 @@ int ssimu2_last_averages(ssimu2_ctx* c, double* out, int* out_num_scales) {
         int rc = ssimu2_wait(c, nullptr);
         if (rc) return rc;
     }
-    memcpy(out, c->h_result, 108 * sizeof(double));
-    if (out_num_scales) *out_num_scales = (int)c->h_result[109];
+    memcpy(out, c->h_result.p, 108 * sizeof(double));
+    if (out_num_scales) *out_num_scales = (int)c->h_result.as<double>()[109];
     return SSIMU2_OK;
 }
 
 // ---- batch scoring ---------------------------------------------------------
 int ssimu2_score_batch_rgb8_device(ssimu2_ctx* c, const void* d_refs, const void* d_dists, size_t item_stride_bytes,
                                    uint32_t n, uint32_t w, uint32_t h, double* out_scores) {
-    if (!c) return SSIMU2_ERR_INVALID_ARG;
-    if (n == 0) return SSIMU2_OK;
-    int rc = batch_check(c, n, false);
-    if (rc) return rc;
+    int rc = batch_open(c, n, false);
+    if (rc || n == 0) return rc;
     if ((rc = check_args(c, d_refs, d_dists, w, h))) return rc;
     if (!out_scores) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_scores");
     if ((uint64_t)item_stride_bytes < (uint64_t)w * h * 3)
@@ -1960,10 +1874,8 @@ int ssimu2_score_batch_rgb8_device(ssimu2_ctx* c, const void* d_refs, const void
 
 int ssimu2_score_batch_against_reference_device(ssimu2_ctx* c, const void* d_dists, size_t item_stride_bytes, uint32_t n,
                                                 double* out_scores) {
-    if (!c) return SSIMU2_ERR_INVALID_ARG;
-    if (n == 0) return SSIMU2_OK;
-    int rc = batch_check(c, n, true);
-    if (rc) return rc;
+    int rc = batch_open(c, n, true);
+    if (rc || n == 0) return rc;
     if (!d_dists || !out_scores) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
     if ((uint64_t)item_stride_bytes < (uint64_t)c->ref_w * c->ref_h * 3)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "item_stride_bytes smaller than one frame");
@@ -1973,41 +1885,37 @@ int ssimu2_score_batch_against_reference_device(ssimu2_ctx* c, const void* d_dis
 
 int ssimu2_score_batch_rgb8(ssimu2_ctx* c, const uint8_t* const* refs, const uint8_t* const* dists, uint32_t n, uint32_t w,
                             uint32_t h, double* out_scores) {
-    if (!c) return SSIMU2_ERR_INVALID_ARG;
-    if (n == 0) return SSIMU2_OK;
-    int rc = batch_check(c, n, false);
-    if (rc) return rc;
+    int rc = batch_open(c, n, false);
+    if (rc || n == 0) return rc;
     if ((rc = check_args(c, refs, dists, w, h))) return rc;
     if (!out_scores) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_scores");
     for (uint32_t i = 0; i < n; ++i)
         if (!refs[i] || !dists[i]) return c->fail(SSIMU2_ERR_INVALID_ARG, "null image pointer in the batch");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)w * h * 3, stride = (bytes + 15) & ~(size_t)15;
-    if ((rc = batch_stage(c, &c->b_u8_ref, &c->cap_b_u8_ref, refs, n, bytes, stride)) ||
-        (rc = batch_stage(c, &c->b_u8_dist, &c->cap_b_u8_dist, dists, n, bytes, stride))) {
+    if ((rc = batch_stage(c, c->batch.u8_ref, refs, n, bytes, stride)) ||
+        (rc = batch_stage(c, c->batch.u8_dist, dists, n, bytes, stride))) {
         (void)hipStreamSynchronize(c->stream);  // the caller may free its frames after any return
         return rc;
     }
-    rc = batch_run(c, (const uint8_t*)c->b_u8_ref, (const uint8_t*)c->b_u8_dist, stride, n, w, h, out_scores);
+    rc = batch_run(c, c->batch.u8_ref.as<uint8_t>(), c->batch.u8_dist.as<uint8_t>(), stride, n, w, h, out_scores);
     if (rc) (void)hipStreamSynchronize(c->stream);
     return rc;
 }
 
 int ssimu2_score_batch_against_reference(ssimu2_ctx* c, const uint8_t* const* dists, uint32_t n, double* out_scores) {
-    if (!c) return SSIMU2_ERR_INVALID_ARG;
-    if (n == 0) return SSIMU2_OK;
-    int rc = batch_check(c, n, true);
-    if (rc) return rc;
+    int rc = batch_open(c, n, true);
+    if (rc || n == 0) return rc;
     if (!dists || !out_scores) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
     for (uint32_t i = 0; i < n; ++i)
         if (!dists[i]) return c->fail(SSIMU2_ERR_INVALID_ARG, "null image pointer in the batch");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)c->ref_w * c->ref_h * 3, stride = (bytes + 15) & ~(size_t)15;
-    if ((rc = batch_stage(c, &c->b_u8_dist, &c->cap_b_u8_dist, dists, n, bytes, stride))) {
+    if ((rc = batch_stage(c, c->batch.u8_dist, dists, n, bytes, stride))) {
         (void)hipStreamSynchronize(c->stream);
         return rc;
     }
-    rc = batch_run(c, nullptr, (const uint8_t*)c->b_u8_dist, stride, n, c->ref_w, c->ref_h, out_scores);
+    rc = batch_run(c, nullptr, c->batch.u8_dist.as<uint8_t>(), stride, n, c->ref_w, c->ref_h, out_scores);
     if (rc) (void)hipStreamSynchronize(c->stream);
     return rc;
 }
@@ -2015,7 +1923,7 @@ int ssimu2_score_batch_against_reference(ssimu2_ctx* c, const uint8_t* const* di
 int ssimu2_last_batch_averages(ssimu2_ctx* c, uint32_t item, double* out, int* out_num_scales) {
     if (!c || !out) return SSIMU2_ERR_INVALID_ARG;
     if (item >= c->batch_n) return c->fail(SSIMU2_ERR_INVALID_ARG, "ssimu2_last_batch_averages: no such item in the last batch");
-    const double* r = c->bh_result + (size_t)item * kResultDoubles;
+    const double* r = c->batch.result.as<double>() + (size_t)item * kResultDoubles;
     memcpy(out, r, 108 * sizeof(double));
     if (out_num_scales) *out_num_scales = (int)r[109];
     return SSIMU2_OK;

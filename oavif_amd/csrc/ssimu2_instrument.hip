@@ -52,7 +52,7 @@ int ssimu2_instr_set_segment_rows(ssimu2_ctx* c, int rows_scale0, int rows_other
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->seg_rows_override = rows_scale0;
     c->seg_rows_tail_override = rows_other_scales;
-    free_buffers(c);  // the partial-sum buffer is sized by the segment rule
+    release_frame_groups(c);  // the partial-sum buffer is sized by the segment rule
     c->have_ref = false;
     return SSIMU2_OK;
 }
@@ -107,37 +107,37 @@ int ssimu2_debug_download(ssimu2_ctx* c, int what, int scale, uint32_t w, uint32
     if ((what == SSIMU2_DEBUG_LIN_REF || what == SSIMU2_DEBUG_LIN_DIST) && scale == 0) {
         // a 16-bit FIR call's scale-0 linear planes (what k_march_lin reads), while they are the last score's
         const bool r = what == SSIMU2_DEBUG_LIN_REF;
-        const void* planes = r ? c->d_lin0_ref : c->d_lin0_dist;
+        const void* planes = r ? c->hbd.lin0_ref.p : c->hbd.lin0_dist.p;
         if (!planes || p.nscales < 1 || (r ? c->lin0_ref_w : c->lin0_dist_w) != w ||
             (r ? c->lin0_ref_h : c->lin0_dist_h) != h)
             return c->fail(SSIMU2_ERR_INVALID_ARG, "no 16-bit scale-0 planes of that frame from the last score");
         src = (const float*)planes;
     } else if (what == SSIMU2_DEBUG_LIN_REF || what == SSIMU2_DEBUG_LIN_DIST) {
-        if (scale < 1 || scale >= p.nscales || !c->d_lin_ref) return c->fail(SSIMU2_ERR_INVALID_ARG, "no such level");
-        src = (what == SSIMU2_DEBUG_LIN_REF ? c->d_lin_ref : c->d_lin_dist) + p.lin_off[scale];
+        if (scale < 1 || scale >= p.nscales || !c->frame.lin_ref.p) return c->fail(SSIMU2_ERR_INVALID_ARG, "no such level");
+        src = (what == SSIMU2_DEBUG_LIN_REF ? c->frame.lin_ref : c->frame.lin_dist).as<float>() + p.lin_off[scale];
     } else if (what == SSIMU2_DEBUG_XYB_REF) {
-        if (scale < 0 || scale >= p.nscales || !c->d_xyb_ref || !c->have_ref || c->ref_w != w || c->ref_h != h)
+        if (scale < 0 || scale >= p.nscales || !c->cache.xyb.p || !c->have_ref || c->ref_w != w || c->ref_h != h)
             return c->fail(SSIMU2_ERR_INVALID_ARG, "no cached reference XYB for that level");
-        src = c->d_xyb_ref + xyb_off(p, scale);
+        src = c->cache.xyb.as<float>() + xyb_off(p, scale);
     } else if (what == SSIMU2_DEBUG_RG_H || what == SSIMU2_DEBUG_RG_V) {
         // 15 raw planes of the scale selected with ssimu2_instr_rg_stop_after_scale before the score
-        if (scale < 0 || scale >= p.nscales || scale != c->rg_dbg_scale || !c->d_rg_dbg || !c->d_rg)
+        if (scale < 0 || scale >= p.nscales || scale != c->rg_dbg_scale || !c->rg.dbg.p || !c->rg.planes.p)
             return c->fail(SSIMU2_ERR_INVALID_ARG, "no recursive-blur planes kept for that scale");
         // device planes keep their rows rg_pitch(w) floats apart (ssimu2_recursive.h "Row pitch"); `out` is tight
         const size_t pitch = (size_t)rg_pitch(p.w[scale]), wd = (size_t)p.w[scale], ht = (size_t)p.h[scale];
         const size_t nd = pitch * ht, n1 = wd * ht;
-        if (24 * nd > c->cap_rg_dbg) return c->fail(SSIMU2_ERR_INVALID_ARG, "recursive-blur planes are of another frame size");
+        if (24 * nd * sizeof(float) > c->rg.dbg.cap) return c->fail(SSIMU2_ERR_INVALID_ARG, "recursive-blur planes are of another frame size");
         HIP_TRY(c, hipSetDevice(c->device));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         auto plane = [&](float* dst, const float* src) {
             return hipMemcpy2D(dst, wd * sizeof(float), src, pitch * sizeof(float), wd * sizeof(float), ht, hipMemcpyDeviceToHost);
         };
         if (what == SSIMU2_DEBUG_RG_H) {
-            for (int k = 0; k < 15; ++k) HIP_TRY(c, plane(out + (size_t)k * n1, c->d_rg_dbg + (size_t)k * nd));
+            for (int k = 0; k < 15; ++k) HIP_TRY(c, plane(out + (size_t)k * n1, c->rg.dbg.as<float>() + (size_t)k * nd));
         } else {
             // x, xx: the reference cache [channel][{mu1, s11}]; y, yy, xy: k_rg_v_emit's planes
-            const float* cache = c->d_rg + 6 * rg_plane_off(p, p.nscales) + 6 * rg_plane_off(p, scale);
-            const float* pass = c->d_rg_dbg + 15 * nd;
+            const float* cache = c->rg.planes.as<float>() + 6 * rg_plane_off(p, p.nscales) + 6 * rg_plane_off(p, scale);
+            const float* pass = c->rg.dbg.as<float>() + 15 * nd;
             for (int ch = 0; ch < 3; ++ch) {
                 for (int k = 0; k < 2; ++k)
                     HIP_TRY(c, plane(out + (size_t)rg_plane15(true, ch, k) * n1, cache + (size_t)(ch * 2 + k) * nd));
@@ -149,9 +149,9 @@ int ssimu2_debug_download(ssimu2_ctx* c, int what, int scale, uint32_t w, uint32
         if (out_h) *out_h = (uint32_t)p.h[scale];
         return SSIMU2_OK;
     } else if (what == SSIMU2_DEBUG_REF_BLUR) {
-        if (scale < 0 || scale >= p.nscales || !c->d_ref_blur || !c->have_ref || c->ref_w != w || c->ref_h != h)
+        if (scale < 0 || scale >= p.nscales || !c->cache.blur.p || !c->have_ref || c->ref_w != w || c->ref_h != h)
             return c->fail(SSIMU2_ERR_INVALID_ARG, "no cached reference blur for that level");
-        src = c->d_ref_blur + xyb_off(p, scale);
+        src = c->cache.blur.as<float>() + xyb_off(p, scale);
     } else {
         return c->fail(SSIMU2_ERR_INVALID_ARG, "bad `what`");
     }
@@ -202,7 +202,7 @@ int ssimu2_time_stage(ssimu2_ctx* c, const void* d_ref, const void* d_dist, uint
     for (int i = 0; i < iters; ++i) {
         if (stage == SSIMU2_STAGE_PYRAMID && p.nscales > 1) {
             const uint8_t* frames[2] = {(const uint8_t*)d_ref, (const uint8_t*)d_dist};
-            float* lin[2] = {c->d_lin_ref, c->d_lin_dist};
+            float* lin[2] = {c->frame.lin_ref.as<float>(), c->frame.lin_dist.as<float>()};
             launch_pyramid(c, p, 2, frames, lin);
         } else if (stage == SSIMU2_STAGE_MARCH && blocks > 0) {
             hipLaunchKernelGGL(k_march, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
@@ -317,12 +317,12 @@ int ssimu2_time_blur_stage_rotating(ssimu2_ctx* c, const void* const* d_frames, 
         float* blur = buf + (size_t)(2 * i + 1) * planes;
         if (p.nscales > 1) {
             const uint8_t* frames[1] = {f};
-            float* lins[1] = {c->d_lin_ref};
+            float* lins[1] = {c->frame.lin_ref.as<float>()};
             launch_pyramid(c, p, 1, frames, lins);
         }
         for (int sc = 0; sc < p.nscales; ++sc) {
             const size_t n = (size_t)p.w[sc] * p.h[sc];
-            const void* in = sc == 0 ? (const void*)f : (const void*)(c->d_lin_ref + p.lin_off[sc]);
+            const void* in = sc == 0 ? (const void*)f : (const void*)(c->frame.lin_ref.as<float>() + p.lin_off[sc]);
             hipLaunchKernelGGL(k_ref_xyb, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, in, sc == 0,
                                p.w[sc], p.h[sc], xyb + xyb_off(p, sc));
         }
@@ -387,7 +387,7 @@ int ssimu2_time_kernels(ssimu2_ctx* c, const void* d_ref, const void* const* d_r
         c->have_ref = false;
     }
     auto one = [&](int j) {
-        return cached ? enqueue_score(c, c->d_ref_u8, (const uint8_t*)d_dists[j % n], w, h, true)
+        return cached ? enqueue_score(c, c->frame.ref_u8.as<uint8_t>(), (const uint8_t*)d_dists[j % n], w, h, true)
                       : enqueue_score(c, (const uint8_t*)d_refs[j % n], (const uint8_t*)d_dists[j % n], w, h, false);
     };
     constexpr int kMaxLaunches = 8;

@@ -58,6 +58,59 @@ def test_contexts_give_their_device_memory_back(hip_lib):
         assert abs(after) <= SLACK, f"cycle {cycle}: {after / MB:.1f} MB not returned"
 
 
+def _every_optional_group(s, f, free_before=None):
+    """One context through every call that allocates an optional buffer group at 1920 x 1080 -> (its scores and maps,
+    device bytes alive after the FIR map, device bytes alive with every FIR-side group allocated)."""
+    big, d_big, big16, d_big16, rgba16 = f
+    a, map_fir = s.error_map(big, d_big)                               # frame buffers + the map planes
+    alive_map = None if free_before is None else free_before - _free()
+    b = s.compute_ssimu2_hbd(big16, d_big16, 10)                       # both 16-bit frames, both scale-0 plane sets, the table
+    s.set_reference_hbd(big16, 10)                                     # the reference's cached XYB and blur planes
+    c = s.score_against_reference_hbd(d_big16, 10)
+    d = s.score_decoded_against_reference_hbd(rgba16, bit_depth=10)    # RGBA: the 16.6 MB staging buffer
+    e = tuple(s.score_batch([big, d_big, big, d_big], [d_big, big, d_big, d_big]))   # staged frames of both sides
+    s.set_reference(big)
+    g = tuple(s.score_batch_against_reference([d_big, big, d_big, d_big]))
+    alive_all = None if free_before is None else free_before - _free()
+    s.set_blur(_lib.BLUR_RECURSIVE)
+    h, map_rec = s.error_map(big, d_big)                               # the same map from the recursive modes' planes
+    return (a, b, c, d, e, g, h), (map_fir, map_rec), alive_map, alive_all
+
+
+def test_optional_buffers_come_back_too(hip_lib):
+    """The groups the test above never allocates -- map planes, 16-bit frames and scale-0 planes, the staging buffer,
+    the batch scratch -- come back with the context as well.  16 cycles: the smallest group, the staging buffer of a
+    1920 x 1080 RGBA16 frame (16.6 MB), would by itself leave 265 MB behind, about twice SLACK.  Measured on an
+    MI355X: 68 MB alive after the FIR map, 332 MB with every FIR-side group; the 16 cycles take 0.4 s."""
+    cycles = 16
+    big = synth.make_ref(1920, 1080, 2)
+    d_big = synth.distort(big, "noise", 2)
+    big16 = (big.astype(np.uint16) << 2) | (big >> 6)                  # 10-bit samples
+    d_big16 = (d_big.astype(np.uint16) << 2) | (d_big >> 6)
+    rgba16 = np.full((1080, 1920, 4), 1023, np.uint16)
+    rgba16[..., :3] = d_big16
+    f = (big, d_big, big16, d_big16, rgba16)
+    with oavif_amd.Ssimu2(0) as warm:                                  # as above: the process-wide pieces come first
+        _every_optional_group(warm, f)
+    base = _free()
+    want = maps = None
+    for cycle in range(cycles):
+        s = oavif_amd.Ssimu2(0)
+        got, got_maps, alive_map, alive_all = _every_optional_group(s, f, base)
+        s.close()
+        after = base - _free()
+        if want is None:
+            want, maps = got, got_maps
+            print(f"alive after the FIR map {alive_map / MB:.1f} MB, with every FIR-side group {alive_all / MB:.1f} MB")
+            # not vacuous: 16-bit frames 24.9 MB + scale-0 planes 49.8 + cached planes 66 + staging 16.6 + batch
+            # scratch 116 were allocated on top of the frame buffers and the map
+            assert alive_all - alive_map > 2 * SLACK / cycles, (alive_map / MB, alive_all / MB)
+        assert got == want, (cycle, got, want)                         # bit for bit
+        assert all(np.array_equal(m, w) for m, w in zip(got_maps, maps)), cycle
+        assert got[2] == got[3]                                        # the strided RGBA frame is the tight RGB one
+        assert abs(after) <= SLACK, f"cycle {cycle}: {after / MB:.1f} MB not returned"
+
+
 def test_many_contexts_at_once_and_out_of_order_destruction(hip_lib):
     ref = synth.make_ref(512, 384, 3)
     dist = synth.distort(ref, "blur", 1)
