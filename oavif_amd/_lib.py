@@ -27,30 +27,7 @@ STATS_PER_SCALE = 18
 TQ_MAX_PASS = 12
 MAX_BATCH = 4096   # SSIMU2_MAX_BATCH (include/ssimu2_hip.h): items of one ssimu2_score_batch_* call
 
-# every symbol the public headers declare; tests/test_abi.py checks that liboavif_hip.so exports
-# exactly these (and that the Zig shim / INTEGRATION.md bind nothing else)
-BLUR_FIR, BLUR_RECURSIVE, BLUR_RECURSIVE_FMA = 0, 1, 2   # ssimu2_ctx_set_blur (include/ssimu2_hip.h)
-
-EXPORTED_SYMBOLS = (
-    "ssimu2_ctx_create", "ssimu2_query_device", "ssimu2_ctx_device_info", "ssimu2_host_alloc", "ssimu2_host_free",
-    "ssimu2_prefetch", "ssimu2_prefetch_join", "ssimu2_ctx_destroy", "ssimu2_ctx_set_blur",
-    "ssimu2_last_error",
-    "ssimu2_score_rgb8", "ssimu2_set_reference", "ssimu2_score_against_reference",
-    "ssimu2_score_against_reference_strided", "ssimu2_set_reference_device",
-    "ssimu2_enqueue_against_reference_device", "ssimu2_score_rgb8_device",
-    "ssimu2_enqueue_rgb8_device", "ssimu2_wait", "ssimu2_last_averages",
-    "ssimu2_error_map_rgb8", "ssimu2_error_map_against_reference",
-    "ssimu2_linear_table", "ssimu2_score_rgb16", "ssimu2_set_reference_rgb16",
-    "ssimu2_score_against_reference_rgb16", "ssimu2_score_against_reference_strided16",
-    "ssimu2_score_batch_rgb8", "ssimu2_score_batch_against_reference", "ssimu2_score_batch_rgb8_device",
-    "ssimu2_score_batch_against_reference_device", "ssimu2_last_batch_averages",
-    "ssimu2_version",
-    "oavif_tq_default_options", "oavif_tq_predict_q_from_score",
-    "oavif_tq_interpolate_quantizer", "oavif_tq_find_target_quality", "oavif_tq_search_hip",
-    "oavif_tq_find_target_quality_speculative",
-    "oavif_prescale_8_to_10", "oavif_prescale_16_to_10", "oavif_prescale_16_to_8",
-    "oavif_png_info_from_memory", "oavif_png_decode",
-)
+BLUR_FIR, BLUR_RECURSIVE, BLUR_RECURSIVE_FMA = 0, 1, 2   # SSIMU2_BLUR_* (include/ssimu2_hip.h)
 
 
 class TQOptions(ctypes.Structure):
@@ -109,15 +86,6 @@ class TQSpecStats(ctypes.Structure):
                 ("cache_hits", ctypes.c_uint32)]
 
 
-# include/ssimu2_hip_internal.h: only liboavif_hip_instr.so has these
-INSTR_SYMBOLS = ("ssimu2_debug_download", "ssimu2_time_device", "ssimu2_time_stage",
-                 "ssimu2_time_march_rotating", "ssimu2_measure_read_stream",
-                 "ssimu2_instr_set_segment_rows", "ssimu2_instr_cache_reference_blur",
-                 "ssimu2_instr_rg_stop_after_scale", "ssimu2_time_blur_stage_rotating",
-                 "ssimu2_instr_placed_streams", "ssimu2_time_kernels",
-                 "ssimu2_instr_set_batch_segment_rows", "ssimu2_instr_batch_segment_rows",
-                 "ssimu2_instr_last_march")
-
 TQ_MAX_FANOUT = 16
 BATCH_PROBE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
                                   ctypes.c_uint32, ctypes.POINTER(ctypes.c_double))
@@ -125,6 +93,83 @@ PROBE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32,
                             ctypes.POINTER(ctypes.c_double))
 CODEC_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32,
                             ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_size_t))
+
+# ---- every C function, declared once: name -> (restype, argtypes) ------------------------------------
+# In header order.  EXPORTED_SYMBOLS / INSTR_SYMBOLS are the names (tests/test_abi.py holds them to the
+# libraries' exports and to the Zig shim), tests/test_binding_signatures.py holds every entry to its prototype.
+_vp, _ci, _u32, _sz, _f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_double
+_u8p, _u16p, _u32p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint16), ctypes.POINTER(ctypes.c_uint32)
+_f32p, _f64p, _cip, _szp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_f64), ctypes.POINTER(_ci), ctypes.POINTER(_sz)
+_vpp, _u8pp = ctypes.POINTER(_vp), ctypes.POINTER(_u8p)
+_P = ctypes.POINTER
+
+PUBLIC_FUNCTIONS = {   # include/ssimu2_hip.h, then include/oavif_tq.h
+    "ssimu2_ctx_create": (_ci, [_ci, _vp, _vpp]),
+    "ssimu2_query_device": (_ci, [_ci, _P(DeviceInfo)]),
+    "ssimu2_ctx_device_info": (_ci, [_vp, _P(DeviceInfo)]),
+    "ssimu2_host_alloc": (_ci, [_vp, _sz, _vpp]),
+    "ssimu2_host_free": (_ci, [_vp, _vp]),
+    "ssimu2_prefetch": (_ci, [_ci]),
+    "ssimu2_prefetch_join": (_ci, [_ci]),
+    "ssimu2_ctx_destroy": (None, [_vp]),
+    "ssimu2_ctx_set_blur": (_ci, [_vp, _ci]),
+    "ssimu2_last_error": (ctypes.c_char_p, [_vp]),
+    "ssimu2_score_rgb8": (_ci, [_vp, _u8p, _u8p, _u32, _u32, _u32, _f64p]),
+    "ssimu2_set_reference": (_ci, [_vp, _u8p, _u32, _u32]),
+    "ssimu2_score_against_reference": (_ci, [_vp, _u8p, _f64p]),
+    "ssimu2_score_against_reference_strided": (_ci, [_vp, _u8p, _u32, _u32, _f64p]),
+    "ssimu2_score_rgb8_device": (_ci, [_vp, _vp, _vp, _u32, _u32, _f64p]),
+    "ssimu2_enqueue_rgb8_device": (_ci, [_vp, _vp, _vp, _u32, _u32]),
+    "ssimu2_wait": (_ci, [_vp, _f64p]),
+    "ssimu2_set_reference_device": (_ci, [_vp, _vp, _u32, _u32]),
+    "ssimu2_enqueue_against_reference_device": (_ci, [_vp, _vp]),
+    "ssimu2_last_averages": (_ci, [_vp, _f64p, _cip]),
+    "ssimu2_error_map_rgb8": (_ci, [_vp, _u8p, _u8p, _u32, _u32, _u32, _f32p, _f64p]),
+    "ssimu2_error_map_against_reference": (_ci, [_vp, _u8p, _f32p, _f64p]),
+    "ssimu2_linear_table": (_ci, [_u32, _f32p]),
+    "ssimu2_score_rgb16": (_ci, [_vp, _u16p, _u16p, _u32, _u32, _u32, _u32, _f64p]),
+    "ssimu2_set_reference_rgb16": (_ci, [_vp, _u16p, _u32, _u32, _u32]),
+    "ssimu2_score_against_reference_rgb16": (_ci, [_vp, _u16p, _u32, _f64p]),
+    "ssimu2_score_against_reference_strided16": (_ci, [_vp, _u16p, _u32, _u32, _u32, _f64p]),
+    "ssimu2_score_batch_rgb8": (_ci, [_vp, _u8pp, _u8pp, _u32, _u32, _u32, _f64p]),
+    "ssimu2_score_batch_against_reference": (_ci, [_vp, _u8pp, _u32, _f64p]),
+    "ssimu2_score_batch_rgb8_device": (_ci, [_vp, _vp, _vp, _sz, _u32, _u32, _u32, _f64p]),
+    "ssimu2_score_batch_against_reference_device": (_ci, [_vp, _vp, _sz, _u32, _f64p]),
+    "ssimu2_last_batch_averages": (_ci, [_vp, _u32, _f64p, _cip]),
+    "ssimu2_version": (ctypes.c_char_p, []),
+    "oavif_tq_default_options": (None, [_P(TQOptions)]),
+    "oavif_tq_predict_q_from_score": (_u32, [_f64]),
+    "oavif_tq_interpolate_quantizer": (_u32, [_u32, _u32, _P(TQPass), _u32, _f64]),
+    "oavif_tq_find_target_quality": (_ci, [_P(TQOptions), PROBE_FN, _vp, _P(TQResult)]),
+    "oavif_tq_search_hip": (_ci, [_P(TQOptions), _vp, _u8p, _u32, _u32, CODEC_FN, _vp, _P(TQResult), _szp]),
+    "oavif_tq_find_target_quality_speculative": (_ci, [_P(TQOptions), _P(TQSpecOptions), BATCH_PROBE_FN, _vp,
+                                                       _P(TQResult), _P(TQSpecStats)]),
+    "oavif_prescale_8_to_10": (None, [_u8p, _sz, _u16p]),
+    "oavif_prescale_16_to_10": (None, [_u16p, _sz, _u16p]),
+    "oavif_prescale_16_to_8": (None, [_u16p, _sz, _u8p]),
+    "oavif_png_info_from_memory": (_ci, [_u8p, _sz, _P(PngInfo)]),
+    "oavif_png_decode": (_ci, [_u8p, _sz, _vp, _sz, _vp, _sz]),
+}
+
+HOOK_FUNCTIONS = {     # include/ssimu2_hip_internal.h: only liboavif_hip_instr.so has these
+    "ssimu2_debug_download": (_ci, [_vp, _ci, _ci, _u32, _u32, _f32p, _u32p, _u32p]),
+    "ssimu2_time_device": (_ci, [_vp, _vp, _vp, _u32, _u32, _ci, _f32p, _f64p]),
+    "ssimu2_time_stage": (_ci, [_vp, _vp, _vp, _u32, _u32, _ci, _ci, _f32p]),
+    "ssimu2_time_march_rotating": (_ci, [_vp, _vpp, _vpp, _ci, _u32, _u32, _ci, _f32p]),
+    "ssimu2_measure_read_stream": (_ci, [_vp, _sz, _ci, _f64p]),
+    "ssimu2_instr_set_segment_rows": (_ci, [_vp, _ci, _ci]),
+    "ssimu2_instr_cache_reference_blur": (_ci, [_vp, _ci]),
+    "ssimu2_instr_last_march": (_ci, [_vp, _cip]),
+    "ssimu2_instr_set_batch_segment_rows": (_ci, [_vp, _ci]),
+    "ssimu2_instr_batch_segment_rows": (_ci, [_vp, _u32, _u32, _ci, _cip]),
+    "ssimu2_time_blur_stage_rotating": (_ci, [_vp, _vpp, _ci, _u32, _u32, _ci, _f32p, _f64p]),
+    "ssimu2_time_kernels": (_ci, [_vp, _vp, _vpp, _vpp, _ci, _u32, _u32, _ci, _f32p, _cip, _f32p, _f32p]),
+    "ssimu2_instr_placed_streams": (_ci, [_vp, _cip]),
+    "ssimu2_instr_rg_stop_after_scale": (_ci, [_vp, _ci]),
+}
+
+EXPORTED_SYMBOLS = tuple(PUBLIC_FUNCTIONS)
+INSTR_SYMBOLS = tuple(HOOK_FUNCTIONS)
 
 _lib = None
 _instr = None
@@ -134,7 +179,7 @@ def lib() -> ctypes.CDLL:
     """The product library (what a caller of the C ABI links)."""
     global _lib
     if _lib is None:
-        _lib = _load(LIB_PATH, False)
+        _lib = _load(LIB_PATH)
     return _lib
 
 
@@ -142,11 +187,11 @@ def instr_lib() -> ctypes.CDLL:
     """The instrumented build (include/ssimu2_hip_internal.h); never used by the product path."""
     global _instr
     if _instr is None:
-        _instr = _load(INSTR_LIB_PATH, True)
+        _instr = _load(INSTR_LIB_PATH)
     return _instr
 
 
-def _load(path: str, instrumented: bool) -> ctypes.CDLL:
+def _load(path: str) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise ImportError(
             f"{path} is missing: build it with `python -m oavif_amd.build` "
@@ -161,134 +206,9 @@ def _load(path: str, instrumented: bool) -> ctypes.CDLL:
         except Exception:
             pass
     L = ctypes.CDLL(path)
-    vp, u8p, f64p = ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_double)
-    u32, ci = ctypes.c_uint32, ctypes.c_int
-    L.ssimu2_ctx_create.argtypes = [ci, vp, ctypes.POINTER(vp)]
-    L.ssimu2_ctx_create.restype = ci
-    L.ssimu2_prefetch.argtypes = [ci]
-    L.ssimu2_prefetch.restype = ci
-    if hasattr(L, "ssimu2_query_device"):   # absent from builds before v8 (scripts/gpu_ab.py loads those too)
-        L.ssimu2_query_device.argtypes = [ci, ctypes.POINTER(DeviceInfo)]
-        L.ssimu2_query_device.restype = ci
-        L.ssimu2_ctx_device_info.argtypes = [vp, ctypes.POINTER(DeviceInfo)]
-        L.ssimu2_ctx_device_info.restype = ci
-        L.ssimu2_host_alloc.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(vp)]
-        L.ssimu2_host_alloc.restype = ci
-        L.ssimu2_host_free.argtypes = [vp, vp]
-        L.ssimu2_host_free.restype = ci
-    if hasattr(L, "ssimu2_prefetch_join"):
-        L.ssimu2_prefetch_join.argtypes = [ci]
-        L.ssimu2_prefetch_join.restype = ci
-    L.ssimu2_ctx_destroy.argtypes = [vp]
-    L.ssimu2_ctx_destroy.restype = None
-    if hasattr(L, "ssimu2_ctx_set_blur"):   # absent from round-1 builds (scripts/gpu_ab.py loads those too)
-        L.ssimu2_ctx_set_blur.argtypes = [vp, ci]
-        L.ssimu2_ctx_set_blur.restype = ci
-    L.ssimu2_last_error.argtypes = [vp]
-    L.ssimu2_last_error.restype = ctypes.c_char_p
-    L.ssimu2_score_rgb8.argtypes = [vp, u8p, u8p, u32, u32, u32, f64p]
-    L.ssimu2_score_rgb8.restype = ci
-    L.ssimu2_set_reference.argtypes = [vp, u8p, u32, u32]
-    L.ssimu2_set_reference.restype = ci
-    L.ssimu2_score_against_reference.argtypes = [vp, u8p, f64p]
-    L.ssimu2_score_against_reference.restype = ci
-    L.ssimu2_score_against_reference_strided.argtypes = [vp, u8p, u32, u32, f64p]
-    L.ssimu2_score_against_reference_strided.restype = ci
-    L.ssimu2_set_reference_device.argtypes = [vp, vp, u32, u32]
-    L.ssimu2_set_reference_device.restype = ci
-    L.ssimu2_enqueue_against_reference_device.argtypes = [vp, vp]
-    L.ssimu2_enqueue_against_reference_device.restype = ci
-    L.ssimu2_score_rgb8_device.argtypes = [vp, vp, vp, u32, u32, f64p]
-    L.ssimu2_score_rgb8_device.restype = ci
-    L.ssimu2_enqueue_rgb8_device.argtypes = [vp, vp, vp, u32, u32]
-    L.ssimu2_enqueue_rgb8_device.restype = ci
-    L.ssimu2_wait.argtypes = [vp, f64p]
-    L.ssimu2_wait.restype = ci
-    L.ssimu2_last_averages.argtypes = [vp, f64p, ctypes.POINTER(ci)]
-    L.ssimu2_last_averages.restype = ci
-    if hasattr(L, "ssimu2_error_map_rgb8"):   # absent from builds before the error map (scripts/gpu_ab.py loads those too)
-        f32p = ctypes.POINTER(ctypes.c_float)
-        L.ssimu2_error_map_rgb8.argtypes = [vp, u8p, u8p, u32, u32, u32, f32p, f64p]
-        L.ssimu2_error_map_rgb8.restype = ci
-        L.ssimu2_error_map_against_reference.argtypes = [vp, u8p, f32p, f64p]
-        L.ssimu2_error_map_against_reference.restype = ci
-    if hasattr(L, "ssimu2_score_rgb16"):   # absent from builds before 16-bit input (scripts/gpu_ab.py loads those too)
-        u16p = ctypes.POINTER(ctypes.c_uint16)
-        L.ssimu2_linear_table.argtypes = [u32, ctypes.POINTER(ctypes.c_float)]
-        L.ssimu2_linear_table.restype = ci
-        L.ssimu2_score_rgb16.argtypes = [vp, u16p, u16p, u32, u32, u32, u32, f64p]
-        L.ssimu2_score_rgb16.restype = ci
-        L.ssimu2_set_reference_rgb16.argtypes = [vp, u16p, u32, u32, u32]
-        L.ssimu2_set_reference_rgb16.restype = ci
-        L.ssimu2_score_against_reference_rgb16.argtypes = [vp, u16p, u32, f64p]
-        L.ssimu2_score_against_reference_rgb16.restype = ci
-        L.ssimu2_score_against_reference_strided16.argtypes = [vp, u16p, u32, u32, u32, f64p]
-        L.ssimu2_score_against_reference_strided16.restype = ci
-    if hasattr(L, "ssimu2_score_batch_rgb8"):   # absent from builds before batch scoring (scripts/gpu_ab.py loads those too)
-        u8pp = ctypes.POINTER(u8p)
-        L.ssimu2_score_batch_rgb8.argtypes = [vp, u8pp, u8pp, u32, u32, u32, f64p]
-        L.ssimu2_score_batch_rgb8.restype = ci
-        L.ssimu2_score_batch_against_reference.argtypes = [vp, u8pp, u32, f64p]
-        L.ssimu2_score_batch_against_reference.restype = ci
-        L.ssimu2_score_batch_rgb8_device.argtypes = [vp, vp, vp, ctypes.c_size_t, u32, u32, u32, f64p]
-        L.ssimu2_score_batch_rgb8_device.restype = ci
-        L.ssimu2_score_batch_against_reference_device.argtypes = [vp, vp, ctypes.c_size_t, u32, f64p]
-        L.ssimu2_score_batch_against_reference_device.restype = ci
-        L.ssimu2_last_batch_averages.argtypes = [vp, u32, f64p, ctypes.POINTER(ci)]
-        L.ssimu2_last_batch_averages.restype = ci
-    if instrumented:
-        sigs = {
-            "ssimu2_instr_set_batch_segment_rows": [vp, ci],
-            "ssimu2_instr_batch_segment_rows": [vp, u32, u32, ci, ctypes.POINTER(ci)],
-            "ssimu2_measure_read_stream": [vp, ctypes.c_size_t, ci, f64p],
-            "ssimu2_debug_download": [vp, ci, ci, u32, u32, ctypes.POINTER(ctypes.c_float),
-                                      ctypes.POINTER(u32), ctypes.POINTER(u32)],
-            "ssimu2_time_device": [vp, vp, vp, u32, u32, ci, ctypes.POINTER(ctypes.c_float), f64p],
-            "ssimu2_time_stage": [vp, vp, vp, u32, u32, ci, ci, ctypes.POINTER(ctypes.c_float)],
-            "ssimu2_time_march_rotating": [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ci, u32, u32, ci,
-                                           ctypes.POINTER(ctypes.c_float)],
-            "ssimu2_instr_set_segment_rows": [vp, ci, ci],
-            "ssimu2_instr_cache_reference_blur": [vp, ci],
-            "ssimu2_instr_last_march": [vp, ctypes.POINTER(ci)],
-            "ssimu2_instr_rg_stop_after_scale": [vp, ci],
-            "ssimu2_instr_placed_streams": [vp, ctypes.POINTER(ci)],
-            "ssimu2_time_blur_stage_rotating": [vp, ctypes.POINTER(vp), ci, u32, u32, ci,
-                                                ctypes.POINTER(ctypes.c_float), f64p],
-            "ssimu2_time_kernels": [vp, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ci, u32, u32, ci, ctypes.POINTER(ctypes.c_float),
-                                    ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)],
-        }
-        for name, argtypes in sigs.items():
-            if hasattr(L, name):  # scripts/gpu_ab.py also binds older builds that lack some hooks
-                getattr(L, name).argtypes = argtypes
-                getattr(L, name).restype = ci
-    L.ssimu2_version.argtypes = []
-    L.ssimu2_version.restype = ctypes.c_char_p
-    L.oavif_tq_default_options.argtypes = [ctypes.POINTER(TQOptions)]
-    L.oavif_tq_default_options.restype = None
-    L.oavif_tq_predict_q_from_score.argtypes = [ctypes.c_double]
-    L.oavif_tq_predict_q_from_score.restype = u32
-    L.oavif_tq_interpolate_quantizer.argtypes = [u32, u32, ctypes.POINTER(TQPass), u32, ctypes.c_double]
-    L.oavif_tq_interpolate_quantizer.restype = u32
-    L.oavif_tq_find_target_quality.argtypes = [ctypes.POINTER(TQOptions), PROBE_FN, vp,
-                                               ctypes.POINTER(TQResult)]
-    L.oavif_tq_find_target_quality.restype = ci
-    L.oavif_tq_find_target_quality_speculative.argtypes = [
-        ctypes.POINTER(TQOptions), ctypes.POINTER(TQSpecOptions), BATCH_PROBE_FN, vp,
-        ctypes.POINTER(TQResult), ctypes.POINTER(TQSpecStats)]
-    L.oavif_tq_find_target_quality_speculative.restype = ci
-    u16p = ctypes.POINTER(ctypes.c_uint16)
-    L.oavif_prescale_8_to_10.argtypes = [u8p, ctypes.c_size_t, u16p]
-    L.oavif_prescale_8_to_10.restype = None
-    L.oavif_prescale_16_to_10.argtypes = [u16p, ctypes.c_size_t, u16p]
-    L.oavif_prescale_16_to_10.restype = None
-    L.oavif_prescale_16_to_8.argtypes = [u16p, ctypes.c_size_t, u8p]
-    L.oavif_prescale_16_to_8.restype = None
-    if hasattr(L, "oavif_png_decode"):   # absent from older builds (scripts/gpu_ab.py loads those too)
-        L.oavif_png_info_from_memory.argtypes = [u8p, ctypes.c_size_t, ctypes.POINTER(PngInfo)]
-        L.oavif_png_info_from_memory.restype = ci
-        L.oavif_png_decode.argtypes = [u8p, ctypes.c_size_t, vp, ctypes.c_size_t, vp, ctypes.c_size_t]
-        L.oavif_png_decode.restype = ci
-    L.oavif_tq_search_hip.argtypes = [ctypes.POINTER(TQOptions), vp, u8p, u32, u32, CODEC_FN, vp,
-                                      ctypes.POINTER(TQResult), ctypes.POINTER(ctypes.c_size_t)]
-    L.oavif_tq_search_hip.restype = ci
+    for table in (PUBLIC_FUNCTIONS, HOOK_FUNCTIONS):
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(L, name, None)   # a build older than a symbol lacks it (scripts/gpu_ab.py loads such builds)
+            if fn is not None:
+                fn.restype, fn.argtypes = restype, argtypes
     return L

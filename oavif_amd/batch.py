@@ -103,41 +103,18 @@ def deal_largest_first(sizes: Sequence[int], world: int) -> List[List[int]]:
 def encode_image(scorer, path: Path, out_path: Optional[Path], score_tgt: float = 80.0,
                  tolerance: float = 2.0, max_pass: int = 6, speed: int = 9, options=None):
     """main.zig:73-116 for one file with the search on the GPU scorer, through the CLI mirror's
-    own load and encode functions (one path for `python -m oavif_amd.cli` and the batch).
+    own load, encode and search functions (one path for `python -m oavif_amd.cli` and the batch).
 
     Returns (q, score, passes, final_bytes)."""
-    from . import cli, tq
+    from . import cli, search
     o = options
     if o is None:
         o = cli.AvifEncOptions()   # the reference's defaults (parse_args.zig:48-63): 1 thread, auto tiling
         o.speed, o.score_tgt, o.tolerance, o.max_pass = speed, score_tgt, tolerance, max_pass
     src = cli.load_source(str(path))
     prepared = cli.encoder_input(src.pixels, o, src.icc) if cli._bridge_on() else None   # hoisted out of the pass loop
-    cache = {}
-
-    def codec(q: int):
-        data = cli._encode(src.pixels, o, q, icc=src.icc, prepared=prepared)
-        cache.clear()
-        cache[q] = data                      # EncBuffer holds only the last probe (tq.zig:31-35)
-        return cli._decode_rgb(data), len(data)
-
     try:
-        if cli._bridge_on():
-            from . import avif_bridge
-
-            def codec_frame(q: int):             # the decoded frame stays in libavif's buffer (SURVEY.md 8f rank 3)
-                data = cli._encode(src.pixels, o, q, icc=src.icc, prepared=prepared)
-                cache.clear()
-                cache[q] = data
-                return avif_bridge.decode_common(data), len(data)
-            r = tq.search_hip_frames(scorer, src.rgb, codec_frame, score_tgt=o.score_tgt, tolerance=o.tolerance,
-                                     max_pass=o.max_pass)
-        else:
-            r = tq.search_hip(scorer, src.rgb, codec, score_tgt=o.score_tgt, tolerance=o.tolerance,
-                              max_pass=o.max_pass)
-        data = cache.get(r.q) if r.buf_q == r.q else None
-        if data is None:                         # main.zig:109-113: re-encode at the chosen q
-            data = cli._encode(src.pixels, o, r.q, icc=src.icc, prepared=prepared)
+        r, data = search.search_image(src, o, [scorer], prepared)
     finally:
         if prepared is not None:
             prepared.close()

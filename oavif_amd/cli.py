@@ -301,28 +301,23 @@ def load_source(path: str) -> Source:
             if arr.ndim == 2:
                 arr = arr[..., None]
         icc = im.info.get("icc_profile")  # Image.icc (io.zig:48): handed to the encoder unchanged (io.zig:556-560)
-    ch = arr.shape[2]
-    if ch == 1 or ch == 2:
-        rgb = np.repeat(arr[..., :1], 3, axis=2)
-    else:
-        rgb = arr[..., :3]
-    if rgb.dtype == np.uint16:   # Image.toRGB8: 16-bit -> >> 8 truncation (io.zig:63-95)
+    return Source(to_rgb8(arr), arr, arr.shape[2], hbd, icc)
+
+
+def to_rgb8(arr):
+    """Image.toRGB8 (io.zig:57-133) of (h, w, channels) u8 / u16 pixels: gray replicated, alpha dropped, 16 bits
+    truncated with >> 8 -> contiguous (h, w, 3) u8, the scorer's frame."""
+    import numpy as np
+    rgb = np.repeat(arr[..., :1], 3, axis=2) if arr.shape[2] < 3 else arr[..., :3]
+    if rgb.dtype == np.uint16:
         rgb = (rgb >> 8).astype(np.uint8)
-    return Source(np.ascontiguousarray(rgb), arr, ch, hbd, icc)
+    return np.ascontiguousarray(rgb)
 
 
 def load_image(path: str):
-    """-> (rgb8 (h,w,3) u8, source pixels, channels, hbd); the ICC profile of the last image
-    loaded this way is what `_encode` passes through when none is given (the CLI handles one
-    image per process; the batch driver uses `load_source` and passes `icc` explicitly)."""
-    global _src_icc
+    """-> (rgb8 (h,w,3) u8, source pixels, channels, hbd) of load_source."""
     s = load_source(path)
-    _src_icc = s.icc
     return s.rgb, s.pixels, s.channels, s.hbd
-
-
-_src_icc = None
-_USE_CLI_ICC = object()
 
 
 def codec_depth(tenbit: bool, hbd: bool):
@@ -344,7 +339,7 @@ def codec_depth(tenbit: bool, hbd: bool):
     return 10, None
 
 
-def encoder_input(pixels, o: AvifEncOptions, icc=_USE_CLI_ICC):
+def encoder_input(pixels, o: AvifEncOptions, icc=None):
     """The source as the encoder gets it, made ONCE per image instead of on every pass: rescaled to the encoder's
     depth (io.zig:566-617; SURVEY.md 8f rank 4, the loops are oavif_prescale_* of the C ABI), then wrapped,
     tagged and converted to YUV444 (io.zig:550-623: avifImageCreate + avifImageRGBToYUV, 15 % of a 4K encode) --
@@ -353,8 +348,6 @@ def encoder_input(pixels, o: AvifEncOptions, icc=_USE_CLI_ICC):
     row-stride bug this mirror does not reproduce."""
     import numpy as np
     from . import avif_bridge
-    if icc is _USE_CLI_ICC:
-        icc = _src_icc
     hbd = pixels.dtype == np.uint16
     depth, _note = codec_depth(o.tenbit, hbd)
     ch = pixels.shape[2]
@@ -366,12 +359,10 @@ def encoder_input(pixels, o: AvifEncOptions, icc=_USE_CLI_ICC):
     return avif_bridge.EncoderSource(scaled, depth, o, icc)
 
 
-def _encode(src, o: AvifEncOptions, q: int, icc=_USE_CLI_ICC, prepared=None) -> bytes:
+def _encode(src, o: AvifEncOptions, q: int, icc=None, prepared=None) -> bytes:
     """io.encodeAvifToBuffer (io.zig:544-636).  `prepared` = encoder_input(src, o, icc), hoisted by the callers
     that encode one source many times (then `src` and `icc` are not looked at again)."""
     from . import avif_bridge
-    if icc is _USE_CLI_ICC:
-        icc = _src_icc
     if avif_bridge.available():
         if prepared is not None:
             return prepared.encode(o, q)
@@ -434,18 +425,18 @@ def main(argv: Optional[List[str]] = None, scorer=None) -> int:
             _lib.lib().ssimu2_prefetch(prefetched)
         if inp is None or out is None:
             raise CliError("MissingInputOrOutput")
-        rgb, src, channels, hbd = load_image(inp)
-        h, w, _ = rgb.shape
-        eprint(f"Read {w}x{h}, {'RGBA' if channels > 3 else 'RGB'}, {16 if hbd else 8}-bit, "
+        src = load_source(inp)
+        h, w, _ = src.rgb.shape
+        eprint(f"Read {w}x{h}, {'RGBA' if src.channels > 3 else 'RGB'}, {16 if src.hbd else 8}-bit, "
                f"{os.path.getsize(inp)} bytes")
         # The reference encodes 10-bit when --tenbit 1 or the source is 16-bit (io.zig:546-548): say what
         # IS written (the note goes after the reference's own lines, so that their order -- main.zig:78-116,
         # what tools parse -- is kept)
-        out_depth, depth_note = codec_depth(o.tenbit, hbd)
-        prepared = encoder_input(src, o) if _bridge_on() else None   # once per image, not once per pass
+        out_depth, depth_note = codec_depth(o.tenbit, src.hbd)
+        prepared = encoder_input(src.pixels, o, src.icc) if _bridge_on() else None   # once per image, not once per pass
         if o.quality is not None:  # bypass the search (main.zig:93-100)
             eprint(f"Encoding [q{o.quality}, speed {o.speed}, {out_depth}-bit]")
-            data = _encode(src, o, o.quality, prepared=prepared)
+            data = _encode(src.pixels, o, o.quality, icc=src.icc, prepared=prepared)
             open(out, "wb").write(data)
             eprint(f"Compressed to {len(data)} bytes ({len(data) * 8 / (w * h):.3f} bpp)")
             if depth_note:
@@ -453,59 +444,24 @@ def main(argv: Optional[List[str]] = None, scorer=None) -> int:
             return 0
 
         eprint(f"Searching [tgt {_fmt_num(o.score_tgt)}±{o.tolerance:.1f}, speed {o.speed}, {out_depth}-bit]")
-        from . import tq
+        from . import Ssimu2, search
+        dev = int(os.environ.get("LOCAL_RANK", "0"))
         if scorer is None:
-            from . import Ssimu2
-            scorer = Ssimu2(int(os.environ.get("LOCAL_RANK", "0")), blur=blur_from_env())
+            scorer = Ssimu2(dev, blur=blur_from_env())
             own_scorer = True
-        cache = {}
-
-        def codec(q: int):
-            data = _encode(src, o, q, prepared=prepared)
-            cache.clear()
-            cache[q] = data  # EncBuffer keeps only the last probe (tq.zig:31-35)
-            return _decode_rgb(data), len(data)
-
+        fanned = []
         fan = int(os.environ.get("OAVIF_PROBE_FANOUT", "1") or 1)
-        if fan > 1 and own_scorer:
-            # probes of the search fanned over `fan` scorer contexts (HIP streams) and host
-            # threads (include/oavif_tq.h); same q, score and pass count as the plain search.
-            # Not a CLI flag: the option surface stays the reference's (parse_args.zig:76-122).
-            from . import Ssimu2
-            dev = int(os.environ.get("LOCAL_RANK", "0"))
-            ctxs = [scorer] + [Ssimu2(dev, blur=blur_from_env()) for _ in range(min(fan, 16) - 1)]
-
-            def codec_keep(q: int):
-                data = _encode(src, o, q, prepared=prepared)
-                cache[q] = data  # every probe of a wave is kept: any of them may be the answer
-                return _decode_rgb(data), len(data)
-            try:
-                r, _stats, _sizes = tq.search_speculative_hip(
-                    ctxs, rgb, codec_keep, score_tgt=o.score_tgt, tolerance=o.tolerance,
-                    max_pass=o.max_pass)
-            finally:
-                for c in ctxs[1:]:
-                    c.close()
-            r.buf_q = r.q if r.q in cache else r.buf_q
-        elif _bridge_on():
-            # decoded-frame hand-off: libavif's own RGB(A) rows go to the device as they
-            # are; the alpha-dropping copy loop of io.decodeAvifToRgb (io.zig:654-663) does not run on the host
-            from . import avif_bridge
-
-            def codec_frame(q: int):
-                data = _encode(src, o, q, prepared=prepared)
-                cache.clear()
-                cache[q] = data
-                return avif_bridge.decode_common(data), len(data)
-            r = tq.search_hip_frames(scorer, rgb, codec_frame, score_tgt=o.score_tgt, tolerance=o.tolerance,
-                                     max_pass=o.max_pass)
-        else:
-            r = tq.search_hip(scorer, rgb, codec, score_tgt=o.score_tgt, tolerance=o.tolerance,
-                              max_pass=o.max_pass)
-        eprint(f"Found q{r.q} (score {r.score:.2f}, {r.num_pass} passes)")
-        data = cache.get(r.q) if r.buf_q == r.q else None
-        if data is None:  # main.zig:109-113
-            data = _encode(src, o, r.q, prepared=prepared)
+        try:
+            if fan > 1 and own_scorer:
+                # probes of the search fanned over `fan` scorer contexts (HIP streams) and host threads.
+                # Not a CLI flag: the option surface stays the reference's (parse_args.zig:76-122).
+                fanned = [Ssimu2(dev, blur=blur_from_env()) for _ in range(min(fan, 16) - 1)]
+            r, data = search.search_image(
+                src, o, [scorer] + fanned, prepared,
+                found=lambda r: eprint(f"Found q{r.q} (score {r.score:.2f}, {r.num_pass} passes)"))
+        finally:
+            for c in fanned:
+                c.close()
         open(out, "wb").write(data)
         eprint(f"Compressed to {len(data)} bytes ({len(data) * 8 / (w * h):.3f} bpp)")
         if depth_note:

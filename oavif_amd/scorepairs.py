@@ -39,12 +39,10 @@ def load_rgb8(path: str) -> np.ndarray:
     elif ext == ".png":
         from .png import load_png
         arr, _ch, _hbd, _icc = load_png(data)
-        if arr.dtype == np.uint16:
-            arr = (arr >> 8).astype(np.uint8)
     else:
         raise ValueError(f"unsupported image format {ext or path!r} (PNG or PAM)")
-    rgb = np.repeat(arr[..., :1], 3, axis=2) if arr.shape[2] < 3 else arr[..., :3]
-    return np.ascontiguousarray(rgb)
+    from .cli import to_rgb8
+    return to_rgb8(arr)
 
 
 def parse_pairs(text: str, base_dir: str = "") -> List[Tuple[int, str, str]]:

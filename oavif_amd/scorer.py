@@ -8,6 +8,7 @@
 from __future__ import annotations
 
 import ctypes
+import weakref
 
 import numpy as np
 
@@ -18,6 +19,9 @@ class Ssimu2Error(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"ssimu2 error {code}: {msg}")
         self.code = code
+
+
+_F64P = ctypes.POINTER(ctypes.c_double)
 
 
 def _u8p(a: np.ndarray):
@@ -47,6 +51,14 @@ def _check_rgb16(a, name: str) -> np.ndarray:
     if a.ndim != 3 or a.shape[2] != 3:
         raise ValueError(f"{name} must be (h, w, 3) uint16, got {a.shape}")
     return np.ascontiguousarray(a)
+
+
+def _check_pair(ref, dist, check):
+    """Two frames of one shape, each through `check` (_check_rgb8 / _check_rgb16)."""
+    ref, dist = check(ref, "ref"), check(dist, "dist")
+    if ref.shape != dist.shape:
+        raise ValueError("ref and dist must have the same shape")
+    return ref, dist
 
 
 def linear_table(bit_depth: int) -> np.ndarray:
@@ -122,6 +134,9 @@ class _PinnedBuffer:
 class Ssimu2:
     """One scorer context = one HIP stream + device scratch (not re-entrant)."""
 
+    # (h, w, 3) of the cached reference, recorded by the calls that set one; None = none recorded, the library decides
+    _ref_shape = None
+
     def __init__(self, device: int = 0, stream: int | None = None, instrumented: bool = False,
                  blur: int | None = None):
         """`instrumented=True` binds liboavif_hip_instr.so (the hooks of
@@ -152,12 +167,62 @@ class Ssimu2:
             self._pinned = {}
             self._holder.release_owner()
 
+    # -- the one call path: every C function of a context goes through here ---------------------
+    def _raise(self, rc: int):
+        raise Ssimu2Error(rc, self._L.ssimu2_last_error(self._ctx).decode())
+
+    def _call(self, fn, *args) -> None:
+        """fn(ctx, *args); a non-zero code raises Ssimu2Error with the library's text.  `fn` is the bound function
+        object (self._L.ssimu2_...): no name lookup per call."""
+        rc = fn(self._ctx, *args)
+        if rc != 0:
+            self._raise(rc)
+
+    def _need_instr(self):
+        if not self.instrumented:
+            raise RuntimeError("this hook needs Ssimu2(..., instrumented=True) (liboavif_hip_instr.so)")
+
+    def _icall(self, hook: str, *args) -> None:
+        """A hook of include/ssimu2_hip_internal.h whose arguments are passed as they are, by name: the product library
+        has no such attribute to pass, and the refusal comes first.  A hook that converts, sizes or allocates
+        anything for its call does _need_instr() itself, before that, and then _call."""
+        self._need_instr()
+        self._call(getattr(self._L, hook), *args)
+
+    # The three shapes of result.  The two scoring ones make the C call themselves, not through _call: one Python frame
+    # per score, not two.
+    def _score(self, fn, *args) -> float:
+        """A call whose last parameter is `double* out_score`."""
+        out = ctypes.c_double()
+        rc = fn(self._ctx, *args, ctypes.byref(out))
+        if rc != 0:
+            self._raise(rc)
+        return out.value
+
+    def _scores(self, fn, n: int, *args) -> np.ndarray:
+        """A batch call whose last parameter is `double* out_scores` (n of them)."""
+        out = np.zeros(int(n), np.float64)
+        rc = fn(self._ctx, *args, out.ctypes.data_as(_F64P))
+        if rc != 0:
+            self._raise(rc)
+        return out
+
+    def _averages(self, fn, *args):
+        """-> ((6, 18) float64 plane averages, number of scales) of ssimu2_last_averages / ssimu2_last_batch_averages."""
+        avg = np.zeros(_lib.NUM_SCALES * _lib.STATS_PER_SCALE, np.float64)
+        ns = ctypes.c_int()
+        self._call(fn, *args, avg.ctypes.data_as(_F64P), ctypes.byref(ns))
+        return avg.reshape(_lib.NUM_SCALES, _lib.STATS_PER_SCALE), ns.value
+
+    def _check_ref_shape(self, shape, what: str = "dist shape") -> None:
+        """`shape`, (h, w, 3) or (h, w), against the recorded shape of the cached reference."""
+        if self._ref_shape is not None and shape != self._ref_shape[:len(shape)]:
+            raise ValueError(f"{what} differs from the reference's")
+
     def device_info(self) -> dict:
         """ssimu2_ctx_device_info: the record the context was created with (arch, LDS per CU, PCI bus id, ...)."""
         d = _lib.DeviceInfo()
-        rc = self._L.ssimu2_ctx_device_info(self._ctx, ctypes.byref(d))
-        if rc != 0:
-            self._raise(rc)
+        self._call(self._L.ssimu2_ctx_device_info, ctypes.byref(d))
         return d.as_dict()
 
     def host_alloc(self, shape) -> np.ndarray:
@@ -169,12 +234,9 @@ class Ssimu2:
         shape = tuple(int(x) for x in (shape if hasattr(shape, "__len__") else (shape,)))
         n = int(np.prod(shape))
         ptr = ctypes.c_void_p()
-        rc = self._L.ssimu2_host_alloc(self._ctx, n, ctypes.byref(ptr))
-        if rc != 0:
-            self._raise(rc)
+        self._call(self._L.ssimu2_host_alloc, n, ctypes.byref(ptr))
         buf = _PinnedBuffer(self._holder, ptr.value, n)
         a = np.asarray(buf).reshape(shape)      # a.base chain ends at `buf`
-        import weakref
         self._pinned[a.ctypes.data] = weakref.ref(buf)
         return a
 
@@ -201,70 +263,52 @@ class Ssimu2:
     def __exit__(self, *exc):
         self.close()
 
-    def _raise(self, rc: int):
-        raise Ssimu2Error(rc, self._L.ssimu2_last_error(self._ctx).decode())
-
     # -- host-buffer entry points ---------------------------------------------------------
     def compute_ssimu2(self, ref, dist, channels: int = 3) -> float:
-        ref = _check_rgb8(ref, "ref")
-        dist = _check_rgb8(dist, "dist")
-        if ref.shape != dist.shape:
-            raise ValueError("ref and dist must have the same shape")
+        ref, dist = _check_pair(ref, dist, _check_rgb8)
         h, w, _ = ref.shape
-        out = ctypes.c_double()
-        rc = self._L.ssimu2_score_rgb8(self._ctx, _u8p(ref), _u8p(dist), w, h, channels,
-                                       ctypes.byref(out))
-        if rc != 0:
-            self._raise(rc)
-        return out.value
+        return self._score(self._L.ssimu2_score_rgb8, _u8p(ref), _u8p(dist), w, h, channels)
 
     def error_map(self, ref, dist, channels: int = 3):
         """ssimu2_error_map_rgb8 -> (score, (h, w) float32 map): the score bit for bit as compute_ssimu2, and
         where the frame is damaged (the map's definition: include/ssimu2_hip.h)."""
-        ref = _check_rgb8(ref, "ref")
-        dist = _check_rgb8(dist, "dist")
-        if ref.shape != dist.shape:
-            raise ValueError("ref and dist must have the same shape")
+        ref, dist = _check_pair(ref, dist, _check_rgb8)
         h, w, _ = ref.shape
         out = np.empty((h, w), np.float32)
-        score = ctypes.c_double()
-        rc = self._L.ssimu2_error_map_rgb8(self._ctx, _u8p(ref), _u8p(dist), w, h, channels, _f32p(out),
-                                           ctypes.byref(score))
-        if rc != 0:
-            self._raise(rc)
-        return score.value, out
+        return self._score(self._L.ssimu2_error_map_rgb8, _u8p(ref), _u8p(dist), w, h, channels, _f32p(out)), out
 
     def error_map_against_reference(self, dist):
         """ssimu2_error_map_against_reference -> (score, (h, w) float32 map) against the cached reference."""
         dist = _check_rgb8(dist, "dist")
-        shape = getattr(self, "_ref_shape", None)
-        if shape is not None and dist.shape != shape:
-            raise ValueError("dist shape differs from the reference's")
+        self._check_ref_shape(dist.shape)
         h, w, _ = dist.shape
         out = np.empty((h, w), np.float32)
-        score = ctypes.c_double()
-        rc = self._L.ssimu2_error_map_against_reference(self._ctx, _u8p(dist), _f32p(out), ctypes.byref(score))
-        if rc != 0:
-            self._raise(rc)
-        return score.value, out
+        return self._score(self._L.ssimu2_error_map_against_reference, _u8p(dist), _f32p(out)), out
 
     def set_reference(self, ref) -> None:
         ref = _check_rgb8(ref, "ref")
         h, w, _ = ref.shape
-        rc = self._L.ssimu2_set_reference(self._ctx, _u8p(ref), w, h)
-        if rc != 0:
-            self._raise(rc)
+        self._call(self._L.ssimu2_set_reference, _u8p(ref), w, h)
         self._ref_shape = ref.shape
 
     def score_against_reference(self, dist) -> float:
         dist = _check_rgb8(dist, "dist")
-        if getattr(self, "_ref_shape", None) is not None and dist.shape != self._ref_shape:
-            raise ValueError("dist shape differs from the reference's")
-        out = ctypes.c_double()
-        rc = self._L.ssimu2_score_against_reference(self._ctx, _u8p(dist), ctypes.byref(out))
-        if rc != 0:
-            self._raise(rc)
-        return out.value
+        self._check_ref_shape(dist.shape)
+        return self._score(self._L.ssimu2_score_against_reference, _u8p(dist))
+
+    def _score_decoded(self, fn, a: np.ndarray, sample, row_bytes, channels, *bit_depth) -> float:
+        """The body of score_decoded_against_reference[_hbd]: `a` holds samples of ctypes type `sample`."""
+        size = ctypes.sizeof(sample)
+        if a.ndim == 3:
+            if a.strides[2] != size or a.strides[1] != size * a.shape[2]:
+                raise ValueError("pixels of a row must be tightly packed")
+            self._check_ref_shape(a.shape[:2], "frame size")
+            row_bytes = a.strides[0] if row_bytes is None else row_bytes
+            channels = a.shape[2] if channels is None else channels
+        elif row_bytes is None or channels is None:
+            raise ValueError("flat buffers need row_bytes and channels")
+        ptr = ctypes.cast(ctypes.c_void_p(a.ctypes.data), ctypes.POINTER(sample))
+        return self._score(fn, ptr, int(row_bytes), int(channels), *bit_depth)
 
     def score_decoded_against_reference(self, pixels, row_bytes: int | None = None,
                                         channels: int | None = None) -> float:
@@ -276,56 +320,27 @@ class Ssimu2:
         a = np.asarray(pixels)
         if a.dtype != np.uint8:
             raise TypeError("pixels must be uint8")
-        if a.ndim == 3:
-            if a.strides[2] != 1 or a.strides[1] != a.shape[2]:
-                raise ValueError("pixels of a row must be tightly packed")
-            if getattr(self, "_ref_shape", None) is not None and a.shape[:2] != self._ref_shape[:2]:
-                raise ValueError("frame size differs from the reference's")
-            row_bytes = a.strides[0] if row_bytes is None else row_bytes
-            channels = a.shape[2] if channels is None else channels
-        elif row_bytes is None or channels is None:
-            raise ValueError("flat buffers need row_bytes and channels")
-        out = ctypes.c_double()
-        ptr = ctypes.cast(ctypes.c_void_p(a.ctypes.data), ctypes.POINTER(ctypes.c_uint8))
-        rc = self._L.ssimu2_score_against_reference_strided(self._ctx, ptr, int(row_bytes),
-                                                            int(channels), ctypes.byref(out))
-        if rc != 0:
-            self._raise(rc)
-        return out.value
+        return self._score_decoded(self._L.ssimu2_score_against_reference_strided, a, ctypes.c_uint8, row_bytes, channels)
 
     # -- 16-bit input (include/ssimu2_hip.h) --------------------------------
     def compute_ssimu2_hbd(self, ref, dist, bit_depth: int) -> float:
         """ssimu2_score_rgb16: (h, w, 3) uint16 frames of `bit_depth` (8..16) bits; samples above 2^d - 1 are clamped."""
-        ref = _check_rgb16(ref, "ref")
-        dist = _check_rgb16(dist, "dist")
-        if ref.shape != dist.shape:
-            raise ValueError("ref and dist must have the same shape")
+        ref, dist = _check_pair(ref, dist, _check_rgb16)
         h, w, _ = ref.shape
-        out = ctypes.c_double()
-        rc = self._L.ssimu2_score_rgb16(self._ctx, _u16p(ref), _u16p(dist), w, h, 3, int(bit_depth), ctypes.byref(out))
-        if rc != 0:
-            self._raise(rc)
-        return out.value
+        return self._score(self._L.ssimu2_score_rgb16, _u16p(ref), _u16p(dist), w, h, 3, int(bit_depth))
 
     def set_reference_hbd(self, ref, bit_depth: int) -> None:
         """ssimu2_set_reference_rgb16; later 8-bit and 16-bit frames can both be scored against it."""
         ref = _check_rgb16(ref, "ref")
         h, w, _ = ref.shape
-        rc = self._L.ssimu2_set_reference_rgb16(self._ctx, _u16p(ref), w, h, int(bit_depth))
-        if rc != 0:
-            self._raise(rc)
+        self._call(self._L.ssimu2_set_reference_rgb16, _u16p(ref), w, h, int(bit_depth))
         self._ref_shape = ref.shape
 
     def score_against_reference_hbd(self, dist, bit_depth: int) -> float:
         """ssimu2_score_against_reference_rgb16 against the reference of set_reference or set_reference_hbd."""
         dist = _check_rgb16(dist, "dist")
-        if getattr(self, "_ref_shape", None) is not None and dist.shape != self._ref_shape:
-            raise ValueError("dist shape differs from the reference's")
-        out = ctypes.c_double()
-        rc = self._L.ssimu2_score_against_reference_rgb16(self._ctx, _u16p(dist), int(bit_depth), ctypes.byref(out))
-        if rc != 0:
-            self._raise(rc)
-        return out.value
+        self._check_ref_shape(dist.shape)
+        return self._score(self._L.ssimu2_score_against_reference_rgb16, _u16p(dist), int(bit_depth))
 
     def score_decoded_against_reference_hbd(self, rows, row_bytes: int | None = None, channels: int | None = None,
                                             bit_depth: int = 16) -> float:
@@ -335,42 +350,27 @@ class Ssimu2:
         a = np.asarray(rows)
         if a.dtype != np.uint16:
             raise TypeError(f"rows must be uint16, got {a.dtype}")
-        if a.ndim == 3:
-            if a.strides[2] != 2 or a.strides[1] != 2 * a.shape[2]:
-                raise ValueError("pixels of a row must be tightly packed")
-            if getattr(self, "_ref_shape", None) is not None and a.shape[:2] != self._ref_shape[:2]:
-                raise ValueError("frame size differs from the reference's")
-            row_bytes = a.strides[0] if row_bytes is None else row_bytes
-            channels = a.shape[2] if channels is None else channels
-        elif row_bytes is None or channels is None:
-            raise ValueError("flat buffers need row_bytes and channels")
-        out = ctypes.c_double()
-        ptr = ctypes.cast(ctypes.c_void_p(a.ctypes.data), ctypes.POINTER(ctypes.c_uint16))
-        rc = self._L.ssimu2_score_against_reference_strided16(self._ctx, ptr, int(row_bytes), int(channels),
-                                                              int(bit_depth), ctypes.byref(out))
-        if rc != 0:
-            self._raise(rc)
-        return out.value
+        return self._score_decoded(self._L.ssimu2_score_against_reference_strided16, a, ctypes.c_uint16, row_bytes,
+                                   channels, int(bit_depth))
 
     # -- device-resident entry points (pointers are raw device addresses) -------------------
+    # The per-frame ones make their C call in their own body, not through _call / _score / _scores: a 512x512 score is
+    # bound by its 29 us of host time, and the helper's extra Python frame is 0.15 to 0.3 % of its rate, measured.
     def score_device(self, d_ref: int, d_dist: int, w: int, h: int) -> float:
         out = ctypes.c_double()
-        rc = self._L.ssimu2_score_rgb8_device(self._ctx, ctypes.c_void_p(d_ref),
-                                              ctypes.c_void_p(d_dist), w, h, ctypes.byref(out))
+        rc = self._L.ssimu2_score_rgb8_device(self._ctx, ctypes.c_void_p(d_ref), ctypes.c_void_p(d_dist), w, h,
+                                              ctypes.byref(out))
         if rc != 0:
             self._raise(rc)
         return out.value
 
     def enqueue_device(self, d_ref: int, d_dist: int, w: int, h: int) -> None:
-        rc = self._L.ssimu2_enqueue_rgb8_device(self._ctx, ctypes.c_void_p(d_ref),
-                                                ctypes.c_void_p(d_dist), w, h)
+        rc = self._L.ssimu2_enqueue_rgb8_device(self._ctx, ctypes.c_void_p(d_ref), ctypes.c_void_p(d_dist), w, h)
         if rc != 0:
             self._raise(rc)
 
     def set_reference_device(self, d_ref: int, w: int, h: int) -> None:
-        rc = self._L.ssimu2_set_reference_device(self._ctx, ctypes.c_void_p(d_ref), w, h)
-        if rc != 0:
-            self._raise(rc)
+        self._call(self._L.ssimu2_set_reference_device, ctypes.c_void_p(d_ref), w, h)
         self._ref_shape = (h, w, 3)
 
     def enqueue_against_reference_device(self, d_dist: int) -> None:
@@ -404,38 +404,27 @@ class Ssimu2:
         refs, dists = self._check_batch(refs, "refs"), self._check_batch(dists, "dists")
         if len(refs) != len(dists):
             raise ValueError("refs and dists must hold the same number of frames")
-        out = np.zeros(len(refs), np.float64)
         if not refs:
-            return out
+            return np.zeros(0, np.float64)
         if refs[0].shape != dists[0].shape:
             raise ValueError("refs and dists must have the same shape")
         h, w, _ = refs[0].shape
-        rc = self._L.ssimu2_score_batch_rgb8(self._ctx, self._ptr_array(refs), self._ptr_array(dists), len(refs), w, h,
-                                             out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
-        if rc != 0:
-            self._raise(rc)
-        return out
+        return self._scores(self._L.ssimu2_score_batch_rgb8, len(refs), self._ptr_array(refs), self._ptr_array(dists),
+                            len(refs), w, h)
 
     def score_batch_against_reference(self, dists) -> np.ndarray:
         """ssimu2_score_batch_against_reference: N distorted frames against the cached reference (kept)."""
         dists = self._check_batch(dists, "dists")
-        out = np.zeros(len(dists), np.float64)
         if not dists:
-            return out
-        if getattr(self, "_ref_shape", None) is not None and dists[0].shape != self._ref_shape:
-            raise ValueError("dist shape differs from the reference's")
-        rc = self._L.ssimu2_score_batch_against_reference(self._ctx, self._ptr_array(dists), len(dists),
-                                                          out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
-        if rc != 0:
-            self._raise(rc)
-        return out
+            return np.zeros(0, np.float64)
+        self._check_ref_shape(dists[0].shape)
+        return self._scores(self._L.ssimu2_score_batch_against_reference, len(dists), self._ptr_array(dists), len(dists))
 
     def score_batch_device(self, d_refs: int, d_dists: int, item_stride_bytes: int, n: int, w: int, h: int) -> np.ndarray:
         """ssimu2_score_batch_rgb8_device: item i at d_refs + i * item_stride_bytes / d_dists + i * item_stride_bytes."""
-        out = np.zeros(int(n), np.float64)
+        out = np.zeros(int(n), np.float64)   # in its own body: see "device-resident entry points"
         rc = self._L.ssimu2_score_batch_rgb8_device(self._ctx, ctypes.c_void_p(d_refs), ctypes.c_void_p(d_dists),
-                                                    int(item_stride_bytes), int(n), w, h,
-                                                    out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+                                                    int(item_stride_bytes), int(n), w, h, out.ctypes.data_as(_F64P))
         if rc != 0:
             self._raise(rc)
         return out
@@ -443,90 +432,67 @@ class Ssimu2:
     def score_batch_against_reference_device(self, d_dists: int, item_stride_bytes: int, n: int) -> np.ndarray:
         """ssimu2_score_batch_against_reference_device against the reference of set_reference / set_reference_device."""
         out = np.zeros(int(n), np.float64)
-        rc = self._L.ssimu2_score_batch_against_reference_device(self._ctx, ctypes.c_void_p(d_dists), int(item_stride_bytes),
-                                                                 int(n), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        rc = self._L.ssimu2_score_batch_against_reference_device(self._ctx, ctypes.c_void_p(d_dists),
+                                                                 int(item_stride_bytes), int(n), out.ctypes.data_as(_F64P))
         if rc != 0:
             self._raise(rc)
         return out
 
     def last_batch_averages(self, item: int):
         """-> ((6, 18) float64 plane averages of `item` of the last batch, number of scales)."""
-        avg = np.zeros(_lib.NUM_SCALES * _lib.STATS_PER_SCALE, np.float64)
-        ns = ctypes.c_int()
-        rc = self._L.ssimu2_last_batch_averages(self._ctx, int(item), avg.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                                ctypes.byref(ns))
-        if rc != 0:
-            self._raise(rc)
-        return avg.reshape(_lib.NUM_SCALES, _lib.STATS_PER_SCALE), ns.value
+        return self._averages(self._L.ssimu2_last_batch_averages, int(item))
 
+    def last_averages(self):
+        """-> ((6, 18) float64 plane averages of the last score, number of scales)."""
+        return self._averages(self._L.ssimu2_last_averages)
+
+    def set_blur(self, mode: int) -> None:
+        """ssimu2_ctx_set_blur: _lib.BLUR_FIR (default, the fused 9-tap kernels) or
+        _lib.BLUR_RECURSIVE (the published recursion, operation for operation: 0.4 ms per 4K pass
+        against a cached reference where the default takes 0.16)."""
+        self._call(self._L.ssimu2_ctx_set_blur, int(mode))
+
+    # -- measurement / parity hooks: instrumented build only ------------------------------------
     def set_batch_segment_rows(self, rows_scale0: int) -> None:
         """Instrumented build: scale-0 rows of a batch item (0 = the rule, -1 = the single-score rule, 8..160)."""
         self._need_instr()
-        rc = self._L.ssimu2_instr_set_batch_segment_rows(self._ctx, int(rows_scale0))
-        if rc != 0:
-            self._raise(rc)
+        self._call(self._L.ssimu2_instr_set_batch_segment_rows, int(rows_scale0))
 
     def batch_segment_rows(self, w: int, h: int, scale: int) -> int:
         """Instrumented build: rows per workgroup a batch item of w x h gets at `scale` (ssimu2_instr_batch_segment_rows)."""
         self._need_instr()
         rows = ctypes.c_int()
-        rc = self._L.ssimu2_instr_batch_segment_rows(self._ctx, int(w), int(h), int(scale), ctypes.byref(rows))
-        if rc != 0:
-            self._raise(rc)
+        self._call(self._L.ssimu2_instr_batch_segment_rows, int(w), int(h), int(scale), ctypes.byref(rows))
         return int(rows.value)
-
-    # -- measurement / parity hooks: instrumented build only ------------------------------------
-    def _need_instr(self):
-        if not self.instrumented:
-            raise RuntimeError("this hook needs Ssimu2(..., instrumented=True) (liboavif_hip_instr.so)")
 
     def time_device(self, d_ref: int, d_dist: int, w: int, h: int, iters: int):
         """-> (total device ms for `iters` back-to-back scores, score)."""
         self._need_instr()
-        ms = ctypes.c_float()
-        out = ctypes.c_double()
-        rc = self._L.ssimu2_time_device(self._ctx, ctypes.c_void_p(d_ref), ctypes.c_void_p(d_dist),
-                                        w, h, iters, ctypes.byref(ms), ctypes.byref(out))
-        if rc != 0:
-            self._raise(rc)
+        ms, out = ctypes.c_float(), ctypes.c_double()
+        self._call(self._L.ssimu2_time_device, ctypes.c_void_p(d_ref), ctypes.c_void_p(d_dist), w, h, iters,
+                    ctypes.byref(ms), ctypes.byref(out))
         return ms.value, out.value
 
     def time_stage(self, d_ref: int, d_dist: int, w: int, h: int, stage: int, iters: int) -> float:
         """-> average device ms of one execution of `stage` (_lib.STAGE_*) of the score."""
         self._need_instr()
         ms = ctypes.c_float()
-        rc = self._L.ssimu2_time_stage(self._ctx, ctypes.c_void_p(d_ref), ctypes.c_void_p(d_dist),
-                                       w, h, stage, iters, ctypes.byref(ms))
-        if rc != 0:
-            self._raise(rc)
+        self._call(self._L.ssimu2_time_stage, ctypes.c_void_p(d_ref), ctypes.c_void_p(d_dist), w, h, stage, iters,
+                    ctypes.byref(ms))
         return ms.value
 
     def measure_read_stream(self, nbytes: int = 2 << 30, iters: int = 10) -> float:
         """-> measured HBM read-stream bandwidth of the device in GB/s (ssimu2_measure_read_stream)."""
         self._need_instr()
         out = ctypes.c_double()
-        rc = self._L.ssimu2_measure_read_stream(self._ctx, ctypes.c_size_t(nbytes), iters,
-                                                ctypes.byref(out))
-        if rc != 0:
-            self._raise(rc)
+        self._call(self._L.ssimu2_measure_read_stream, ctypes.c_size_t(nbytes), iters, ctypes.byref(out))
         return out.value
-
-    def set_blur(self, mode: int) -> None:
-        """ssimu2_ctx_set_blur: _lib.BLUR_FIR (default, the fused 9-tap kernels) or
-        _lib.BLUR_RECURSIVE (the published recursion, operation for operation: 0.4 ms per 4K pass
-        against a cached reference where the default takes 0.16)."""
-        rc = self._L.ssimu2_ctx_set_blur(self._ctx, int(mode))
-        if rc != 0:
-            self._raise(rc)
 
     def placed_streams(self) -> int:
         """Instrumented build: streams on distinct hardware queues its library instance holds for this
         context's device (ssimu2_instr_placed_streams)."""
-        self._need_instr()
         n = ctypes.c_int(0)
-        rc = self._L.ssimu2_instr_placed_streams(self._ctx, ctypes.byref(n))
-        if rc != 0:
-            self._raise(rc)
+        self._icall("ssimu2_instr_placed_streams", ctypes.byref(n))
         return int(n.value)
 
     def rg_stop_after_scale(self, scale: int) -> None:
@@ -534,9 +500,7 @@ class Ssimu2:
         horizontal pass and after both passes) downloadable (debug_download what = 4 / 5);
         negative = keep nothing.  (The name is round 2's, when the run stopped after that scale.)"""
         self._need_instr()
-        rc = self._L.ssimu2_instr_rg_stop_after_scale(self._ctx, int(scale))
-        if rc != 0:
-            self._raise(rc)
+        self._call(self._L.ssimu2_instr_rg_stop_after_scale, int(scale))
 
     def debug_download(self, what: int, scale: int, w: int, h: int) -> np.ndarray:
         """-> (3, h_s, w_s) float32 planes; (15, h_s, w_s) for what = 4 / 5 (see ssimu2_debug_download)."""
@@ -546,11 +510,7 @@ class Ssimu2:
             sw, sh = (sw + 1) // 2, (sh + 1) // 2
         out = np.empty((15 if what in (4, 5) else 3, sh, sw), np.float32)
         ow, oh = ctypes.c_uint32(), ctypes.c_uint32()
-        rc = self._L.ssimu2_debug_download(self._ctx, what, scale, w, h,
-                                           out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                           ctypes.byref(ow), ctypes.byref(oh))
-        if rc != 0:
-            self._raise(rc)
+        self._call(self._L.ssimu2_debug_download, what, scale, w, h, _f32p(out), ctypes.byref(ow), ctypes.byref(oh))
         assert (ow.value, oh.value) == (sw, sh)
         return out
 
@@ -562,10 +522,7 @@ class Ssimu2:
         assert n == len(d_dists) and n > 0
         arr = ctypes.c_void_p * n
         ms = ctypes.c_float()
-        rc = self._L.ssimu2_time_march_rotating(self._ctx, arr(*d_refs), arr(*d_dists), n, w, h, iters,
-                                                ctypes.byref(ms))
-        if rc != 0:
-            self._raise(rc)
+        self._call(self._L.ssimu2_time_march_rotating, arr(*d_refs), arr(*d_dists), n, w, h, iters, ctypes.byref(ms))
         return ms.value
 
     def time_blur_stage_rotating(self, d_frames, w: int, h: int, iters: int):
@@ -574,12 +531,9 @@ class Ssimu2:
         `iters` launches rotating over the plane sets of the device-resident frames (HBM-fed)."""
         self._need_instr()
         n = len(d_frames)
-        arr = ctypes.c_void_p * n
         ms, nbytes = ctypes.c_float(), ctypes.c_double()
-        rc = self._L.ssimu2_time_blur_stage_rotating(self._ctx, arr(*d_frames), n, w, h, iters,
-                                                     ctypes.byref(ms), ctypes.byref(nbytes))
-        if rc != 0:
-            self._raise(rc)
+        self._call(self._L.ssimu2_time_blur_stage_rotating, (ctypes.c_void_p * n)(*d_frames), n, w, h, iters,
+                    ctypes.byref(ms), ctypes.byref(nbytes))
         return ms.value, nbytes.value
 
     KERNEL_NAMES = {(False, True): ("pyramid", "march_refblur", "finalize"), (False, False): ("pyramid", "march", "finalize"),
@@ -597,10 +551,8 @@ class Ssimu2:
         ms = (ctypes.c_float * 8)()
         nl = ctypes.c_int()
         wt, wp = ctypes.c_float(), ctypes.c_float()
-        rc = self._L.ssimu2_time_kernels(self._ctx, ctypes.c_void_p(d_ref or 0), arr(*d_refs) if d_refs is not None else None,
-                                         arr(*d_dists), n, w, h, iters, ms, ctypes.byref(nl), ctypes.byref(wt), ctypes.byref(wp))
-        if rc != 0:
-            self._raise(rc)
+        self._call(self._L.ssimu2_time_kernels, ctypes.c_void_p(d_ref or 0), arr(*d_refs) if d_refs is not None else None,
+                    arr(*d_dists), n, w, h, iters, ms, ctypes.byref(nl), ctypes.byref(wt), ctypes.byref(wp))
         if d_refs is None:
             self._ref_shape = (h, w, 3)
         names = self.KERNEL_NAMES[(bool(recursive), d_refs is None)]
@@ -609,16 +561,10 @@ class Ssimu2:
         return dict(zip(names, (float(ms[k]) for k in range(nl.value)))), float(wt.value), float(wp.value)
 
     def set_segment_rows(self, rows_scale0: int, rows_other_scales: int) -> None:
-        self._need_instr()
-        rc = self._L.ssimu2_instr_set_segment_rows(self._ctx, rows_scale0, rows_other_scales)
-        if rc != 0:
-            self._raise(rc)
+        self._icall("ssimu2_instr_set_segment_rows", rows_scale0, rows_other_scales)
 
     def cache_reference_blur(self, enabled: bool) -> None:
-        self._need_instr()
-        rc = self._L.ssimu2_instr_cache_reference_blur(self._ctx, 1 if enabled else 0)
-        if rc != 0:
-            self._raise(rc)
+        self._icall("ssimu2_instr_cache_reference_blur", 1 if enabled else 0)
 
     MARCH_KERNELS = (None, "k_march", "k_march_refblur", "k_march_lin", "k_march_refblur_lin", "k_march_batch",
                      "k_march_refblur_batch")
@@ -626,23 +572,9 @@ class Ssimu2:
     def last_march(self):
         """Instrumented build: the marching kernel the last score or batch launched (ssimu2_instr_last_march), by name;
         None when it launched none (a frame below 8 x 8)."""
-        self._need_instr()
         kind = ctypes.c_int()
-        rc = self._L.ssimu2_instr_last_march(self._ctx, ctypes.byref(kind))
-        if rc != 0:
-            self._raise(rc)
+        self._icall("ssimu2_instr_last_march", ctypes.byref(kind))
         return self.MARCH_KERNELS[kind.value]
-
-    def last_averages(self):
-        """-> ((6, 18) float64 plane averages of the last score, number of scales)."""
-        avg = np.zeros(_lib.NUM_SCALES * _lib.STATS_PER_SCALE, np.float64)
-        ns = ctypes.c_int()
-        rc = self._L.ssimu2_last_averages(self._ctx,
-                                          avg.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                          ctypes.byref(ns))
-        if rc != 0:
-            self._raise(rc)
-        return avg.reshape(_lib.NUM_SCALES, _lib.STATS_PER_SCALE), ns.value
 
 
 def score_many(scorers, d_ref: int, d_dists, w: int, h: int):

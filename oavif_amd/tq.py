@@ -37,6 +37,31 @@ def _result(r: _lib.TQResult) -> TQResult:
                              for i in range(r.history_len)])
 
 
+def _trampoline(cfunctype, body):
+    """`body(*args)` as a C callback of type `cfunctype` (the `user` pointer is dropped).  An exception in it is
+    collected and the callback returns -100, which ends the C search like the Zig `try` at tq.zig:150; `_finish`
+    raises it again once the C call has returned.  -> (callback, collected exceptions)"""
+    err: list = []
+
+    def cb(_user, *args):
+        try:
+            body(*args)
+            return 0
+        except Exception as e:
+            err.append(e)
+            return -100
+
+    return cfunctype(cb), err
+
+
+def _finish(rc: int, err: list, what: Callable[[], str]) -> None:
+    """After the C search: the callback's own exception first, else the search's code with the text `what()` fetches."""
+    if err:
+        raise err[0]
+    if rc != 0:
+        raise Ssimu2Error(rc, what())
+
+
 def predict_q_from_score(tgt: float) -> int:
     return int(_lib.lib().oavif_tq_predict_q_from_score(float(tgt)))
 
@@ -51,25 +76,14 @@ def interpolate_quantizer(lo: int, hi: int, history, target: float) -> int:
 
 def find_target_quality(probe: Callable[[int], float], score_tgt: float = 80.0,
                         tolerance: float = 2.0, max_pass: int = 6) -> TQResult:
-    L = _lib.lib()
-    err: list = []
+    def body(q, out):
+        out[0] = float(probe(int(q)))
 
-    def _cb(_user, q, out):
-        try:
-            out[0] = float(probe(int(q)))
-            return 0
-        except Exception as e:  # surfaces like the Zig `try` at tq.zig:150
-            err.append(e)
-            return -100
-
-    cb = _lib.PROBE_FN(_cb)
+    cb, err = _trampoline(_lib.PROBE_FN, body)
     res = _lib.TQResult()
     opts = _options(score_tgt, tolerance, max_pass)
-    rc = L.oavif_tq_find_target_quality(ctypes.byref(opts), cb, None, ctypes.byref(res))
-    if err:
-        raise err[0]
-    if rc != 0:
-        raise Ssimu2Error(rc, "oavif_tq_find_target_quality failed")
+    rc = _lib.lib().oavif_tq_find_target_quality(ctypes.byref(opts), cb, None, ctypes.byref(res))
+    _finish(rc, err, lambda: "oavif_tq_find_target_quality failed")
     return _result(res)
 
 
@@ -88,33 +102,22 @@ def find_target_quality_speculative(batch_probe: Callable[[List[int]], List[floa
     the search waits for.  `first_wave_fanout`: probes of the first wave (0 = max_fanout; 1 = the
     model's guess alone, so a one-pass search costs what the sequential search costs).
     -> (TQResult, SpecStats); the TQResult equals the sequential one."""
-    L = _lib.lib()
-    err: list = []
+    def body(qs, n, out):
+        want = [int(qs[i]) for i in range(n)]
+        got = list(batch_probe(want))
+        if len(got) != n:
+            raise ValueError(f"batch_probe returned {len(got)} scores for {n} quantizers")
+        for i in range(n):
+            out[i] = float(got[i])
 
-    def _cb(_user, qs, n, out):
-        try:
-            want = [int(qs[i]) for i in range(n)]
-            got = list(batch_probe(want))
-            if len(got) != n:
-                raise ValueError(f"batch_probe returned {len(got)} scores for {n} quantizers")
-            for i in range(n):
-                out[i] = float(got[i])
-            return 0
-        except Exception as e:
-            err.append(e)
-            return -100
-
-    cb = _lib.BATCH_PROBE_FN(_cb)
+    cb, err = _trampoline(_lib.BATCH_PROBE_FN, body)
     res = _lib.TQResult()
     stats = _lib.TQSpecStats()
     opts = _options(score_tgt, tolerance, max_pass)
     so = _lib.TQSpecOptions(int(max_fanout), int(first_wave_fanout))
-    rc = L.oavif_tq_find_target_quality_speculative(ctypes.byref(opts), ctypes.byref(so), cb, None,
-                                                    ctypes.byref(res), ctypes.byref(stats))
-    if err:
-        raise err[0]
-    if rc != 0:
-        raise Ssimu2Error(rc, "oavif_tq_find_target_quality_speculative failed")
+    rc = _lib.lib().oavif_tq_find_target_quality_speculative(ctypes.byref(opts), ctypes.byref(so), cb, None,
+                                                             ctypes.byref(res), ctypes.byref(stats))
+    _finish(rc, err, lambda: "oavif_tq_find_target_quality_speculative failed")
     return _result(res), SpecStats(int(stats.waves), int(stats.probes_issued), int(stats.cache_hits))
 
 
@@ -170,32 +173,23 @@ def search_hip(scorer: Ssimu2, ref_rgb: np.ndarray,
     ref = np.ascontiguousarray(ref_rgb, dtype=np.uint8)
     h, w, _ = ref.shape
     nbytes = w * h * 3
-    err: list = []
 
-    def _cb(_user, q, out_rgb, out_size):
-        try:
-            dec, size = codec(int(q))
-            dec = np.ascontiguousarray(dec, dtype=np.uint8)
-            if dec.shape != ref.shape:
-                raise ValueError(f"codec returned {dec.shape}, expected {ref.shape}")
-            ctypes.memmove(out_rgb, dec.ctypes.data, nbytes)
-            out_size[0] = int(size)
-            return 0
-        except Exception as e:
-            err.append(e)
-            return -100
+    def body(q, out_rgb, out_size):
+        dec, size = codec(int(q))
+        dec = np.ascontiguousarray(dec, dtype=np.uint8)
+        if dec.shape != ref.shape:
+            raise ValueError(f"codec returned {dec.shape}, expected {ref.shape}")
+        ctypes.memmove(out_rgb, dec.ctypes.data, nbytes)
+        out_size[0] = int(size)
 
-    cb = _lib.CODEC_FN(_cb)
+    cb, err = _trampoline(_lib.CODEC_FN, body)
     res = _lib.TQResult()
     last = ctypes.c_size_t()
     opts = _options(score_tgt, tolerance, max_pass)
     rc = L.oavif_tq_search_hip(ctypes.byref(opts), scorer._ctx,
                                ref.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), w, h, cb, None,
                                ctypes.byref(res), ctypes.byref(last))
-    if err:
-        raise err[0]
-    if rc != 0:
-        raise Ssimu2Error(rc, L.ssimu2_last_error(scorer._ctx).decode())
+    _finish(rc, err, lambda: L.ssimu2_last_error(scorer._ctx).decode())
     out = _result(res)
     out.last_avif_size = int(last.value)
     return out
