@@ -712,12 +712,14 @@ void rg_launch_convert(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_frame, 
     launch(k_pyramid_bands_xyb, dim3(a.bands_x * a.bands_y), dim3(PYR_THREADS), 0, c->stream, a);
 }
 
+// Grid of the persistent vertical pass (k_rg_v, k_rg_vmap): one workgroup per CU, or per job where those are fewer.
+dim3 rg_v_grid(const ssimu2_ctx* c, int vblocks) { return dim3(vblocks < c->num_cus ? vblocks : c->num_cus); }
+
 // The horizontal pass: one workgroup per 20 rows and channel.
 template <bool REF>
 void rg_launch_h(ssimu2_ctx* c, bool fma, int hblocks, const RgPlan& rp) {
     if (hblocks <= 0) return;
-    if (fma) launch((k_rg_h<true, REF>), dim3(hblocks), dim3(REF ? 128 : 192), 0, c->stream, rp);
-    else launch((k_rg_h<false, REF>), dim3(hblocks), dim3(REF ? 128 : 192), 0, c->stream, rp);
+    launch(fma ? k_rg_h<true, REF> : k_rg_h<false, REF>, dim3(hblocks), dim3(REF ? 128 : 192), 0, c->stream, rp);
 }
 
 // What depends on the reference alone: its XYB planes and mu1 = blur(x), s11 = blur(x * x) at
@@ -732,8 +734,7 @@ void rg_enqueue_reference(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_ref,
     rg_launch_convert(c, p, d_ref, rp, s16);
     rg_launch_h<true>(c, fma, hblocks, rp);
     if (dbg) rg_debug_keep_h(c, p, rp, true);
-    if (fma) launch((k_rg_v_emit<true, 2>), dim3(vblocks), dim3(128), 0, c->stream, rp);
-    else launch((k_rg_v_emit<false, 2>), dim3(vblocks), dim3(128), 0, c->stream, rp);
+    launch(fma ? k_rg_v_emit<true, 2> : k_rg_v_emit<false, 2>, dim3(vblocks), dim3(128), 0, c->stream, rp);
 }
 
 // The tail of every single score: the final reduction, which writes its 880 bytes straight into the context's
@@ -759,16 +760,13 @@ int rg_enqueue_pass(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_dist, cons
     }
     if (p.nscales > 0) {  // a frame below 8 x 8 has no scale to score
         rg_launch_convert(c, p, d_dist, rp, s16);
-        const int vgrid = vblocks < c->num_cus ? vblocks : c->num_cus;
         rg_launch_h<false>(c, fma, hblocks, rp);
-        if (fma) launch((k_rg_v<true>), dim3(vgrid), dim3(512), c->rg_v_pad, c->stream, rp);
-        else launch((k_rg_v<false>), dim3(vgrid), dim3(512), c->rg_v_pad, c->stream, rp);
+        launch(fma ? k_rg_v<true> : k_rg_v<false>, rg_v_grid(c, vblocks), dim3(512), c->rg_v_pad, c->stream, rp);
         if (dbg) {
             rg_debug_keep_h(c, p, rp, false);
             const int s = c->rg_dbg_scale;
             rp.emit[s] = c->rg.dbg.as<float>() + (size_t)15 * rg_pitch(p.w[s]) * p.h[s];  // [channel][{y, yy, xy}][n]
-            if (fma) launch((k_rg_v_emit<true, 3>), dim3(vblocks), dim3(192), 0, c->stream, rp);
-            else launch((k_rg_v_emit<false, 3>), dim3(vblocks), dim3(192), 0, c->stream, rp);
+            launch(fma ? k_rg_v_emit<true, 3> : k_rg_v_emit<false, 3>, dim3(vblocks), dim3(192), 0, c->stream, rp);
         }
     }
     return finish_score(c, fa);
@@ -817,12 +815,8 @@ int enqueue_score(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, ui
     int blocks = 0;
     build_plans(c, p, d_ref, d_dist, ref_pyramid_ready && c->cache.xyb.p != nullptr, &mp, &fa, &blocks);
     note_march(c, blocks <= 0 ? 0 : mp.ref_s11[0] ? 2 : 1);
-    if (blocks > 0) {
-        if (mp.ref_s11[0])  // reference XYB and blur(ref*ref) cached: the search's per-pass kernel
-            launch(k_march_refblur, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
-        else
-            launch(k_march, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
-    }
+    if (blocks > 0)  // reference XYB and blur(ref*ref) cached: the search's per-pass kernel
+        launch(mp.ref_s11[0] ? k_march_refblur : k_march, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
     return finish_score(c, fa);
 }
 
@@ -861,10 +855,8 @@ int enqueue_score16(ssimu2_ctx* c, const Src16* ref, const Src16& dist, uint32_t
     int blocks = 0;
     build_plans(c, p, c->hbd.lin0_ref.as<uint8_t>(), c->hbd.lin0_dist.as<uint8_t>(), cached, &mp, &fa, &blocks);
     note_march(c, blocks <= 0 ? 0 : cached ? 4 : 3);
-    if (blocks > 0) {
-        if (cached) launch(k_march_refblur_lin, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
-        else launch(k_march_lin, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
-    }
+    if (blocks > 0)
+        launch(cached ? k_march_refblur_lin : k_march_lin, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
     return finish_score(c, fa);
 }
 
@@ -986,11 +978,8 @@ int map_pass(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, uint32_
             ma.coef = mc;
             for (int s = 0; s < p.nscales; ++s) ma.dens[s] = dens + xyb_off(p, s);
             HIP_TRY(c, hipMemsetAsync(c->d_rg_q, 0, 4 * sizeof(unsigned), c->stream));  // the job cursor
-            const int vgrid = vblocks < c->num_cus ? vblocks : c->num_cus;
-            if (c->blur_mode == SSIMU2_BLUR_RECURSIVE_FMA)
-                launch((k_rg_vmap<true>), dim3(vgrid), dim3(512), c->rg_v_pad, c->stream, rp, ma);
-            else
-                launch((k_rg_vmap<false>), dim3(vgrid), dim3(512), c->rg_v_pad, c->stream, rp, ma);
+            launch(c->blur_mode == SSIMU2_BLUR_RECURSIVE_FMA ? k_rg_vmap<true> : k_rg_vmap<false>, rg_v_grid(c, vblocks),
+                   dim3(512), c->rg_v_pad, c->stream, rp, ma);
         }
         MapComposeArgs ca;
         memset(&ca, 0, sizeof ca);
@@ -1093,10 +1082,9 @@ int batch_run(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dists, size
         launch(k_pyramid_bands_batch, dim3((unsigned)(bands * nframes * n)), dim3(PYR_THREADS), 0, c->stream, pb);
     }
     note_march(c, blocks <= 0 ? 0 : cached ? 6 : 5);
-    if (blocks > 0) {
-        if (cached) launch(k_march_refblur_batch, dim3((unsigned)(blocks * n)), dim3(MARCH_THREADS), 0, c->stream, bp);
-        else launch(k_march_batch, dim3((unsigned)(blocks * n)), dim3(MARCH_THREADS), 0, c->stream, bp);
-    }
+    if (blocks > 0)
+        launch(cached ? k_march_refblur_batch : k_march_batch, dim3((unsigned)(blocks * n)), dim3(MARCH_THREADS), 0,
+               c->stream, bp);
     launch(k_finalize_batch, dim3(n), dim3(1024), 0, c->stream, fa, part_stride, b.result.as<double>());
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));

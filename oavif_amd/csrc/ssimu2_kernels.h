@@ -1273,15 +1273,18 @@ struct FinalizeArgs {
     int nscales;
 };
 
-// result layout: [0..107] averages [scale][18], [108] score, [109] nscales.  `result` is the context's page-locked
-// host mirror: the kernel writes the 880 bytes over the bus itself (round 5: no device-side copy of them and no D2H
-// copy command per score; -1.7 us per pair score, bits equal).
+// result layout: [0..107] averages [scale][18], [108] score, [109] nscales.  `result` is page-locked host memory: the
+// kernel writes the 880 bytes over the bus itself (round 5: no device-side copy of them and no D2H copy command per
+// score; -1.7 us per pair score, bits equal).
 // 8 lanes per (scale, stat) item stride over the workgroup partials; lane-local sums, then a
 // fixed-order 8-lane shuffle tree: deterministic, and 128 items run in parallel instead of 16.
 // A launch of its own by measurement (round 5, profiles/r05_finalize_ab.log): folded into the last workgroup of the
 // marching launch (an atomic done-counter behind a device-scope release) it made k_march 20 us SLOWER at 4K -- every
 // one of its ~1000 workgroups pays an L2 write-back for the release -- and the recursive pass 2.5 us slower.
-__global__ __launch_bounds__(1024) void k_finalize(FinalizeArgs fa, double* __restrict__ result) {
+// One body for both entries.  BATCH: one workgroup per item of a batch, whose partial sums lie `part_stride` doubles
+// per item behind fa.part[scale]; an item's result depends on its own sums alone.
+template <bool BATCH>
+__device__ __forceinline__ void finalize_body(const FinalizeArgs& fa, size_t part_stride, double* __restrict__ result) {
     __shared__ double s_avg[kNumScales * kStats];
     const int item = threadIdx.x >> 3, sub = threadIdx.x & 7;
     double v = 0.0;
@@ -1291,6 +1294,7 @@ __global__ __launch_bounds__(1024) void k_finalize(FinalizeArgs fa, double* __re
         // each lane sums runs of 8 consecutive partials: the 8 loads of a run are independent,
         // so the loop is 8x shorter than one dependent load + add per partial
         const double* p = fa.part[scale] + (size_t)stat * fa.nblocks[scale];
+        if constexpr (BATCH) p += (size_t)blockIdx.x * part_stride;
         const int nb = fa.nblocks[scale];
         for (int b = sub * 8; b < nb; b += 64) {
             double t[8];
@@ -1343,71 +1347,13 @@ __global__ __launch_bounds__(1024) void k_finalize(FinalizeArgs fa, double* __re
     }
 }
 
-// One workgroup per item of a batch: k_finalize's reduction, statement for statement (a copy, not a shared body: as an
-// inlined function with the offsets as arguments it moved k_finalize's register allocation), over the item's partial
-// sums -- `part_stride` doubles per item behind fa.part[scale] -- with its 110 doubles going to result + 110 * item of the
-// context's page-locked batch mirror.  An item's result depends on its own sums alone.
+__global__ __launch_bounds__(1024) void k_finalize(FinalizeArgs fa, double* __restrict__ result) {
+    finalize_body<false>(fa, 0, result);
+}
+
+// Item i's 110 doubles go to results + 110 i of the context's page-locked batch mirror.
 __global__ __launch_bounds__(1024) void k_finalize_batch(FinalizeArgs fa, size_t part_stride, double* __restrict__ results) {
-    double* __restrict__ result = results + (size_t)blockIdx.x * (kNumScales * kStats + 2);
-    __shared__ double s_avg[kNumScales * kStats];
-    const int item = threadIdx.x >> 3, sub = threadIdx.x & 7;
-    double v = 0.0;
-    const int scale = item / kStats, stat = item - scale * kStats;
-    const bool live = item < kNumScales * kStats && scale < fa.nscales;
-    if (live) {
-        // each lane sums runs of 8 consecutive partials: the 8 loads of a run are independent,
-        // so the loop is 8x shorter than one dependent load + add per partial
-        const double* p = fa.part[scale] + (size_t)blockIdx.x * part_stride + (size_t)stat * fa.nblocks[scale];
-        const int nb = fa.nblocks[scale];
-        for (int b = sub * 8; b < nb; b += 64) {
-            double t[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) t[k] = b + k < nb ? p[b + k] : 0.0;
-            v += ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
-        }
-    }
-    v += __shfl_down(v, 4, 8);
-    v += __shfl_down(v, 2, 8);
-    v += __shfl_down(v, 1, 8);
-    if (sub == 0 && item < kNumScales * kStats) {
-        if (live) {
-            v *= fa.inv_pixels[scale];
-            if (stat & 1) v = sqrt(sqrt(v));  // odd stats are L4 norms
-        }
-        s_avg[item] = v;
-    }
-    __syncthreads();
-    // published Score(): weights are consumed with a running index over (channel, scale present,
-    // norm, {ssim, artifact, detail}); term j of that walk is evaluated by thread j and the
-    // terms are summed with a fixed shuffle tree (two waves), then by thread 0.
-    __shared__ double s_red[2];
-    if (threadIdx.x < 128) {
-        const int j = threadIdx.x;
-        const int nterms = 3 * fa.nscales * 2 * 3;
-        double term = 0.0;
-        if (j < nterms) {
-            const int k = j % 3, n = (j / 3) & 1, cs = j / 6;
-            const int sc = cs % fa.nscales, c = cs / fa.nscales;
-            const double* a = s_avg + sc * kStats;
-            const double val = k == 0 ? a[c * 2 + n] : a[6 + c * 4 + n + (k == 2 ? 2 : 0)];
-            term = c_k.weights[j] * fabs(val);
-        }
-        term = wave_sum(term);
-        if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = term;
-    }
-    __syncthreads();
-    // the averages leave as two full-wave stores of consecutive doubles (they cross PCIe: not 108 scattered ones)
-    if (threadIdx.x < kNumScales * kStats) result[threadIdx.x] = s_avg[threadIdx.x];
-    if (threadIdx.x == 0) {
-        double ssim = s_red[0] + s_red[1];
-        ssim = ssim * 0.9562382616834844;
-        ssim = 2.326765642916932 * ssim - 0.020884521182843837 * ssim * ssim +
-               6.248496625763138e-05 * ssim * ssim * ssim;
-        if (ssim > 0.0) ssim = 100.0 - 10.0 * pow(ssim, 0.6276336467831387);
-        else ssim = 100.0;
-        result[108] = ssim;
-        result[109] = (double)fa.nscales;
-    }
+    finalize_body<true>(fa, part_stride, results + (size_t)blockIdx.x * (kNumScales * kStats + 2));
 }
 
 // ---------------------------------------------------------------------------------------------

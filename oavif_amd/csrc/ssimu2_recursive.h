@@ -532,11 +532,23 @@ constexpr unsigned rg_v_pad_bytes(unsigned lds_bytes_per_cu) {
 static_assert(rg_v_pad_bytes(160u * 1024u) + RG_V_STATIC_LDS > 80u * 1024u && rg_v_pad_bytes(160u * 1024u) + RG_V_STATIC_LDS + 1024u <= 160u * 1024u,
               "k_rg_v: one workgroup per 160 KB CU, and the request fits");
 
-template <bool FMA>
-__global__ __launch_bounds__(512) void k_rg_v(RgPlan p) {
+// What the error-map pass takes besides the plan: the [3][h][w] output plane of each scale and the coefficients.
+struct RgMapArgs {
+    MapCoef coef;
+    float* dens[kNumScales];
+};
+
+// One body for the score pass (k_rg_v) and the error-map pass of the recursive modes (k_rg_vmap, ssimu2_error_map_*, run
+// after a score whose planes are still in place): the same jobs, recursion waves, barriers and prefetch queue.  MAP: the
+// maps waves write each pixel's density -- map_density() with the coefficients of its (scale, channel) -- into
+// m->dens[scale] instead of summing, and no partial sums exist (s_part is never named, so it costs that instantiation
+// no LDS).  `m` is null in the score pass.  Both are the entry's kernel arguments, which no store of the kernel aliases
+// (__restrict__: their fields may stay in registers across the job loop's atomic and barriers).
+template <bool FMA, bool MAP>
+__device__ __forceinline__ void rg_v_body(const RgPlan& __restrict__ p, const RgMapArgs* __restrict__ m) {
     constexpr int NK = 3;
     __shared__ float s_out[2][NK][RG_VB][RG_VW];
-    __shared__ double s_part[RG_MAPS_WAVES][6];
+    __shared__ double s_part[RG_MAPS_WAVES][6];  // !MAP only
     __shared__ int s_job;
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -580,7 +592,16 @@ __global__ __launch_bounds__(512) void k_rg_v(RgPlan p) {
             const float* g_s11 = g_mu1 + n;
             const float* g_r1 = p.xa[sc] + (size_t)ch * n + xc;
             const float* g_r2 = p.xb[sc] + (size_t)ch * n + xc;
-            double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // !MAP
+            float mc[6];  // MAP; statistic index as k_finalize reads it: 0..5 ssim (c*2 + n), 6..17 edge (c*4 + j)
+            float* dens = nullptr;
+            if constexpr (MAP) {
+                mc[0] = m->coef.c[sc][ch * 2];
+                mc[1] = m->coef.c[sc][ch * 2 + 1];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) mc[2 + k] = m->coef.c[sc][6 + ch * 4 + k];
+                dens = m->dens[sc] + (size_t)ch * w * h + xc;
+            }
             float g[RG_PF][2][4];
 #define RG_M_LOAD(B, SLOT)                                                \
     _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) {                    \
@@ -607,135 +628,56 @@ __global__ __launch_bounds__(512) void k_rg_v(RgPlan p) {
                             const float mu2 = s_out[b & 1][0][j0 + jj][lane];
                             const float s22 = s_out[b & 1][1][j0 + jj][lane];
                             const float s12 = s_out[b & 1][2][j0 + jj][lane];
-                            double z[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-                            rg_maps_pixel(g[u][jj][0], mu2, g[u][jj][1], s22, s12, g[u][jj][2], g[u][jj][3], z);
-                            if (ok) {
+                            if constexpr (MAP) {
+                                float t[6];
+                                rg_map_terms(g[u][jj][0], mu2, g[u][jj][1], s22, s12, g[u][jj][2], g[u][jj][3], t);
+                                if (ok) dens[(size_t)r * w] = map_density(t[0], t[1], t[2], t[3], t[4], t[5], mc);
+                            } else {
+                                double z[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+                                rg_maps_pixel(g[u][jj][0], mu2, g[u][jj][1], s22, s12, g[u][jj][2], g[u][jj][3], z);
+                                if (ok) {
 #pragma unroll
-                                for (int k = 0; k < 6; ++k) acc[k] += z[k];
+                                    for (int k = 0; k < 6; ++k) acc[k] += z[k];
+                                }
                             }
                         }
                     }
                 }
             }
 #undef RG_M_LOAD
+            if constexpr (!MAP) {
 #pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                const double sum = wave_sum(acc[k]);
-                if (lane == 0) s_part[wave - NK][k] = sum;
+                for (int k = 0; k < 6; ++k) {
+                    const double sum = wave_sum(acc[k]);
+                    if (lane == 0) s_part[wave - NK][k] = sum;
+                }
             }
         }
+        // every wave is done with s_out and s_job before the next job's pull; the next job's first barrier (behind its
+        // pull) orders the reads of s_part below before anything overwrites them
         __syncthreads();
-        if (threadIdx.x < 6) {
-            const int k = threadIdx.x;
-            double sum = s_part[0][k];
+        if constexpr (!MAP) {
+            if (threadIdx.x < 6) {
+                const int k = threadIdx.x;
+                double sum = s_part[0][k];
 #pragma unroll
-            for (int m = 1; m < RG_MAPS_WAVES; ++m) sum += s_part[m][k];
-            // statistic index as k_finalize reads it: 0..5 ssim (c*2 + n), 6..17 edge (c*4 + j)
-            const int stat = k < 2 ? ch * 2 + k : 6 + ch * 4 + (k - 2);
-            p.part[sc][(size_t)stat * p.vgroups[sc] + cg] = sum;
+                for (int mw = 1; mw < RG_MAPS_WAVES; ++mw) sum += s_part[mw][k];
+                // statistic index as k_finalize reads it: 0..5 ssim (c*2 + n), 6..17 edge (c*4 + j)
+                const int stat = k < 2 ? ch * 2 + k : 6 + ch * 4 + (k - 2);
+                p.part[sc][(size_t)stat * p.vgroups[sc] + cg] = sum;
+            }
         }
-        // the next job's first barrier (behind its pull) orders these reads of s_part / s_job before
-        // anything overwrites them
     }
 }
 
-// The error-map pass of the recursive modes (ssimu2_error_map_*), run after a score whose planes are still in place:
-// k_rg_v's jobs, recursion waves and barriers, but the maps waves write each pixel's density -- map_density() with the
-// coefficients of its (scale, channel) -- into the [3][h][w] plane dens[scale] instead of summing.  A kernel of its own
-// (not a template flag of k_rg_v) so that the score kernel's code stays exactly as it is.
-struct RgMapArgs {
-    MapCoef coef;
-    float* dens[kNumScales];
-};
+template <bool FMA>
+__global__ __launch_bounds__(512) void k_rg_v(RgPlan p) {
+    rg_v_body<FMA, false>(p, nullptr);
+}
 
 template <bool FMA>
 __global__ __launch_bounds__(512) void k_rg_vmap(RgPlan p, RgMapArgs m) {
-    constexpr int NK = 3;
-    __shared__ float s_out[2][NK][RG_VB][RG_VW];
-    __shared__ int s_job;
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-#pragma unroll 1
-    for (;;) {
-        if (threadIdx.x == 0) {
-            const int j = (int)atomicAdd(p.q + 2, 1u);
-            s_job = j < p.vjobs ? j : -1;
-        }
-        __syncthreads();
-        const int job = __builtin_amdgcn_readfirstlane(s_job);
-        if (job < 0) break;
-        int sc = 0, first = 0;
-#pragma unroll
-        for (int s = 0; s < kNumScales - 1; ++s)
-            if (s + 1 < p.nscales && job >= p.vblk_end[s]) {
-                sc = s + 1;
-                first = p.vblk_end[s];
-            }
-        const int blk = job - first;
-        const int ch = blk % 3, cg = blk / 3;
-        const int w = p.w[sc], h = p.h[sc], pitch = p.pitch[sc];
-        const size_t n = (size_t)pitch * h;
-        const int x = cg * RG_VW + lane;
-        const bool ok = x < w;
-        const int xc = min(x, w - 1);
-        const int nb = rg_v_batches(h);
-
-        if (wave < NK) {
-            const int kind = wave;
-            const float* in = p.hbuf[sc] + (size_t)(ch * NK + kind) * n + xc;
-            rg_v_column<FMA>(in, pitch, h, [&](int b, const float (&o)[RG_VB]) {
-#pragma unroll
-                for (int j = 0; j < RG_VB; ++j) s_out[b & 1][kind][j][lane] = o[j];
-                __syncthreads();  // batch b is in the tile
-            });
-        } else {
-            const int j0 = 2 * (wave - NK);
-            const float* g_mu1 = p.cache[sc] + (size_t)(2 * ch) * n + xc;
-            const float* g_s11 = g_mu1 + n;
-            const float* g_r1 = p.xa[sc] + (size_t)ch * n + xc;
-            const float* g_r2 = p.xb[sc] + (size_t)ch * n + xc;
-            float mc[6];  // statistic index as k_finalize reads it: 0..5 ssim (c*2 + n), 6..17 edge (c*4 + j)
-            mc[0] = m.coef.c[sc][ch * 2];
-            mc[1] = m.coef.c[sc][ch * 2 + 1];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) mc[2 + k] = m.coef.c[sc][6 + ch * 4 + k];
-            float* dens = m.dens[sc] + (size_t)ch * w * h + xc;
-            float g[RG_PF][2][4];
-#define RG_M_LOAD(B, SLOT)                                                \
-    _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) {                    \
-        const int r_ = (B) * RG_VB + j0 + jj - (RG_N - 1);                \
-        const size_t o_ = (size_t)min(max(r_, 0), h - 1) * pitch;         \
-        g[SLOT][jj][0] = __builtin_nontemporal_load(g_mu1 + o_);          \
-        g[SLOT][jj][1] = __builtin_nontemporal_load(g_s11 + o_);          \
-        g[SLOT][jj][2] = __builtin_nontemporal_load(g_r1 + o_);           \
-        g[SLOT][jj][3] = __builtin_nontemporal_load(g_r2 + o_);           \
-    }
-#pragma unroll
-            for (int k = 0; k < RG_PF - 1; ++k) { RG_M_LOAD(k, k) }
-#pragma unroll 1
-            for (int b0 = 0; b0 < nb; b0 += RG_PF) {
-#pragma unroll
-                for (int u = 0; u < RG_PF; ++u) {
-                    const int b = b0 + u;
-                    RG_M_LOAD(b + RG_PF - 1, (u + RG_PF - 1) % RG_PF)
-                    __syncthreads();  // batch b is in the tile
-#pragma unroll
-                    for (int jj = 0; jj < 2; ++jj) {
-                        const int r = b * RG_VB + j0 + jj - (RG_N - 1);
-                        if (r >= 0 && r < h) {  // uniform
-                            float t[6];
-                            rg_map_terms(g[u][jj][0], s_out[b & 1][0][j0 + jj][lane], g[u][jj][1],
-                                         s_out[b & 1][1][j0 + jj][lane], s_out[b & 1][2][j0 + jj][lane],
-                                         g[u][jj][2], g[u][jj][3], t);
-                            if (ok) dens[(size_t)r * w] = map_density(t[0], t[1], t[2], t[3], t[4], t[5], mc);
-                        }
-                    }
-                }
-            }
-#undef RG_M_LOAD
-        }
-        __syncthreads();  // every wave is done with s_out and s_job before the next job's pull
-    }
+    rg_v_body<FMA, true>(p, &m);
 }
 
 }  // namespace ssimu2

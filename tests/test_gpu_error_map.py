@@ -48,14 +48,22 @@ def test_map_matches_the_reference_on_the_golden_pairs(mode, oracle, golden):
     _check_against_reference(oracle, s, blur, arrays["odd_ref"], arrays["odd_dist"], f"{name} odd")
 
 
-@pytest.mark.parametrize("w,h", [(1, 1), (7, 5), (33, 17), (129, 67)])
+# 4160 x 75: five scales, 3 * (65 + 33 + 17 + 9 + 5) = 387 jobs of the recursive vertical pass -- more than the device has
+# CUs, so its persistent workgroups each take a second job behind the job-tail barrier (1920 x 1080 is 180 jobs) -- and
+# scale 0 runs two rounds of the prefetch queue, batches past the image included.
+@pytest.mark.parametrize("w,h", [(1, 1), (7, 5), (33, 17), (129, 67), (4160, 75)])
 def test_map_matches_the_reference_on_ragged_and_tiny_sizes(mode, oracle, w, h):
     name, s, blur = mode
+    if (w, h) == (4160, 75):
+        jobs = 3 * sum(-(-w // (64 << k)) for k in range(5))
+        assert jobs == 387 and jobs > s.device_info()["compute_units"]
     ref = synth.make_ref(w, h, seed=w * 7 + h) if min(w, h) >= 2 else np.full((h, w, 3), 77, np.uint8)
     dist = synth.distort(ref, "blockq", 2, seed=5) if min(w, h) >= 2 else np.full((h, w, 3), 200, np.uint8)
     score, m = _check_against_reference(oracle, s, blur, ref, dist, f"{name} {w}x{h}")
     if min(w, h) < 8:  # no scale to score
         assert score == 100.0 and not m.any()
+    if (w, h) == (4160, 75):
+        assert s.last_averages()[1] == 5
 
 
 def test_map_matches_the_reference_at_1080p(mode, oracle):
