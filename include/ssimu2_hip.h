@@ -19,6 +19,24 @@
  *
  * Threading: one ssimu2_ctx = one HIP stream + its device scratch; a ctx is not
  * re-entrant; distinct ctxs are independent (different streams and/or devices).
+ *
+ * Scoring service: a host that starts one process per image pays HIP's start-up in every one of
+ * them.  With OAVIF_SCORER_SOCKET=PATH in the environment (read by every ssimu2_ctx_create; "%d" in it is replaced by
+ * the `device` argument; unset or empty = everything below as written) the context lives in a running `oavif_scored`
+ * process instead (oavif_amd/lib/oavif_scored --socket PATH; python -m oavif_amd.service), and this process makes no HIP
+ * call for it: no function is added, the same calls are served over a Unix-domain socket, frames through shared memory.
+ *   - served, with the bytes the service's context returned: ssimu2_ctx_set_blur, every host-pointer score, reference,
+ *     error-map and batch call, ssimu2_last_averages, ssimu2_last_batch_averages, ssimu2_last_error, ssimu2_ctx_destroy;
+ *     bad arguments are answered as by a local context.  ssimu2_host_alloc returns memory the service reads in place
+ *     (a frame decoded into it is not copied again); any other pointer is copied once.
+ *   - ssimu2_query_device / ssimu2_ctx_device_info return the service's record; ssimu2_prefetch / _join only check
+ *     their argument; ssimu2_linear_table and ssimu2_version stay local.
+ *   - refused with SSIMU2_ERR_UNSUPPORTED: every *_device form, ssimu2_enqueue_*, ssimu2_wait (a device pointer of
+ *     this process means nothing to the service); a non-NULL hip_stream is SSIMU2_ERR_INVALID_ARG.
+ *   - no service at PATH, or one of another build (ssimu2_version() must be equal): SSIMU2_ERR_NO_DEVICE, path and
+ *     reason in ssimu2_last_error(NULL); every slot of the service taken: SSIMU2_ERR_OOM.  Never a fallback to a local GPU.
+ *   - a lost or silent service (OAVIF_SCORER_TIMEOUT_S, default 120) is SSIMU2_ERR_HIP, "scoring service: connection
+ *     lost" / "timed out", on that call and every later one of the context; no call blocks forever.
  */
 #ifndef SSIMU2_HIP_H_
 #define SSIMU2_HIP_H_

@@ -388,12 +388,18 @@ def parse_cli(argv=None):
                     help="run OAVIF_PATH once per image exactly as measure.py does (measure.py:41-107), in this rank's "
                          "shard and on this rank's GPU (LOCAL_RANK is handed to the child), instead of searching in "
                          "this process: e.g. oavif_amd/lib/oavif_host, the compiled C host of this repository")
+    ap.add_argument("--service", action="store_true",
+                    help="with --exec: start one scoring service (oavif_amd/lib/oavif_scored, oavif_amd/service.py) per rank "
+                         "for the run and hand its socket to the per-image processes (OAVIF_SCORER_SOCKET): they score "
+                         "through it and never start HIP, and the GPU is held open by one process per rank")
     ap.add_argument("--out-dir", default="temp_avif_output")
     ap.add_argument("--collective-json", default=None, metavar="PATH",
                     help="rank 0 writes the job's `collective` record (oavif_amd/collective.py: backend, world size, every "
                          "rank's device / PCI bus id / NUMA node / pinned cores, library versions) and the run's totals "
                          "(images, wall seconds, images per second) to PATH")
     args = ap.parse_args(argv)
+    if args.service and not args.exec_oavif:
+        ap.error("--service goes with --exec (the in-process search has the GPU already)")
     args.oavif_path = None
     if len(args.paths) == 2:
         args.images_dir, args.output_csv = args.paths
@@ -518,6 +524,11 @@ def main(argv=None) -> int:
         child_env = dict(os.environ, LOCAL_RANK=str(local_rank))        # the child scores on this rank's GPU
         if "OAVIF_LIBAVIF" not in child_env and avif_bridge._find_library():
             child_env["OAVIF_LIBAVIF"] = avif_bridge._find_library()    # the C host opens libavif by this name
+    scoring_service = None
+    if args.service:
+        from . import service
+        scoring_service = service.start(device=local_rank)              # leaves with this rank (--parent-pid)
+        child_env[service.ENV] = scoring_service.socket
 
     def encode_fn(i, path):
         if args.exec_oavif:
@@ -540,6 +551,8 @@ def main(argv=None) -> int:
                         gather_device=torch.device("cuda", local_rank) if (world > 1 or gather_always) and backend == "nccl" else None,
                         log=lambda s: print(s, file=sys.stderr), workers=args.workers, gather_always=gather_always)
     wall = time.perf_counter() - t0
+    if scoring_service is not None:
+        scoring_service.stop()
     if not args.keep:
         for i in deal_largest_first([_size_or_zero(p) for p in files], world)[rank]:
             try:

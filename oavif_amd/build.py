@@ -16,8 +16,10 @@ LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip.so")              # the product: C ABI of include/ssimu2_hip.h, oavif_tq.h
 INSTR_LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip_instr.so")  # + include/ssimu2_hip_internal.h (bench / tests only)
 HOST_PATH = os.path.join(LIB_DIR, "oavif_host")   # csrc/oavif_host.c: main.zig's flow in C over the two public headers + libavif
-SOURCES = ["ssimu2_hip.hip", "tq.cpp", "png_ingest.cpp"]
-INSTR_SOURCES = ["ssimu2_instrument.hip", "tq.cpp", "png_ingest.cpp"]  # ssimu2_instrument.hip includes ssimu2_hip.hip
+SERVICE_PATH = os.path.join(LIB_DIR, "oavif_scored")  # csrc/oavif_scored.cpp: the resident scoring service
+SOURCES = ["ssimu2_hip.hip", "tq.cpp", "png_ingest.cpp", "remote_client.cpp"]
+INSTR_SOURCES = ["ssimu2_instrument.hip", "tq.cpp", "png_ingest.cpp", "remote_client.cpp"]  # ssimu2_instrument.hip includes ssimu2_hip.hip
+_PROGRAMS = ("oavif_host.c", "oavif_scored.cpp")  # linked against the library, not into it
 
 
 def _hipcc() -> str:
@@ -40,7 +42,7 @@ def libs_need_build() -> bool:
     if not os.path.exists(LIB_PATH) or not os.path.exists(INSTR_LIB_PATH):
         return True
     t = min(os.path.getmtime(LIB_PATH), os.path.getmtime(INSTR_LIB_PATH))
-    return _newer_than(t, [os.path.join(CSRC, s) for s in os.listdir(CSRC) if s != "oavif_host.c"] + _headers())
+    return _newer_than(t, [os.path.join(CSRC, s) for s in os.listdir(CSRC) if s not in _PROGRAMS] + _headers())
 
 
 def host_needs_build() -> bool:
@@ -49,8 +51,15 @@ def host_needs_build() -> bool:
     return _newer_than(os.path.getmtime(HOST_PATH), [os.path.join(CSRC, "oavif_host.c"), LIB_PATH] + _headers())
 
 
+def service_needs_build() -> bool:
+    if not os.path.exists(SERVICE_PATH):
+        return True
+    deps = [os.path.join(CSRC, "oavif_scored.cpp"), os.path.join(CSRC, "remote_client.h"), LIB_PATH] + _headers()
+    return _newer_than(os.path.getmtime(SERVICE_PATH), deps)
+
+
 def needs_build() -> bool:
-    return libs_need_build() or host_needs_build()
+    return libs_need_build() or host_needs_build() or service_needs_build()
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -83,6 +92,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
                 if os.path.exists(tmp):
                     os.unlink(tmp)
         build_host(verbose)
+        build_service(verbose)
     return LIB_PATH
 
 
@@ -103,6 +113,37 @@ def build_host(verbose: bool = False) -> str:
         if os.path.exists(tmp):
             os.unlink(tmp)
     return HOST_PATH
+
+
+def build_service(verbose: bool = False, scorer=None, out=None, flags=()) -> str:
+    """The scoring service (plain C++ over include/ssimu2_hip.h), linked against the product library next to it like
+    the C host.  `scorer` (tests): C sources of a stand-in scorer to link instead of the library, `out` the program to
+    write, `flags` extra compiler flags (sanitizers)."""
+    inc = os.path.join(os.path.dirname(_HERE), "include")
+    target = out or SERVICE_PATH
+    tmp = target + f".tmp{os.getpid()}"
+    cxx = os.environ.get("CXX", "g++")
+    cmd = [cxx, "-O2", "-std=c++17", "-Wall", "-Wextra", *flags, "-I", inc, os.path.join(CSRC, "oavif_scored.cpp"), "-o", tmp]
+    objs = []
+    try:
+        if scorer:
+            for i, src in enumerate(scorer):
+                obj = f"{tmp}.{i}.o"
+                subprocess.run([os.environ.get("CC", "gcc"), "-O2", "-std=gnu11", *flags, "-I", inc, "-c", src, "-o", obj], check=True)
+                objs.append(obj)
+            cmd += objs + ["-lm", "-lpthread"]
+        else:
+            cmd += ["-L", LIB_DIR, "-loavif_hip", "-lpthread", "-Wl,-rpath,$ORIGIN",
+                    "-Wl,-rpath-link," + os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")]
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.run(cmd, check=True)
+        os.replace(tmp, target)
+    finally:
+        for f in objs + [tmp]:
+            if os.path.exists(f):
+                os.unlink(f)
+    return target
 
 
 if __name__ == "__main__":

@@ -437,7 +437,9 @@ typedef struct {
     double encode_ms, decode_ms, score_ms;
     /* decodeAvifCommon's RGB buffer (io.zig:452-482) in page-locked memory of the scorer (ssimu2_host_alloc), used by
        every pass once the context exists: libavif converts straight into it and the upload is one DMA.  NULL = the
-       context is not up yet (the first pass's CPU half runs during HIP start-up), or OAVIF_HOST_PINNED=0. */
+       context is not up yet (the first pass's CPU half runs during HIP start-up), or OAVIF_HOST_PINNED=0.
+       With OAVIF_SCORER_SOCKET set (a scoring service, include/ssimu2_hip.h) nothing here changes: the same call
+       returns memory the service maps, and it reads the frame where libavif wrote it. */
     uint8_t* pinned;
 } EncCtx;
 

@@ -45,6 +45,7 @@
 #include <type_traits>
 
 #include "../../include/ssimu2_hip.h"
+#include "remote_client.h"
 #include "ssimu2_kernels.h"
 #include "ssimu2_recursive.h"
 
@@ -166,6 +167,9 @@ struct ssimu2_ctx {
     bool own_stream = false;   // created here, destroyed with the ctx
     bool pool_stream = false;  // borrowed from the process-wide set of streams on distinct hardware queues
     std::string err;
+    // set: the context lives in a scoring service (OAVIF_SCORER_SOCKET at ssimu2_ctx_create, remote_client.h); nothing
+    // below is used then, and every entry point hands over to it on its first line (REMOTE)
+    ssimu2r::Remote* remote = nullptr;
 
     int blur_mode = SSIMU2_BLUR_FIR;
     ssimu2_device_info dev{};  // what ctx_create saw of the device (and checked: gfx950, 160 KB of LDS per CU)
@@ -251,6 +255,10 @@ struct ssimu2_ctx {
         return code;
     }
 };
+
+#define REMOTE(c, call) \
+    if ((c) && (c)->remote) return ssimu2r::call
+#define REMOTE_REFUSE(c, name) REMOTE(c, unsupported((c)->remote, name))
 
 namespace {
 
@@ -1109,6 +1117,7 @@ extern "C" {
 const char* ssimu2_version(void) { return "oavif_amd ssimu2 gfx950 v8 (pair ring, b64 taps, dword pixel loads; recursive blur: cached reference, 3 lanes per line, persistent vertical pass; placed streams; tagged option structs; device check at context creation; pinned host buffers)"; }
 
 int ssimu2_ctx_set_blur(ssimu2_ctx* c, int mode) {
+    REMOTE(c, set_blur(c->remote, mode));
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     if (mode != SSIMU2_BLUR_FIR && mode != SSIMU2_BLUR_RECURSIVE && mode != SSIMU2_BLUR_RECURSIVE_FMA)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "unknown blur mode");
@@ -1124,6 +1133,7 @@ int ssimu2_ctx_set_blur(ssimu2_ctx* c, int mode) {
 }
 
 const char* ssimu2_last_error(const ssimu2_ctx* ctx) {
+    REMOTE(ctx, last_error(ctx->remote));
     return ctx ? ctx->err.c_str() : g_create_error.c_str();
 }
 
@@ -1264,6 +1274,7 @@ static std::mutex g_prefetch_mu;
 static std::shared_future<void> g_prefetch[64];
 
 int ssimu2_prefetch(int device) {
+    if (ssimu2r::enabled()) return device < 0 || device >= 64 ? SSIMU2_ERR_INVALID_ARG : SSIMU2_OK;  // HIP is not started
     if (device < 0 || device >= 64) return SSIMU2_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lock(g_prefetch_mu);
     if (g_prefetch[device].valid()) return SSIMU2_OK;
@@ -1279,6 +1290,7 @@ int ssimu2_prefetch(int device) {
 }
 
 int ssimu2_prefetch_join(int device) {
+    if (ssimu2r::enabled()) return device < 0 || device >= 64 ? SSIMU2_ERR_INVALID_ARG : SSIMU2_OK;
     if (device < 0 || device >= 64) return SSIMU2_ERR_INVALID_ARG;
     std::shared_future<void> f;
     {
@@ -1289,7 +1301,25 @@ int ssimu2_prefetch_join(int device) {
     return SSIMU2_OK;
 }
 
+// OAVIF_SCORER_SOCKET is set: the context is a connection to the scoring service, and this process makes no HIP call
+// for it.  No fallback to a local GPU when the service cannot be reached.
+static int remote_create(int device, void* hip_stream, ssimu2_ctx** out_ctx) {
+    if (!out_ctx) return SSIMU2_ERR_INVALID_ARG;
+    *out_ctx = nullptr;
+    ssimu2_ctx* c = new (std::nothrow) ssimu2_ctx();
+    if (!c) return SSIMU2_ERR_OOM;
+    c->device = device;
+    const int rc = ssimu2r::create(device, hip_stream, ssimu2_version(), &c->remote, &c->dev, &g_create_error);
+    if (rc != SSIMU2_OK) {
+        delete c;
+        return rc;
+    }
+    *out_ctx = c;
+    return SSIMU2_OK;
+}
+
 int ssimu2_ctx_create(int device, void* hip_stream, ssimu2_ctx** out_ctx) {
+    if (ssimu2r::enabled()) return remote_create(device, hip_stream, out_ctx);
     if (device >= 0 && device < 64) {
         std::shared_future<void> f;
         {
@@ -1383,6 +1413,7 @@ static int query_device_impl(int device, ssimu2_device_info* d, std::string* why
 
 int ssimu2_query_device(int device, ssimu2_device_info* out) {
     if (!out || out->struct_size != sizeof(ssimu2_device_info)) return SSIMU2_ERR_INVALID_ARG;
+    if (ssimu2r::enabled()) return ssimu2r::query_device(device, ssimu2_version(), out, &g_create_error);  // the server's record
     ssimu2_device_info d;
     std::string why;
     const int rc = query_device_impl(device, &d, &why);
@@ -1405,6 +1436,7 @@ int ssimu2_ctx_device_info(const ssimu2_ctx* c, ssimu2_device_info* out) {
 }
 
 int ssimu2_host_alloc(ssimu2_ctx* c, size_t bytes, void** out_ptr) {
+    REMOTE(c, host_alloc(c->remote, bytes, out_ptr));
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     if (!out_ptr || bytes == 0) return c->fail(SSIMU2_ERR_INVALID_ARG, "ssimu2_host_alloc: null out_ptr or zero bytes");
     *out_ptr = nullptr;
@@ -1419,6 +1451,7 @@ int ssimu2_host_alloc(ssimu2_ctx* c, size_t bytes, void** out_ptr) {
 }
 
 int ssimu2_host_free(ssimu2_ctx* c, void* ptr) {
+    REMOTE(c, host_free(c->remote, ptr));
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     if (!ptr) return SSIMU2_OK;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1501,6 +1534,11 @@ static int ctx_create_impl(int device, void* hip_stream, ssimu2_ctx** out_ctx) {
 
 void ssimu2_ctx_destroy(ssimu2_ctx* c) {
     if (!c) return;
+    if (c->remote) {
+        ssimu2r::destroy(c->remote);
+        delete c;
+        return;
+    }
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     release_frame_groups(c);
@@ -1516,6 +1554,7 @@ void ssimu2_ctx_destroy(ssimu2_ctx* c) {
 }
 
 int ssimu2_wait(ssimu2_ctx* c, double* out_score) {
+    REMOTE_REFUSE(c, "ssimu2_wait");
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     if (!c->pending) return c->fail(SSIMU2_ERR_INVALID_ARG, "ssimu2_wait: nothing enqueued");
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1526,6 +1565,7 @@ int ssimu2_wait(ssimu2_ctx* c, double* out_score) {
 
 int ssimu2_enqueue_rgb8_device(ssimu2_ctx* c, const void* d_ref, const void* d_dist, uint32_t w,
                                uint32_t h) {
+    REMOTE_REFUSE(c, "ssimu2_enqueue_rgb8_device");
     int rc = check_args(c, d_ref, d_dist, w, h);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1536,6 +1576,7 @@ int ssimu2_enqueue_rgb8_device(ssimu2_ctx* c, const void* d_ref, const void* d_d
 
 int ssimu2_score_rgb8_device(ssimu2_ctx* c, const void* d_ref, const void* d_dist, uint32_t w,
                              uint32_t h, double* out_score) {
+    REMOTE_REFUSE(c, "ssimu2_score_rgb8_device");
     if (!out_score)
         return c ? c->fail(SSIMU2_ERR_INVALID_ARG, "null out_score") : SSIMU2_ERR_INVALID_ARG;
     int rc = ssimu2_enqueue_rgb8_device(c, d_ref, d_dist, w, h);
@@ -1545,6 +1586,7 @@ int ssimu2_score_rgb8_device(ssimu2_ctx* c, const void* d_ref, const void* d_dis
 
 int ssimu2_score_rgb8(ssimu2_ctx* c, const uint8_t* ref, const uint8_t* dist, uint32_t w,
                       uint32_t h, uint32_t channels, double* out_score) {
+    REMOTE(c, score_rgb8(c->remote, ref, dist, w, h, channels, out_score));
     int rc = check_args(c, ref, dist, w, h);
     if (rc) return rc;
     if (channels != 3) return c->fail(SSIMU2_ERR_UNSUPPORTED, "channels must be 3");
@@ -1640,10 +1682,12 @@ static int set_reference_impl(ssimu2_ctx* c, const void* ref, uint32_t w, uint32
 }
 
 int ssimu2_set_reference(ssimu2_ctx* c, const uint8_t* ref, uint32_t w, uint32_t h) {
+    REMOTE(c, set_reference(c->remote, ref, w, h));
     return set_reference_impl(c, ref, w, h, hipMemcpyHostToDevice);
 }
 
 int ssimu2_set_reference_device(ssimu2_ctx* c, const void* d_ref, uint32_t w, uint32_t h) {
+    REMOTE_REFUSE(c, "ssimu2_set_reference_device");
     return set_reference_impl(c, d_ref, w, h, hipMemcpyDeviceToDevice);
 }
 
@@ -1656,6 +1700,7 @@ static int check_against(ssimu2_ctx* c, bool pointers) {
 }
 
 int ssimu2_enqueue_against_reference_device(ssimu2_ctx* c, const void* d_dist) {
+    REMOTE_REFUSE(c, "ssimu2_enqueue_against_reference_device");
     int rc = check_against(c, d_dist != nullptr);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1679,6 +1724,7 @@ static int stage_upload(ssimu2_ctx* c, const void* pixels, size_t bytes) {
 }
 
 int ssimu2_score_against_reference(ssimu2_ctx* c, const uint8_t* dist, double* out_score) {
+    REMOTE(c, score_against_reference(c->remote, dist, out_score));
     int rc = check_against(c, dist && out_score);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1689,6 +1735,7 @@ int ssimu2_score_against_reference(ssimu2_ctx* c, const uint8_t* dist, double* o
 
 int ssimu2_score_against_reference_strided(ssimu2_ctx* c, const uint8_t* pixels, uint32_t row_bytes,
                                            uint32_t channels, double* out_score) {
+    REMOTE(c, score_strided(c->remote, pixels, row_bytes, channels, out_score));
     int rc = check_against(c, pixels && out_score);
     if (rc) return rc;
     if (channels != 3 && channels != 4)
@@ -1714,6 +1761,7 @@ int ssimu2_score_against_reference_strided(ssimu2_ctx* c, const uint8_t* pixels,
 
 int ssimu2_error_map_rgb8(ssimu2_ctx* c, const uint8_t* ref, const uint8_t* dist, uint32_t w, uint32_t h,
                           uint32_t channels, float* out_map, double* out_score) {
+    REMOTE(c, error_map_rgb8(c->remote, ref, dist, w, h, channels, out_map, out_score));
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     if (!out_map) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_map");
     int rc = ssimu2_score_rgb8(c, ref, dist, w, h, channels, out_score);
@@ -1722,6 +1770,7 @@ int ssimu2_error_map_rgb8(ssimu2_ctx* c, const uint8_t* ref, const uint8_t* dist
 }
 
 int ssimu2_error_map_against_reference(ssimu2_ctx* c, const uint8_t* dist, float* out_map, double* out_score) {
+    REMOTE(c, error_map_against_reference(c->remote, dist, out_map, out_score));
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     if (!out_map) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_map");
     if (c->have_ref && c->ref_hbd)  // the map pass reads the reference's 8-bit frame
@@ -1743,6 +1792,7 @@ int ssimu2_linear_table(uint32_t bit_depth, float* out) {
 
 int ssimu2_score_rgb16(ssimu2_ctx* c, const uint16_t* ref, const uint16_t* dist, uint32_t w, uint32_t h,
                        uint32_t channels, uint32_t bit_depth, double* out_score) {
+    REMOTE(c, score_rgb16(c->remote, ref, dist, w, h, channels, bit_depth, out_score));
     int rc = check_args(c, ref, dist, w, h);
     if (rc) return rc;
     if ((rc = check16(c, ref, bit_depth)) || (rc = check16(c, dist, bit_depth))) return rc;
@@ -1767,6 +1817,7 @@ int ssimu2_score_rgb16(ssimu2_ctx* c, const uint16_t* ref, const uint16_t* dist,
 }
 
 int ssimu2_set_reference_rgb16(ssimu2_ctx* c, const uint16_t* ref, uint32_t w, uint32_t h, uint32_t bit_depth) {
+    REMOTE(c, set_reference_rgb16(c->remote, ref, w, h, bit_depth));
     int rc = check_args(c, ref, ref, w, h);
     if (rc) return rc;
     if ((rc = check16(c, ref, bit_depth))) return rc;
@@ -1805,6 +1856,7 @@ static int score_against_reference16(ssimu2_ctx* c, const Src16& src, double* ou
 }
 
 int ssimu2_score_against_reference_rgb16(ssimu2_ctx* c, const uint16_t* dist, uint32_t bit_depth, double* out_score) {
+    REMOTE(c, score_against_reference_rgb16(c->remote, dist, bit_depth, out_score));
     int rc = check_against(c, out_score != nullptr);
     if (rc || (rc = check16(c, dist, bit_depth))) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1820,6 +1872,7 @@ int ssimu2_score_against_reference_rgb16(ssimu2_ctx* c, const uint16_t* dist, ui
 
 int ssimu2_score_against_reference_strided16(ssimu2_ctx* c, const uint16_t* pixels, uint32_t row_bytes,
                                              uint32_t channels, uint32_t bit_depth, double* out_score) {
+    REMOTE(c, score_strided16(c->remote, pixels, row_bytes, channels, bit_depth, out_score));
     int rc = check_against(c, out_score != nullptr);
     if (rc || (rc = check16(c, pixels, bit_depth))) return rc;
     if (channels != 3 && channels != 4)
@@ -1837,6 +1890,7 @@ int ssimu2_score_against_reference_strided16(ssimu2_ctx* c, const uint16_t* pixe
 }
 
 int ssimu2_last_averages(ssimu2_ctx* c, double* out, int* out_num_scales) {
+    REMOTE(c, last_averages(c->remote, out, out_num_scales));
     if (!c || !out) return SSIMU2_ERR_INVALID_ARG;
     if (c->pending) {
         int rc = ssimu2_wait(c, nullptr);
@@ -1850,6 +1904,7 @@ int ssimu2_last_averages(ssimu2_ctx* c, double* out, int* out_num_scales) {
 // ---- batch scoring ---------------------------------------------------------
 int ssimu2_score_batch_rgb8_device(ssimu2_ctx* c, const void* d_refs, const void* d_dists, size_t item_stride_bytes,
                                    uint32_t n, uint32_t w, uint32_t h, double* out_scores) {
+    REMOTE_REFUSE(c, "ssimu2_score_batch_rgb8_device");
     int rc = batch_open(c, n, false);
     if (rc || n == 0) return rc;
     if ((rc = check_args(c, d_refs, d_dists, w, h))) return rc;
@@ -1862,6 +1917,7 @@ int ssimu2_score_batch_rgb8_device(ssimu2_ctx* c, const void* d_refs, const void
 
 int ssimu2_score_batch_against_reference_device(ssimu2_ctx* c, const void* d_dists, size_t item_stride_bytes, uint32_t n,
                                                 double* out_scores) {
+    REMOTE_REFUSE(c, "ssimu2_score_batch_against_reference_device");
     int rc = batch_open(c, n, true);
     if (rc || n == 0) return rc;
     if (!d_dists || !out_scores) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
@@ -1873,6 +1929,7 @@ int ssimu2_score_batch_against_reference_device(ssimu2_ctx* c, const void* d_dis
 
 int ssimu2_score_batch_rgb8(ssimu2_ctx* c, const uint8_t* const* refs, const uint8_t* const* dists, uint32_t n, uint32_t w,
                             uint32_t h, double* out_scores) {
+    REMOTE(c, score_batch_rgb8(c->remote, refs, dists, n, w, h, out_scores));
     int rc = batch_open(c, n, false);
     if (rc || n == 0) return rc;
     if ((rc = check_args(c, refs, dists, w, h))) return rc;
@@ -1892,6 +1949,7 @@ int ssimu2_score_batch_rgb8(ssimu2_ctx* c, const uint8_t* const* refs, const uin
 }
 
 int ssimu2_score_batch_against_reference(ssimu2_ctx* c, const uint8_t* const* dists, uint32_t n, double* out_scores) {
+    REMOTE(c, score_batch_against_reference(c->remote, dists, n, out_scores));
     int rc = batch_open(c, n, true);
     if (rc || n == 0) return rc;
     if (!dists || !out_scores) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
@@ -1909,6 +1967,7 @@ int ssimu2_score_batch_against_reference(ssimu2_ctx* c, const uint8_t* const* di
 }
 
 int ssimu2_last_batch_averages(ssimu2_ctx* c, uint32_t item, double* out, int* out_num_scales) {
+    REMOTE(c, last_batch_averages(c->remote, item, out, out_num_scales));
     if (!c || !out) return SSIMU2_ERR_INVALID_ARG;
     if (item >= c->batch_n) return c->fail(SSIMU2_ERR_INVALID_ARG, "ssimu2_last_batch_averages: no such item in the last batch");
     const double* r = c->batch.result.as<double>() + (size_t)item * kResultDoubles;

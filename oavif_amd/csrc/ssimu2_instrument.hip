@@ -44,6 +44,7 @@ __global__ __launch_bounds__(256) void k_read_stream(const uint4* __restrict__ s
 extern "C" {
 
 int ssimu2_instr_set_segment_rows(ssimu2_ctx* c, int rows_scale0, int rows_other_scales) {
+    REMOTE_REFUSE(c, "ssimu2_instr_set_segment_rows");
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     if ((rows_scale0 != 0 && (rows_scale0 < 8 || rows_scale0 > 160)) ||
         (rows_other_scales != 0 && (rows_other_scales < 8 || rows_other_scales > 160)))
@@ -58,6 +59,7 @@ int ssimu2_instr_set_segment_rows(ssimu2_ctx* c, int rows_scale0, int rows_other
 }
 
 int ssimu2_instr_set_batch_segment_rows(ssimu2_ctx* c, int rows_scale0) {
+    REMOTE_REFUSE(c, "ssimu2_instr_set_batch_segment_rows");
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     if (rows_scale0 != 0 && rows_scale0 != -1 && (rows_scale0 < 8 || rows_scale0 > 160))
         return c->fail(SSIMU2_ERR_INVALID_ARG, "batch segment rows must be 0 (the rule), -1 (the single-score rule) or 8..160");
@@ -68,24 +70,28 @@ int ssimu2_instr_set_batch_segment_rows(ssimu2_ctx* c, int rows_scale0) {
 }
 
 int ssimu2_instr_batch_segment_rows(ssimu2_ctx* c, uint32_t w, uint32_t h, int scale, int* out_rows) {
+    REMOTE_REFUSE(c, "ssimu2_instr_batch_segment_rows");
     if (!c || !out_rows || scale < 0 || scale >= kNumScales || w == 0 || h == 0) return SSIMU2_ERR_INVALID_ARG;
     *out_rows = batch_seg_rows(c, make_pyramid(w, h), scale);
     return SSIMU2_OK;
 }
 
 int ssimu2_instr_placed_streams(ssimu2_ctx* c, int* out_n) {
+    REMOTE_REFUSE(c, "ssimu2_instr_placed_streams");
     if (!c || !out_n) return SSIMU2_ERR_INVALID_ARG;
     *out_n = pool_size(c->device);
     return SSIMU2_OK;
 }
 
 int ssimu2_instr_rg_stop_after_scale(ssimu2_ctx* c, int scale) {
+    REMOTE_REFUSE(c, "ssimu2_instr_rg_stop_after_scale");
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     c->rg_dbg_scale = scale < 0 || scale >= kNumScales ? -1 : scale;
     return SSIMU2_OK;
 }
 
 int ssimu2_instr_cache_reference_blur(ssimu2_ctx* c, int enabled) {
+    REMOTE_REFUSE(c, "ssimu2_instr_cache_reference_blur");
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     c->cache_ref_blur = enabled != 0;
     c->have_ref = false;
@@ -93,6 +99,7 @@ int ssimu2_instr_cache_reference_blur(ssimu2_ctx* c, int enabled) {
 }
 
 int ssimu2_instr_last_march(ssimu2_ctx* c, int* out_kind) {
+    REMOTE_REFUSE(c, "ssimu2_instr_last_march");
     if (!c || !out_kind) return SSIMU2_ERR_INVALID_ARG;
     *out_kind = c->last_march;
     return SSIMU2_OK;
@@ -100,6 +107,7 @@ int ssimu2_instr_last_march(ssimu2_ctx* c, int* out_kind) {
 
 int ssimu2_debug_download(ssimu2_ctx* c, int what, int scale, uint32_t w, uint32_t h, float* out,
                           uint32_t* out_w, uint32_t* out_h) {
+    REMOTE_REFUSE(c, "ssimu2_debug_download");
     if (!c || !out) return SSIMU2_ERR_INVALID_ARG;
     if (w == 0 || h == 0) return c->fail(SSIMU2_ERR_INVALID_ARG, "zero image dimension");
     const Pyramid p = make_pyramid(w, h);
@@ -166,6 +174,7 @@ int ssimu2_debug_download(ssimu2_ctx* c, int what, int scale, uint32_t w, uint32
 
 int ssimu2_time_device(ssimu2_ctx* c, const void* d_ref, const void* d_dist, uint32_t w,
                        uint32_t h, int iters, float* out_ms_total, double* out_score) {
+    REMOTE_REFUSE(c, "ssimu2_time_device");
     int rc = check_args(c, d_ref, d_dist, w, h);
     if (rc) return rc;
     if (iters <= 0 || !out_ms_total) return c->fail(SSIMU2_ERR_INVALID_ARG, "bad iters/out");
@@ -187,6 +196,7 @@ int ssimu2_time_device(ssimu2_ctx* c, const void* d_ref, const void* d_dist, uin
 
 int ssimu2_time_stage(ssimu2_ctx* c, const void* d_ref, const void* d_dist, uint32_t w, uint32_t h,
                       int stage, int iters, float* out_ms_avg) {
+    REMOTE_REFUSE(c, "ssimu2_time_stage");
     int rc = check_args(c, d_ref, d_dist, w, h);
     if (rc) return rc;
     if (iters <= 0 || !out_ms_avg) return c->fail(SSIMU2_ERR_INVALID_ARG, "bad iters/out");
@@ -221,6 +231,7 @@ int ssimu2_time_stage(ssimu2_ctx* c, const void* d_ref, const void* d_dist, uint
 
 int ssimu2_time_march_rotating(ssimu2_ctx* c, const void* const* d_refs, const void* const* d_dists,
                                int npairs, uint32_t w, uint32_t h, int iters, float* out_ms_avg) {
+    REMOTE_REFUSE(c, "ssimu2_time_march_rotating");
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     if (!d_refs || !d_dists || npairs <= 0 || npairs > 64 || iters <= 0 || !out_ms_avg)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "bad pairs/iters/out");
@@ -292,6 +303,7 @@ int ssimu2_time_march_rotating(ssimu2_ctx* c, const void* const* d_refs, const v
 // sets so that inputs and outputs come from / go to HBM, not the Infinity Cache.
 int ssimu2_time_blur_stage_rotating(ssimu2_ctx* c, const void* const* d_frames, int nframes, uint32_t w,
                                     uint32_t h, int iters, float* out_ms_avg, double* out_bytes_per_launch) {
+    REMOTE_REFUSE(c, "ssimu2_time_blur_stage_rotating");
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     if (!d_frames || nframes <= 0 || nframes > 16 || iters <= 0 || !out_ms_avg)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "bad frames/iters/out");
@@ -370,6 +382,7 @@ int ssimu2_time_blur_stage_rotating(ssimu2_ctx* c, const void* const* d_frames, 
 int ssimu2_time_kernels(ssimu2_ctx* c, const void* d_ref, const void* const* d_refs, const void* const* d_dists, int n,
                         uint32_t w, uint32_t h, int iters, float* out_ms_avg, int* out_launches, float* out_ms_wall_timed,
                         float* out_ms_wall_plain) {
+    REMOTE_REFUSE(c, "ssimu2_time_kernels");
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     if (!d_dists || n <= 0 || n > 256 || iters <= 0 || iters > 512 || !out_ms_avg || !out_launches)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "bad frames/iters/out");
@@ -444,6 +457,7 @@ int ssimu2_time_kernels(ssimu2_ctx* c, const void* d_ref, const void* const* d_r
 }
 
 int ssimu2_measure_read_stream(ssimu2_ctx* c, size_t bytes, int iters, double* out_gbps) {
+    REMOTE_REFUSE(c, "ssimu2_measure_read_stream");
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     if (bytes < (1u << 20) || iters <= 0 || !out_gbps)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "bad bytes/iters/out");

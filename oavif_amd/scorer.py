@@ -8,6 +8,8 @@
 from __future__ import annotations
 
 import ctypes
+import os
+import threading
 import weakref
 
 import numpy as np
@@ -22,6 +24,10 @@ class Ssimu2Error(RuntimeError):
 
 
 _F64P = ctypes.POINTER(ctypes.c_double)
+
+# OAVIF_SCORER_SOCKET is read by ssimu2_ctx_create at every call: Ssimu2(..., service=...) sets it around that one call
+SERVICE_ENV = "OAVIF_SCORER_SOCKET"
+_service_lock = threading.Lock()
 
 
 def _u8p(a: np.ndarray):
@@ -138,8 +144,10 @@ class Ssimu2:
     _ref_shape = None
 
     def __init__(self, device: int = 0, stream: int | None = None, instrumented: bool = False,
-                 blur: int | None = None):
-        """`instrumented=True` binds liboavif_hip_instr.so (the hooks of
+                 blur: int | None = None, service: str | None = None):
+        """`service`: socket path of a running scoring service (oavif_amd.service): the context lives there, and this
+        process makes no HIP call for it (OAVIF_SCORER_SOCKET set around ssimu2_ctx_create, then restored; None = the
+        environment as it is).  `instrumented=True` binds liboavif_hip_instr.so (the hooks of
         include/ssimu2_hip_internal.h: stage timing, plane download, experiment knobs); the
         default is the product library, which has none of them.  `blur`: _lib.BLUR_FIR /
         _lib.BLUR_RECURSIVE (ssimu2_ctx_set_blur); None = FIR."""
@@ -147,8 +155,19 @@ class Ssimu2:
         self._L = _lib.instr_lib() if instrumented else _lib.lib()
         self._ctx = ctypes.c_void_p()
         self._holder = None
-        rc = self._L.ssimu2_ctx_create(int(device), ctypes.c_void_p(stream or 0),
-                                       ctypes.byref(self._ctx))
+        if service is None:
+            rc = self._L.ssimu2_ctx_create(int(device), ctypes.c_void_p(stream or 0), ctypes.byref(self._ctx))
+        else:
+            with _service_lock:
+                before = os.environ.get(SERVICE_ENV)
+                os.environ[SERVICE_ENV] = os.fspath(service)
+                try:
+                    rc = self._L.ssimu2_ctx_create(int(device), ctypes.c_void_p(stream or 0), ctypes.byref(self._ctx))
+                finally:
+                    if before is None:
+                        del os.environ[SERVICE_ENV]
+                    else:
+                        os.environ[SERVICE_ENV] = before
         if rc != 0:
             msg = self._L.ssimu2_last_error(None).decode()
             self._ctx = ctypes.c_void_p()
