@@ -45,6 +45,7 @@
 #include <type_traits>
 
 #include "../../include/ssimu2_hip.h"
+#include "../../include/ssimu2_hip_internal.h"  // SSIMU2_MARCH_*
 #include "remote_client.h"
 #include "ssimu2_kernels.h"
 #include "ssimu2_recursive.h"
@@ -227,10 +228,13 @@ struct ssimu2_ctx {
     double* d_result = nullptr;         // 110 doubles in device memory: the stage timing of the instrumented build only
     DevBuf h_result{nullptr, 0, true};  // page-locked host memory k_finalize writes the result into (110 doubles)
 
-    // reference state
-    bool have_ref = false;
-    uint32_t ref_w = 0, ref_h = 0;
-    bool ref_hbd = false;  // the cached reference was set from 16-bit samples (its 8-bit frame buffer is not it)
+    // The cached reference: set by reference_set, dropped where its storage is released or overwritten
+    struct {
+        bool have = false, hbd = false;  // hbd: set from 16-bit samples (its 8-bit frame buffer is not it)
+        uint32_t w = 0, h = 0;
+        void drop() { have = hbd = false, w = h = 0; }
+        void set(uint32_t w_, uint32_t h_, bool hbd_) { have = true, hbd = hbd_, w = w_, h = h_; }
+    } ref;
     bool pending = false;
 
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -403,32 +407,52 @@ FinalizeArgs finalize_args(const Pyramid& p) {
     return fa;
 }
 
-// The size-only fields of a marching plan and its final reduction under a segment-rows rule (march_seg_rows or
-// batch_seg_rows): per scale w, h, segment rows, strips, workgroups and their running total, 1 / pixels, and in
-// poff[s] the offset (doubles) of scale s in one pair's partial sums.  Every pointer of *mp and *fa is left null for
-// the caller.  Returns the doubles of partial sums of one pair; its workgroups are mp->blk_end[nscales - 1].
-size_t plan_geometry(const ssimu2_ctx* c, const Pyramid& p, SegRows seg_rows, MarchPlan* mp, FinalizeArgs* fa,
-                     size_t poff[kNumScales]) {
+// float offset of scale s in a plane set of every scale (the cached reference's XYB and blur planes; scale 0 first)
+size_t xyb_off(const Pyramid& p, int s) {
+    size_t off = 0;
+    for (int k = 0; k < s; ++k) off += (size_t)3 * p.w[k] * p.h[k];
+    return off;
+}
+
+// Where a marching plan reads and writes: what build_plans turns into the per-scale pointers.
+struct PlanSources {
+    const void *ref0, *dist0;         // scale 0 of the two frames: 8-bit frames, or linear planes (the *_lin kernels)
+    const float *lin_ref, *lin_dist;  // their linear pyramids: scale s >= 1 at Pyramid::lin_off[s]
+    const float* ref_xyb;             // null, or plane sets with scale s at xyb_off(p, s): the reference's positive XYB
+    float* ref_s11;                   // and blur(ref*ref) (k_ref_blur, k_march_map: the planes the kernel writes)
+    double* part;                     // partial sums of one pair; null: sizes only, the plans' pointers stay null
+};
+
+// A marching plan and its final reduction under a segment-rows rule (march_seg_rows or batch_seg_rows).  The one place
+// for the sizes -- per scale w, h, segment rows, strips, workgroups and their running total, 1 / pixels -- and the one
+// place that writes the per-scale pointers, from `src`.  Returns the workgroups of one pair's marching launch (none
+// for a frame below 8 x 8), each with kStats doubles of partial sums.
+int build_plans(const ssimu2_ctx* c, const Pyramid& p, SegRows seg_rows, const PlanSources& src, MarchPlan* mp,
+                FinalizeArgs* fa) {
     memset(mp, 0, sizeof *mp);
     *fa = finalize_args(p);
     mp->nscales = p.nscales;
-    size_t doubles = 0;
     int blocks = 0;
     for (int s = 0; s < p.nscales; ++s) {
         const int seg = seg_rows(c, p, s);
         const int nstrips = (p.w[s] + MW - 1) / MW;
         const int nb = nstrips * ((p.h[s] + seg - 1) / seg);
-        blocks += nb;
-        mp->blk_end[s] = blocks;
+        mp->blk_end[s] = blocks + nb;
         mp->w[s] = p.w[s];
         mp->h[s] = p.h[s];
         mp->seg[s] = seg;
         mp->nstrips[s] = nstrips;
         mp->nblocks[s] = fa->nblocks[s] = nb;
-        poff[s] = doubles;
-        doubles += (size_t)nb * kStats;
+        if (src.part) {
+            mp->ref[s] = s == 0 ? src.ref0 : (const void*)(src.lin_ref + p.lin_off[s]);
+            mp->dist[s] = s == 0 ? src.dist0 : (const void*)(src.lin_dist + p.lin_off[s]);
+            mp->ref_xyb[s] = src.ref_xyb ? src.ref_xyb + xyb_off(p, s) : nullptr;
+            mp->ref_s11[s] = src.ref_s11 ? src.ref_s11 + xyb_off(p, s) : nullptr;
+            fa->part[s] = mp->part[s] = src.part + (size_t)blocks * kStats;
+        }
+        blocks += nb;
     }
-    return doubles;
+    return blocks;
 }
 
 // ---- the buffers: one grow, one release ---------------------------------------------------------
@@ -466,8 +490,9 @@ void release_recursive(ssimu2_ctx* c) {
 }
 
 // Everything sized by the frame or holding content of the frame buffers: every group except the batch scratch, the
-// 16-bit tables and the result.  The caller has drained the stream and drops the reference.
+// 16-bit tables and the result -- and with them the reference they held.  The caller has drained the stream.
 void release_frame_groups(ssimu2_ctx* c) {
+    c->ref.drop();
     release(c->frame);
     release(c->cache);
     release(c->stage);
@@ -483,9 +508,8 @@ int ensure_capacity(ssimu2_ctx* c, uint32_t w, uint32_t h) {
     const Pyramid p = make_pyramid(w, h);
     MarchPlan mp;
     FinalizeArgs fa;
-    size_t poff[kNumScales];
     const size_t need_u8 = (size_t)w * h * 3, need_lin = (p.lin_total + 4) * sizeof(float),
-                 need_part = (plan_geometry(c, p, march_seg_rows, &mp, &fa, poff) + 8) * sizeof(double);
+                 need_part = ((size_t)build_plans(c, p, march_seg_rows, {}, &mp, &fa) * kStats + 8) * sizeof(double);
     struct {
         DevBuf& b;
         size_t bytes;
@@ -499,7 +523,6 @@ int ensure_capacity(ssimu2_ctx* c, uint32_t w, uint32_t h) {
     if (ok) return SSIMU2_OK;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     release_frame_groups(c);
-    c->have_ref = false;
     for (auto& x : want) {
         const int rc = grow(c, x.b, x.bytes, "hipMalloc(frame buffers)");
         if (rc) {
@@ -571,31 +594,39 @@ void launch_pyramid16(ssimu2_ctx* c, const Pyramid& p, int nframes, const Src16*
            dim3(PYR_THREADS), 0, c->stream, a, hb);
 }
 
-// float offset of scale s in the cached reference XYB buffer (scale 0 first)
-size_t xyb_off(const Pyramid& p, int s) {
-    size_t off = 0;
-    for (int k = 0; k < s; ++k) off += (size_t)3 * p.w[k] * p.h[k];
-    return off;
-}
-
 // The reference's cached planes, both sets (FIR mode): what the refblur kernels and every 16-bit pass need.
 bool ref_cached(const ssimu2_ctx* c) { return c->cache.xyb.p && c->cache.blur.p; }
 
-// The plans of a single score's marching launch and final reduction: scale 0 read from d_ref / d_dist, the scales
-// below it from the context's linear pyramids.
-void build_plans(const ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_ref, const uint8_t* d_dist,
-                 bool ref_xyb_cached, MarchPlan* mp, FinalizeArgs* fa, int* total_blocks) {
-    size_t poff[kNumScales];
-    plan_geometry(c, p, march_seg_rows, mp, fa, poff);
-    const bool blur_cached = ref_xyb_cached && ref_cached(c);
-    for (int s = 0; s < p.nscales; ++s) {
-        mp->ref[s] = s == 0 ? (const void*)d_ref : (const void*)(c->frame.lin_ref.as<float>() + p.lin_off[s]);
-        mp->dist[s] = s == 0 ? (const void*)d_dist : (const void*)(c->frame.lin_dist.as<float>() + p.lin_off[s]);
-        mp->ref_xyb[s] = ref_xyb_cached ? c->cache.xyb.as<float>() + xyb_off(p, s) : nullptr;
-        mp->ref_s11[s] = blur_cached ? c->cache.blur.as<float>() + xyb_off(p, s) : nullptr;
-        fa->part[s] = mp->part[s] = c->frame.partials.as<double>() + poff[s];
-    }
-    *total_blocks = p.nscales > 0 ? mp->blk_end[p.nscales - 1] : 0;
+// A single score on the context's own buffers: scale 0 from ref0 / dist0, the scales below from its linear pyramids,
+// with `ref_xyb_cached` the reference's cached planes as far as they exist.  Other sources: change the field.
+PlanSources score_sources(const ssimu2_ctx* c, const void* ref0, const void* dist0, bool ref_xyb_cached) {
+    return {ref0, dist0, c->frame.lin_ref.as<float>(), c->frame.lin_dist.as<float>(),
+            ref_xyb_cached ? c->cache.xyb.as<float>() : nullptr,
+            ref_xyb_cached && ref_cached(c) ? c->cache.blur.as<float>() : nullptr, c->frame.partials.as<double>()};
+}
+
+// The marching launch of a score or (`batch`: the plan around `mp`) a batch, chosen from three facts: the reference's
+// blur is cached, scale 0 is linear planes (16-bit input), this is a batch.  Launches only if there are workgroups.
+void launch_march(ssimu2_ctx* c, bool cached, bool lin0, const MarchPlan& mp, const MarchBatchPlan* batch = nullptr) {
+    const int blocks = mp.nscales > 0 ? (batch ? batch->blk_end : mp.blk_end)[mp.nscales - 1] : 0;
+    note_march(c, blocks <= 0 ? SSIMU2_MARCH_NONE
+                  : batch     ? (cached ? SSIMU2_MARCH_REFBLUR_BATCH : SSIMU2_MARCH_PAIR_BATCH)
+                  : lin0      ? (cached ? SSIMU2_MARCH_REFBLUR_LIN : SSIMU2_MARCH_PAIR_LIN)
+                              : (cached ? SSIMU2_MARCH_REFBLUR_U8 : SSIMU2_MARCH_PAIR_U8));
+    if (blocks <= 0) return;
+    const dim3 grid((unsigned)blocks), threads(MARCH_THREADS);
+    if (batch) launch(cached ? k_march_refblur_batch : k_march_batch, grid, threads, 0, c->stream, *batch);
+    else if (lin0) launch(cached ? k_march_refblur_lin : k_march_lin, grid, threads, 0, c->stream, mp);
+    else launch(cached ? k_march_refblur : k_march, grid, threads, 0, c->stream, mp);
+}
+
+// Positive-XYB planes of one frame at every scale into the plane set `xyb` (scale s at xyb_off(p, s)): scale 0 from
+// `scale0` (`scale0_u8`: an 8-bit frame, else linear planes), the scales below from the linear pyramid `lin`.
+void launch_ref_xyb(ssimu2_ctx* c, const Pyramid& p, const void* scale0, bool scale0_u8, const float* lin, float* xyb) {
+    for (int sc = 0; sc < p.nscales; ++sc)
+        launch(k_ref_xyb, dim3((unsigned)(((size_t)p.w[sc] * p.h[sc] + 255) / 256)), dim3(256), 0, c->stream,
+               sc == 0 ? scale0 : (const void*)(lin + p.lin_off[sc]), sc == 0 && scale0_u8, p.w[sc], p.h[sc],
+               xyb + xyb_off(p, sc));
 }
 
 // ---- the published-recursion modes (ssimu2_recursive.h) ------------------------------------------
@@ -627,7 +658,7 @@ int rg_ensure(ssimu2_ctx* c, const Pyramid& p) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->rg.planes.release();
         c->rg.part.release();
-        c->have_ref = false;
+        c->ref.drop();
         int rc;
         if ((rc = grow(c, c->rg.planes, need, what)) || (rc = grow(c, c->rg.part, need_part, what))) {
             c->rg.planes.release();
@@ -785,9 +816,9 @@ int rg_enqueue_pass(ssimu2_ctx* c, const Pyramid& p, const uint8_t* d_dist, cons
 int rg_prepare(ssimu2_ctx* c, const Pyramid& p, uint32_t w, uint32_t h, bool needs_ref) {
     int rc = rg_check_size(c, w, h);
     if (rc) return rc;
-    const bool had_ref = c->have_ref;
+    const bool had_ref = c->ref.have;
     if ((rc = rg_ensure(c, p))) return rc;
-    if (needs_ref && had_ref && !c->have_ref)
+    if (needs_ref && had_ref && !c->ref.have)
         return c->fail(SSIMU2_ERR_NO_REFERENCE, "recursive blur mode: the cached reference was dropped");
     return SSIMU2_OK;
 }
@@ -803,16 +834,11 @@ int enqueue_score(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, ui
         const int rc = rg_prepare(c, p, w, h, ref_pyramid_ready);
         if (rc) return rc;
     }
-    if (p.nscales > 1 && !recursive) {  // the recursive modes convert straight to XYB planes
-        if (ref_pyramid_ready) {
-            const uint8_t* frames[1] = {d_dist};
-            float* lin[1] = {c->frame.lin_dist.as<float>()};
-            launch_pyramid(c, p, 1, frames, lin);
-        } else {
-            const uint8_t* frames[2] = {d_ref, d_dist};
-            float* lin[2] = {c->frame.lin_ref.as<float>(), c->frame.lin_dist.as<float>()};
-            launch_pyramid(c, p, 2, frames, lin);
-        }
+    if (!recursive) {  // the recursive modes convert straight to XYB planes; a ready reference pyramid is skipped
+        const uint8_t* frames[2] = {d_ref, d_dist};
+        float* lin[2] = {c->frame.lin_ref.as<float>(), c->frame.lin_dist.as<float>()};
+        const int skip = ref_pyramid_ready ? 1 : 0;
+        launch_pyramid(c, p, 2 - skip, frames + skip, lin + skip);
     }
     if (recursive) {
         if (!ref_pyramid_ready) rg_enqueue_reference(c, p, d_ref);
@@ -820,11 +846,8 @@ int enqueue_score(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, ui
     }
     MarchPlan mp;
     FinalizeArgs fa;
-    int blocks = 0;
-    build_plans(c, p, d_ref, d_dist, ref_pyramid_ready && c->cache.xyb.p != nullptr, &mp, &fa, &blocks);
-    note_march(c, blocks <= 0 ? 0 : mp.ref_s11[0] ? 2 : 1);
-    if (blocks > 0)  // reference XYB and blur(ref*ref) cached: the search's per-pass kernel
-        launch(mp.ref_s11[0] ? k_march_refblur : k_march, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
+    build_plans(c, p, march_seg_rows, score_sources(c, d_ref, d_dist, ref_pyramid_ready && c->cache.xyb.p), &mp, &fa);
+    launch_march(c, mp.ref_s11[0] != nullptr, false, mp);
     return finish_score(c, fa);
 }
 
@@ -842,29 +865,16 @@ int enqueue_score16(ssimu2_ctx* c, const Src16* ref, const Src16& dist, uint32_t
     const bool cached = !ref && ref_cached(c);
     if (!ref && !cached)  // 16-bit scale 0 cannot be paired with an 8-bit reference frame in one marching kernel
         return c->fail(SSIMU2_ERR_OOM, "16-bit frames against a reference need its cached planes, which are missing");
-    {
-        const Src16* src[2];
-        float* lin[2];
-        float* lin0[2];
-        int n = 0;
-        if (ref) {
-            src[n] = ref;
-            lin[n] = c->frame.lin_ref.as<float>();
-            lin0[n++] = c->hbd.lin0_ref.as<float>();
-        }
-        src[n] = &dist;
-        lin[n] = c->frame.lin_dist.as<float>();
-        lin0[n++] = c->hbd.lin0_dist.as<float>();
-        launch_pyramid16(c, p, n, src, lin, lin0);
-        if (p.nscales >= 1) note_lin0(c, ref ? 1 : -1, 1, w, h);
-    }
+    const Src16* src[2] = {ref, &dist};
+    float* lin[2] = {c->frame.lin_ref.as<float>(), c->frame.lin_dist.as<float>()};
+    float* lin0[2] = {c->hbd.lin0_ref.as<float>(), c->hbd.lin0_dist.as<float>()};
+    const int skip = ref ? 0 : 1;  // against the cached reference: the distorted frame alone
+    launch_pyramid16(c, p, 2 - skip, src + skip, lin + skip, lin0 + skip);
+    if (p.nscales >= 1) note_lin0(c, ref ? 1 : -1, 1, w, h);
     MarchPlan mp;
     FinalizeArgs fa;
-    int blocks = 0;
-    build_plans(c, p, c->hbd.lin0_ref.as<uint8_t>(), c->hbd.lin0_dist.as<uint8_t>(), cached, &mp, &fa, &blocks);
-    note_march(c, blocks <= 0 ? 0 : cached ? 4 : 3);
-    if (blocks > 0)
-        launch(cached ? k_march_refblur_lin : k_march_lin, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
+    build_plans(c, p, march_seg_rows, score_sources(c, c->hbd.lin0_ref.p, c->hbd.lin0_dist.p, cached), &mp, &fa);
+    launch_march(c, cached, true, mp);
     return finish_score(c, fa);
 }
 
@@ -906,14 +916,22 @@ int device_table(ssimu2_ctx* c, uint32_t d, const float** out) {
     return SSIMU2_OK;
 }
 
-// Scale-0 linear planes for the frames of a FIR-mode 16-bit call (`ref`: the reference's too).
-int hbd_lin0(ssimu2_ctx* c, uint32_t w, uint32_t h, bool ref) {
+// What every 16-bit call needs besides its frames: in FIR mode the scale-0 linear planes of the frames it converts
+// (`ref`: the reference's too), then the device table of the depth (*tab).
+int hbd_prepare(ssimu2_ctx* c, uint32_t w, uint32_t h, bool ref, uint32_t bit_depth, const float** tab) {
     note_lin0(c, ref ? 0 : -1, 0, w, h);  // the call may regrow or rewrite them: valid again once launched
-    if (c->blur_mode != SSIMU2_BLUR_FIR) return SSIMU2_OK;
-    const size_t bytes = (size_t)w * h * 3 * sizeof(float);
-    int rc = grow(c, c->hbd.lin0_dist, bytes, "hipMalloc(16-bit scale-0 planes)");
-    if (!rc && ref) rc = grow(c, c->hbd.lin0_ref, bytes, "hipMalloc(16-bit scale-0 planes)");
-    return rc;
+    if (c->blur_mode == SSIMU2_BLUR_FIR) {
+        const size_t bytes = (size_t)w * h * 3 * sizeof(float);
+        int rc = grow(c, c->hbd.lin0_dist, bytes, "hipMalloc(16-bit scale-0 planes)");
+        if (!rc && ref) rc = grow(c, c->hbd.lin0_ref, bytes, "hipMalloc(16-bit scale-0 planes)");
+        if (rc) return rc;
+    }
+    return device_table(c, bit_depth, tab);
+}
+
+// The tight RGB frame of w pixels per row uploaded into `frame`, read through the table of its depth.
+Src16 tight16(const DevBuf& frame, uint32_t w, const float* tab, uint32_t bit_depth) {
+    return {frame.p, w * 6u, 3u, tab, (1u << bit_depth) - 1u};
 }
 
 // Argument checks of the 16-bit calls (the ctx is not null).
@@ -973,9 +991,9 @@ int map_pass(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, uint32_
         if (c->blur_mode == SSIMU2_BLUR_FIR) {
             MarchPlan mp;
             FinalizeArgs fa;
-            int blocks = 0;
-            build_plans(c, p, d_ref, d_dist, false, &mp, &fa, &blocks);
-            for (int s = 0; s < p.nscales; ++s) mp.ref_s11[s] = dens + xyb_off(p, s);  // the output planes
+            PlanSources src = score_sources(c, d_ref, d_dist, false);
+            src.ref_s11 = dens;  // the output planes
+            const int blocks = build_plans(c, p, march_seg_rows, src, &mp, &fa);
             launch(k_march_map, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp, mc);
         } else {
             RgPlan rp;
@@ -1026,7 +1044,7 @@ int batch_open(ssimu2_ctx* c, uint32_t n, bool against_reference) {
     if (c->blur_mode != SSIMU2_BLUR_FIR)
         return c->fail(SSIMU2_ERR_UNSUPPORTED, "batch scoring runs in SSIMU2_BLUR_FIR only: switch the context with "
                                                "ssimu2_ctx_set_blur, or score the pairs one by one");
-    if (against_reference && !c->have_ref) return c->fail(SSIMU2_ERR_NO_REFERENCE, "no reference set");
+    if (against_reference && !c->ref.have) return c->fail(SSIMU2_ERR_NO_REFERENCE, "no reference set");
     if (n > SSIMU2_MAX_BATCH) return c->fail(SSIMU2_ERR_INVALID_ARG, "batch larger than SSIMU2_MAX_BATCH items");
     return SSIMU2_OK;
 }
@@ -1042,15 +1060,14 @@ int batch_run(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dists, size
     FinalizeArgs fa;
     memset(&bp, 0, sizeof bp);
     MarchPlan& mp = bp.item;
-    size_t poff[kNumScales];
-    const size_t part_stride = plan_geometry(c, p, batch_seg_rows, &mp, &fa, poff);  // doubles between items' partial sums
-    const long long blocks = p.nscales > 0 ? mp.blk_end[p.nscales - 1] : 0;
+    const long long blocks = build_plans(c, p, batch_seg_rows, {}, &mp, &fa);  // the sizes
+    const size_t part_stride = (size_t)blocks * kStats;  // doubles between items' partial sums
     const int nframes = against_ref ? 1 : 2;
     const long long bands = (long long)((p.w[0] + PYR_BAND_W - 1) / PYR_BAND_W) * ((p.h[0] + PYR_BAND_H - 1) / PYR_BAND_H);
     if (blocks * n > 0x7fffffffLL || bands * nframes * n > 0x7fffffffLL)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "batch too large for one launch: fewer items per call");
     const bool cached = against_ref && ref_cached(c);
-    if (against_ref && !cached && c->ref_hbd)  // as ssimu2_score_against_reference_rgb16: no 8-bit frame of that reference
+    if (against_ref && !cached && c->ref.hbd)  // as ssimu2_score_against_reference_rgb16: no 8-bit frame of that reference
         return c->fail(SSIMU2_ERR_OOM, "a batch against a 16-bit reference needs its cached planes, which are missing");
     const size_t lin_stride = (p.lin_total + 3) & ~(size_t)3;  // floats between items' pyramids
     auto& b = c->batch;
@@ -1064,16 +1081,12 @@ int batch_run(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dists, size
     // takes the last batch's averages with it
     if (!fits(b.result, res_bytes)) c->batch_n = 0;
     if ((rc = grow(c, b.result, res_bytes, "hipHostMalloc(batch results)"))) return rc;
-    const float* lin_ref = against_ref ? c->frame.lin_ref.as<float>() : b.lin_ref.as<float>();
-    const uint8_t* ref0 = against_ref ? c->frame.ref_u8.as<uint8_t>() : d_refs;
-    for (int s = 0; s < p.nscales; ++s) {
-        mp.ref[s] = s == 0 ? (const void*)ref0 : (const void*)(lin_ref + p.lin_off[s]);
-        mp.dist[s] = s == 0 ? (const void*)d_dists : (const void*)(b.lin_dist.as<float>() + p.lin_off[s]);
-        mp.ref_xyb[s] = cached ? c->cache.xyb.as<float>() + xyb_off(p, s) : nullptr;
-        mp.ref_s11[s] = cached ? c->cache.blur.as<float>() + xyb_off(p, s) : nullptr;
-        fa.part[s] = mp.part[s] = b.part.as<double>() + poff[s];
-        bp.blk_end[s] = (int)(mp.blk_end[s] * (long long)n);
-    }
+    PlanSources src = score_sources(c, against_ref ? c->frame.ref_u8.p : d_refs, d_dists, cached);
+    if (!against_ref) src.lin_ref = b.lin_ref.as<float>();
+    src.lin_dist = b.lin_dist.as<float>();
+    src.part = b.part.as<double>();
+    build_plans(c, p, batch_seg_rows, src, &mp, &fa);  // item 0; the others lie the strides below behind it
+    for (int s = 0; s < p.nscales; ++s) bp.blk_end[s] = (int)(mp.blk_end[s] * (long long)n);
     bp.n_items = (int)n;
     bp.ref_stride0 = against_ref ? 0 : stride0;  // one reference for all items
     bp.dist_stride0 = stride0;
@@ -1089,10 +1102,7 @@ int batch_run(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dists, size
         pb.out_stride = lin_stride;
         launch(k_pyramid_bands_batch, dim3((unsigned)(bands * nframes * n)), dim3(PYR_THREADS), 0, c->stream, pb);
     }
-    note_march(c, blocks <= 0 ? 0 : cached ? 6 : 5);
-    if (blocks > 0)
-        launch(cached ? k_march_refblur_batch : k_march_batch, dim3((unsigned)(blocks * n)), dim3(MARCH_THREADS), 0,
-               c->stream, bp);
+    launch_march(c, cached, false, mp, &bp);
     launch(k_finalize_batch, dim3(n), dim3(1024), 0, c->stream, fa, part_stride, b.result.as<double>());
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1128,7 +1138,7 @@ int ssimu2_ctx_set_blur(ssimu2_ctx* c, int mode) {
         release_recursive(c);
     }
     c->blur_mode = mode;
-    c->have_ref = false;
+    c->ref.drop();
     return SSIMU2_OK;
 }
 
@@ -1570,7 +1580,7 @@ int ssimu2_enqueue_rgb8_device(ssimu2_ctx* c, const void* d_ref, const void* d_d
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = ensure_capacity(c, w, h))) return rc;
-    c->have_ref = false;  // the lin_ref pyramid is overwritten
+    c->ref.drop();  // the lin_ref pyramid is overwritten
     return enqueue_score(c, (const uint8_t*)d_ref, (const uint8_t*)d_dist, w, h, false);
 }
 
@@ -1593,7 +1603,7 @@ int ssimu2_score_rgb8(ssimu2_ctx* c, const uint8_t* ref, const uint8_t* dist, ui
     if (!out_score) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_score");
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = ensure_capacity(c, w, h))) return rc;
-    c->have_ref = false;
+    c->ref.drop();
     const size_t bytes = (size_t)w * h * 3;
     uint8_t *d_ref = c->frame.ref_u8.as<uint8_t>(), *d_dist = c->frame.dist_u8.as<uint8_t>();
     HIP_TRY(c, hipMemcpyAsync(d_ref, ref, bytes, hipMemcpyHostToDevice, c->stream));
@@ -1615,14 +1625,7 @@ static int cache_reference_fir(ssimu2_ctx* c, const Pyramid& p, const void* scal
     const char* what = "hipMalloc(cached reference planes)";
     (void)grow(c, c->cache.xyb, bytes, what);
     float* const xyb = c->cache.xyb.as<float>();
-    if (xyb) {
-        for (int sc = 0; sc < p.nscales; ++sc) {
-            const size_t n = (size_t)p.w[sc] * p.h[sc];
-            const void* in = sc == 0 ? scale0 : (const void*)(c->frame.lin_ref.as<float>() + p.lin_off[sc]);
-            launch(k_ref_xyb, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, in,
-                               sc == 0 && scale0_u8, p.w[sc], p.h[sc], xyb + xyb_off(p, sc));
-        }
-    }
+    if (xyb) launch_ref_xyb(c, p, scale0, scale0_u8, c->frame.lin_ref.as<float>(), xyb);
     // ... and blur(ref*ref) at every scale, which depends on the reference alone: the per-pass
     // kernel then blurs four planes instead of five (caching blur(ref) too was measured slower)
     if (xyb && c->cache_ref_blur) {
@@ -1630,9 +1633,9 @@ static int cache_reference_fir(ssimu2_ctx* c, const Pyramid& p, const void* scal
         if (c->cache.blur.p) {
             MarchPlan mp;
             FinalizeArgs fa;
-            int blocks = 0;
-            build_plans(c, p, (const uint8_t*)scale0, (const uint8_t*)scale0, true, &mp, &fa, &blocks);
-            for (int sc = 0; sc < p.nscales; ++sc) mp.dist[sc] = mp.ref[sc];  // second frame unused
+            PlanSources src = score_sources(c, scale0, scale0, true);  // XYB planes in, blur(x*x) out
+            src.lin_dist = src.lin_ref;                                // second frame unused
+            const int blocks = build_plans(c, p, march_seg_rows, src, &mp, &fa);
             if (blocks > 0)
                 launch(k_ref_blur, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
         }
@@ -1648,10 +1651,7 @@ static int cache_reference_fir(ssimu2_ctx* c, const Pyramid& p, const void* scal
 static int reference_set(ssimu2_ctx* c, uint32_t w, uint32_t h, bool hbd) {
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // caller may free `ref` after return
-    c->have_ref = true;
-    c->ref_hbd = hbd;
-    c->ref_w = w;
-    c->ref_h = h;
+    c->ref.set(w, h, hbd);
     return SSIMU2_OK;
 }
 
@@ -1664,7 +1664,7 @@ static int set_reference_impl(ssimu2_ctx* c, const void* ref, uint32_t w, uint32
     const Pyramid p = make_pyramid(w, h);
     const bool fir = c->blur_mode == SSIMU2_BLUR_FIR;
     if (!fir && (rc = rg_prepare(c, p, w, h, false))) return rc;  // before any launch
-    c->have_ref = false;
+    c->ref.drop();
     note_lin0(c, 0, 0, w, h);
     uint8_t* const d_ref = c->frame.ref_u8.as<uint8_t>();
     HIP_TRY(c, hipMemcpyAsync(d_ref, ref, (size_t)w * h * 3, kind, c->stream));
@@ -1672,11 +1672,9 @@ static int set_reference_impl(ssimu2_ctx* c, const void* ref, uint32_t w, uint32
         rg_enqueue_reference(c, p, d_ref);
         return reference_set(c, w, h, false);
     }
-    if (p.nscales > 1) {  // the reference's linear pyramid, once per search
-        const uint8_t* frames[1] = {d_ref};
-        float* lin[1] = {c->frame.lin_ref.as<float>()};
-        launch_pyramid(c, p, 1, frames, lin);
-    }
+    const uint8_t* frames[1] = {d_ref};
+    float* lin[1] = {c->frame.lin_ref.as<float>()};
+    launch_pyramid(c, p, 1, frames, lin);  // the reference's linear pyramid, once per search
     (void)cache_reference_fir(c, p, d_ref, true, false);  // not required: an 8-bit pass can convert the reference
     return reference_set(c, w, h, false);
 }
@@ -1694,7 +1692,7 @@ int ssimu2_set_reference_device(ssimu2_ctx* c, const void* d_ref, uint32_t w, ui
 // What every against-reference call checks first, in this order; `pointers`: none of the call's pointers is null.
 static int check_against(ssimu2_ctx* c, bool pointers) {
     if (!c) return SSIMU2_ERR_INVALID_ARG;
-    if (!c->have_ref) return c->fail(SSIMU2_ERR_NO_REFERENCE, "no reference set");
+    if (!c->ref.have) return c->fail(SSIMU2_ERR_NO_REFERENCE, "no reference set");
     if (!pointers) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
     return SSIMU2_OK;
 }
@@ -1704,12 +1702,12 @@ int ssimu2_enqueue_against_reference_device(ssimu2_ctx* c, const void* d_dist) {
     int rc = check_against(c, d_dist != nullptr);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    return enqueue_score(c, c->frame.ref_u8.as<uint8_t>(), (const uint8_t*)d_dist, c->ref_w, c->ref_h, true);
+    return enqueue_score(c, c->frame.ref_u8.as<uint8_t>(), (const uint8_t*)d_dist, c->ref.w, c->ref.h, true);
 }
 
 // The 8-bit frame now in frame.dist_u8 against the cached reference.
 static int score_against_reference8(ssimu2_ctx* c, double* out_score) {
-    int rc = enqueue_score(c, c->frame.ref_u8.as<uint8_t>(), c->frame.dist_u8.as<uint8_t>(), c->ref_w, c->ref_h, true);
+    int rc = enqueue_score(c, c->frame.ref_u8.as<uint8_t>(), c->frame.dist_u8.as<uint8_t>(), c->ref.w, c->ref.h, true);
     if (rc) return rc;
     return ssimu2_wait(c, out_score);
 }
@@ -1728,7 +1726,7 @@ int ssimu2_score_against_reference(ssimu2_ctx* c, const uint8_t* dist, double* o
     int rc = check_against(c, dist && out_score);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)c->ref_w * c->ref_h * 3;
+    const size_t bytes = (size_t)c->ref.w * c->ref.h * 3;
     HIP_TRY(c, hipMemcpyAsync(c->frame.dist_u8.p, dist, bytes, hipMemcpyHostToDevice, c->stream));
     return score_against_reference8(c, out_score);
 }
@@ -1740,7 +1738,7 @@ int ssimu2_score_against_reference_strided(ssimu2_ctx* c, const uint8_t* pixels,
     if (rc) return rc;
     if (channels != 3 && channels != 4)
         return c->fail(SSIMU2_ERR_UNSUPPORTED, "channels must be 3 (RGB) or 4 (RGBA)");
-    const uint32_t w = c->ref_w, h = c->ref_h;
+    const uint32_t w = c->ref.w, h = c->ref.h;
     if ((uint64_t)row_bytes < (uint64_t)w * channels)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "row_bytes smaller than one row of pixels");
     if (channels == 3 && row_bytes == w * 3)  // already the scorer's layout
@@ -1773,11 +1771,11 @@ int ssimu2_error_map_against_reference(ssimu2_ctx* c, const uint8_t* dist, float
     REMOTE(c, error_map_against_reference(c->remote, dist, out_map, out_score));
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     if (!out_map) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_map");
-    if (c->have_ref && c->ref_hbd)  // the map pass reads the reference's 8-bit frame
+    if (c->ref.have && c->ref.hbd)  // the map pass reads the reference's 8-bit frame
         return c->fail(SSIMU2_ERR_UNSUPPORTED, "no error map against a reference set from 16-bit samples");
     int rc = ssimu2_score_against_reference(c, dist, out_score);
     if (rc) return rc;
-    return map_pass(c, c->frame.ref_u8.as<uint8_t>(), c->frame.dist_u8.as<uint8_t>(), c->ref_w, c->ref_h, out_map);
+    return map_pass(c, c->frame.ref_u8.as<uint8_t>(), c->frame.dist_u8.as<uint8_t>(), c->ref.w, c->ref.h, out_map);
 }
 
 // ---- 16-bit input ----------------------------------------------------------
@@ -1801,18 +1799,17 @@ int ssimu2_score_rgb16(ssimu2_ctx* c, const uint16_t* ref, const uint16_t* dist,
     if (c->blur_mode != SSIMU2_BLUR_FIR && (rc = rg_check_size(c, w, h))) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = ensure_capacity(c, w, h))) return rc;
-    c->have_ref = false;  // the lin_ref pyramid is overwritten
+    c->ref.drop();  // the lin_ref pyramid is overwritten
     const size_t bytes = (size_t)w * h * 3 * sizeof(uint16_t);
     const float* tab = nullptr;
     if ((rc = grow(c, c->hbd.ref16, bytes, "hipMalloc(16-bit frames)")) ||
         (rc = grow(c, c->hbd.dist16, bytes, "hipMalloc(16-bit frames)")) ||
-        (rc = hbd_lin0(c, w, h, true)) || (rc = device_table(c, bit_depth, &tab)))
+        (rc = hbd_prepare(c, w, h, true, bit_depth, &tab)))
         return rc;
     HIP_TRY(c, hipMemcpyAsync(c->hbd.ref16.p, ref, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->hbd.dist16.p, dist, bytes, hipMemcpyHostToDevice, c->stream));
-    const uint32_t maxv = (1u << bit_depth) - 1u;
-    const Src16 r{c->hbd.ref16.p, w * 6u, 3u, tab, maxv}, d{c->hbd.dist16.p, w * 6u, 3u, tab, maxv};
-    if ((rc = enqueue_score16(c, &r, d, w, h))) return rc;
+    const Src16 r = tight16(c->hbd.ref16, w, tab, bit_depth);
+    if ((rc = enqueue_score16(c, &r, tight16(c->hbd.dist16, w, tab, bit_depth), w, h))) return rc;
     return ssimu2_wait(c, out_score);
 }
 
@@ -1827,14 +1824,14 @@ int ssimu2_set_reference_rgb16(ssimu2_ctx* c, const uint16_t* ref, uint32_t w, u
     if ((rc = ensure_capacity(c, w, h))) return rc;
     const Pyramid p = make_pyramid(w, h);
     if (!fir && (rc = rg_ensure(c, p))) return rc;
-    c->have_ref = false;
+    c->ref.drop();  // the lin_ref pyramid and the cached planes are overwritten
     const size_t bytes = (size_t)w * h * 3 * sizeof(uint16_t);
     const float* tab = nullptr;
     if ((rc = grow(c, c->hbd.ref16, bytes, "hipMalloc(16-bit frames)")) ||
-        (rc = hbd_lin0(c, w, h, true)) || (rc = device_table(c, bit_depth, &tab)))
+        (rc = hbd_prepare(c, w, h, true, bit_depth, &tab)))
         return rc;
     HIP_TRY(c, hipMemcpyAsync(c->hbd.ref16.p, ref, bytes, hipMemcpyHostToDevice, c->stream));
-    const Src16 r{c->hbd.ref16.p, w * 6u, 3u, tab, (1u << bit_depth) - 1u};
+    const Src16 r = tight16(c->hbd.ref16, w, tab, bit_depth);
     if (fir) {  // linear pyramid and scale-0 planes, then the same caches as an 8-bit reference's (required here)
         const Src16* src[1] = {&r};
         float* lin[1] = {c->frame.lin_ref.as<float>()};
@@ -1850,7 +1847,7 @@ int ssimu2_set_reference_rgb16(ssimu2_ctx* c, const uint16_t* ref, uint32_t w, u
 
 // Score the 16-bit frame at `src.px` (already on the device) against the cached reference.
 static int score_against_reference16(ssimu2_ctx* c, const Src16& src, double* out_score) {
-    int rc = enqueue_score16(c, nullptr, src, c->ref_w, c->ref_h);
+    int rc = enqueue_score16(c, nullptr, src, c->ref.w, c->ref.h);
     if (rc) return rc;
     return ssimu2_wait(c, out_score);
 }
@@ -1860,14 +1857,14 @@ int ssimu2_score_against_reference_rgb16(ssimu2_ctx* c, const uint16_t* dist, ui
     int rc = check_against(c, out_score != nullptr);
     if (rc || (rc = check16(c, dist, bit_depth))) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    const uint32_t w = c->ref_w, h = c->ref_h;
+    const uint32_t w = c->ref.w, h = c->ref.h;
     const size_t bytes = (size_t)w * h * 3 * sizeof(uint16_t);
     const float* tab = nullptr;
     if ((rc = grow(c, c->hbd.dist16, bytes, "hipMalloc(16-bit frames)")) ||
-        (rc = hbd_lin0(c, w, h, false)) || (rc = device_table(c, bit_depth, &tab)))
+        (rc = hbd_prepare(c, w, h, false, bit_depth, &tab)))
         return rc;
     HIP_TRY(c, hipMemcpyAsync(c->hbd.dist16.p, dist, bytes, hipMemcpyHostToDevice, c->stream));
-    return score_against_reference16(c, Src16{c->hbd.dist16.p, w * 6u, 3u, tab, (1u << bit_depth) - 1u}, out_score);
+    return score_against_reference16(c, tight16(c->hbd.dist16, w, tab, bit_depth), out_score);
 }
 
 int ssimu2_score_against_reference_strided16(ssimu2_ctx* c, const uint16_t* pixels, uint32_t row_bytes,
@@ -1877,15 +1874,14 @@ int ssimu2_score_against_reference_strided16(ssimu2_ctx* c, const uint16_t* pixe
     if (rc || (rc = check16(c, pixels, bit_depth))) return rc;
     if (channels != 3 && channels != 4)
         return c->fail(SSIMU2_ERR_UNSUPPORTED, "channels must be 3 (RGB) or 4 (RGBA)");
-    const uint32_t w = c->ref_w, h = c->ref_h;
+    const uint32_t w = c->ref.w, h = c->ref.h;
     if ((row_bytes & 1u) || (uint64_t)row_bytes < (uint64_t)w * channels * 2)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "row_bytes odd or smaller than one row of 16-bit pixels");
     HIP_TRY(c, hipSetDevice(c->device));
     // rows are read where they are, padding and alpha skipped by the front end; the last row needs only its pixels
     const size_t bytes = (size_t)row_bytes * (h - 1) + (size_t)w * channels * 2;
     const float* tab = nullptr;
-    if ((rc = hbd_lin0(c, w, h, false)) || (rc = device_table(c, bit_depth, &tab))) return rc;
-    if ((rc = stage_upload(c, pixels, bytes))) return rc;
+    if ((rc = hbd_prepare(c, w, h, false, bit_depth, &tab)) || (rc = stage_upload(c, pixels, bytes))) return rc;
     return score_against_reference16(c, Src16{c->stage.p, row_bytes, channels, tab, (1u << bit_depth) - 1u}, out_score);
 }
 
@@ -1921,10 +1917,10 @@ int ssimu2_score_batch_against_reference_device(ssimu2_ctx* c, const void* d_dis
     int rc = batch_open(c, n, true);
     if (rc || n == 0) return rc;
     if (!d_dists || !out_scores) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
-    if ((uint64_t)item_stride_bytes < (uint64_t)c->ref_w * c->ref_h * 3)
+    if ((uint64_t)item_stride_bytes < (uint64_t)c->ref.w * c->ref.h * 3)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "item_stride_bytes smaller than one frame");
     HIP_TRY(c, hipSetDevice(c->device));
-    return batch_run(c, nullptr, (const uint8_t*)d_dists, item_stride_bytes, n, c->ref_w, c->ref_h, out_scores);
+    return batch_run(c, nullptr, (const uint8_t*)d_dists, item_stride_bytes, n, c->ref.w, c->ref.h, out_scores);
 }
 
 int ssimu2_score_batch_rgb8(ssimu2_ctx* c, const uint8_t* const* refs, const uint8_t* const* dists, uint32_t n, uint32_t w,
@@ -1956,12 +1952,12 @@ int ssimu2_score_batch_against_reference(ssimu2_ctx* c, const uint8_t* const* di
     for (uint32_t i = 0; i < n; ++i)
         if (!dists[i]) return c->fail(SSIMU2_ERR_INVALID_ARG, "null image pointer in the batch");
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)c->ref_w * c->ref_h * 3, stride = (bytes + 15) & ~(size_t)15;
+    const size_t bytes = (size_t)c->ref.w * c->ref.h * 3, stride = (bytes + 15) & ~(size_t)15;
     if ((rc = batch_stage(c, c->batch.u8_dist, dists, n, bytes, stride))) {
         (void)hipStreamSynchronize(c->stream);
         return rc;
     }
-    rc = batch_run(c, nullptr, c->batch.u8_dist.as<uint8_t>(), stride, n, c->ref_w, c->ref_h, out_scores);
+    rc = batch_run(c, nullptr, c->batch.u8_dist.as<uint8_t>(), stride, n, c->ref.w, c->ref.h, out_scores);
     if (rc) (void)hipStreamSynchronize(c->stream);
     return rc;
 }

@@ -7,6 +7,8 @@
 #define SSIMU2_INSTRUMENTED_BUILD 1
 #include "ssimu2_hip.hip"
 
+#include <vector>
+
 #include "../../include/ssimu2_hip_internal.h"
 
 namespace ssimu2 {
@@ -53,8 +55,7 @@ int ssimu2_instr_set_segment_rows(ssimu2_ctx* c, int rows_scale0, int rows_other
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->seg_rows_override = rows_scale0;
     c->seg_rows_tail_override = rows_other_scales;
-    release_frame_groups(c);  // the partial-sum buffer is sized by the segment rule
-    c->have_ref = false;
+    release_frame_groups(c);  // the partial-sum buffer is sized by the segment rule; the reference goes with it
     return SSIMU2_OK;
 }
 
@@ -94,7 +95,7 @@ int ssimu2_instr_cache_reference_blur(ssimu2_ctx* c, int enabled) {
     REMOTE_REFUSE(c, "ssimu2_instr_cache_reference_blur");
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     c->cache_ref_blur = enabled != 0;
-    c->have_ref = false;
+    c->ref.drop();
     return SSIMU2_OK;
 }
 
@@ -124,7 +125,7 @@ int ssimu2_debug_download(ssimu2_ctx* c, int what, int scale, uint32_t w, uint32
         if (scale < 1 || scale >= p.nscales || !c->frame.lin_ref.p) return c->fail(SSIMU2_ERR_INVALID_ARG, "no such level");
         src = (what == SSIMU2_DEBUG_LIN_REF ? c->frame.lin_ref : c->frame.lin_dist).as<float>() + p.lin_off[scale];
     } else if (what == SSIMU2_DEBUG_XYB_REF) {
-        if (scale < 0 || scale >= p.nscales || !c->cache.xyb.p || !c->have_ref || c->ref_w != w || c->ref_h != h)
+        if (scale < 0 || scale >= p.nscales || !c->cache.xyb.p || !c->ref.have || c->ref.w != w || c->ref.h != h)
             return c->fail(SSIMU2_ERR_INVALID_ARG, "no cached reference XYB for that level");
         src = c->cache.xyb.as<float>() + xyb_off(p, scale);
     } else if (what == SSIMU2_DEBUG_RG_H || what == SSIMU2_DEBUG_RG_V) {
@@ -157,7 +158,7 @@ int ssimu2_debug_download(ssimu2_ctx* c, int what, int scale, uint32_t w, uint32
         if (out_h) *out_h = (uint32_t)p.h[scale];
         return SSIMU2_OK;
     } else if (what == SSIMU2_DEBUG_REF_BLUR) {
-        if (scale < 0 || scale >= p.nscales || !c->cache.blur.p || !c->have_ref || c->ref_w != w || c->ref_h != h)
+        if (scale < 0 || scale >= p.nscales || !c->cache.blur.p || !c->ref.have || c->ref.w != w || c->ref.h != h)
             return c->fail(SSIMU2_ERR_INVALID_ARG, "no cached reference blur for that level");
         src = c->cache.blur.as<float>() + xyb_off(p, scale);
     } else {
@@ -180,7 +181,7 @@ int ssimu2_time_device(ssimu2_ctx* c, const void* d_ref, const void* d_dist, uin
     if (iters <= 0 || !out_ms_total) return c->fail(SSIMU2_ERR_INVALID_ARG, "bad iters/out");
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = ensure_capacity(c, w, h))) return rc;
-    c->have_ref = false;
+    c->ref.drop();  // the lin_ref pyramid is overwritten
     HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
     for (int i = 0; i < iters; ++i)
         if ((rc = enqueue_score(c, (const uint8_t*)d_ref, (const uint8_t*)d_dist, w, h, false)))
@@ -194,6 +195,53 @@ int ssimu2_time_device(ssimu2_ctx* c, const void* d_ref, const void* d_dist, uin
     return SSIMU2_OK;
 }
 
+}  // extern "C"
+
+// ---- the timing hooks: one timed loop, scratch that ends with the call ---------------------------
+namespace {
+
+// What a hook call holds for its length only, released on every way out: its scratch device memory (a local DevBuf
+// filled by grow(), freed once the context stream has drained; never kept in the context, so a hook's footprint does
+// not outlive the hook) and its events.
+template <class F>
+struct AtExit {
+    F f;
+    ~AtExit() { f(); }
+};
+template <class F>
+AtExit(F) -> AtExit<F>;
+auto scratch_guard(ssimu2_ctx* c, DevBuf& b) {
+    return AtExit{[c, &b] { (void)hipStreamSynchronize(c->stream), b.release(); }};
+}
+
+// n value-initialised elements; empty when the host has no memory for them.
+template <class T>
+std::vector<T> host_array(int n) {
+    try {
+        return std::vector<T>((size_t)n);
+    } catch (const std::bad_alloc&) {
+        return {};
+    }
+}
+
+// The timed loop of every hook: `warm` untimed calls of fn(j), then `iters` timed ones between ev0 and ev1 on the
+// context stream, the launch-error check and the wait.  *ms = stream time of the timed calls together.
+template <class F>
+hipError_t timed_loop(ssimu2_ctx* c, int warm, int iters, float* ms, F&& fn) {
+    for (int j = 0; j < warm; ++j) fn(j);
+    hipError_t e = hipEventRecord(c->ev0, c->stream);
+    for (int j = 0; j < iters && e == hipSuccess; ++j) fn(j);
+    if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventSynchronize(c->ev1);
+    if (e == hipSuccess) e = hipEventElapsedTime(ms, c->ev0, c->ev1);
+    return e;
+}
+
+}  // namespace
+
+extern "C" {
+
 int ssimu2_time_stage(ssimu2_ctx* c, const void* d_ref, const void* d_dist, uint32_t w, uint32_t h,
                       int stage, int iters, float* out_ms_avg) {
     REMOTE_REFUSE(c, "ssimu2_time_stage");
@@ -205,26 +253,17 @@ int ssimu2_time_stage(ssimu2_ctx* c, const void* d_ref, const void* d_dist, uint
     const Pyramid p = make_pyramid(w, h);
     MarchPlan mp;
     FinalizeArgs fa;
-    int blocks = 0;
-    build_plans(c, p, (const uint8_t*)d_ref, (const uint8_t*)d_dist, false, &mp, &fa, &blocks);
+    const int blocks = build_plans(c, p, march_seg_rows, score_sources(c, d_ref, d_dist, false), &mp, &fa);
     if (stage < 0 || stage > 2) return c->fail(SSIMU2_ERR_INVALID_ARG, "bad stage");
-    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    for (int i = 0; i < iters; ++i) {
-        if (stage == SSIMU2_STAGE_PYRAMID && p.nscales > 1) {
-            const uint8_t* frames[2] = {(const uint8_t*)d_ref, (const uint8_t*)d_dist};
-            float* lin[2] = {c->frame.lin_ref.as<float>(), c->frame.lin_dist.as<float>()};
-            launch_pyramid(c, p, 2, frames, lin);
-        } else if (stage == SSIMU2_STAGE_MARCH && blocks > 0) {
-            hipLaunchKernelGGL(k_march, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
-        } else if (stage == SSIMU2_STAGE_FINALIZE) {
-            hipLaunchKernelGGL(k_finalize, dim3(1), dim3(1024), 0, c->stream, fa, c->d_result);
-        }
-    }
-    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventSynchronize(c->ev1));
+    const uint8_t* frames[2] = {(const uint8_t*)d_ref, (const uint8_t*)d_dist};
+    float* lin[2] = {c->frame.lin_ref.as<float>(), c->frame.lin_dist.as<float>()};
     float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    const hipError_t e = timed_loop(c, 0, iters, &ms, [&](int) {
+        if (stage == SSIMU2_STAGE_PYRAMID) launch_pyramid(c, p, 2, frames, lin);
+        else if (stage == SSIMU2_STAGE_FINALIZE) launch(k_finalize, dim3(1), dim3(1024), 0, c->stream, fa, c->d_result);
+        else if (blocks > 0) launch(k_march, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
+    });
+    if (e != hipSuccess) return c->fail(SSIMU2_ERR_HIP, "stage timing", e);
     *out_ms_avg = ms / (float)iters;
     return SSIMU2_OK;
 }
@@ -239,60 +278,37 @@ int ssimu2_time_march_rotating(ssimu2_ctx* c, const void* const* d_refs, const v
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = ensure_capacity(c, w, h))) return rc;
-    c->have_ref = false;
+    c->ref.drop();
     const Pyramid p = make_pyramid(w, h);
     // per-pair linear-light pyramids (what the marching kernel reads at scales >= 1)
     const size_t lin_floats = p.lin_total + 4;
-    float* lin = nullptr;
-    hipError_t e = hipMalloc(&lin, (size_t)npairs * 2 * lin_floats * sizeof(float));
-    if (e != hipSuccess) return c->fail(SSIMU2_ERR_OOM, "hipMalloc(rotating pyramids)", e);
-    MarchPlan* plans = new (std::nothrow) MarchPlan[npairs];
-    if (!plans) {
-        (void)hipFree(lin);
-        return c->fail(SSIMU2_ERR_OOM, "plans");
-    }
+    DevBuf lin;
+    const auto free_lin = scratch_guard(c, lin);
+    rc = grow(c, lin, (size_t)npairs * 2 * lin_floats * sizeof(float), "hipMalloc(rotating pyramids)");
+    if (rc) return rc;
+    std::vector<MarchPlan> plans = host_array<MarchPlan>(npairs);
+    if (plans.empty()) return c->fail(SSIMU2_ERR_OOM, "plans");
     int blocks = 0;
     for (int i = 0; i < npairs; ++i) {
-        if (!d_refs[i] || !d_dists[i]) {
-            delete[] plans;
-            (void)hipFree(lin);
-            return c->fail(SSIMU2_ERR_INVALID_ARG, "null pair pointer");
-        }
-        float* lr = lin + (size_t)(2 * i) * lin_floats;
-        float* ld = lin + (size_t)(2 * i + 1) * lin_floats;
-        if (p.nscales > 1) {
-            const uint8_t* frames[2] = {(const uint8_t*)d_refs[i], (const uint8_t*)d_dists[i]};
-            float* lins[2] = {lr, ld};
-            launch_pyramid(c, p, 2, frames, lins);
-        }
+        if (!d_refs[i] || !d_dists[i]) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pair pointer");
+        const uint8_t* frames[2] = {(const uint8_t*)d_refs[i], (const uint8_t*)d_dists[i]};
+        float* const lr = lin.as<float>() + (size_t)(2 * i) * lin_floats;
+        float* lins[2] = {lr, lr + lin_floats};
+        launch_pyramid(c, p, 2, frames, lins);
+        PlanSources src = score_sources(c, d_refs[i], d_dists[i], false);
+        src.lin_ref = lins[0];
+        src.lin_dist = lins[1];
         FinalizeArgs fa;
-        build_plans(c, p, (const uint8_t*)d_refs[i], (const uint8_t*)d_dists[i], false, &plans[i], &fa, &blocks);
-        for (int s = 1; s < p.nscales; ++s) {
-            plans[i].ref[s] = lr + p.lin_off[s];
-            plans[i].dist[s] = ld + p.lin_off[s];
-        }
+        blocks = build_plans(c, p, march_seg_rows, src, &plans[i], &fa);
     }
     float ms = 0.f;
-    if (blocks > 0) {
-        // untimed: ~30 ms of the same launches first.  Allocating the scratch above leaves the GPU
-        // idle for a moment, and an MI355X that has been idle runs its next ~100 launches 5-15 %
-        // slower while its clocks come back up (kernel-trace of bench.py: 166 -> 154 -> 144 -> 141 us)
-        const int warm = npairs * 2 > 192 ? npairs * 2 : 192;
-        for (int j = 0; j < warm; ++j)
-            hipLaunchKernelGGL(k_march, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, plans[j % npairs]);
-        e = hipEventRecord(c->ev0, c->stream);
-        for (int j = 0; j < iters && e == hipSuccess; ++j)
-            hipLaunchKernelGGL(k_march, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, plans[j % npairs]);
-        if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventSynchronize(c->ev1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    } else {
-        e = hipStreamSynchronize(c->stream);
-    }
-    (void)hipStreamSynchronize(c->stream);
-    delete[] plans;
-    (void)hipFree(lin);
+    // untimed: ~30 ms of the same launches first.  Allocating the scratch above leaves the GPU
+    // idle for a moment, and an MI355X that has been idle runs its next ~100 launches 5-15 %
+    // slower while its clocks come back up (kernel-trace of bench.py: 166 -> 154 -> 144 -> 141 us)
+    const dim3 grid(blocks), threads(MARCH_THREADS);
+    const auto one = [&](int j) { launch(k_march, grid, threads, 0, c->stream, plans[j % npairs]); };
+    const hipError_t e = blocks > 0 ? timed_loop(c, npairs * 2 > 192 ? npairs * 2 : 192, iters, &ms, one)
+                                    : hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return c->fail(SSIMU2_ERR_HIP, "rotating march timing", e);
     *out_ms_avg = ms / (float)iters;
     return SSIMU2_OK;
@@ -311,56 +327,35 @@ int ssimu2_time_blur_stage_rotating(ssimu2_ctx* c, const void* const* d_frames, 
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = ensure_capacity(c, w, h))) return rc;
-    c->have_ref = false;
+    c->ref.drop();  // the lin_ref pyramid is overwritten
     const Pyramid p = make_pyramid(w, h);
     const size_t planes = xyb_off(p, p.nscales) + 4;  // floats of one plane set (all scales)
-    float* buf = nullptr;
-    hipError_t e = hipMalloc(&buf, (size_t)nframes * 2 * planes * sizeof(float));
-    if (e != hipSuccess) return c->fail(SSIMU2_ERR_OOM, "hipMalloc(rotating blur-stage planes)", e);
-    MarchPlan* plans = new (std::nothrow) MarchPlan[nframes];
-    if (!plans) {
-        (void)hipFree(buf);
-        return c->fail(SSIMU2_ERR_OOM, "plans");
-    }
+    DevBuf buf;
+    const auto free_buf = scratch_guard(c, buf);
+    rc = grow(c, buf, (size_t)nframes * 2 * planes * sizeof(float), "hipMalloc(rotating blur-stage planes)");
+    if (rc) return rc;
+    std::vector<MarchPlan> plans = host_array<MarchPlan>(nframes);
+    if (plans.empty()) return c->fail(SSIMU2_ERR_OOM, "plans");
     int blocks = 0;
     for (int i = 0; i < nframes; ++i) {
-        const uint8_t* f = (const uint8_t*)d_frames[i];
-        float* xyb = buf + (size_t)(2 * i) * planes;
-        float* blur = buf + (size_t)(2 * i + 1) * planes;
-        if (p.nscales > 1) {
-            const uint8_t* frames[1] = {f};
-            float* lins[1] = {c->frame.lin_ref.as<float>()};
-            launch_pyramid(c, p, 1, frames, lins);
-        }
-        for (int sc = 0; sc < p.nscales; ++sc) {
-            const size_t n = (size_t)p.w[sc] * p.h[sc];
-            const void* in = sc == 0 ? (const void*)f : (const void*)(c->frame.lin_ref.as<float>() + p.lin_off[sc]);
-            hipLaunchKernelGGL(k_ref_xyb, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, in, sc == 0,
-                               p.w[sc], p.h[sc], xyb + xyb_off(p, sc));
-        }
+        const uint8_t* frames[1] = {(const uint8_t*)d_frames[i]};
+        float* lins[1] = {c->frame.lin_ref.as<float>()};
+        float* xyb = buf.as<float>() + (size_t)(2 * i) * planes;
+        launch_pyramid(c, p, 1, frames, lins);
+        launch_ref_xyb(c, p, frames[0], true, lins[0], xyb);
         FinalizeArgs fa;
-        build_plans(c, p, f, f, false, &plans[i], &fa, &blocks);
-        for (int sc = 0; sc < p.nscales; ++sc) {
-            plans[i].dist[sc] = plans[i].ref[sc];
-            plans[i].ref_xyb[sc] = xyb + xyb_off(p, sc);
-            plans[i].ref_s11[sc] = blur + xyb_off(p, sc);
-        }
+        PlanSources src = score_sources(c, frames[0], frames[0], false);
+        src.lin_dist = src.lin_ref;  // second frame unused
+        src.ref_xyb = xyb;
+        src.ref_s11 = xyb + planes;
+        blocks = build_plans(c, p, march_seg_rows, src, &plans[i], &fa);
     }
     float ms = 0.f;
-    if (blocks > 0) {
-        for (int j = 0; j < 64; ++j)  // clocks (see ssimu2_time_march_rotating)
-            hipLaunchKernelGGL(k_ref_blur, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, plans[j % nframes]);
-        e = hipEventRecord(c->ev0, c->stream);
-        for (int j = 0; j < iters && e == hipSuccess; ++j)
-            hipLaunchKernelGGL(k_ref_blur, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, plans[j % nframes]);
-        if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventSynchronize(c->ev1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    }
-    (void)hipStreamSynchronize(c->stream);
-    delete[] plans;
-    (void)hipFree(buf);
+    hipError_t e = hipSuccess;
+    if (blocks > 0)  // 64 untimed: clocks (see ssimu2_time_march_rotating)
+        e = timed_loop(c, 64, iters, &ms, [&](int j) {
+            launch(k_ref_blur, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, plans[j % nframes]);
+        });
     if (e != hipSuccess) return c->fail(SSIMU2_ERR_HIP, "rotating blur-stage timing", e);
     *out_ms_avg = ms / (float)iters;
     // algorithmic bytes of one launch: every plane element read once and written once
@@ -397,37 +392,36 @@ int ssimu2_time_kernels(ssimu2_ctx* c, const void* d_ref, const void* const* d_r
     } else {
         HIP_TRY(c, hipSetDevice(c->device));
         if ((rc = ensure_capacity(c, w, h))) return rc;
-        c->have_ref = false;
+        c->ref.drop();  // the lin_ref pyramid is overwritten
     }
-    auto one = [&](int j) {
-        return cached ? enqueue_score(c, c->frame.ref_u8.as<uint8_t>(), (const uint8_t*)d_dists[j % n], w, h, true)
-                      : enqueue_score(c, (const uint8_t*)d_refs[j % n], (const uint8_t*)d_dists[j % n], w, h, false);
+    auto one = [&](int j) {  // score j of a window; nothing more once one has failed
+        if (rc) return;
+        rc = cached ? enqueue_score(c, c->frame.ref_u8.as<uint8_t>(), (const uint8_t*)d_dists[j % n], w, h, true)
+                    : enqueue_score(c, (const uint8_t*)d_refs[j % n], (const uint8_t*)d_dists[j % n], w, h, false);
     };
     constexpr int kMaxLaunches = 8;
     const int nev = 2 * kMaxLaunches * iters;
-    hipEvent_t* ev = new (std::nothrow) hipEvent_t[nev];
-    if (!ev) return c->fail(SSIMU2_ERR_OOM, "events");
-    int made = 0;
+    std::vector<hipEvent_t> ev = host_array<hipEvent_t>(nev);
+    if (ev.empty()) return c->fail(SSIMU2_ERR_OOM, "events");
+    AtExit destroy_events{[&] {
+        for (hipEvent_t x : ev)
+            if (x) (void)hipEventDestroy(x);
+    }};
     hipError_t e = hipSuccess;
-    for (; made < nev; ++made)
-        if ((e = hipEventCreate(&ev[made])) != hipSuccess) break;
+    for (int i = 0; i < nev && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
     double sum[kMaxLaunches] = {0};
     float wall_timed = 0.f, wall_plain = 0.f;
     int per_score = 0;
     if (e == hipSuccess) {
-        const int warm = 2 * n > 24 ? 2 * n : 24;  // clocks and caches as in a run of scores
-        for (int j = 0; j < warm && rc == 0; ++j) rc = one(j);
-        // plain launches first: the stream time per score without the timestamps
-        if (rc == 0) e = hipEventRecord(c->ev0, c->stream);
-        for (int j = 0; j < iters && rc == 0; ++j) rc = one(j);
-        if (rc == 0 && e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-        if (rc == 0 && e == hipSuccess) e = hipEventSynchronize(c->ev1);
-        if (rc == 0 && e == hipSuccess) e = hipEventElapsedTime(&wall_plain, c->ev0, c->ev1);
-        // the same scores with a start / stop event pair on every launch
-        LaunchTimer timer{ev, 0, nev};
+        // plain launches first, after a warm-up (clocks and caches as in a run of scores): the stream time per score
+        // without the timestamps
+        e = timed_loop(c, 2 * n > 24 ? 2 * n : 24, iters, &wall_plain, one);
+        // the same scores with a start / stop event pair on every launch.  Not timed_loop: the per-launch events below
+        // are read after a wait for the whole stream, not for ev1 alone
+        LaunchTimer timer{ev.data(), 0, nev};
         if (rc == 0 && e == hipSuccess) e = hipEventRecord(c->ev0, c->stream);
         g_launch_timer = &timer;
-        for (int j = 0; j < iters && rc == 0; ++j) rc = one(j);
+        for (int j = 0; j < iters; ++j) one(j);
         g_launch_timer = nullptr;
         if (rc == 0 && e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
         if (rc == 0 && e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -445,8 +439,6 @@ int ssimu2_time_kernels(ssimu2_ctx* c, const void* d_ref, const void* const* d_r
     }
     (void)hipStreamSynchronize(c->stream);
     c->pending = false;
-    for (int i = 0; i < made; ++i) (void)hipEventDestroy(ev[i]);
-    delete[] ev;
     if (rc) return rc;
     if (e != hipSuccess) return c->fail(SSIMU2_ERR_HIP, "per-kernel timing", e);
     for (int k = 0; k < per_score; ++k) out_ms_avg[k] = (float)(sum[k] / iters);
@@ -462,30 +454,22 @@ int ssimu2_measure_read_stream(ssimu2_ctx* c, size_t bytes, int iters, double* o
     if (bytes < (1u << 20) || iters <= 0 || !out_gbps)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "bad bytes/iters/out");
     HIP_TRY(c, hipSetDevice(c->device));
-    void* buf = nullptr;
-    hipError_t e = hipMalloc(&buf, bytes + 64);
-    if (e != hipSuccess) return c->fail(SSIMU2_ERR_OOM, "hipMalloc(read-stream scratch)", e);
-    uint32_t* sink = (uint32_t*)((uint8_t*)buf + (bytes & ~(size_t)15));
-    int rc = SSIMU2_OK;
+    DevBuf buf;
+    const auto free_buf = scratch_guard(c, buf);
+    const int rc = grow(c, buf, bytes + 64, "hipMalloc(read-stream scratch)");
+    if (rc) return rc;
+    uint32_t* sink = (uint32_t*)(buf.as<uint8_t>() + (bytes & ~(size_t)15));
     float ms = 0.f;
     const size_t n16 = bytes / 16;
     const int grid = 256 * 16;  // 16 workgroups of 4 waves per CU: the CUs' full wave capacity
-    if ((e = hipMemsetAsync(buf, 0, bytes + 64, c->stream)) != hipSuccess) goto hip_fail;
-    hipLaunchKernelGGL(k_read_stream, dim3(grid), dim3(256), 0, c->stream, (const uint4*)buf, n16, sink);
-    if ((e = hipEventRecord(c->ev0, c->stream)) != hipSuccess) goto hip_fail;
-    for (int i = 0; i < iters; ++i)
-        hipLaunchKernelGGL(k_read_stream, dim3(grid), dim3(256), 0, c->stream, (const uint4*)buf, n16, sink);
-    if ((e = hipEventRecord(c->ev1, c->stream)) != hipSuccess) goto hip_fail;
-    if ((e = hipGetLastError()) != hipSuccess) goto hip_fail;
-    if ((e = hipEventSynchronize(c->ev1)) != hipSuccess) goto hip_fail;
-    if ((e = hipEventElapsedTime(&ms, c->ev0, c->ev1)) != hipSuccess) goto hip_fail;
+    hipError_t e = hipMemsetAsync(buf.p, 0, bytes + 64, c->stream);
+    if (e == hipSuccess)  // one untimed launch first
+        e = timed_loop(c, 1, iters, &ms, [&](int) {
+            launch(k_read_stream, dim3(grid), dim3(256), 0, c->stream, buf.as<uint4>(), n16, sink);
+        });
+    if (e != hipSuccess) return c->fail(SSIMU2_ERR_HIP, "read-stream probe", e);
     *out_gbps = (double)(n16 * 16) / ((double)ms / iters * 1e-3) * 1e-9;
-    (void)hipFree(buf);
-    return rc;
-hip_fail:
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(buf);
-    return c->fail(SSIMU2_ERR_HIP, "read-stream probe", e);
+    return SSIMU2_OK;
 }
 
 }  // extern "C"
