@@ -42,6 +42,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <sys/stat.h>
+#include <time.h>
 #include <unistd.h>
 
 #include "oavif_tq.h"
@@ -127,9 +128,43 @@ static int fail(const char* name, const char* detail) {
     pthread_mutex_unlock(&g_lock);
     return -1;
 }
+static void forget_failure(void) { /* after a failure that was a question, not an error (supports_10bit) */
+    g_err = NULL;
+    g_detail[0] = 0;
+}
 
-static int load_libavif(void) {
-    const char* path = getenv("OAVIF_LIBAVIF");
+/* ---- the environment, read once (run(); print_version for the library's name) ------------------------- */
+typedef struct {
+    const char* libavif; /* OAVIF_LIBAVIF: the library to open; NULL or "" = libavif.so */
+    int pinned;          /* OAVIF_HOST_PINNED=0 switches the page-locked frame buffers off */
+    int times;           /* OAVIF_HOST_TIMES: the phase timeline and the times: / speculative: lines */
+    int blur;            /* OAVIF_SSIMU2_BLUR: the blur of the search path, the published recursion unless it says
+                            otherwise (as the Zig shim's `blur` and the Python mirror: INTEGRATION.md section 2e) */
+    int fanout;          /* OAVIF_PROBE_FANOUT, at most OAVIF_TQ_MAX_FANOUT; above 1 the probes of a search are fanned.
+                            Not a CLI flag: the option surface stays the reference's (parse_args.zig:76-122) */
+    int device;          /* LOCAL_RANK */
+} Env;
+static void env_read(Env* v) {
+    const char *pinned = getenv("OAVIF_HOST_PINNED"), *bm = getenv("OAVIF_SSIMU2_BLUR");
+    const char *fan = getenv("OAVIF_PROBE_FANOUT"), *rank = getenv("LOCAL_RANK");
+    v->libavif = getenv("OAVIF_LIBAVIF");
+    v->pinned = !(pinned && !strcmp(pinned, "0"));
+    v->times = getenv("OAVIF_HOST_TIMES") != NULL;
+    v->blur = SSIMU2_BLUR_RECURSIVE;
+    if (bm && !strcmp(bm, "fir")) v->blur = SSIMU2_BLUR_FIR;
+    else if (bm && (!strcmp(bm, "recursive_fma") || !strcmp(bm, "iir_fma"))) v->blur = SSIMU2_BLUR_RECURSIVE_FMA;
+    v->fanout = fan ? atoi(fan) : 1;
+    if (v->fanout > OAVIF_TQ_MAX_FANOUT) v->fanout = OAVIF_TQ_MAX_FANOUT;
+    v->device = rank ? atoi(rank) : 0;
+}
+
+static double now_ms(void) {
+    struct timespec t;
+    clock_gettime(CLOCK_MONOTONIC, &t);
+    return t.tv_sec * 1e3 + t.tv_nsec * 1e-6;
+}
+
+static int load_libavif(const char* path) {
     void* h = dlopen(path && *path ? path : "libavif.so", RTLD_NOW | RTLD_LOCAL);
     if (!h) h = dlopen("libavif.so.16", RTLD_NOW | RTLD_LOCAL);
     if (!h) return fail("LibavifUnavailable", dlerror());
@@ -193,49 +228,49 @@ typedef struct {
 } Options;
 #define OPTIONS_DEFAULT {0, 9, 1, 0, 0, 1, 80.0, 1, "iq", 2.0, 6, -1, 2, 2, 2} /* parse_args.zig:48-63 */
 
-static int int_arg(int* i, int argc, char** argv, long lo, long hi, const char* name, int* out) {
+static const char* arg_value(int* i, int argc, char** argv, const char* name) { /* the next argument, consumed */
     if (*i >= argc || argv[*i][0] == '-') { /* parse_args.zig:126: a value starting with '-' counts as missing */
         fprintf(stderr, "Error: Missing %s value\n", name);
-        return fail("MissingOptionValue", NULL);
+        fail("MissingOptionValue", NULL);
+        return NULL;
     }
+    return argv[(*i)++];
+}
+static int int_arg(int* i, int argc, char** argv, long lo, long hi, const char* name, int* out) {
+    const char* a = arg_value(i, argc, argv, name);
+    if (!a) return -1;
     char* end;
     errno = 0;
-    const long v = strtol(argv[*i], &end, 10);
+    const long v = strtol(a, &end, 10);
     if (*end || errno) return fail("InvalidCharacter", NULL);
     if (v < lo || v > hi) {
         fprintf(stderr, "Error: %s must be between %ld and %ld\n", name, lo, hi);
         return fail("InvalidOptionValue", NULL);
     }
-    ++*i;
     *out = (int)v;
     return 0;
 }
 static int float_arg(int* i, int argc, char** argv, double lo, double hi, const char* name, double* out) {
-    if (*i >= argc || argv[*i][0] == '-') {
-        fprintf(stderr, "Error: Missing %s value\n", name);
-        return fail("MissingOptionValue", NULL);
-    }
+    const char* a = arg_value(i, argc, argv, name);
+    if (!a) return -1;
     char* end;
-    const double v = strtod(argv[*i], &end);
-    if (*end || end == argv[*i]) return fail("InvalidCharacter", NULL);
+    const double v = strtod(a, &end);
+    if (*end || end == a) return fail("InvalidCharacter", NULL);
     if (v < lo || v > hi) {
         fprintf(stderr, "Error: %s must be between %g and %g\n", name, lo, hi);
         return fail("InvalidOptionValue", NULL);
     }
-    ++*i;
     *out = v;
     return 0;
 }
 static int bool_arg(int* i, int argc, char** argv, const char* name, int* out) {
-    if (*i >= argc || argv[*i][0] == '-') {
-        fprintf(stderr, "Error: Missing %s value\n", name);
-        return fail("MissingOptionValue", NULL);
-    }
-    if (strcmp(argv[*i], "0") != 0 && strcmp(argv[*i], "1") != 0) {
+    const char* a = arg_value(i, argc, argv, name);
+    if (!a) return -1;
+    if (strcmp(a, "0") != 0 && strcmp(a, "1") != 0) {
         fprintf(stderr, "Error: %s must be 0 or 1\n", name);
         return fail("InvalidOptionValue", NULL);
     }
-    *out = argv[(*i)++][0] == '1';
+    *out = a[0] == '1';
     return 0;
 }
 
@@ -252,8 +287,8 @@ static int parse_args(Options* o, int argc, char** argv, const char** in, const 
         else if (IS("--tile-cols-log2")) rc = int_arg(&i, argc, argv, 0, 6, "--tile-cols-log2", &o->tile_cols_log2);
         else if (IS("--auto-tiling")) rc = bool_arg(&i, argc, argv, "--auto-tiling", &o->auto_tiling);
         else if (IS("--tune")) {
-            if (i >= argc || argv[i][0] == '-') { fprintf(stderr, "Error: Missing --tune value\n"); return fail("MissingOptionValue", NULL); }
-            const char* t = argv[i++];
+            const char* t = arg_value(&i, argc, argv, "--tune");
+            if (!t) return -1;
             if (strcmp(t, "ssim") && strcmp(t, "iq") && strcmp(t, "ssimulacra2")) {
                 fprintf(stderr, "Error: --tune must be one of: ssim, iq, ssimulacra2\n");
                 return fail("InvalidTuneMode", NULL);
@@ -421,40 +456,19 @@ static int load_image(const char* path, Image* im) {
 }
 
 /* ---- the pass: io.encodeAvifToBuffer + decodeAvifCommon + the score (tq.zig:21-38) ------------------------- */
-typedef struct {
+typedef struct { /* what every pass encodes: filled once, then only read (the probes of a wave share it on threads) */
     const Options* o;
     const Image* src;
-    const void* scaled; /* the source at the encoder's depth, computed once */
+    const void* scaled;   /* the source at the encoder's depth, computed once */
     uint32_t out_depth;
     avifImageHead* image; /* ... and as the encoder takes it (YUV444), converted once: make_source_image() */
-    ssimu2_ctx* scorer; /* made when the first score needs it (ensure_scorer) */
-    int device, blur;
-    const uint8_t* rgb8; /* e.rgb: the scorer's reference */
-    /* EncBuffer (main.zig:11-19): the AVIF bytes of the LAST probe */
-    uint8_t* buf;
-    size_t buf_size;
-    int buf_q;
-    double encode_ms, decode_ms, score_ms;
-    /* decodeAvifCommon's RGB buffer (io.zig:452-482) in page-locked memory of the scorer (ssimu2_host_alloc), used by
-       every pass once the context exists: libavif converts straight into it and the upload is one DMA.  NULL = the
-       context is not up yet (the first pass's CPU half runs during HIP start-up), or OAVIF_HOST_PINNED=0.
-       With OAVIF_SCORER_SOCKET set (a scoring service, include/ssimu2_hip.h) nothing here changes: the same call
-       returns memory the service maps, and it reads the frame where libavif wrote it. */
-    uint8_t* pinned;
-} EncCtx;
-
-#include <time.h>
-static double now_ms(void) {
-    struct timespec t;
-    clock_gettime(CLOCK_MONOTONIC, &t);
-    return t.tv_sec * 1e3 + t.tv_nsec * 1e-6;
-}
+} Source;
 
 /* io.zig:550-623, hoisted out of the pass loop: the avifImage of the source -- created, tagged (CICP, ICC) and
    converted to YUV444 -- is made ONCE.  The reference rebuilds it on every pass (avifImageCreate +
    avifImageRGBToYUV over the whole frame, 15 % of a 4K encode at speed 9) although only `quality` changes between
    passes (io.zig:625).  Same planes, same bitstream. */
-static int make_source_image(EncCtx* e) {
+static int make_source_image(Source* e) {
     const Options* o = e->o;
     const Image* s = e->src;
     int r;
@@ -482,12 +496,11 @@ static int make_source_image(EncCtx* e) {
     return 0;
 }
 
-static int encode_to_buffer(EncCtx* e, uint32_t q, uint8_t** out, size_t* out_size) { /* io.zig:619-635 */
+static int encode_to_buffer(const Source* e, uint32_t q, uint8_t** out, size_t* out_size) { /* io.zig:619-635 */
     const Options* o = e->o;
     avifEncoderHead* enc = NULL;
     avifRWData output = {NULL, 0};
     int rc = -1, r;
-    if (!e->image && make_source_image(e)) return -1;
     enc = av.EncoderCreate();
     if (!enc) { fail("OutOfMemory", NULL); goto done; }
     enc->qualityAlpha = o->quality_alpha; /* copyToEncoder (parse_args.zig:65-74) */
@@ -512,8 +525,26 @@ done:
     return rc;
 }
 
+/* io.zig:546: can the loaded libavif write 10-bit?  A libaom without high-bit-depth support cannot; asked once, with
+   a 16x16 gray image at speed 10 and the run's other options. */
+static int supports_10bit(const Options* o) {
+    Options po = *o;
+    po.speed = 10;
+    uint16_t tiny[16 * 16 * 3];
+    for (int i = 0; i < 16 * 16 * 3; ++i) tiny[i] = 512;
+    const Image ti = {16, 16, 3, 0, (uint8_t*)tiny, NULL, 0};
+    Source s = {&po, &ti, tiny, 10, NULL};
+    uint8_t* b = NULL;
+    size_t n = 0;
+    const int refused = make_source_image(&s) || encode_to_buffer(&s, 50, &b, &n);
+    if (s.image) av.ImageDestroy(s.image);
+    free(b);
+    forget_failure();
+    return !refused;
+}
+
 /* One pass (computeScoreAtQuality, tq.zig:21-38) in two halves: the CPU half (encode at q, decode to libavif's
-   8-bit RGB(A) rows) touches nothing shared but the read-only source image, so the probes of a speculative wave
+   8-bit RGB(A) rows) touches nothing shared but the read-only source, so the probes of a speculative wave
    run it on threads and the FIRST pass of a run runs it while the scorer is still starting up; the GPU half
    scores those rows on a given context. */
 typedef struct { avifDecoderHead* dec; avifRGBImage rgb; int caller_pixels; } Decoded;
@@ -522,20 +553,13 @@ static void decoded_free(Decoded* d) {
     if (d->dec) av.DecoderDestroy(d->dec);
     memset(d, 0, sizeof *d);
 }
-static uint8_t* pinned_frame(ssimu2_ctx* scorer, const Image* src) { /* room for RGBA rows; NULL = use libavif's own */
-    void* p = NULL;
-    const char* v = getenv("OAVIF_HOST_PINNED");
-    if (v && !strcmp(v, "0")) return NULL;
-    if (ssimu2_host_alloc(scorer, (size_t)src->w * src->h * 4, &p) != SSIMU2_OK) return NULL; /* not fatal */
-    return (uint8_t*)p;
-}
-static int pass_cpu(const EncCtx* e, uint32_t q, uint8_t** out_avif, size_t* out_size, Decoded* d, double times_ms[3],
+static int pass_cpu(const Source* e, uint32_t q, uint8_t** out_avif, size_t* out_size, Decoded* d, double times_ms[3],
                     uint8_t* pinned) {
     uint8_t* avif = NULL;
     size_t avif_size = 0;
     memset(d, 0, sizeof *d);
     double t0 = now_ms();
-    if (encode_to_buffer((EncCtx*)(uintptr_t)e, q, &avif, &avif_size)) return -1; /* e->image exists: read-only use */
+    if (encode_to_buffer(e, q, &avif, &avif_size)) return -1;
     double t1 = now_ms();
     /* decodeAvifCommon(avif, use_8bit = true) (io.zig:452-482) */
     int rc = -1, r;
@@ -574,93 +598,125 @@ static int pass_score(ssimu2_ctx* scorer, Decoded* d, double* out_score, double 
     return r == SSIMU2_OK ? 0 : fail("ScorerFailed", ssimu2_last_error(scorer));
 }
 
-static void phase(const char* what);
-static int ensure_scorer(EncCtx* e) { /* ssimu2_prefetch started this at process start; the first score waits for it */
-    if (e->scorer) return 0;
-    int rc = ssimu2_ctx_create(e->device, NULL, &e->scorer);
-    if (rc != SSIMU2_OK) return fail(rc == SSIMU2_ERR_NO_DEVICE ? "NoDevice" : "ScorerFailed", ssimu2_last_error(NULL));
-    phase("scorer context created");
-    if ((rc = ssimu2_ctx_set_blur(e->scorer, e->blur)) || (rc = ssimu2_set_reference(e->scorer, e->rgb8, e->src->w, e->src->h)))
-        return fail("ScorerFailed", ssimu2_last_error(e->scorer));
-    phase("reference uploaded and cached");
-    e->pinned = pinned_frame(e->scorer, e->src);
-    return 0;
-}
+/* ---- the run: everything it allocates, released on every path (run_free) -------------------------------------- */
+/* One scorer context (= one HIP stream + scratch) and what a probe on it needs.  `pinned` is decodeAvifCommon's RGB
+   buffer (io.zig:452-482) in page-locked memory of the scorer (ssimu2_host_alloc): libavif converts straight into it
+   and the upload is one DMA.  NULL = libavif's own buffer: the context is not up yet, OAVIF_HOST_PINNED=0, or the
+   allocation failed (not fatal, tried once).  With OAVIF_SCORER_SOCKET set (a scoring service, include/ssimu2_hip.h)
+   nothing here changes: the same call returns memory the service maps, and it reads the frame where libavif wrote it.
+   A sequential search uses slot 0; a wave of a fanned one runs probe i on slot i, one thread per slot at a time. */
+typedef struct { ssimu2_ctx* ctx; int ready /* blur and reference set */; uint8_t* pinned; int pinned_tried; } Slot;
 
-static int probe(void* user, uint32_t q, double* out_score) { /* the sequential search's pass */
-    EncCtx* e = (EncCtx*)user;
-    uint8_t* avif = NULL;
-    size_t n = 0;
-    double t[3] = {0, 0, 0};
-    Decoded d;
-    if (pass_cpu(e, q, &avif, &n, &d, t, e->pinned)) return -1;
-    if (e->scorer == NULL) phase("first probe encoded and decoded");
-    if (ensure_scorer(e) || pass_score(e->scorer, &d, out_score, t)) { decoded_free(&d); free(avif); return -1; }
-    e->encode_ms += t[0]; e->decode_ms += t[1]; e->score_ms += t[2];
-    free(e->buf); /* tq.zig:31-35: the buffer of this probe replaces the previous one */
-    e->buf = avif; e->buf_size = n; e->buf_q = (int)q;
-    return 0;
-}
-
-/* ---- the probes of one search fanned over scorer contexts and host threads (SURVEY.md 8e row 2; BASELINE
-   configs[2]): oavif_tq_find_target_quality_speculative asks for waves of quantizers, each probe of a wave runs
-   the pass above on its own context (= its own HIP stream) and thread.  OAVIF_PROBE_FANOUT=N, as the Python
-   mirror; the result is the sequential search's (include/oavif_tq.h). ------------------------------------------ */
 typedef struct {
-    EncCtx* e;
-    const uint8_t* rgb8;
-    int blur;
-    uint32_t fan;
-    ssimu2_ctx* ctx[OAVIF_TQ_MAX_FANOUT];
-    int have_ref[OAVIF_TQ_MAX_FANOUT]; /* a context gets the reference when a wave first uses it */
-    uint8_t* pinned[OAVIF_TQ_MAX_FANOUT]; /* ... and its page-locked frame buffer (EncCtx.pinned) */
-    struct { int q; uint8_t* b; size_t n; } kept[OAVIF_TQ_MAX_PASS * OAVIF_TQ_MAX_FANOUT]; /* every probe's bytes: any may be the answer */
+    Env env;
+    double t0;
+    Options o;
+    Image src;
+    uint8_t* rgb8; /* e.rgb: the scorer's reference */
+    void* scaled;
+    const char* depth_note;
+    Source source;
+    Slot slots[OAVIF_TQ_MAX_FANOUT]; /* the only owner of scorer contexts and page-locked frame buffers */
+    /* EncBuffer (main.zig:11-19) for every probe, not the last one only: any may be the answer.  Under g_lock. */
+    struct { uint32_t q; uint8_t* b; size_t n; } kept[OAVIF_TQ_MAX_PASS * OAVIF_TQ_MAX_FANOUT];
     int nkept;
-} Spec;
-typedef struct { Spec* s; uint32_t slot, q; double score; int rc; } SpecJob;
+    double encode_ms, decode_ms, score_ms; /* summed over the probes, under g_lock */
+    uint8_t* encoded; /* the bytes of -q, or of a chosen q that no probe encoded */
+} Run;
 
-static void* spec_job(void* arg) {
-    SpecJob* j = (SpecJob*)arg;
-    Spec* s = j->s;
-    j->rc = -1;
-    if (!s->have_ref[j->slot]) { /* a slot is used by one thread at a time */
-        if (ssimu2_ctx_set_blur(s->ctx[j->slot], s->blur) || ssimu2_set_reference(s->ctx[j->slot], s->rgb8, s->e->src->w, s->e->src->h)) {
-            fail("ScorerFailed", ssimu2_last_error(s->ctx[j->slot]));
-            return NULL;
-        }
-        s->have_ref[j->slot] = 1;
+static void phase(const Run* r, const char* what) { /* OAVIF_HOST_TIMES: where a one-image run spends its wall time */
+    if (r->env.times) fprintf(stderr, "  [%7.1f ms] %s\n", now_ms() - r->t0, what);
+}
+
+static int slot_create(Run* r, Slot* s) { /* ssimu2_prefetch started the runtime at process start; this waits for it */
+    if (s->ctx) return 0;
+    const int rc = ssimu2_ctx_create(r->env.device, NULL, &s->ctx);
+    if (rc != SSIMU2_OK)
+        return fail(rc == SSIMU2_ERR_NO_DEVICE && s == r->slots ? "NoDevice" : "ScorerFailed", ssimu2_last_error(NULL));
+    if (s == r->slots) phase(r, "scorer context created");
+    return 0;
+}
+static int slot_prepare(Run* r, Slot* s) { /* the context, blur and reference set, the page-locked buffer tried: each once */
+    if (slot_create(r, s)) return -1;
+    if (!s->ready) {
+        if (ssimu2_ctx_set_blur(s->ctx, r->env.blur) || ssimu2_set_reference(s->ctx, r->rgb8, r->src.w, r->src.h))
+            return fail("ScorerFailed", ssimu2_last_error(s->ctx));
+        s->ready = 1;
+        if (s == r->slots) phase(r, "reference uploaded and cached");
     }
-    if (!s->pinned[j->slot]) s->pinned[j->slot] = j->slot == 0 && s->e->pinned ? s->e->pinned : pinned_frame(s->ctx[j->slot], s->e->src);
+    if (!s->pinned_tried) {
+        void* p = NULL; /* room for RGBA rows */
+        s->pinned_tried = 1;
+        if (r->env.pinned && ssimu2_host_alloc(s->ctx, (size_t)r->src.w * r->src.h * 4, &p) == SSIMU2_OK) s->pinned = (uint8_t*)p;
+    }
+    return 0;
+}
+static void slot_release(Slot* s) {
+    if (!s->ctx) return;
+    ssimu2_host_free(s->ctx, s->pinned);
+    ssimu2_ctx_destroy(s->ctx);
+    memset(s, 0, sizeof *s);
+}
+
+static void run_free(Run* r) {
+    for (uint32_t i = 0; i < OAVIF_TQ_MAX_FANOUT; ++i) slot_release(&r->slots[i]);
+    for (int k = 0; k < r->nkept; ++k) free(r->kept[k].b);
+    if (r->source.image) av.ImageDestroy(r->source.image);
+    free(r->encoded);
+    if (r->scaled != r->src.data) free(r->scaled);
+    if (r->rgb8 != r->src.data) free(r->rgb8);
+    free(r->src.data);
+    free(r->src.icc);
+}
+
+/* The pass of both searches: probe q on a slot and keep its bytes.  A slot whose context exists is prepared before
+   the CPU half, so that the frame is decoded into its page-locked buffer.  Slot 0 of a sequential search has none at
+   its first probe: the scorer's start-up (0.1-0.25 s, begun by ssimu2_prefetch) runs behind that probe's CPU half --
+   its quantizer does not depend on any score (tq.zig:136) -- and the context is made when the score needs it. */
+static int run_probe(Run* r, uint32_t slot, uint32_t q, double* out_score) {
+    Slot* s = &r->slots[slot];
     uint8_t* avif = NULL;
     size_t n = 0;
     double t[3] = {0, 0, 0};
     Decoded d;
-    if (pass_cpu(s->e, j->q, &avif, &n, &d, t, s->pinned[j->slot])) return NULL;
-    if (pass_score(s->ctx[j->slot], &d, &j->score, t)) { free(avif); return NULL; }
+    if (s->ctx && slot_prepare(r, s)) return -1;
+    if (pass_cpu(&r->source, q, &avif, &n, &d, t, s->pinned)) return -1;
+    if (!s->ctx) phase(r, "first probe encoded and decoded");
+    if (slot_prepare(r, s) || pass_score(s->ctx, &d, out_score, t)) { decoded_free(&d); free(avif); return -1; }
     pthread_mutex_lock(&g_lock);
-    s->e->encode_ms += t[0]; s->e->decode_ms += t[1]; s->e->score_ms += t[2];
-    if (s->nkept < (int)(sizeof s->kept / sizeof s->kept[0])) {
-        s->kept[s->nkept].q = (int)j->q; s->kept[s->nkept].b = avif; s->kept[s->nkept].n = n;
-        ++s->nkept;
+    r->encode_ms += t[0]; r->decode_ms += t[1]; r->score_ms += t[2];
+    if (r->nkept < (int)(sizeof r->kept / sizeof r->kept[0])) {
+        r->kept[r->nkept].q = q; r->kept[r->nkept].b = avif; r->kept[r->nkept].n = n;
+        ++r->nkept;
         avif = NULL;
     }
     pthread_mutex_unlock(&g_lock);
     free(avif);
-    j->rc = 0;
+    return 0;
+}
+static int probe_one(void* user, uint32_t q, double* out_score) { return run_probe((Run*)user, 0, q, out_score); }
+
+/* ---- the probes of one search fanned over scorer contexts and host threads (SURVEY.md 8e row 2; BASELINE
+   configs[2]): oavif_tq_find_target_quality_speculative asks for waves of quantizers, each probe of a wave runs
+   the pass above on its own slot and thread.  OAVIF_PROBE_FANOUT=N, as the Python mirror; the result is the
+   sequential search's (include/oavif_tq.h). ------------------------------------------------------------------ */
+typedef struct { Run* r; uint32_t slot, q; double score; int rc; } Job;
+static void* job_run(void* arg) {
+    Job* j = (Job*)arg;
+    j->rc = run_probe(j->r, j->slot, j->q, &j->score);
     return NULL;
 }
-
-static int spec_batch(void* user, const uint32_t* qs, uint32_t n, double* out_scores) {
-    Spec* s = (Spec*)user;
-    SpecJob jobs[OAVIF_TQ_MAX_FANOUT];
+static int probe_wave(void* user, const uint32_t* qs, uint32_t n, double* out_scores) {
+    Run* r = (Run*)user;
+    Job jobs[OAVIF_TQ_MAX_FANOUT];
     pthread_t th[OAVIF_TQ_MAX_FANOUT];
     int started[OAVIF_TQ_MAX_FANOUT] = {0};
-    if (n > s->fan) return fail("SearchFailed", "wave larger than the fan-out");
+    if (n > (uint32_t)r->env.fanout) return fail("SearchFailed", "wave larger than the fan-out");
     for (uint32_t i = 0; i < n; ++i) {
-        jobs[i].s = s; jobs[i].slot = i; jobs[i].q = qs[i]; jobs[i].score = 0; jobs[i].rc = -1;
-        if (i + 1 == n) spec_job(&jobs[i]); /* the last probe of a wave runs on the calling thread */
-        else started[i] = pthread_create(&th[i], NULL, spec_job, &jobs[i]) == 0;
-        if (i + 1 < n && !started[i]) spec_job(&jobs[i]);
+        jobs[i].r = r; jobs[i].slot = i; jobs[i].q = qs[i]; jobs[i].score = 0; jobs[i].rc = -1;
+        if (i + 1 == n) job_run(&jobs[i]); /* the last probe of a wave runs on the calling thread */
+        else started[i] = pthread_create(&th[i], NULL, job_run, &jobs[i]) == 0;
+        if (i + 1 < n && !started[i]) job_run(&jobs[i]);
     }
     int rc = 0;
     for (uint32_t i = 0; i < n; ++i) {
@@ -671,67 +727,18 @@ static int spec_batch(void* user, const uint32_t* qs, uint32_t n, double* out_sc
     return rc;
 }
 
-static int write_file(const char* path, const uint8_t* b, size_t n) {
-    FILE* f = fopen(path, "wb");
-    if (!f || fwrite(b, 1, n, f) != n) { if (f) fclose(f); return fail("WriteFailed", path); }
-    fclose(f);
-    return 0;
-}
-
-typedef struct { /* everything run() allocates, released on every path */
-    Image src;
-    uint8_t* rgb8;
-    void* scaled;
-    EncCtx e;
-    uint8_t* once;
-    Spec spec;
-} Run;
-
-static void run_free(Run* r) {
-    for (uint32_t i = 1; i < OAVIF_TQ_MAX_FANOUT; ++i)
-        if (r->spec.ctx[i]) {
-            ssimu2_host_free(r->spec.ctx[i], r->spec.pinned[i]);
-            ssimu2_ctx_destroy(r->spec.ctx[i]);
-        }
-    for (int k = 0; k < r->spec.nkept; ++k) free(r->spec.kept[k].b);
-    if (r->e.scorer) {
-        ssimu2_host_free(r->e.scorer, r->e.pinned ? r->e.pinned : r->spec.pinned[0]);
-        ssimu2_ctx_destroy(r->e.scorer);
-    }
-    if (r->e.image) av.ImageDestroy(r->e.image);
-    free(r->e.buf);
-    free(r->once);
-    if (r->scaled != r->src.data) free(r->scaled);
-    if (r->rgb8 != r->src.data) free(r->rgb8);
-    free(r->src.data);
-    free(r->src.icc);
-}
-
-static double g_t0;
-static void phase(const char* what) { /* OAVIF_HOST_TIMES: where a one-image run spends its wall time */
-    if (getenv("OAVIF_HOST_TIMES")) fprintf(stderr, "  [%7.1f ms] %s\n", now_ms() - g_t0, what);
-}
-
-static int run_inner(Run* r, int argc, char** argv) {
-    Options o = OPTIONS_DEFAULT;
-    const char *in = NULL, *out = NULL;
-    if (parse_args(&o, argc, argv, &in, &out)) return -1;
-    if (!in || !out) return fail("MissingInputOrOutput", NULL);
-    const int device = getenv("LOCAL_RANK") ? atoi(getenv("LOCAL_RANK")) : 0;
-    if (o.quality < 0) ssimu2_prefetch(device); /* the HIP start-up runs behind the image load and the first encode */
-    phase("arguments parsed, scorer start-up begun in the background");
-    if (load_libavif()) return -1;
-    phase("libavif opened and checked");
+/* ---- the phases of a run (main.zig:73-116) ------------------------------------------------------------------ */
+static int load_source(Run* r, const char* in) { /* main.zig:73-91: the image and the scorer's RGB8 reference */
     Image* src = &r->src;
     if (load_image(in, src)) return -1;
-    phase("image loaded");
+    phase(r, "image loaded");
     struct stat st;
     memset(&st, 0, sizeof st);
     stat(in, &st);
     fprintf(stderr, "Read %ux%u, %s, %d-bit, %lld bytes\n", src->w, src->h, src->channels > 3 ? "RGBA" : "RGB",
             src->hbd ? 16 : 8, (long long)st.st_size);
-    const size_t px = (size_t)src->w * src->h, nsamp = px * src->channels;
     /* e.rgb: Image.toRGB8 (io.zig:57-133) unless the source already is RGB8 (main.zig:86) */
+    const size_t px = (size_t)src->w * src->h;
     r->rgb8 = src->data;
     if (src->channels != 3 || src->hbd) {
         r->rgb8 = (uint8_t*)malloc(px * 3);
@@ -741,129 +748,116 @@ static int run_inner(Run* r, int argc, char** argv) {
                 r->rgb8[i * 3 + c] = src->hbd ? (uint8_t)(((const uint16_t*)src->data)[i * src->channels + c] >> 8)
                                               : src->data[i * src->channels + c];
     }
-    /* io.zig:546; a libaom without high-bit-depth support (this image's) cannot write 10-bit: probed once */
-    uint32_t out_depth = (o.tenbit || src->hbd) ? 10 : 8;
-    const char* depth_note = NULL;
-    if (out_depth == 10) {
-        Options po = o;
-        po.speed = 10;
-        uint16_t tiny[16 * 16 * 3];
-        for (int i = 0; i < 16 * 16 * 3; ++i) tiny[i] = 512;
-        Image ti = {16, 16, 3, 0, (uint8_t*)tiny, NULL, 0};
-        EncCtx pe;
-        memset(&pe, 0, sizeof pe);
-        pe.o = &po; pe.src = &ti; pe.scaled = tiny; pe.out_depth = 10; pe.buf_q = -1;
-        uint8_t* pb = NULL;
-        size_t pn = 0;
-        const int refused = encode_to_buffer(&pe, 50, &pb, &pn);
-        if (pe.image) av.ImageDestroy(pe.image);
-        if (refused) {
-            out_depth = 8;
-            depth_note = "note: the reference would write 10-bit here (--tenbit 1 / 16-bit source, io.zig:546-548); this "
-                         "image's libaom has no high-bit-depth support, so the bitstream is 8-bit";
-        }
-        free(pb);
-        g_err = NULL;
-        g_detail[0] = 0;
-    }
-    /* io.zig:566-617, hoisted out of the pass loop */
-    r->scaled = src->data;
-    if (!src->hbd && out_depth == 10) {
-        r->scaled = malloc(nsamp * 2);
-        if (!r->scaled) return fail("OutOfMemory", NULL);
-        oavif_prescale_8_to_10(src->data, nsamp, (uint16_t*)r->scaled);
-    } else if (src->hbd && out_depth == 10) {
-        r->scaled = malloc(nsamp * 2);
-        if (!r->scaled) return fail("OutOfMemory", NULL);
-        oavif_prescale_16_to_10((const uint16_t*)src->data, nsamp, (uint16_t*)r->scaled);
-    } else if (src->hbd) {
-        r->scaled = malloc(nsamp);
-        if (!r->scaled) return fail("OutOfMemory", NULL);
-        oavif_prescale_16_to_8((const uint16_t*)src->data, nsamp, (uint8_t*)r->scaled);
-    }
-    EncCtx* e = &r->e;
-    e->o = &o; e->src = src; e->scaled = r->scaled; e->out_depth = out_depth; e->buf_q = -1;
-    if (o.quality >= 0) { /* main.zig:93-100 */
-        fprintf(stderr, "Encoding [q%d, speed %d, %u-bit]\n", o.quality, o.speed, out_depth);
-        size_t n = 0;
-        if (encode_to_buffer(e, (uint32_t)o.quality, &r->once, &n) || write_file(out, r->once, n)) return -1;
-        fprintf(stderr, "Compressed to %zu bytes (%.3f bpp)\n", n, n * 8.0 / (double)px);
-        if (depth_note) fprintf(stderr, "%s\n", depth_note);
-        return 0;
-    }
-    if (o.score_tgt == floor(o.score_tgt)) /* Zig's {} on an f64 prints 80 for 80.0 */
-        fprintf(stderr, "Searching [tgt %.0f±%.1f, speed %d, %u-bit]\n", o.score_tgt, o.tolerance, o.speed, out_depth);
-    else
-        fprintf(stderr, "Searching [tgt %g±%.1f, speed %d, %u-bit]\n", o.score_tgt, o.tolerance, o.speed, out_depth);
-    /* the blur of the search path: the published recursion unless OAVIF_SSIMU2_BLUR says otherwise (as the
-       Zig shim's `blur` and the Python mirror: INTEGRATION.md section 2e) */
-    const char* bm = getenv("OAVIF_SSIMU2_BLUR");
-    int mode = SSIMU2_BLUR_RECURSIVE;
-    if (bm && !strcmp(bm, "fir")) mode = SSIMU2_BLUR_FIR;
-    else if (bm && (!strcmp(bm, "recursive_fma") || !strcmp(bm, "iir_fma"))) mode = SSIMU2_BLUR_RECURSIVE_FMA;
-    e->device = device; e->blur = mode; e->rgb8 = r->rgb8;
-    int rc;
-    if (make_source_image(e)) return -1;
-    phase("source converted to YUV444");
-    /* The scorer context is NOT created here: the HIP runtime started initialising in the background at process
-       start (ssimu2_prefetch) and takes 0.1-0.25 s; the CPU half of the first pass -- its quantizer does not
-       depend on any score (tq.zig:136) -- runs meanwhile, and the first score waits for whatever is left. */
-    oavif_tq_options to = {o.score_tgt, o.tolerance, (uint32_t)o.max_pass};
-    oavif_tq_result res;
-    int spec_used = 0;
-    oavif_tq_spec_stats spec_stats = {0, 0, 0};
-    const int fan = getenv("OAVIF_PROBE_FANOUT") ? atoi(getenv("OAVIF_PROBE_FANOUT")) : 1;
-    if (fan > 1) { /* not a CLI flag: the option surface stays the reference's (parse_args.zig:76-122) */
-        Spec* sp = &r->spec; /* the source image exists before the first wave: the threads only read it */
-        sp->e = e; sp->rgb8 = r->rgb8; sp->blur = mode;
-        sp->fan = fan > OAVIF_TQ_MAX_FANOUT ? OAVIF_TQ_MAX_FANOUT : (uint32_t)fan;
-        if (ensure_scorer(e)) return -1; /* the fan-out needs its contexts up front */
-        sp->ctx[0] = e->scorer;
-        sp->have_ref[0] = 1;
-        for (uint32_t i = 1; i < sp->fan; ++i) /* contexts are made here, on one thread; each is one HIP stream + scratch */
-            if (ssimu2_ctx_create(device, NULL, &sp->ctx[i]) != SSIMU2_OK) return fail("ScorerFailed", ssimu2_last_error(NULL));
-        oavif_tq_spec_options so = OAVIF_TQ_SPEC_OPTIONS_INIT(sp->fan, 1);
-        oavif_tq_spec_stats sst;
-        rc = oavif_tq_find_target_quality_speculative(&to, &so, spec_batch, sp, &res, &sst);
-        if (rc) return g_err ? -1 : fail("SearchFailed", NULL);
-        for (int k = 0; k < sp->nkept; ++k)
-            if (sp->kept[k].q == (int)res.q && !e->buf) { /* EncBuffer: here the bytes of the chosen q, if it was probed */
-                e->buf = sp->kept[k].b; e->buf_size = sp->kept[k].n; e->buf_q = sp->kept[k].q;
-                sp->kept[k].b = NULL;
-            }
-        spec_used = 1; spec_stats = sst;
-    } else {
-        rc = oavif_tq_find_target_quality(&to, probe, e, &res);
-        if (rc) return g_err ? -1 : fail("SearchFailed", NULL);
-    }
-    phase("search done");
-    fprintf(stderr, "Found q%u (score %.2f, %u passes)\n", res.q, res.score, res.num_pass);
-    if (e->buf_q == (int)res.q) { /* main.zig:109-113 */
-        if (write_file(out, e->buf, e->buf_size)) return -1;
-    } else {
-        free(e->buf);
-        e->buf = NULL;
-        if (encode_to_buffer(e, res.q, &e->buf, &e->buf_size) || write_file(out, e->buf, e->buf_size)) return -1;
-    }
-    fprintf(stderr, "Compressed to %zu bytes (%.3f bpp)\n", e->buf_size, e->buf_size * 8.0 / (double)px);
-    if (depth_note) fprintf(stderr, "%s\n", depth_note);
-    if (getenv("OAVIF_HOST_TIMES") && spec_used)
-        fprintf(stderr, "speculative: %u waves, %u probes issued, %u cache hits\n", spec_stats.waves,
-                spec_stats.probes_issued, spec_stats.cache_hits);
-    if (getenv("OAVIF_HOST_TIMES")) /* not one of the reference's lines: only on request */
-        fprintf(stderr, "times: encode %.1f ms, decode %.1f ms, upload+score %.2f ms over %u passes\n", e->encode_ms,
-                e->decode_ms, e->score_ms, res.num_pass);
     return 0;
+}
+
+/* The encoder's depth (io.zig:546) and the source rescaled to it (io.zig:566-617), hoisted out of the pass loop
+   (SURVEY.md 8f rank 4); r->source describes the result, its avifImage still to be made. */
+static int scale_source(Run* r) {
+    const Image* src = &r->src;
+    const size_t nsamp = (size_t)src->w * src->h * src->channels;
+    uint32_t out_depth = (r->o.tenbit || src->hbd) ? 10 : 8;
+    if (out_depth == 10 && !supports_10bit(&r->o)) {
+        out_depth = 8;
+        r->depth_note = "note: the reference would write 10-bit here (--tenbit 1 / 16-bit source, io.zig:546-548); this "
+                        "image's libaom has no high-bit-depth support, so the bitstream is 8-bit";
+    }
+    r->scaled = src->data;
+    if (src->hbd || out_depth == 10) {
+        r->scaled = malloc(nsamp * (out_depth == 10 ? 2 : 1));
+        if (!r->scaled) return fail("OutOfMemory", NULL);
+        if (!src->hbd) oavif_prescale_8_to_10(src->data, nsamp, (uint16_t*)r->scaled);
+        else if (out_depth == 10) oavif_prescale_16_to_10((const uint16_t*)src->data, nsamp, (uint16_t*)r->scaled);
+        else oavif_prescale_16_to_8((const uint16_t*)src->data, nsamp, (uint8_t*)r->scaled);
+    }
+    r->source = (Source){&r->o, src, r->scaled, out_depth, NULL};
+    return 0;
+}
+
+static int write_file(const char* path, const uint8_t* b, size_t n) {
+    FILE* f = fopen(path, "wb");
+    if (!f || fwrite(b, 1, n, f) != n) { if (f) fclose(f); return fail("WriteFailed", path); }
+    fclose(f);
+    return 0;
+}
+static int write_output(const Run* r, const char* out, const uint8_t* b, size_t n) {
+    if (write_file(out, b, n)) return -1;
+    fprintf(stderr, "Compressed to %zu bytes (%.3f bpp)\n", n, n * 8.0 / ((double)r->src.w * r->src.h));
+    if (r->depth_note) fprintf(stderr, "%s\n", r->depth_note);
+    return 0;
+}
+
+static int encode_once(Run* r, const char* out) { /* -q, main.zig:93-100 */
+    size_t n = 0;
+    fprintf(stderr, "Encoding [q%d, speed %d, %u-bit]\n", r->o.quality, r->o.speed, r->source.out_depth);
+    if (make_source_image(&r->source) || encode_to_buffer(&r->source, (uint32_t)r->o.quality, &r->encoded, &n)) return -1;
+    return write_output(r, out, r->encoded, n);
+}
+
+static int search(Run* r, const char* out) { /* main.zig:102-116 */
+    const Options* o = &r->o;
+    if (o->score_tgt == floor(o->score_tgt)) /* Zig's {} on an f64 prints 80 for 80.0 */
+        fprintf(stderr, "Searching [tgt %.0f±%.1f, speed %d, %u-bit]\n", o->score_tgt, o->tolerance, o->speed, r->source.out_depth);
+    else
+        fprintf(stderr, "Searching [tgt %g±%.1f, speed %d, %u-bit]\n", o->score_tgt, o->tolerance, o->speed, r->source.out_depth);
+    if (make_source_image(&r->source)) return -1; /* before the first wave: the threads only read it */
+    phase(r, "source converted to YUV444");
+    const oavif_tq_options to = {o->score_tgt, o->tolerance, (uint32_t)o->max_pass};
+    oavif_tq_result res;
+    oavif_tq_spec_stats stats = {0, 0, 0};
+    const int fanned = r->env.fanout > 1;
+    int rc;
+    if (fanned) { /* its contexts up front, made here on one thread; the reference goes to slot i when a wave first uses it */
+        if (slot_prepare(r, &r->slots[0])) return -1;
+        for (int i = 1; i < r->env.fanout; ++i)
+            if (slot_create(r, &r->slots[i])) return -1;
+        const oavif_tq_spec_options so = OAVIF_TQ_SPEC_OPTIONS_INIT((uint32_t)r->env.fanout, 1);
+        rc = oavif_tq_find_target_quality_speculative(&to, &so, probe_wave, r, &res, &stats);
+    } else {
+        rc = oavif_tq_find_target_quality(&to, probe_one, r, &res);
+    }
+    if (rc) return g_err ? -1 : fail("SearchFailed", NULL);
+    phase(r, "search done");
+    fprintf(stderr, "Found q%u (score %.2f, %u passes)\n", res.q, res.score, res.num_pass);
+    int k = 0; /* main.zig:109-113: the bytes of the chosen q if a probe encoded it, else one more encode */
+    while (k < r->nkept && r->kept[k].q != res.q) ++k;
+    if (k < r->nkept) {
+        if (write_output(r, out, r->kept[k].b, r->kept[k].n)) return -1;
+    } else {
+        size_t n = 0;
+        if (encode_to_buffer(&r->source, res.q, &r->encoded, &n) || write_output(r, out, r->encoded, n)) return -1;
+    }
+    if (r->env.times && fanned)
+        fprintf(stderr, "speculative: %u waves, %u probes issued, %u cache hits\n", stats.waves, stats.probes_issued,
+                stats.cache_hits);
+    if (r->env.times) /* not one of the reference's lines: only on request */
+        fprintf(stderr, "times: encode %.1f ms, decode %.1f ms, upload+score %.2f ms over %u passes\n", r->encode_ms,
+                r->decode_ms, r->score_ms, res.num_pass);
+    return 0;
+}
+
+static int run_inner(Run* r, int argc, char** argv) {
+    const char *in = NULL, *out = NULL;
+    r->o = (Options)OPTIONS_DEFAULT;
+    if (parse_args(&r->o, argc, argv, &in, &out)) return -1;
+    if (!in || !out) return fail("MissingInputOrOutput", NULL);
+    if (r->o.quality < 0) ssimu2_prefetch(r->env.device); /* the HIP start-up runs behind the image load and the first encode */
+    phase(r, "arguments parsed, scorer start-up begun in the background");
+    if (load_libavif(r->env.libavif)) return -1;
+    phase(r, "libavif opened and checked");
+    if (load_source(r, in) || scale_source(r)) return -1;
+    return r->o.quality >= 0 ? encode_once(r, out) : search(r, out);
 }
 
 static int run(int argc, char** argv) {
     Run r;
     memset(&r, 0, sizeof r);
-    g_t0 = now_ms();
+    r.t0 = now_ms();
+    env_read(&r.env);
     const int rc = run_inner(&r, argc, argv);
-    phase("output written");
+    phase(&r, "output written");
     run_free(&r);
-    phase("contexts and buffers released");
+    phase(&r, "contexts and buffers released");
     return rc;
 }
 
@@ -897,7 +891,9 @@ static void print_usage(void) {
 /* io.printVersion (io.zig:14-39) for what this host links: itself, the scorer library, libavif and its codecs */
 static void print_version(void) {
     fprintf(stderr, "oavif %s\nscorer %s\n", VERSION, ssimu2_version());
-    if (load_libavif() == 0) fprintf(stderr, "libavif %s\n", av.Version());
+    Env env;
+    env_read(&env);
+    if (load_libavif(env.libavif) == 0) fprintf(stderr, "libavif %s\n", av.Version());
 }
 
 int main(int argc, char** argv) {

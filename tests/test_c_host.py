@@ -252,15 +252,18 @@ def test_host_is_clean_under_sanitizers(tmp_path, hip_lib):
         assert r.returncode == want, (args, r.stderr[-800:])
 
 
-@pytest.mark.parametrize("san", ["address,undefined", "thread"])
-def test_search_path_of_the_host_under_sanitizers_with_a_stub_scorer(tmp_path, san):
-    """The host's whole search path on the CPU: oavif_host.c + the real search code (tq.cpp) + the real PNG ingest
-    + the real libavif, with tests/c/stub_scorer.c standing in for the GPU scorer (test infrastructure: a monotone
-    stand-in score).  ASan + UBSan + LSan, and TSan for the pthread fan-out of the speculative search
-    (OAVIF_PROBE_FANOUT): no report, and the fanned search prints and writes what the sequential one does."""
+_STUB_HOSTS = {}
+
+
+def _stub_host(san, tmp_path_factory):
+    """oavif_host.c + tq.cpp + png_ingest.cpp + tests/c/stub_scorer.c as one stand-alone program built with
+    -fsanitize=<san>, once per module."""
     import shutil
+    if san in _STUB_HOSTS:
+        return _STUB_HOSTS[san]
     if shutil.which("gcc") is None or shutil.which("g++") is None:
         pytest.skip("gcc / g++ missing")
+    tmp = tmp_path_factory.mktemp("stub_host")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     csrc = os.path.join(root, "oavif_amd", "csrc")
     inc = os.path.join(root, "include")
@@ -270,12 +273,23 @@ def test_search_path_of_the_host_under_sanitizers_with_a_stub_scorer(tmp_path, s
                          ("png_ingest.cpp", "g++", "-std=c++17"),
                          (os.path.join(root, "tests", "c", "stub_scorer.c"), "gcc", "-std=gnu11")):
         path = src if os.path.isabs(src) else os.path.join(csrc, src)
-        obj = str(tmp_path / (os.path.basename(src) + ".o"))
+        obj = str(tmp / (os.path.basename(src) + ".o"))
         subprocess.run([cc, std, *flags, "-c", path, "-o", obj], check=True, capture_output=True)
         objs.append(obj)
-    exe = str(tmp_path / "host_stub")
+    exe = str(tmp / "host_stub")
     subprocess.run(["g++", f"-fsanitize={san}", *objs, "-o", exe, "-ldl", "-lm", "-lz", "-lpthread"], check=True,
                    capture_output=True)
+    _STUB_HOSTS[san] = exe
+    return exe
+
+
+@pytest.mark.parametrize("san", ["address,undefined", "thread"])
+def test_search_path_of_the_host_under_sanitizers_with_a_stub_scorer(tmp_path, tmp_path_factory, san):
+    """The host's whole search path on the CPU: oavif_host.c + the real search code (tq.cpp) + the real PNG ingest
+    + the real libavif, with tests/c/stub_scorer.c standing in for the GPU scorer (test infrastructure: a monotone
+    stand-in score).  ASan + UBSan + LSan, and TSan for the pthread fan-out of the speculative search
+    (OAVIF_PROBE_FANOUT): no report, and the fanned search prints and writes what the sequential one does."""
+    exe = _stub_host(san, tmp_path_factory)
     _ref, png, p = _inputs(tmp_path, 160, 120, seed=5)
     env = dict(ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1", TSAN_OPTIONS="halt_on_error=1",
                OAVIF_HOST_ATEXIT="1", OAVIF_HOST_TIMES="1")
@@ -296,3 +310,98 @@ def test_search_path_of_the_host_under_sanitizers_with_a_stub_scorer(tmp_path, s
                 assert any(l.startswith("speculative: ") for l in lines)
         assert outs[(src, "1")] == outs[(src, "4")] == outs[(src, "16")]
         assert int(re.search(r"(\d+) passes", outs[(src, "1")][0]).group(1)) >= 2      # a real multi-pass search
+
+
+_SAN_ENV = dict(ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1", TSAN_OPTIONS="halt_on_error=1",
+                OAVIF_HOST_ATEXIT="1")         # leave through exit(): LeakSanitizer reports there
+_STUB_SEARCH = ["--score-tgt", "91", "--tolerance", "1", "--max-pass", "8", "--tenbit", "0", "-s", "10"]
+_STUB_DEFAULTS = {}
+
+
+def _stub_search(exe, png, out, args=_STUB_SEARCH, **env):
+    """One search of the stub host on `png`: (return code, stderr, the Found / Compressed lines and the file)."""
+    if out.exists():
+        out.unlink()
+    r = subprocess.run([exe, *args, str(png), str(out)], capture_output=True, text=True, timeout=600,
+                       env=_env(**_SAN_ENV, **env))
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, (env, r.stderr[-3000:])
+    lines = r.stderr.splitlines()
+    result = ([l for l in lines if l.startswith("Found q")], [l for l in lines if l.startswith("Compressed to")],
+              out.read_bytes() if out.exists() else None)
+    return r.returncode, r.stderr, result
+
+
+def _stub_default(san, exe, png, tmp_path):
+    """The default run (sequential, page-locked frame buffer tried) of _STUB_SEARCH on the 160x120 input, once."""
+    if san not in _STUB_DEFAULTS:
+        rc, err, result = _stub_search(exe, png, tmp_path / "default.avif")
+        assert rc == 0 and len(result[0]) == 1 and len(result[1]) == 1 and result[2], err[-1500:]
+        _STUB_DEFAULTS[san] = result
+    return _STUB_DEFAULTS[san]
+
+
+@pytest.mark.parametrize("san", ["address,undefined", "thread"])
+def test_phase_timeline_keeps_its_order_and_no_pinned_buffer_changes_nothing(tmp_path, tmp_path_factory, san):
+    """(i) The timeline of a sequential search: the CPU half of the first probe runs BEFORE the scorer context is
+    created (that is what hides the scorer's start-up), and the reference is uploaded after that.  (ii) The
+    page-locked frame buffer is an optimisation only: switched off (OAVIF_HOST_PINNED=0), or with every
+    ssimu2_host_alloc failing, a sequential search and one fanned over 4 contexts print and write what the
+    default run does."""
+    exe = _stub_host(san, tmp_path_factory)
+    _ref, png, _p = _inputs(tmp_path, 160, 120, seed=5)
+    default = _stub_default(san, exe, png, tmp_path)
+    rc, err, result = _stub_search(exe, png, tmp_path / "t.avif", OAVIF_HOST_TIMES="1", OAVIF_PROBE_FANOUT="1")
+    assert rc == 0 and result == default, err[-1500:]
+    timeline = [l.split("] ", 1)[1] for l in err.splitlines() if l.startswith("  [")]
+    order = [timeline.index(what) for what in ("first probe encoded and decoded", "scorer context created",
+                                               "reference uploaded and cached")]
+    assert order == sorted(order) and len(set(order)) == 3, timeline
+    for switch in (dict(OAVIF_HOST_PINNED="0"), dict(STUB_FAIL_HOST_ALLOC="1")):
+        for fan in ("1", "4"):
+            rc, err, result = _stub_search(exe, png, tmp_path / "n.avif", OAVIF_PROBE_FANOUT=fan, **switch)
+            assert rc == 0 and result == default, (switch, fan, err[-1500:])
+
+
+@pytest.mark.parametrize("what", ["SCORE", "CTX_CREATE", "SET_REFERENCE"])
+@pytest.mark.parametrize("san", ["address,undefined", "thread"])
+def test_a_failing_scorer_call_ends_the_run_and_releases_everything(tmp_path, tmp_path_factory, san, what):
+    """The k-th score, context creation or reference upload fails (tests/c/stub_scorer.c), k = 1, 2, sequential and
+    fanned over 4 contexts: exit code 1 with error: ScorerFailed, no output file, and no sanitizer or leak report on
+    the way out (contexts, frame buffers, kept probe bytes and the decoded frame of the failing probe are all
+    released).  A sequential search makes ONE context and uploads ONE reference, so there a second call that could
+    fail does not exist: that run is the default run."""
+    exe = _stub_host(san, tmp_path_factory)
+    _ref, png, _p = _inputs(tmp_path, 160, 120, seed=5)
+    default = _stub_default(san, exe, png, tmp_path)
+    for fan in ("1", "4"):
+        for k in ("1", "2"):
+            rc, err, result = _stub_search(exe, png, tmp_path / "f.avif", OAVIF_PROBE_FANOUT=fan,
+                                           **{"STUB_FAIL_" + what: k})
+            if fan == "1" and k == "2" and what != "SCORE":
+                assert rc == 0 and result == default, (what, k, fan, err[-1500:])
+                continue
+            assert rc == 1 and "error: ScorerFailed" in err, (what, k, fan, err[-1500:])
+            assert result[2] is None and not result[1], (what, k, fan)
+
+
+@pytest.mark.parametrize("san", ["address,undefined", "thread"])
+def test_a_search_that_ends_on_an_earlier_probe_writes_that_probes_bytes(tmp_path, tmp_path_factory, san):
+    """Targets 79, 80 and 81 with --max-pass 3 on the 160x120 input: the search runs out of passes below the target
+    and chooses the SECOND of its three probes (with the stub scorer: 65 -> 86.10, 51 -> 81.76, 45 -> 78.57 for 80:
+    q51), so the file is not the last probe's.  Sequential, and fanned over 4 and 16 contexts: same lines, same
+    file -- which is also the file that encoding q directly writes."""
+    exe = _stub_host(san, tmp_path_factory)
+    _ref, png, _p = _inputs(tmp_path, 160, 120, seed=5)
+    for tgt in ("79", "80", "81"):
+        args = ["-t", tgt, "--tolerance", "1", "--max-pass", "3", "--tenbit", "0", "-s", "10"]
+        runs = {}
+        for fan in ("1", "4", "16"):
+            rc, err, runs[fan] = _stub_search(exe, png, tmp_path / f"k{fan}.avif", args=args, OAVIF_PROBE_FANOUT=fan)
+            assert rc == 0 and len(runs[fan][0]) == 1, (tgt, fan, err[-1500:])
+        assert runs["1"] == runs["4"] == runs["16"], tgt
+        m = re.fullmatch(r"Found q(\d+) \(score (-?\d+\.\d{2}), 3 passes\)", runs["1"][0][0])
+        assert m, runs["1"][0]
+        direct = tmp_path / "direct.avif"
+        r = subprocess.run([exe, "-q", m.group(1), "--tenbit", "0", "-s", "10", str(png), str(direct)],
+                           capture_output=True, text=True, timeout=600, env=_env(**_SAN_ENV))
+        assert r.returncode == 0 and direct.read_bytes() == runs["1"][2], (tgt, r.stderr[-1500:])
