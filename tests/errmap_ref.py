@@ -2,10 +2,14 @@
 oracle's public helpers.  The per-pixel terms are evaluated in fp32 in the kernels' operation order; a fused
 multiply-add of fp32 operands is correctly rounded (`_fma`), and the map's coefficients restate the host's fp64
 expression (`coefficients`).  `kernel_averages` are the 108 averages of those terms in fp64: what the kernels' sums
-of the same terms approach (the recursive modes exactly up to fp64 summation)."""
+of the same terms approach (the recursive modes exactly up to fp64 summation).  Given the
+segment rows of every scale, `kernel_averages`, `averages` and `reference_map` also return, from the same terms, the
+SSIM averages summed in k_march's own order (tests/fir_sums.py)."""
 from __future__ import annotations
 
 import numpy as np
+
+import fir_sums
 
 F32 = np.float32
 C2 = F32(0.0009)
@@ -80,13 +84,21 @@ def _put(avg, s, c, m):
         avg[s, 6 + c * 4 + k] = m[2 + k] if k % 2 == 0 else m[2 + k] ** 0.25
 
 
-def averages(tm):
-    """-> (6, 18) float64 averages [scale][stat] of the terms (0..5 ssim c*2+n, 6..17 edge c*4+k)."""
-    avg = np.zeros((6, 18))
+def _put_sums(kord, s, c, t, seg):
+    """the SSIM averages of one channel's terms t (6, h, w) summed in k_march's order at `seg` rows per segment."""
+    kord[s, c * 2], kord[s, c * 2 + 1] = fir_sums.means(t[0], t[1], seg)
+
+
+def averages(tm, seg_rows=None):
+    """-> (6, 18) float64 averages [scale][stat] of the terms (0..5 ssim c*2+n, 6..17 edge c*4+k).  With `seg_rows`
+    (rows per k_march segment, by scale): -> (those, (6, 6) averages 0..5 summed in the kernel's order)."""
+    avg, kord = np.zeros((6, 18)), np.zeros((6, 6))
     for s, t in enumerate(tm):
         for c in range(3):
             _put(avg, s, c, _means(t[c]))
-    return avg
+            if seg_rows is not None:
+                _put_sums(kord, s, c, t[c], seg_rows[s])
+    return avg if seg_rows is None else (avg, kord)
 
 
 def _means(t):
@@ -96,15 +108,19 @@ def _means(t):
     return [float(t[k].sum(dtype=np.longdouble) / n) for k in range(6)]
 
 
-def kernel_averages(orc, ref, dist, blur):
+def kernel_averages(orc, ref, dist, blur, seg_rows=None):
     """-> ((6, 18) float64, nscales): averages(terms(orc, ref, dist, blur)), one channel's terms at a time (a 4K pair's
-    terms would take about 1 GB at once)."""
-    avg, ns = np.zeros((6, 18)), 0
+    terms would take about 1 GB at once).  With `seg_rows` (by scale): -> (those, nscales, (6, 6) averages 0..5 in the
+    kernel's order), from the same pass over the terms."""
+    avg, kord, ns = np.zeros((6, 18)), np.zeros((6, 6)), 0
     for s, (x1, x2) in enumerate(_xyb_pairs(orc, ref, dist)):
         for c in range(3):
-            _put(avg, s, c, _means(channel_terms(orc, x1[c], x2[c], blur)))
+            t = channel_terms(orc, x1[c], x2[c], blur)
+            _put(avg, s, c, _means(t))
+            if seg_rows is not None:
+                _put_sums(kord, s, c, t, seg_rows[s])
         ns = s + 1
-    return avg, ns
+    return (avg, ns) if seg_rows is None else (avg, ns, kord)
 
 
 def weighted_terms(orc, avg, nscales):
@@ -164,11 +180,14 @@ def compose(tm, coef, w, h):
     return m
 
 
-def reference_map(orc, ref, dist, blur, avg=None):
+def reference_map(orc, ref, dist, blur, avg=None, seg_rows=None):
     """-> (map, averages of the reference's own terms, nscales).  `avg` (e.g. the device's) overrides the
-    averages the coefficients are derived from."""
+    averages the coefficients are derived from.  With `seg_rows` (by scale) a fourth value: the (6, 6) averages 0..5
+    of the same terms in the kernel's order."""
     h, w, _ = ref.shape
     tm = terms(orc, ref, dist, blur)
-    own = averages(tm)
+    own = averages(tm, seg_rows)
+    kord = () if seg_rows is None else (own[1],)
+    own = own if seg_rows is None else own[0]
     coef = coefficients(orc, own if avg is None else avg, len(tm))
-    return compose(tm, coef, w, h), own, len(tm)
+    return (compose(tm, coef, w, h), own, len(tm)) + kord

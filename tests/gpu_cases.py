@@ -1,6 +1,8 @@
 """Test-side helpers shared by the GPU modules: the blur-mode table (scorer mode -> the checker's mode of the same
-blur), synthetic content kinds, libavif-like padded RGB(A) layouts, the hold of a score's averages and of k_finalize
-to the kernel-order terms (check_against_terms), the error-map check against tests/errmap_ref.py (check_map), and
+blur), synthetic content kinds and the pairs that reach the clamps and the zero paths, libavif-like padded RGB(A)
+layouts, the hold of a score's averages and of k_finalize to the kernel-order terms (check_against_terms) and of the
+FIR d / d^4 averages to k_march's own summing order (check_fir_sums, tests/fir_sums.py), the error-map check against
+tests/errmap_ref.py (check_map), and
 what the batch modules share: the batch rule's rows and bound, seeded neighbours and the comparison of score and
 averages for bits."""
 from __future__ import annotations
@@ -11,6 +13,7 @@ from oavif_amd import _lib, synth
 from oracle import ssimu2_oracle as orc
 
 import errmap_ref
+import fir_sums
 
 # mode name -> (ssimu2_ctx_set_blur mode, the checker's OR_BLUR_* of the same blur)
 MODES = {"fir": (_lib.BLUR_FIR, orc.BLUR_FIR),
@@ -60,6 +63,50 @@ def content(kind, w, h, seed):
     return np.ascontiguousarray(img.astype(np.uint8))
 
 
+def extreme_pairs():
+    h, w = 70, 90
+    black = np.zeros((h, w, 3), np.uint8)
+    white = np.full((h, w, 3), 255, np.uint8)
+    noise = np.random.default_rng(0).integers(0, 256, (h, w, 3), dtype=np.uint8)
+    return [(black, white), (white, black), (noise, black), (black, noise), (noise, noise[::-1].copy())]
+
+
+def flat_pairs():
+    out = []
+    for v in (0, 255):
+        flat = np.full((96, 80, 3), v, np.uint8)
+        out += [(flat, flat), (flat, synth.distort(flat, "noise", 2, seed=v)),
+                (synth.distort(flat, "noise", 3, seed=v + 1), flat)]
+    return out
+
+
+def content_pairs(kind):
+    ref = content(kind, 250, 190, 5)
+    return [(ref, synth.distort(ref, dk, ds, seed=3)) for dk, ds in [("blur", 0), ("band", 2), ("noise", 2)]]
+
+
+def one_sample_pairs():
+    """333 x 217 frames that differ in a single sample: one step, and black to white."""
+    ref = synth.make_ref(333, 217, seed=9)
+    out = []
+    for to in (int(ref[100, 200, 1]) ^ 1, 255 if ref[100, 200, 1] < 128 else 0):
+        dist = ref.copy()
+        dist[100, 200, 1] = to
+        out.append((ref, dist))
+    return out
+
+
+# content that reaches the clamps and the zero paths: most of the 108 averages exactly 0, L4 coefficients up to 3e27,
+# map densities from 1e-15 to 1e3, fourth powers close to the subnormal range
+HARD_GROUPS = ["extreme", "flat", "content-gradient", "content-primaries", "content-checker", "content-text",
+               "content-noise", "one-sample"]
+
+
+def group_pairs(group):
+    fixed = {"extreme": extreme_pairs, "flat": flat_pairs, "one-sample": one_sample_pairs}
+    return fixed[group]() if group in fixed else content_pairs(group[len("content-"):])
+
+
 def decoded_like(dist, channels, pad, seed):
     """`dist` laid out like libavif's avifRGBImage: `channels` bytes per pixel (alpha random),
     rows `pad` bytes longer than their pixels, padding filled with noise."""
@@ -94,6 +141,11 @@ def decoded_like(dist, channels, pad, seed):
 #   powers within 4 * 4 + 3 + 3 = 22 units (two squarings on each side), 22 / 4 = 5.5 units after an L4 norm's 4th
 #   root.  d and d^4 are the reference's bits.  Per average: (seg - 1 + 4) * 2^-24 for an L1 statistic,
 #   (seg - 1 + 22) / 4 * 2^-24 <= (seg + 3) * 2^-24 for an L4 one (seg >= 8); plus the fp64 part, n * 2^-53.
+#   That bound lets pass whatever moves a sum by less than a few 1e-6 of it -- a term lost at a strip or segment corner
+#   of a large frame, say.  The d and d^4 statistics (0..5) need no rounding bound: their terms are the reference's
+#   bits, so summing them in the kernel's own order (tests/fir_sums.py) leaves only the order of the fp64 part,
+#   (w_s * ceil(h_s / seg) + 4) * 2^-53 (derived there): check_fir_sums.  The edge statistics share the accumulator
+#   loop, the masks, the reduction and the partial index with them, and keep the bound above.
 FINALIZE_TOL = 1e-11
 RTOL_RECURSIVE = 1e-9
 MAX_TERMS = 3840 * 2160
@@ -117,12 +169,57 @@ def fir_rtol(w: int, h: int, scale: int) -> float:
     return (march_seg_rows(w, h, scale) + 3) * 2.0 ** -24 + sw * sh * 2.0 ** -53
 
 
-def check_against_terms(oracle, score, avg, ns, ref, dist, mode, what, kavg=None):
+def scale_size(w: int, h: int, scale: int):
+    for _ in range(scale):
+        w, h = (w + 1) // 2, (h + 1) // 2
+    return w, h
+
+
+def seg_rows(w: int, h: int, rule=march_seg_rows):
+    """Rows per k_march segment at each of the six scales of a w x h frame under `rule` (march_seg_rows, batch_seg_rows;
+    both take the frame's FULL size)."""
+    return [rule(w, h, s) for s in range(6)]
+
+
+def override_rows(rows_scale0: int, rows_other_scales: int):
+    """seg_rows under ssimu2_instr_set_segment_rows(rows_scale0, rows_other_scales), neither 0."""
+    return [rows_scale0] + [rows_other_scales] * 5
+
+
+def check_fir_sums(avg, ns, w, h, kord, rows, what):
+    """FIR averages 0..5 (the d and d^4 statistics, whose terms are the reference's bits) of every scale of a w x h
+    frame against `kord`, the same terms summed in k_march's own order at `rows` rows per segment (errmap_ref's
+    seg_rows results): within fir_sums.rtol, the order of an fp64 sum, and 0 exactly where the reference is 0.  The edge
+    statistics stay with check_against_terms.  -> the largest deviation in units of its bound."""
+    assert avg.shape == (6, 18) and kord.shape == (6, 6), what
+    worst = 0.0
+    for s in range(6):
+        got, exp = avg[s, :6], kord[s]
+        assert np.array_equal(got == 0, exp == 0), (what, s, got, exp)
+        if s >= ns:
+            continue
+        sw, sh = scale_size(w, h, s)
+        rtol = fir_sums.rtol(sw, sh, rows[s])
+        dev = np.abs(got - exp) / np.where(exp == 0, 1.0, exp)
+        worst = max(worst, float(dev.max()) / rtol)
+        assert (dev <= rtol).all(), (what, s, int(np.argmax(dev)), float(dev.max()), rtol)
+    print(f"measured: {what}: kernel-order sums {worst:.3e} of the bound")
+    return worst
+
+
+def rows_rtol(w: int, h: int, scale: int, rows: int) -> float:
+    """fir_rtol's formula for segments of `rows` rows set by hand (ssimu2_instr_set_segment_rows): a lane sums at
+    most min(rows, rows of the scale) terms."""
+    sw, sh = scale_size(w, h, scale)
+    return (min(rows, sh) + 3) * 2.0 ** -24 + sw * sh * 2.0 ** -53
+
+
+def check_against_terms(oracle, score, avg, ns, ref, dist, mode, what, kavg=None, rows=None):
     """A device score of (ref, dist) in scorer mode `mode` (a key of MODES), its averages `avg` over `ns` scales:
     k_finalize against oracle.score_from_averages(avg) to FINALIZE_TOL, and every average against
     errmap_ref.kernel_averages (or `kavg`, the same computed by the caller) to RTOL_RECURSIVE in the recursive modes,
-    fir_rtol in FIR, exactly 0 where the reference is 0.  -> the largest deviation of an average in units of its bound
-    (0 without a scale)."""
+    fir_rtol in FIR (rows_rtol where `rows`, an override's segment rows by scale, are given), exactly 0 where the
+    reference is 0.  -> the largest deviation of an average in units of its bound (0 without a scale)."""
     h, w, _ = ref.shape
     assert w * h <= MAX_TERMS, what
     if ns == 0:
@@ -140,7 +237,7 @@ def check_against_terms(oracle, score, avg, ns, ref, dist, mode, what, kavg=None
         assert np.array_equal(got == 0, exp == 0), (what, s, got, exp)
         if s >= ns:
             continue
-        rtol = RTOL_RECURSIVE if mode != "fir" else fir_rtol(w, h, s)
+        rtol = RTOL_RECURSIVE if mode != "fir" else fir_rtol(w, h, s) if rows is None else rows_rtol(w, h, s, rows[s])
         dev = np.abs(got - exp) / np.where(exp == 0, 1.0, exp)
         assert (dev <= rtol).all(), (what, s, int(np.argmax(dev)), float(dev.max()), rtol)
         worst = max(worst, float(dev.max()) / rtol)

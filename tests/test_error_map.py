@@ -128,6 +128,35 @@ def test_coefficients_restate_the_hosts_expression(oracle):
     assert coef[0, 0] == np.float32(wts[0]) and coef[0, 1] == np.float32(wts[3] / (0.25 * 0.25 * 0.25))
 
 
+def test_compose_stays_finite_where_coefficients_reach_the_clamp(oracle):
+    """Averages small enough that w / a^3 passes 3e38: 512 x 512 term planes, zero but for one pixel per plane that
+    holds the smallest subnormal (d^4, art^4, det^4) or 2^-30 (d, art, det).  An L4 average is then
+    (2^-149 / pixels)^(1/4) = 2.7e-13 at scale 0, and the statistics of weight above 5.9 there would get a coefficient
+    beyond the clamp.  No natural pair was found that gets there; the map of these terms is finite, and its one
+    non-zero scale-0 pixel is the clamped coefficients times the subnormal terms."""
+    w = h = 512
+    tm = []
+    for s in range(6):
+        t = np.zeros((3, 6, h >> s, w >> s), np.float32)
+        t[:, 1::2, 3, 5] = np.float32(2.0 ** -149)
+        t[:, 0::2, 3, 5] = np.float32(2.0 ** -30)
+        tm.append(t)
+    avg = errmap_ref.averages(tm)
+    coef = errmap_ref.coefficients(oracle, avg, 6)
+    clamped = np.argwhere(coef == np.float32(3.0e38))
+    assert len(clamped) >= 2 and (clamped[:, 0] == 0).all() and (clamped[:, 1] % 2 == 1).all(), clamped
+    walk, _ = errmap_ref.weighted_terms(oracle, avg, 6)
+    for wt, s, st in walk:
+        unclamped = wt / avg[s, st] ** 3 if st % 2 == 1 else wt
+        assert (unclamped > 3.0e38) == (coef[s, st] == np.float32(3.0e38)), (s, st, unclamped)
+    assert np.isfinite(coef).all() and coef.max() == np.float32(3.0e38)
+    m = errmap_ref.compose(tm, coef, w, h)
+    assert m.dtype == np.float32 and np.isfinite(m).all() and (m >= 0).all()
+    exp = sum(float(coef[0, errmap_ref.stat_of(c, k)]) * float(tm[0][c, k, 3, 5]) for c in range(3) for k in range(6))
+    assert exp > 2 * 3.0e38 * 2.0 ** -149 and m[3, 5] == pytest.approx(exp, rel=1e-6)
+    assert np.count_nonzero(m) == sum(4 ** s for s in range(6))   # one pixel per scale, 2^s x 2^s map pixels each
+
+
 def test_header_declares_both_entry_points():
     text = open(os.path.join(ROOT, "include", "ssimu2_hip.h")).read()
     assert re.search(r"int ssimu2_error_map_rgb8\(ssimu2_ctx\* ctx, const uint8_t\* ref, const uint8_t\* dist, "

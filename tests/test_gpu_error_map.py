@@ -73,6 +73,23 @@ def test_map_matches_the_reference_at_1080p(mode, oracle):
     _check_against_reference(oracle, s, blur, ref, dist, f"{name} 1920x1080")
 
 
+@pytest.mark.parametrize("group", gpu_cases.HARD_GROUPS)
+def test_map_matches_the_reference_on_extreme_content(mode, oracle, group):
+    """Black against white, flat against noise, saturated primaries, a 1-px checkerboard, thin text and frames that
+    differ in one sample: 60 to 90 of the 108 averages are exactly 0 (coefficient 0), L4 coefficients w / a^3 reach
+    3e27, densities span 1e-15 .. 1e3 within one map and fourth powers come close to the subnormal range.  Bit for bit
+    in the recursive modes, per pixel within MAP_K * 2^-24 in FIR and 0 exactly where the reference is 0; a second map
+    of the same pair has the first one's bits."""
+    name, s, blur = mode
+    for i, (ref, dist) in enumerate(gpu_cases.group_pairs(group)):
+        score, m = _check_against_reference(oracle, s, blur, ref, dist, f"{name} {group} {i}")
+        assert np.isfinite(m).all()
+        if np.array_equal(ref, dist):
+            assert score == 100.0 and not m.any()
+        score2, m2 = s.error_map(ref, dist)
+        assert score2 == score and np.array_equal(m2.view(np.uint32), m.view(np.uint32)), (name, group, i)
+
+
 def test_identical_frames_give_a_zero_map(mode):
     _name, s, _blur = mode
     ref = synth.make_ref(256, 160, seed=2)

@@ -27,7 +27,10 @@ from oavif_amd import _lib, synth
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from gpu_cases import (ATOL_AVG, MODES, RTOL_AVG, SIZES, TOL_FAR_BELOW_ZERO, check_against_terms,  # noqa: E402
-                       check_map, content, decoded_like, pseudo_codec, score_tol)
+                       check_fir_sums, check_map, content_pairs as _content_pairs, decoded_like,
+                       extreme_pairs as _extreme_pairs, flat_pairs as _flat_pairs, march_seg_rows, pseudo_codec,
+                       score_tol, seg_rows)
+import errmap_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -122,28 +125,6 @@ def test_every_entry_point_matches_the_checker(ctxs, oracle, mode, w, h):
 
 # ---- 2. extreme frames and content kinds in the recursive modes --------------------------------------------------
 
-def _extreme_pairs():
-    h, w = 70, 90
-    black = np.zeros((h, w, 3), np.uint8)
-    white = np.full((h, w, 3), 255, np.uint8)
-    noise = np.random.default_rng(0).integers(0, 256, (h, w, 3), dtype=np.uint8)
-    return [(black, white), (white, black), (noise, black), (black, noise), (noise, noise[::-1].copy())]
-
-
-def _flat_pairs():
-    out = []
-    for v in (0, 255):
-        flat = np.full((96, 80, 3), v, np.uint8)
-        out += [(flat, flat), (flat, synth.distort(flat, "noise", 2, seed=v)),
-                (synth.distort(flat, "noise", 3, seed=v + 1), flat)]
-    return out
-
-
-def _content_pairs(kind):
-    ref = content(kind, 250, 190, 5)
-    return [(ref, synth.distort(ref, dk, ds, seed=3)) for dk, ds in [("blur", 0), ("band", 2), ("noise", 2)]]
-
-
 GROUPS = ["extreme", "flat", "content-gradient", "content-primaries", "content-checker", "content-text",
           "content-noise"]
 
@@ -170,14 +151,23 @@ def test_extreme_frames_and_content_in_the_recursive_modes(ctxs, oracle, mode, g
 def test_a_4k_pair_against_the_kernel_order_terms(ctxs, oracle, mode):
     """One 3840 x 2160 pair in the search default and in FIR: the averages over 8.3 M terms per statistic within
     RTOL_RECURSIVE (the whole fp64 summation bound) or the FIR sums' bound at a 135-row segment, k_finalize to
-    FINALIZE_TOL."""
+    FINALIZE_TOL.  In FIR the d and d^4 averages are also held to the same terms summed in k_march's order
+    (gpu_cases.check_fir_sums: 32 strips x 16 segments)."""
     s = ctxs[mode]
     ref = synth.make_ref(3840, 2160, seed=21)
     dist = synth.distort(ref, "blockq", 2, seed=22)
     got = s.compute_ssimu2(ref, dist)
     avg, ns = s.last_averages()
     assert ns == 6
-    check_against_terms(oracle, got, avg, ns, ref, dist, mode, f"{mode} 3840x2160")
+    if mode != "fir":
+        check_against_terms(oracle, got, avg, ns, ref, dist, mode, f"{mode} 3840x2160")
+        return
+    assert march_seg_rows(3840, 2160, 0) == 135
+    rows = seg_rows(3840, 2160)
+    kavg, ns_r, kord = errmap_ref.kernel_averages(oracle, ref, dist, MODES[mode][1], seg_rows=rows)
+    assert ns_r == ns
+    check_against_terms(oracle, got, avg, ns, ref, dist, mode, f"{mode} 3840x2160", kavg=kavg)
+    check_fir_sums(avg, ns, 3840, 2160, kord, rows, f"{mode} 3840x2160")
 
 
 # ---- 3. frames shaped like production: RGBA rows against a cached reference --------------------------------------
