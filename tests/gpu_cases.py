@@ -4,7 +4,8 @@ layouts, the hold of a score's averages and of k_finalize to the kernel-order te
 FIR d / d^4 averages to k_march's own summing order (check_fir_sums, tests/fir_sums.py), the error-map check against
 tests/errmap_ref.py (check_map), and
 what the batch modules share: the batch rule's rows and bound, seeded neighbours and the comparison of score and
-averages for bits."""
+averages for bits; and what puts foreign content around a call: a stale pair score of a larger size (stale), the cached
+reference scored against itself (scrub) and device frames between margins of random bytes (in_margins)."""
 from __future__ import annotations
 
 import numpy as np
@@ -370,6 +371,45 @@ def check_rg(s, oracle, blur, scale, w, h, xa, xb, what):
     got = s.debug_download(5, scale, w, h)
     for k, exp in enumerate(rg_planes(oracle, blur, xa, xb)):
         same_bits(got[k], exp, what + (scale, k))
+
+
+# ---- foreign content around a call (tests/test_gpu_planes_grid.py, tests/test_gpu_hbd_planes.py,
+# tests/test_gpu_long_frames.py) ---------------------------------------------------------------------------------------
+MARGIN = 4096
+
+
+def stale_pair(w, h, k):
+    """Other content of a larger size than (w, h), and a noisy copy of it."""
+    big = content(KINDS[(k + 2) % 5], w + 41, h + 23, 1000 + k)
+    return big, synth.distort(big, "noise", 3, seed=k)
+
+
+def stale(s, w, h, k, pair=None):
+    """A pair score of other content at a larger size (`pair`: stale_pair(w, h, k), kept by the caller): the context's
+    buffers then hold its bytes beyond any (w, h) frame and other values inside it."""
+    big, noisy = pair or stale_pair(w, h, k)
+    s.compute_ssimu2(big, noisy)
+
+
+def scrub(s, ref, bits=None):
+    """Score the cached reference against itself, so that every buffer a later pass writes (the 8-bit frame the strided
+    hand-off unpacks into, the 16-bit scale-0 planes and pyramid) holds other content: a pass that skipped rows would
+    then score differently instead of finding the previous call's data in place."""
+    return s.score_against_reference(ref) if bits is None else s.score_against_reference_hbd(ref, bits)
+
+
+def in_margins(frame, off, seed):
+    """`frame` on the device inside a uint8 torch buffer: MARGIN random bytes, then `off` more, the frame, MARGIN random
+    bytes.  -> (buffer, device address of the frame's first byte)."""
+    import torch
+    flat = torch.from_numpy(np.ascontiguousarray(frame).reshape(-1))
+    g = torch.Generator().manual_seed(seed)
+    buf = torch.randint(0, 256, (2 * MARGIN + off + flat.numel(),), dtype=torch.uint8, generator=g)
+    buf[MARGIN + off:MARGIN + off + flat.numel()] = flat
+    buf = buf.cuda()
+    torch.cuda.synchronize()
+    assert buf.data_ptr() % 4 == 0
+    return buf, buf.data_ptr() + MARGIN + off
 
 
 def pseudo_codec(ref):

@@ -4,9 +4,9 @@ Every device test compares the kernels with the checker, and the kernels equal t
 mistake in the checker's statement of the operation (a constant, an edge rule, the scale loop, a formula) would pass
 everything else.  Here the checker is held to a restatement that shares no code with it: first the reference
 itself is pinned (its taps, its blur, identical frames, the scale count), then the checker stage by stage, then
-scores and averages on the fixtures, the kernels' size grid, content kinds and extreme frames, and finally the
-bounds are shown to be tight enough: every structural variant of a stage misses them, every last-bit variant meets
-them.  Bounds and measures: tests/fp64_checks.py, measured by tests/tools/cpu_fp64_campaign.py.
+scores and averages on the fixtures, the kernels' size grid, content kinds, extreme frames and one frame 65,600 px
+long, and finally the bounds are shown to be tight enough: every structural variant of a stage misses them, every
+last-bit variant meets them.  Bounds and measures: tests/fp64_checks.py, measured by tests/tools/cpu_fp64_campaign.py.
 """
 import os
 import sys
@@ -168,6 +168,9 @@ def _cases(golden):
     out.update({f"extreme-{k}": v for k, v in _extreme_pairs().items()})
     ref = synth.make_ref(1920, 1080, 3000)
     out["1080p"] = (ref, synth.distort(ref, "blockq", 1, seed=3))
+    w, h = 65_600, 9                               # W1 of tests/test_gpu_long_frames.py: the checker is the reference there
+    ref = synth.make_ref(w, h, 17 * w + h)
+    out[f"long-{w}x{h}"] = (ref, synth.distort(ref, "noise", 2, seed=w + 3 * h))
     return out
 
 
@@ -177,7 +180,7 @@ def _kind(name):
         else "natural"
 
 
-CASE_GROUPS = ["golden", "size", "content", "extreme", "1080p"]
+CASE_GROUPS = ["golden", "size", "content", "extreme", "1080p", "long"]
 
 
 @pytest.mark.parametrize("group", CASE_GROUPS)

@@ -14,7 +14,7 @@ import fp64_checks as fc
 import gpu_cases
 import hbd_ref
 import ssimu2_fp64 as R
-from gpu_cases import check_rg, same_bits
+from gpu_cases import check_rg, same_bits, scrub
 from oavif_amd import Ssimu2, Ssimu2Error, _lib, synth
 
 pytestmark = pytest.mark.gpu
@@ -77,13 +77,6 @@ def rows16(img, channels, pad, fill):
     view = np.lib.stride_tricks.as_strided(buf, (h, w, channels), (pitch * 2, channels * 2, 2))
     view[..., :3] = img
     return buf, view
-
-
-def scrub(s, ref, bits=None):
-    """Score the cached reference against itself, so that every buffer a later pass writes (the 8-bit frame the strided
-    hand-off unpacks into, the 16-bit scale-0 planes and pyramid) holds other content: a pass that skipped rows would
-    then score differently instead of finding the previous call's data in place."""
-    return s.score_against_reference(ref) if bits is None else s.score_against_reference_hbd(ref, bits)
 
 
 # ---- the ssimu2_debug_download hook at scale 0 --------------------------------------------------------------------

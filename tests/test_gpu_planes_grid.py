@@ -20,7 +20,7 @@ import pytest
 
 import errmap_ref
 import gpu_cases
-from gpu_cases import check_rg, same_bits
+from gpu_cases import check_rg, in_margins, same_bits, stale
 from oavif_amd import Ssimu2, synth
 
 pytestmark = pytest.mark.gpu
@@ -30,7 +30,6 @@ RECURSIVE = [m for m in gpu_cases.MODES if m != "fir"]
 GRID = [(w, h) for w, h in gpu_cases.SIZES if w >= 8 and h >= 8]
 KINDS = ["gradient", "primaries", "checker", "text", "noise"]
 DISTORTIONS = [("blockq", 2), ("noise", 2), ("blur", 1), ("band", 2)]
-MARGIN = 4096
 
 
 @pytest.fixture(scope="module")
@@ -48,27 +47,6 @@ def ictx(ictxs):
     yield ictxs
     for m in RECURSIVE:
         ictxs[m].rg_stop_after_scale(-1)
-
-
-def stale(s, w, h, k):
-    """A pair score of other content at a larger size: the context's buffers then hold its bytes beyond any
-    (w, h) frame and other values inside it."""
-    big = gpu_cases.content(KINDS[(k + 2) % 5], w + 41, h + 23, 1000 + k)
-    s.compute_ssimu2(big, synth.distort(big, "noise", 3, seed=k))
-
-
-def in_margins(frame, off, seed):
-    """`frame` on the device inside a uint8 torch buffer: MARGIN random bytes, then `off` more, the frame, MARGIN random
-    bytes.  -> (buffer, device address of the frame's first byte)."""
-    import torch
-    flat = torch.from_numpy(np.ascontiguousarray(frame).reshape(-1))
-    g = torch.Generator().manual_seed(seed)
-    buf = torch.randint(0, 256, (2 * MARGIN + off + flat.numel(),), dtype=torch.uint8, generator=g)
-    buf[MARGIN + off:MARGIN + off + flat.numel()] = flat
-    buf = buf.cuda()
-    torch.cuda.synchronize()
-    assert buf.data_ptr() % 4 == 0
-    return buf, buf.data_ptr() + MARGIN + off
 
 
 def frames(k):
