@@ -12,6 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OAVIF_AMD_LIB") or os.path.join(_HERE, "lib", "liboavif_hip.so")
 # the same scorer sources plus the hooks of include/ssimu2_hip_internal.h: bench / scripts / a few tests
 INSTR_LIB_PATH = os.environ.get("OAVIF_AMD_INSTR_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_instr.so")
+# the product library's sources plus the RGBA entry points of include/ssimu2_hip_ext.h (Ssimu2(..., extended=True))
+EXT_LIB_PATH = os.environ.get("OAVIF_AMD_EXT_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_ext.so")
 
 OK = 0
 ERR_INVALID_ARG = -1
@@ -25,6 +27,7 @@ STAGE_PYRAMID, STAGE_MARCH, STAGE_FINALIZE = 0, 1, 2
 NUM_SCALES = 6
 STATS_PER_SCALE = 18
 TQ_MAX_PASS = 12
+ALPHA_CODES = 65026   # SSIMU2_ALPHA_CODES (include/ssimu2_hip_ext.h): composite codes 0 .. 255 * 255
 MAX_BATCH = 4096   # SSIMU2_MAX_BATCH (include/ssimu2_hip.h): items of one ssimu2_score_batch_* call
 
 BLUR_FIR, BLUR_RECURSIVE, BLUR_RECURSIVE_FMA = 0, 1, 2   # SSIMU2_BLUR_* (include/ssimu2_hip.h)
@@ -168,11 +171,21 @@ HOOK_FUNCTIONS = {     # include/ssimu2_hip_internal.h: only liboavif_hip_instr.
     "ssimu2_instr_rg_stop_after_scale": (_ci, [_vp, _ci]),
 }
 
+EXT_FUNCTIONS = {      # include/ssimu2_hip_ext.h: only liboavif_hip_ext.so has these
+    "ssimu2_alpha_table": (_ci, [_f32p]),
+    "ssimu2_composite_rgba8": (_ci, [_vp, _u8p, _u32, _u32, _u32, _u32, _u16p]),
+    "ssimu2_score_rgba8": (_ci, [_vp, _u8p, _u32, _u8p, _u32, _u32, _u32, _u32, _f64p]),
+    "ssimu2_set_reference_rgba8": (_ci, [_vp, _u8p, _u32, _u32, _u32, _u32]),
+    "ssimu2_score_against_reference_rgba8": (_ci, [_vp, _u8p, _u32, _f64p]),
+}
+
 EXPORTED_SYMBOLS = tuple(PUBLIC_FUNCTIONS)
 INSTR_SYMBOLS = tuple(HOOK_FUNCTIONS)
+EXT_SYMBOLS = tuple(EXT_FUNCTIONS)
 
 _lib = None
 _instr = None
+_ext = None
 
 
 def lib() -> ctypes.CDLL:
@@ -191,6 +204,14 @@ def instr_lib() -> ctypes.CDLL:
     return _instr
 
 
+def ext_lib() -> ctypes.CDLL:
+    """The extension build (include/ssimu2_hip_ext.h): every public function plus the RGBA entry points."""
+    global _ext
+    if _ext is None:
+        _ext = _load(EXT_LIB_PATH)
+    return _ext
+
+
 def _load(path: str) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise ImportError(
@@ -206,7 +227,7 @@ def _load(path: str) -> ctypes.CDLL:
         except Exception:
             pass
     L = ctypes.CDLL(path)
-    for table in (PUBLIC_FUNCTIONS, HOOK_FUNCTIONS):
+    for table in (PUBLIC_FUNCTIONS, HOOK_FUNCTIONS, EXT_FUNCTIONS):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name, None)   # a build older than a symbol lacks it (scripts/gpu_ab.py loads such builds)
             if fn is not None:

@@ -1,0 +1,128 @@
+"""Alpha-aware SSIMULACRA2: RGBA frames composited over an opaque background on the device and then scored
+(include/ssimu2_hip_ext.h).
+
+    python -m oavif_amd.alpha REF.png DIST.png [--background RRGGBB]... [--blur fir|recursive|recursive_fma]
+
+prints one score per background and their minimum.  One background hides exactly the halos of its own colour, so the
+default is two, a dark and a light grey.  `search_rgba` is the target-quality search of an RGBA source whose passes are
+scored that way: colour hidden under transparent pixels does not move the score, damage to the alpha plane does.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+
+import numpy as np
+
+from . import _lib
+from .scorer import Ssimu2, background_rgb
+
+DEFAULT_BACKGROUNDS = (0x1A1A1A, 0xE6E6E6)
+BLUR_MODES = {"fir": _lib.BLUR_FIR, "recursive": _lib.BLUR_RECURSIVE, "recursive_fma": _lib.BLUR_RECURSIVE_FMA}
+
+
+def parse_background(text: str) -> int:
+    """'RRGGBB' (six hex digits) -> 0xRRGGBB."""
+    if len(text) != 6 or any(ch not in "0123456789abcdefABCDEF" for ch in text):
+        raise argparse.ArgumentTypeError(f"background must be six hex digits RRGGBB, got {text!r}")
+    return int(text, 16)
+
+
+def parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(prog="python -m oavif_amd.alpha",
+                                 description="SSIMULACRA2 of two PNGs with transparency, composited over each background")
+    ap.add_argument("ref")
+    ap.add_argument("dist")
+    ap.add_argument("--background", action="append", type=parse_background, metavar="RRGGBB",
+                    help="opaque background colour; may be given several times (default: 1A1A1A and E6E6E6)")
+    ap.add_argument("--blur", choices=sorted(BLUR_MODES), default="fir")
+    ap.add_argument("--device", type=int, default=0)
+    return ap
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    a = parser().parse_args(argv)
+    if not a.background:
+        a.background = list(DEFAULT_BACKGROUNDS)
+    return a
+
+
+def as_rgba(pixels: np.ndarray) -> np.ndarray:
+    """(h, w, 3|4) uint8 -> (h, w, 4) uint8; an RGB source counts as opaque."""
+    a = np.asarray(pixels)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (3, 4):
+        raise ValueError(f"need an 8-bit RGB or RGBA image, got {a.dtype} {a.shape}")
+    if a.shape[2] == 4:
+        return np.ascontiguousarray(a)
+    return np.concatenate([a, np.full(a.shape[:2] + (1,), 255, np.uint8)], axis=2)
+
+
+def load_rgba(path: str) -> np.ndarray:
+    from . import png
+    with open(path, "rb") as f:
+        pixels, _channels, hbd, _icc = png.load_png(f.read())
+    if hbd:
+        raise ValueError(f"{path}: 16-bit PNG; the RGBA scorer takes 8-bit samples")
+    return as_rgba(pixels)
+
+
+def score_over(scorer: Ssimu2, ref: np.ndarray, dist: np.ndarray, backgrounds) -> list:
+    """[(0xRRGGBB, score)] of the RGBA pair over each background."""
+    return [(bg, scorer.compute_ssimu2_rgba(ref, dist, bg)) for bg in (background_rgb(b) for b in backgrounds)]
+
+
+def search_rgba(source_rgba, options, background, scorer: Ssimu2 | None = None, score_tgt: float | None = None,
+                tolerance: float | None = None, max_pass: int | None = None):
+    """The target-quality search (oavif_tq_find_target_quality) of an (h, w, 4) uint8 source with straight alpha,
+    every pass scored composited over `background`.  `options`: cli.AvifEncOptions (speed, tune, quality_alpha, ...);
+    score_tgt / tolerance / max_pass default to its fields.  Each pass encodes from one avif_bridge.EncoderSource
+    (four channels), decodes with decode_common and hands libavif's RGBA rows to score_against_reference_rgba as they
+    are.  `scorer`: an Ssimu2(..., extended=True); None = one on device 0 for the duration of the call.
+    -> tq.TQResult (last_avif_size: bytes of the last pass)."""
+    from . import avif_bridge as ab, tq
+    if np.asarray(source_rgba).ndim != 3 or np.asarray(source_rgba).shape[2] != 4:
+        raise ValueError("search_rgba needs an (h, w, 4) RGBA source")
+    src = as_rgba(source_rgba)
+    depth = ab.output_depth(options.tenbit, False)
+    own = scorer is None
+    s = Ssimu2(0, extended=True) if own else scorer
+    last = {"size": 0}
+    try:
+        s.set_reference_rgba(src, background)
+        with ab.EncoderSource(ab.prescale_source(src, depth), depth, options) as enc:
+            def probe(q: int) -> float:
+                data = enc.encode(options, int(q))
+                with ab.decode_common(data) as frame:
+                    if (frame.height, frame.width) != src.shape[:2]:
+                        raise ValueError(f"codec returned {frame.width}x{frame.height}, expected {src.shape[1]}x{src.shape[0]}")
+                    rows = frame.rows if frame.channels == 4 else as_rgba(frame.pixels())   # no alpha plane left: opaque
+                    score = s.score_against_reference_rgba(rows)
+                last["size"] = len(data)
+                return score
+
+            out = tq.find_target_quality(probe, options.score_tgt if score_tgt is None else score_tgt,
+                                         options.tolerance if tolerance is None else tolerance,
+                                         options.max_pass if max_pass is None else max_pass)
+    finally:
+        if own:
+            s.close()
+    out.last_avif_size = last["size"]
+    return out
+
+
+def main(argv=None) -> int:
+    a = parse_args(argv)
+    ref, dist = load_rgba(a.ref), load_rgba(a.dist)
+    if ref.shape != dist.shape:
+        print(f"Error: {a.ref} is {ref.shape[1]}x{ref.shape[0]}, {a.dist} is {dist.shape[1]}x{dist.shape[0]}", file=sys.stderr)
+        return 1
+    with Ssimu2(a.device, blur=BLUR_MODES[a.blur], extended=True) as s:
+        scores = score_over(s, ref, dist, a.background)
+    for bg, score in scores:
+        print(f"{bg:06X} {score:.6f}")
+    print(f"min {min(score for _, score in scores):.6f}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

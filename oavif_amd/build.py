@@ -15,10 +15,12 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip.so")              # the product: C ABI of include/ssimu2_hip.h, oavif_tq.h
 INSTR_LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip_instr.so")  # + include/ssimu2_hip_internal.h (bench / tests only)
+EXT_LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip_ext.so")      # + include/ssimu2_hip_ext.h (RGBA input)
 HOST_PATH = os.path.join(LIB_DIR, "oavif_host")   # csrc/oavif_host.c: main.zig's flow in C over the two public headers + libavif
 SERVICE_PATH = os.path.join(LIB_DIR, "oavif_scored")  # csrc/oavif_scored.cpp: the resident scoring service
 SOURCES = ["ssimu2_hip.hip", "tq.cpp", "png_ingest.cpp", "remote_client.cpp"]
 INSTR_SOURCES = ["ssimu2_instrument.hip", "tq.cpp", "png_ingest.cpp", "remote_client.cpp"]  # ssimu2_instrument.hip includes ssimu2_hip.hip
+EXT_SOURCES = ["ssimu2_ext.hip", "tq.cpp", "png_ingest.cpp", "remote_client.cpp"]  # ssimu2_ext.hip includes ssimu2_hip.hip
 _PROGRAMS = ("oavif_host.c", "oavif_scored.cpp")  # linked against the library, not into it
 
 
@@ -39,9 +41,10 @@ def _headers():
 
 
 def libs_need_build() -> bool:
-    if not os.path.exists(LIB_PATH) or not os.path.exists(INSTR_LIB_PATH):
+    libs = (LIB_PATH, INSTR_LIB_PATH, EXT_LIB_PATH)
+    if not all(os.path.exists(p) for p in libs):
         return True
-    t = min(os.path.getmtime(LIB_PATH), os.path.getmtime(INSTR_LIB_PATH))
+    t = min(os.path.getmtime(p) for p in libs)
     return _newer_than(t, [os.path.join(CSRC, s) for s in os.listdir(CSRC) if s not in _PROGRAMS] + _headers())
 
 
@@ -73,7 +76,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         fcntl.flock(lock, fcntl.LOCK_EX)
         if not force and not needs_build():
             return LIB_PATH
-        for target, sources in ((LIB_PATH, SOURCES), (INSTR_LIB_PATH, INSTR_SOURCES)) if force or libs_need_build() else ():
+        targets = ((LIB_PATH, SOURCES), (INSTR_LIB_PATH, INSTR_SOURCES), (EXT_LIB_PATH, EXT_SOURCES))
+        for target, sources in targets if force or libs_need_build() else ():
             tmp = target + f".tmp{os.getpid()}"
             cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                    "-ffp-contract=off",  # arithmetic contract: every FMA is an explicit fmaf()

@@ -17,6 +17,8 @@
 //   map         : first map call only: density planes [scale][3][h_s][w_s] + the fp32 map [h][w] (ssimu2_error_map_*)
 //   hbd, tab    : first 16-bit call only (ssimu2_*_rgb16 / _strided16): the u16 frames as uploaded and in the FIR mode
 //                 their scale-0 linear planes [3][h][w]; the sRGB tables of depths 8..16
+//   alpha       : extension library only (SSIMU2_EXT_BUILD, ssimu2_ext.hip), first RGBA call: the table of the 65,026
+//                 composite codes; the RGBA rows use `stage`, the composited u16 frames `hbd`
 //   batch       : first batch call only (ssimu2_score_batch_*): staged frames, pyramids, partial sums and results of
 //                 every item
 //   result      : fp64 [108 averages][score][nscales], written by k_finalize straight into pinned host memory
@@ -215,6 +217,11 @@ struct ssimu2_ctx {
     // float offset 2^d - 256, uploaded by the first call at that depth
     DevBuf tab;
     uint32_t tab_ready = 0;  // bit d: the depth-d table is in `tab`
+#ifdef SSIMU2_EXT_BUILD
+    // alpha: the first RGBA call of the extension library (ssimu2_ext.hip, include/ssimu2_hip_ext.h); released by
+    // ssimu2_ctx_destroy only.  The table T of the 65,026 composite codes, uploaded once on the context stream
+    DevBuf alpha_tab;
+#endif
     // batch: batch_run / batch_stage (ssimu2_score_batch_*), each buffer when too small; released by ssimu2_ctx_destroy
     // only.  Scratch of its own, so a batch leaves the single-score buffers and a cached reference alone: the staged
     // 8-bit frames of the host-pointer forms, the linear pyramids (scales 1..5) and partial sums of every item, and the
@@ -232,8 +239,14 @@ struct ssimu2_ctx {
     struct {
         bool have = false, hbd = false;  // hbd: set from 16-bit samples (its 8-bit frame buffer is not it)
         uint32_t w = 0, h = 0;
+#ifdef SSIMU2_EXT_BUILD
+        int64_t bg = -1;  // 0xRRGGBB the reference was composited over (ssimu2_set_reference_rgba8); -1: none recorded
+        void drop() { have = hbd = false, w = h = 0, bg = -1; }
+        void set(uint32_t w_, uint32_t h_, bool hbd_) { have = true, hbd = hbd_, w = w_, h = h_, bg = -1; }
+#else
         void drop() { have = hbd = false, w = h = 0; }
         void set(uint32_t w_, uint32_t h_, bool hbd_) { have = true, hbd = hbd_, w = w_, h = h_; }
+#endif
     } ref;
     bool pending = false;
 
@@ -916,9 +929,8 @@ int device_table(ssimu2_ctx* c, uint32_t d, const float** out) {
     return SSIMU2_OK;
 }
 
-// What every 16-bit call needs besides its frames: in FIR mode the scale-0 linear planes of the frames it converts
-// (`ref`: the reference's too), then the device table of the depth (*tab).
-int hbd_prepare(ssimu2_ctx* c, uint32_t w, uint32_t h, bool ref, uint32_t bit_depth, const float** tab) {
+// In FIR mode the scale-0 linear planes of the u16 frames a call converts (`ref`: the reference's too).
+int hbd_planes(ssimu2_ctx* c, uint32_t w, uint32_t h, bool ref) {
     note_lin0(c, ref ? 0 : -1, 0, w, h);  // the call may regrow or rewrite them: valid again once launched
     if (c->blur_mode == SSIMU2_BLUR_FIR) {
         const size_t bytes = (size_t)w * h * 3 * sizeof(float);
@@ -926,6 +938,13 @@ int hbd_prepare(ssimu2_ctx* c, uint32_t w, uint32_t h, bool ref, uint32_t bit_de
         if (!rc && ref) rc = grow(c, c->hbd.lin0_ref, bytes, "hipMalloc(16-bit scale-0 planes)");
         if (rc) return rc;
     }
+    return SSIMU2_OK;
+}
+
+// What every 16-bit call needs besides its frames: those planes, then the device table of the depth (*tab).
+int hbd_prepare(ssimu2_ctx* c, uint32_t w, uint32_t h, bool ref, uint32_t bit_depth, const float** tab) {
+    const int rc = hbd_planes(c, w, h, ref);
+    if (rc) return rc;
     return device_table(c, bit_depth, tab);
 }
 
@@ -1554,6 +1573,9 @@ void ssimu2_ctx_destroy(ssimu2_ctx* c) {
     release_frame_groups(c);
     release(c->batch);
     release(c->tab);
+#ifdef SSIMU2_EXT_BUILD
+    release(c->alpha_tab);
+#endif
     (void)hipFree(c->d_result);
     release(c->h_result);
     if (c->ev0) (void)hipEventDestroy(c->ev0);

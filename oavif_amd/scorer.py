@@ -77,6 +77,42 @@ def linear_table(bit_depth: int) -> np.ndarray:
     return out
 
 
+def alpha_table() -> np.ndarray:
+    """ssimu2_alpha_table: the 65,026-entry table T the RGBA calls read composite codes n = a*c + (255 - a)*b through
+    (include/ssimu2_hip_ext.h; host only, no device).  Needs the extension library."""
+    out = np.empty(_lib.ALPHA_CODES, np.float32)
+    rc = _lib.ext_lib().ssimu2_alpha_table(_f32p(out))
+    if rc != 0:
+        raise Ssimu2Error(rc, "ssimu2_alpha_table failed")
+    return out
+
+
+def background_rgb(background) -> int:
+    """An (r, g, b) tuple of 8-bit values or an 0xRRGGBB int -> 0xRRGGBB."""
+    if isinstance(background, (int, np.integer)):
+        v = int(background)
+        if not 0 <= v <= 0xFFFFFF:
+            raise ValueError(f"background must be 0xRRGGBB, got {v:#x}")
+        return v
+    r, g, b = (int(x) for x in background)
+    if not all(0 <= x <= 255 for x in (r, g, b)):
+        raise ValueError(f"background components must be 0..255, got {(r, g, b)}")
+    return r << 16 | g << 8 | b
+
+
+def _check_rgba8(a, name: str) -> np.ndarray:
+    """An (h, w, 4) uint8 frame whose pixels are tightly packed within a row; rows any distance >= 4 w apart (a view
+    into libavif's padded rows goes through as it is, anything else is copied)."""
+    a = np.asarray(a)
+    if a.dtype != np.uint8:
+        raise TypeError(f"{name} must be uint8 RGBA, got {a.dtype}")
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"{name} must be (h, w, 4) uint8, got {a.shape}")
+    if a.strides[2] != 1 or a.strides[1] != 4 or (a.shape[0] > 1 and a.strides[0] < 4 * a.shape[1]):
+        a = np.ascontiguousarray(a)
+    return a
+
+
 def query_device(device: int = 0, instrumented: bool = False) -> dict:
     """ssimu2_query_device: what the library reads off HIP device `device` without creating a context
     (`usable` False = ssimu2_ctx_create would refuse it: not gfx950, or less than 160 KB of LDS per CU)."""
@@ -143,16 +179,22 @@ class Ssimu2:
     # (h, w, 3) of the cached reference, recorded by the calls that set one; None = none recorded, the library decides
     _ref_shape = None
 
+    extended = False   # bound to liboavif_hip_ext.so (the RGBA calls of include/ssimu2_hip_ext.h)
+
     def __init__(self, device: int = 0, stream: int | None = None, instrumented: bool = False,
-                 blur: int | None = None, service: str | None = None):
+                 blur: int | None = None, service: str | None = None, extended: bool = False):
         """`service`: socket path of a running scoring service (oavif_amd.service): the context lives there, and this
         process makes no HIP call for it (OAVIF_SCORER_SOCKET set around ssimu2_ctx_create, then restored; None = the
         environment as it is).  `instrumented=True` binds liboavif_hip_instr.so (the hooks of
         include/ssimu2_hip_internal.h: stage timing, plane download, experiment knobs); the
         default is the product library, which has none of them.  `blur`: _lib.BLUR_FIR /
-        _lib.BLUR_RECURSIVE (ssimu2_ctx_set_blur); None = FIR."""
-        self.instrumented = bool(instrumented)
-        self._L = _lib.instr_lib() if instrumented else _lib.lib()
+        _lib.BLUR_RECURSIVE (ssimu2_ctx_set_blur); None = FIR.  `extended=True` binds liboavif_hip_ext.so instead: the
+        product library plus the RGBA calls of include/ssimu2_hip_ext.h (composite_rgba, compute_ssimu2_rgba,
+        set_reference_rgba, score_against_reference_rgba); not together with `instrumented`."""
+        if instrumented and extended:
+            raise ValueError("instrumented=True and extended=True are different libraries: choose one")
+        self.instrumented, self.extended = bool(instrumented), bool(extended)
+        self._L = _lib.instr_lib() if instrumented else _lib.ext_lib() if extended else _lib.lib()
         self._ctx = ctypes.c_void_p()
         self._holder = None
         if service is None:
@@ -371,6 +413,57 @@ class Ssimu2:
             raise TypeError(f"rows must be uint16, got {a.dtype}")
         return self._score_decoded(self._L.ssimu2_score_against_reference_strided16, a, ctypes.c_uint16, row_bytes,
                                    channels, int(bit_depth))
+
+    # -- RGBA input (include/ssimu2_hip_ext.h): the extension library only --------
+    def _need_ext(self):
+        if not self.extended:
+            raise Ssimu2Error(_lib.ERR_UNSUPPORTED, "RGBA input needs Ssimu2(..., extended=True) (liboavif_hip_ext.so)")
+
+    def composite_rgba(self, pixels, background) -> np.ndarray:
+        """ssimu2_composite_rgba8: the (h, w, 3) uint16 codes n = a*c + (255 - a)*b of an (h, w, 4) uint8 frame with
+        straight alpha over `background` ((r, g, b) or 0xRRGGBB): the frame as the scorer sees it."""
+        self._need_ext()
+        a, bg = _check_rgba8(pixels, "pixels"), background_rgb(background)
+        h, w, _ = a.shape
+        out = np.empty((h, w, 3), np.uint16)
+        self._call(self._L.ssimu2_composite_rgba8, _u8p(a), a.strides[0] if h > 1 else 4 * w, w, h, bg, _u16p(out))
+        return out
+
+    def compute_ssimu2_rgba(self, ref, dist, background) -> float:
+        """ssimu2_score_rgba8: two (h, w, 4) uint8 frames (rows may be padded), each composited over `background`."""
+        self._need_ext()
+        ref, dist = _check_pair(ref, dist, _check_rgba8)
+        h, w, _ = ref.shape
+        tight = 4 * w
+        return self._score(self._L.ssimu2_score_rgba8, _u8p(ref), ref.strides[0] if h > 1 else tight, _u8p(dist),
+                           dist.strides[0] if h > 1 else tight, w, h, background_rgb(background))
+
+    def set_reference_rgba(self, ref, background) -> None:
+        """ssimu2_set_reference_rgba8; later RGBA frames are composited over the same background, and 8-bit and 16-bit
+        frames can be scored against it too."""
+        self._need_ext()
+        ref, bg = _check_rgba8(ref, "ref"), background_rgb(background)
+        h, w, _ = ref.shape
+        self._call(self._L.ssimu2_set_reference_rgba8, _u8p(ref), ref.strides[0] if h > 1 else 4 * w, w, h, bg)
+        self._ref_shape = (h, w, 3)
+
+    def score_against_reference_rgba(self, pixels, row_bytes: int | None = None) -> float:
+        """ssimu2_score_against_reference_rgba8: an (h, w, 4) uint8 array or view (an avif_bridge.DecodedFrame's
+        pixels()), or libavif's rows as they are -- its (h, rowBytes) `rows`, or a flat buffer with `row_bytes`."""
+        self._need_ext()
+        a = np.asarray(pixels)
+        if a.dtype != np.uint8:
+            raise TypeError(f"pixels must be uint8 RGBA, got {a.dtype}")
+        if a.ndim == 3:
+            a = _check_rgba8(a, "pixels")
+            self._check_ref_shape(a.shape[:2], "frame size")
+            row_bytes = (a.strides[0] if a.shape[0] > 1 else 4 * a.shape[1]) if row_bytes is None else row_bytes
+        elif a.ndim == 2 and a.strides[1] == 1 and row_bytes is None:
+            self._check_ref_shape(a.shape[:1], "frame height")
+            row_bytes = a.strides[0]
+        elif a.ndim != 1 or row_bytes is None or not a.flags.c_contiguous:
+            raise ValueError("pixels must be (h, w, 4), libavif's (h, rowBytes) rows, or a flat buffer with row_bytes")
+        return self._score(self._L.ssimu2_score_against_reference_rgba8, _u8p(a), int(row_bytes))
 
     # -- device-resident entry points (pointers are raw device addresses) -------------------
     # The per-frame ones make their C call in their own body, not through _call / _score / _scores: a 512x512 score is
