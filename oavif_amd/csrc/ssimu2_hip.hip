@@ -17,8 +17,8 @@
 //   map         : first map call only: density planes [scale][3][h_s][w_s] + the fp32 map [h][w] (ssimu2_error_map_*)
 //   hbd, tab    : first 16-bit call only (ssimu2_*_rgb16 / _strided16): the u16 frames as uploaded and in the FIR mode
 //                 their scale-0 linear planes [3][h][w]; the sRGB tables of depths 8..16
-//   alpha       : extension library only (SSIMU2_EXT_BUILD, ssimu2_ext.hip), first RGBA call: the table of the 65,026
-//                 composite codes; the RGBA rows use `stage`, the composited u16 frames `hbd`
+//   alpha       : first RGBA call only (the extension library's, ssimu2_ext.hip): the table of the 65,026 composite
+//                 codes; the RGBA rows use `stage`, the composited u16 frames `hbd`
 //   batch       : first batch call only (ssimu2_score_batch_*): staged frames, pyramids, partial sums and results of
 //                 every item
 //   result      : fp64 [108 averages][score][nscales], written by k_finalize straight into pinned host memory
@@ -191,7 +191,7 @@ struct ssimu2_ctx {
         DevBuf xyb;   // positive-XYB planes of the reference, all scales
         DevBuf blur;  // blur(ref*ref) planes, all scales (null = not cached)
     } cache;
-    // stage: stage_upload, for the _strided and _strided16 calls
+    // stage: feed_reserve, for a frame whose rows are not the scorer's (the _strided, _strided16 and RGBA calls)
     DevBuf stage;  // decoded avifRGBImage as uploaded (RGBA / padded rows)
     // rg: rg_ensure, SSIMU2_BLUR_RECURSIVE modes only (ssimu2_recursive.h); also released by ssimu2_ctx_set_blur(FIR)
     struct {
@@ -216,12 +216,11 @@ struct ssimu2_ctx {
     // tab: device_table; released by ssimu2_ctx_destroy only.  The sRGB -> linear tables of depths 8..16: depth d at
     // float offset 2^d - 256, uploaded by the first call at that depth
     DevBuf tab;
-    uint32_t tab_ready = 0;  // bit d: the depth-d table is in `tab`
-#ifdef SSIMU2_EXT_BUILD
-    // alpha: the first RGBA call of the extension library (ssimu2_ext.hip, include/ssimu2_hip_ext.h); released by
-    // ssimu2_ctx_destroy only.  The table T of the 65,026 composite codes, uploaded once on the context stream
+    // alpha: device_table, by the first RGBA call (the extension library's: ssimu2_ext.hip, include/ssimu2_hip_ext.h;
+    // nothing in the product library feeds RGBA); released by ssimu2_ctx_destroy only.  The table of the 65,026
+    // composite codes
     DevBuf alpha_tab;
-#endif
+    uint32_t tab_ready = 0;  // bit d: the depth-d table is in `tab`; bit 0: the composite table is in `alpha_tab`
     // batch: batch_run / batch_stage (ssimu2_score_batch_*), each buffer when too small; released by ssimu2_ctx_destroy
     // only.  Scratch of its own, so a batch leaves the single-score buffers and a cached reference alone: the staged
     // 8-bit frames of the host-pointer forms, the linear pyramids (scales 1..5) and partial sums of every item, and the
@@ -239,14 +238,11 @@ struct ssimu2_ctx {
     struct {
         bool have = false, hbd = false;  // hbd: set from 16-bit samples (its 8-bit frame buffer is not it)
         uint32_t w = 0, h = 0;
-#ifdef SSIMU2_EXT_BUILD
         int64_t bg = -1;  // 0xRRGGBB the reference was composited over (ssimu2_set_reference_rgba8); -1: none recorded
         void drop() { have = hbd = false, w = h = 0, bg = -1; }
-        void set(uint32_t w_, uint32_t h_, bool hbd_) { have = true, hbd = hbd_, w = w_, h = h_, bg = -1; }
-#else
-        void drop() { have = hbd = false, w = h = 0; }
-        void set(uint32_t w_, uint32_t h_, bool hbd_) { have = true, hbd = hbd_, w = w_, h = h_; }
-#endif
+        void set(uint32_t w_, uint32_t h_, bool hbd_, int64_t bg_) {
+            have = true, hbd = hbd_, w = w_, h = h_, bg = bg_;
+        }
     } ref;
     bool pending = false;
 
@@ -836,121 +832,197 @@ int rg_prepare(ssimu2_ctx* c, const Pyramid& p, uint32_t w, uint32_t h, bool nee
     return SSIMU2_OK;
 }
 
-// Enqueue the whole score of (d_ref, d_dist) on the ctx stream.  `ref_pyramid_ready`:
-// the reference's linear pyramid in d_lin_ref is already valid for this frame size.
-int enqueue_score(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, uint32_t w, uint32_t h,
-                  bool ref_pyramid_ready) {
-    const Pyramid p = make_pyramid(w, h);
-    const bool recursive = c->blur_mode != SSIMU2_BLUR_FIR;
-    note_lin0(c, 0, 0, w, h);  // an 8-bit score: the 16-bit scale-0 planes are older than it
-    if (recursive) {
-        const int rc = rg_prepare(c, p, w, h, ref_pyramid_ready);
-        if (rc) return rc;
-    }
-    if (!recursive) {  // the recursive modes convert straight to XYB planes; a ready reference pyramid is skipped
-        const uint8_t* frames[2] = {d_ref, d_dist};
-        float* lin[2] = {c->frame.lin_ref.as<float>(), c->frame.lin_dist.as<float>()};
-        const int skip = ref_pyramid_ready ? 1 : 0;
-        launch_pyramid(c, p, 2 - skip, frames + skip, lin + skip);
-    }
-    if (recursive) {
-        if (!ref_pyramid_ready) rg_enqueue_reference(c, p, d_ref);
-        return rg_enqueue_pass(c, p, d_dist);
-    }
-    MarchPlan mp;
-    FinalizeArgs fa;
-    build_plans(c, p, march_seg_rows, score_sources(c, d_ref, d_dist, ref_pyramid_ready && c->cache.xyb.p), &mp, &fa);
-    launch_march(c, mp.ref_s11[0] != nullptr, false, mp);
-    return finish_score(c, fa);
-}
+// A frame where the front end reads it: an 8-bit RGB frame (`u8`), or with `u8` null 16-bit codes (`s16`).
+struct Fed {
+    const uint8_t* u8;
+    Src16 s16;
+};
 
-// The score of 16-bit frames: `ref` null = against the cached reference (set from 8- or 16-bit samples; its planes do
-// not depend on the depth).  Same kernels after the front end: k_pyramid_bands16 (FIR, which also writes scale 0's
-// linear planes for k_march_lin / k_march_refblur_lin) or k_pyramid_bands_xyb16 (recursive modes).
-int enqueue_score16(ssimu2_ctx* c, const Src16* ref, const Src16& dist, uint32_t w, uint32_t h) {
-    const Pyramid p = make_pyramid(w, h);
-    if (c->blur_mode != SSIMU2_BLUR_FIR) {
-        const int rc = rg_prepare(c, p, w, h, !ref);
-        if (rc) return rc;
-        if (ref) rg_enqueue_reference(c, p, nullptr, ref);
-        return rg_enqueue_pass(c, p, nullptr, &dist);
-    }
-    const bool cached = !ref && ref_cached(c);
-    if (!ref && !cached)  // 16-bit scale 0 cannot be paired with an 8-bit reference frame in one marching kernel
+// What a pass against the cached reference is refused for once its arguments are in order, before anything of it is
+// enqueued.  FIR: a 16-bit scale 0 (`hbd`) cannot be paired with an 8-bit reference frame in one marching kernel, so it
+// needs the reference's cached planes.  Recursive modes: rg_prepare.
+int pass_prepare(ssimu2_ctx* c, bool hbd) {
+    const uint32_t w = c->ref.w, h = c->ref.h;
+    if (c->blur_mode != SSIMU2_BLUR_FIR) return rg_prepare(c, make_pyramid(w, h), w, h, true);
+    if (hbd && !ref_cached(c))
         return c->fail(SSIMU2_ERR_OOM, "16-bit frames against a reference need its cached planes, which are missing");
-    const Src16* src[2] = {ref, &dist};
+    return SSIMU2_OK;
+}
+
+// Every launch of one score on the context stream, nothing refused any more: `dist` against `ref` (the same kind of
+// frame), or with `ref` null against the cached reference (set from 8- or 16-bit samples; its planes do not depend on
+// the depth).  16-bit frames take the same kernels after the front end: k_pyramid_bands16 (FIR, which also writes scale
+// 0's linear planes for k_march_lin / k_march_refblur_lin) or k_pyramid_bands_xyb16 (recursive modes).
+int launch_score(ssimu2_ctx* c, uint32_t w, uint32_t h, const Fed* ref, const Fed& dist) {
+    const Pyramid p = make_pyramid(w, h);
+    const bool hbd = !dist.u8;
+    const uint8_t* const ref_u8 = ref ? ref->u8 : c->frame.ref_u8.as<uint8_t>();
+    if (!hbd) note_lin0(c, 0, 0, w, h);  // an 8-bit score: the 16-bit scale-0 planes are older than it
+    if (c->blur_mode != SSIMU2_BLUR_FIR) {  // straight to XYB planes; a cached reference's are in place
+        if (ref) rg_enqueue_reference(c, p, ref_u8, hbd ? &ref->s16 : nullptr);
+        return rg_enqueue_pass(c, p, dist.u8, hbd ? &dist.s16 : nullptr);
+    }
     float* lin[2] = {c->frame.lin_ref.as<float>(), c->frame.lin_dist.as<float>()};
-    float* lin0[2] = {c->hbd.lin0_ref.as<float>(), c->hbd.lin0_dist.as<float>()};
-    const int skip = ref ? 0 : 1;  // against the cached reference: the distorted frame alone
-    launch_pyramid16(c, p, 2 - skip, src + skip, lin + skip, lin0 + skip);
-    if (p.nscales >= 1) note_lin0(c, ref ? 1 : -1, 1, w, h);
+    const int skip = ref ? 0 : 1;  // against the cached reference: the distorted frame alone, its pyramid is ready
     MarchPlan mp;
     FinalizeArgs fa;
-    build_plans(c, p, march_seg_rows, score_sources(c, c->hbd.lin0_ref.p, c->hbd.lin0_dist.p, cached), &mp, &fa);
-    launch_march(c, cached, true, mp);
+    if (hbd) {
+        const Src16* src[2] = {ref ? &ref->s16 : nullptr, &dist.s16};
+        float* lin0[2] = {c->hbd.lin0_ref.as<float>(), c->hbd.lin0_dist.as<float>()};
+        launch_pyramid16(c, p, 2 - skip, src + skip, lin + skip, lin0 + skip);
+        if (p.nscales >= 1) note_lin0(c, ref ? 1 : -1, 1, w, h);
+        build_plans(c, p, march_seg_rows, score_sources(c, lin0[0], lin0[1], !ref), &mp, &fa);  // pass_prepare: cached
+    } else {
+        const uint8_t* frames[2] = {ref_u8, dist.u8};
+        launch_pyramid(c, p, 2 - skip, frames + skip, lin + skip);
+        build_plans(c, p, march_seg_rows, score_sources(c, ref_u8, dist.u8, !ref && c->cache.xyb.p), &mp, &fa);
+    }
+    launch_march(c, mp.ref_s11[0] != nullptr, hbd, mp);
     return finish_score(c, fa);
 }
 
-// sRGB -> linear of a d-bit sample s, 8 <= d <= 16: the 8-bit table's expression at v = s / (2^d - 1), fp64, rounded
-// once.  65535 = 255 * 257, so the 16-bit entry 257 u is the 8-bit entry u bit for bit (v is the same double).
-// Built once per process and depth.
-const float* host_table(uint32_t d) {
+// Enqueue the whole score of two 8-bit frames on the device (the enqueue forms, the timing hooks): d_dist against
+// d_ref, or with `against_ref` against the cached reference, whose 8-bit frame d_ref is.
+int enqueue_score(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, uint32_t w, uint32_t h,
+                  bool against_ref) {
+    const int rc = c->blur_mode != SSIMU2_BLUR_FIR ? rg_prepare(c, make_pyramid(w, h), w, h, against_ref) : SSIMU2_OK;
+    if (rc) return rc;
+    const Fed ref{d_ref, {}}, dist{d_dist, {}};
+    return launch_score(c, w, h, against_ref ? nullptr : &ref, dist);
+}
+
+// ---- sRGB -> linear tables (DESIGN.md sections 10 and 13) -----------------------------------------
+// The table of the `n` codes 0..top (n = top + 1): the 8-bit table's expression at v = code / top, fp64, rounded once.
+// 65535 = 255 * 257 and 65025 = 255 * 255, so entry 257 u of depth 16 and entry 255 u of the composite table are the
+// 8-bit entry u bit for bit (v is the same double).  Built once per process and top code: the depths 8..16 and the
+// composite table are ten.
+const float* host_table(uint32_t n, uint32_t top) {
     static std::mutex mu;
-    static float* tabs[17] = {nullptr};
+    static struct {
+        uint32_t top;
+        const float* t;
+    } built[16];
+    static int nbuilt = 0;
     std::lock_guard<std::mutex> lock(mu);
-    if (!tabs[d]) {
-        const uint32_t n = 1u << d;
-        float* t = new (std::nothrow) float[n];
-        if (!t) return nullptr;
-        const double top = (double)(n - 1);
-        for (uint32_t i = 0; i < n; ++i) {
-            const double v = (double)i / top;
-            t[i] = (float)(v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4));
-        }
-        tabs[d] = t;
+    for (int k = 0; k < nbuilt; ++k)
+        if (built[k].top == top) return built[k].t;
+    float* t = nbuilt < 16 ? new (std::nothrow) float[n] : nullptr;
+    if (!t) return nullptr;
+    for (uint32_t i = 0; i < n; ++i) {
+        const double v = (double)i / (double)top;
+        t[i] = (float)(v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4));
     }
-    return tabs[d];
+    built[nbuilt++] = {top, t};
+    return t;
+}
+
+// The tables as the exported functions hand them out.
+int copy_table(uint32_t n, uint32_t top, float* out) {
+    if (!out) return SSIMU2_ERR_INVALID_ARG;
+    const float* t = host_table(n, top);
+    if (!t) return SSIMU2_ERR_OOM;
+    memcpy(out, t, (size_t)n * sizeof(float));
+    return SSIMU2_OK;
 }
 
 size_t table_off(uint32_t d) { return ((size_t)1 << d) - 256; }
 
-// The device table of depth d (uploaded on the context stream by the first call at that depth).
-int device_table(ssimu2_ctx* c, uint32_t d, const float** out) {
-    const int rc = grow(c, c->tab, table_off(17) * sizeof(float), "hipMalloc(16-bit sRGB tables)");  // once per context
+// The device copy of the table of `n` codes 0..top, uploaded on the context stream by the first call that needs it.
+// A depth's table (n = 2^d) lies in `tab` at float offset 2^d - 256; any other is the composite table, alone in
+// `alpha_tab`.
+int device_table(ssimu2_ctx* c, uint32_t n, uint32_t top, const float** out) {
+    const bool depth = (n & (n - 1)) == 0;
+    DevBuf& buf = depth ? c->tab : c->alpha_tab;
+    const size_t total = depth ? table_off(17) : n, off = depth ? n - 256 : 0;
+    const uint32_t bit = depth ? n : 1u;  // of tab_ready
+    const char* what = depth ? "hipMalloc(16-bit sRGB tables)" : "hipMalloc(composite table)";
+    const int rc = grow(c, buf, total * sizeof(float), what);  // once per context
     if (rc) return rc;
-    if (!(c->tab_ready & (1u << d))) {
-        const float* t = host_table(d);
-        if (!t) return c->fail(SSIMU2_ERR_OOM, "16-bit sRGB table");
-        HIP_TRY(c, hipMemcpyAsync(c->tab.as<float>() + table_off(d), t, ((size_t)1 << d) * sizeof(float),
-                                  hipMemcpyHostToDevice, c->stream));
-        c->tab_ready |= 1u << d;
+    if (!(c->tab_ready & bit)) {
+        const float* t = host_table(n, top);
+        if (!t) return c->fail(SSIMU2_ERR_OOM, depth ? "16-bit sRGB table" : "composite table");
+        HIP_TRY(c, hipMemcpyAsync(buf.as<float>() + off, t, (size_t)n * sizeof(float), hipMemcpyHostToDevice,
+                                  c->stream));
+        c->tab_ready |= bit;
     }
-    *out = c->tab.as<float>() + table_off(d);
+    *out = buf.as<float>() + off;
     return SSIMU2_OK;
 }
 
-// In FIR mode the scale-0 linear planes of the u16 frames a call converts (`ref`: the reference's too).
-int hbd_planes(ssimu2_ctx* c, uint32_t w, uint32_t h, bool ref) {
-    note_lin0(c, ref ? 0 : -1, 0, w, h);  // the call may regrow or rewrite them: valid again once launched
-    if (c->blur_mode == SSIMU2_BLUR_FIR) {
-        const size_t bytes = (size_t)w * h * 3 * sizeof(float);
-        int rc = grow(c, c->hbd.lin0_dist, bytes, "hipMalloc(16-bit scale-0 planes)");
-        if (!rc && ref) rc = grow(c, c->hbd.lin0_ref, bytes, "hipMalloc(16-bit scale-0 planes)");
-        if (rc) return rc;
-    }
+// ---- a caller's frame onto the device ("One path for a frame") ---------------
+// How one frame of a call gets onto the device, for either slot of the context (the reference's or the distorted
+// frame's), and how the front end reads it there.
+struct Feed {
+    const void* px;      // the caller's frame
+    hipMemcpyKind kind;  // where that is: host memory, or an 8-bit frame already on the device
+    uint32_t row_bytes;  // bytes between its rows
+    uint32_t ch;         // samples per pixel there: 3, or 4 with the fourth skipped or composited away
+    uint32_t sample;     // bytes per sample there: 1 or 2
+    // 0: the front end reads an 8-bit RGB frame.  Else it reads u16 codes 0..top through the table of top + 1 entries:
+    // 2^d - 1 for samples of depth d, 65025 for composite codes
+    uint32_t top;
+    // The rows go into the slot's tight frame as they are (`staged` false: they are tight RGB), or into `stage`.  From
+    // there `unpack` launches what makes the slot's tight frame `dst` of them; with none the front end reads them in
+    // `stage`, pitch, fourth sample and all (16-bit samples only)
+    bool staged;
+    void (*unpack)(ssimu2_ctx* c, const Feed& f, uint32_t w, uint32_t h, void* dst);
+    int64_t bg;  // 0xRRGGBB the unpacking composites over, which a reference keeps (ref.bg); -1: none
+};
+
+// Tight RGB frames of w pixels per row: 8-bit, and u16 samples of depth `bit_depth` in host memory.
+Feed tight8(const void* px, uint32_t w, hipMemcpyKind kind = hipMemcpyHostToDevice) {
+    return {px, kind, w * 3u, 3u, 1u, 0u, false, nullptr, -1};
+}
+Feed tight16(const void* px, uint32_t w, uint32_t bit_depth) {
+    return {px, hipMemcpyHostToDevice, w * 6u, 3u, 2u, (1u << bit_depth) - 1u, false, nullptr, -1};
+}
+
+// The slot's tight frame: ensure_capacity's 8-bit one, or the u16 one.
+DevBuf& feed_frame(ssimu2_ctx* c, const Feed& f, bool ref) {
+    return f.top ? (ref ? c->hbd.ref16 : c->hbd.dist16) : (ref ? c->frame.ref_u8 : c->frame.dist_u8);
+}
+
+// The last row needs only its pixels, not its padding (libavif allocates rowBytes * height, a cropped view of a larger
+// buffer may not).
+size_t feed_bytes(const Feed& f, uint32_t w, uint32_t h) {
+    return (size_t)f.row_bytes * (h - 1) + (size_t)w * f.ch * f.sample;
+}
+
+// Feeding a frame, first half: every buffer it needs beyond ensure_capacity's -- `stage` (16 bytes of slack behind the
+// frame), and for u16 codes the slot's tight frame, in FIR mode its scale-0 linear planes, the table (fed->s16.tab).
+// Enqueues nothing that reads the caller's memory, so a failure needs no wait.
+int feed_reserve(ssimu2_ctx* c, const Feed& f, bool ref, uint32_t w, uint32_t h, Fed* fed) {
+    int rc;
+    if (f.staged && (rc = grow(c, c->stage, feed_bytes(f, w, h) + 16, "hipMalloc(staging frame)"))) return rc;
+    if (!f.top) return SSIMU2_OK;
+    const size_t px = (size_t)w * h * 3;
+    const bool in_stage = f.staged && !f.unpack;  // no tight frame
+    if (!in_stage && (rc = grow(c, feed_frame(c, f, ref), px * sizeof(uint16_t), "hipMalloc(16-bit frames)")))
+        return rc;
+    note_lin0(c, ref ? 0 : -1, ref ? -1 : 0, w, h);  // the call may regrow or rewrite them: valid again once launched
+    DevBuf& lin0 = ref ? c->hbd.lin0_ref : c->hbd.lin0_dist;
+    if (c->blur_mode == SSIMU2_BLUR_FIR && (rc = grow(c, lin0, px * sizeof(float), "hipMalloc(16-bit scale-0 planes)")))
+        return rc;
+    return device_table(c, f.top + 1, f.top, &fed->s16.tab);
+}
+
+// Second half, after every feed_reserve of the call: the copy from the caller's memory and the unpacking, on the
+// context stream; *fed is what the front end reads.
+int feed_enqueue(ssimu2_ctx* c, const Feed& f, bool ref, uint32_t w, uint32_t h, Fed* fed) {
+    void* const frame = feed_frame(c, f, ref).p;
+    HIP_TRY(c, hipMemcpyAsync(f.staged ? c->stage.p : frame, f.px, feed_bytes(f, w, h), f.kind, c->stream));
+    if (f.unpack) f.unpack(c, f, w, h, frame);
+    fed->u8 = f.top ? nullptr : (const uint8_t*)frame;
+    if (f.staged && !f.unpack) fed->s16 = {c->stage.p, f.row_bytes, f.ch, fed->s16.tab, f.top};
+    else fed->s16 = {frame, w * 6u, 3u, fed->s16.tab, f.top};
     return SSIMU2_OK;
 }
 
-// What every 16-bit call needs besides its frames: those planes, then the device table of the depth (*tab).
-int hbd_prepare(ssimu2_ctx* c, uint32_t w, uint32_t h, bool ref, uint32_t bit_depth, const float** tab) {
-    const int rc = hbd_planes(c, w, h, ref);
-    if (rc) return rc;
-    return device_table(c, bit_depth, tab);
-}
-
-// The tight RGB frame of w pixels per row uploaded into `frame`, read through the table of its depth.
-Src16 tight16(const DevBuf& frame, uint32_t w, const float* tab, uint32_t bit_depth) {
-    return {frame.p, w * 6u, 3u, tab, (1u << bit_depth) - 1u};
+// The one way out of a call from its first copy out of the caller's memory onwards: a failed call waits for the
+// stream, so that the caller may free its frames after any return (a call that succeeds has waited for its result).
+int leave(ssimu2_ctx* c, int rc) {
+    if (rc) (void)hipStreamSynchronize(c->stream);
+    return rc;
 }
 
 // Argument checks of the 16-bit calls (the ctx is not null).
@@ -1573,9 +1645,7 @@ void ssimu2_ctx_destroy(ssimu2_ctx* c) {
     release_frame_groups(c);
     release(c->batch);
     release(c->tab);
-#ifdef SSIMU2_EXT_BUILD
     release(c->alpha_tab);
-#endif
     (void)hipFree(c->d_result);
     release(c->h_result);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1616,24 +1686,6 @@ int ssimu2_score_rgb8_device(ssimu2_ctx* c, const void* d_ref, const void* d_dis
     return ssimu2_wait(c, out_score);
 }
 
-int ssimu2_score_rgb8(ssimu2_ctx* c, const uint8_t* ref, const uint8_t* dist, uint32_t w,
-                      uint32_t h, uint32_t channels, double* out_score) {
-    REMOTE(c, score_rgb8(c->remote, ref, dist, w, h, channels, out_score));
-    int rc = check_args(c, ref, dist, w, h);
-    if (rc) return rc;
-    if (channels != 3) return c->fail(SSIMU2_ERR_UNSUPPORTED, "channels must be 3");
-    if (!out_score) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_score");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if ((rc = ensure_capacity(c, w, h))) return rc;
-    c->ref.drop();
-    const size_t bytes = (size_t)w * h * 3;
-    uint8_t *d_ref = c->frame.ref_u8.as<uint8_t>(), *d_dist = c->frame.dist_u8.as<uint8_t>();
-    HIP_TRY(c, hipMemcpyAsync(d_ref, ref, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_dist, dist, bytes, hipMemcpyHostToDevice, c->stream));
-    if ((rc = enqueue_score(c, d_ref, d_dist, w, h, false))) return rc;
-    return ssimu2_wait(c, out_score);
-}
-
 // FIR mode: the reference's positive-XYB planes and blur(ref*ref) at every scale from its scale 0 (`scale0`: the 8-bit
 // frame, or with !scale0_u8 the linear planes of a 16-bit one) and its linear pyramid in d_lin_ref, already enqueued.
 // `required` (16-bit references): a failed allocation is an error instead of a reference converted on every pass.
@@ -1670,45 +1722,100 @@ static int cache_reference_fir(ssimu2_ctx* c, const Pyramid& p, const void* scal
 }
 
 // The end of every ssimu2_set_reference*: everything of the reference is enqueued.
-static int reference_set(ssimu2_ctx* c, uint32_t w, uint32_t h, bool hbd) {
+static int reference_set(ssimu2_ctx* c, uint32_t w, uint32_t h, bool hbd, int64_t bg) {
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // caller may free `ref` after return
-    c->ref.set(w, h, hbd);
+    c->ref.set(w, h, hbd, bg);
     return SSIMU2_OK;
 }
 
-static int set_reference_impl(ssimu2_ctx* c, const void* ref, uint32_t w, uint32_t h,
-                              hipMemcpyKind kind) {
-    int rc = check_args(c, ref, ref, w, h);
-    if (rc) return rc;
+// ---- the three shapes of a call that feeds frames, each once ----------------
+// Every one of them, after the entry point's own argument checks: what can be refused without the device; the buffers
+// (nothing enqueued yet that reads the caller's memory, so a failure returns as it is); then the copies and launches,
+// from where leave() is the only way out.
+
+// The pair score: `dist` against `ref`, two frames of one kind.
+static int score_pair(ssimu2_ctx* c, const Feed& ref, const Feed& dist, uint32_t w, uint32_t h, double* out_score) {
+    const bool recursive = c->blur_mode != SSIMU2_BLUR_FIR;
+    int rc;
+    if (recursive && (rc = rg_check_size(c, w, h))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = ensure_capacity(c, w, h))) return rc;
+    c->ref.drop();  // the lin_ref pyramid is overwritten
+    Fed r{}, d{};
+    if ((recursive && (rc = rg_ensure(c, make_pyramid(w, h)))) || (rc = feed_reserve(c, ref, true, w, h, &r)) ||
+        (rc = feed_reserve(c, dist, false, w, h, &d)))
+        return rc;
+    if (!(rc = feed_enqueue(c, ref, true, w, h, &r)) && !(rc = feed_enqueue(c, dist, false, w, h, &d)) &&
+        !(rc = launch_score(c, w, h, &r, d)))
+        rc = ssimu2_wait(c, out_score);
+    return leave(c, rc);
+}
+
+// Set-reference: the frame, then everything that depends on the reference alone.
+static int feed_reference(ssimu2_ctx* c, const Feed& ref, uint32_t w, uint32_t h) {
+    const bool fir = c->blur_mode == SSIMU2_BLUR_FIR;
+    int rc;
+    if (!fir && (rc = rg_check_size(c, w, h))) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = ensure_capacity(c, w, h))) return rc;
     const Pyramid p = make_pyramid(w, h);
-    const bool fir = c->blur_mode == SSIMU2_BLUR_FIR;
-    if (!fir && (rc = rg_prepare(c, p, w, h, false))) return rc;  // before any launch
-    c->ref.drop();
-    note_lin0(c, 0, 0, w, h);
-    uint8_t* const d_ref = c->frame.ref_u8.as<uint8_t>();
-    HIP_TRY(c, hipMemcpyAsync(d_ref, ref, (size_t)w * h * 3, kind, c->stream));
-    if (!fir) {  // XYB planes, blur(x) and blur(x*x) by the published recursion
-        rg_enqueue_reference(c, p, d_ref);
-        return reference_set(c, w, h, false);
+    if (!fir && (rc = rg_ensure(c, p))) return rc;
+    c->ref.drop();  // the lin_ref pyramid and the cached planes are overwritten
+    Fed r{};
+    if ((rc = feed_reserve(c, ref, true, w, h, &r))) return rc;
+    if (!(rc = feed_enqueue(c, ref, true, w, h, &r))) {
+        float* lin[1] = {c->frame.lin_ref.as<float>()};
+        if (r.u8) note_lin0(c, 0, 0, w, h);
+        if (!fir) {  // XYB planes, blur(x) and blur(x*x) by the published recursion
+            rg_enqueue_reference(c, p, r.u8, r.u8 ? nullptr : &r.s16);
+        } else if (r.u8) {  // the reference's linear pyramid, once per search, then the caches
+            launch_pyramid(c, p, 1, &r.u8, lin);
+            (void)cache_reference_fir(c, p, r.u8, true, false);  // not required: an 8-bit pass converts the reference
+        } else {  // linear pyramid and scale-0 planes, then the same caches as an 8-bit reference's (required here)
+            const Src16* src[1] = {&r.s16};
+            float* lin0[1] = {c->hbd.lin0_ref.as<float>()};
+            launch_pyramid16(c, p, 1, src, lin, lin0);
+            if (p.nscales >= 1) note_lin0(c, 1, -1, w, h);
+            rc = cache_reference_fir(c, p, lin0[0], false, true);
+        }
+        if (!rc) rc = reference_set(c, w, h, !r.u8, ref.bg);
     }
-    const uint8_t* frames[1] = {d_ref};
-    float* lin[1] = {c->frame.lin_ref.as<float>()};
-    launch_pyramid(c, p, 1, frames, lin);  // the reference's linear pyramid, once per search
-    (void)cache_reference_fir(c, p, d_ref, true, false);  // not required: an 8-bit pass can convert the reference
-    return reference_set(c, w, h, false);
+    return leave(c, rc);
+}
+
+// The pass against the cached reference.
+static int score_against(ssimu2_ctx* c, const Feed& dist, double* out_score) {
+    const uint32_t w = c->ref.w, h = c->ref.h;
+    HIP_TRY(c, hipSetDevice(c->device));
+    Fed d{};
+    int rc = pass_prepare(c, dist.top != 0);
+    if (rc || (rc = feed_reserve(c, dist, false, w, h, &d))) return rc;
+    if (!(rc = feed_enqueue(c, dist, false, w, h, &d)) && !(rc = launch_score(c, w, h, nullptr, d)))
+        rc = ssimu2_wait(c, out_score);
+    return leave(c, rc);
+}
+
+int ssimu2_score_rgb8(ssimu2_ctx* c, const uint8_t* ref, const uint8_t* dist, uint32_t w,
+                      uint32_t h, uint32_t channels, double* out_score) {
+    REMOTE(c, score_rgb8(c->remote, ref, dist, w, h, channels, out_score));
+    int rc = check_args(c, ref, dist, w, h);
+    if (rc) return rc;
+    if (channels != 3) return c->fail(SSIMU2_ERR_UNSUPPORTED, "channels must be 3");
+    if (!out_score) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_score");
+    return score_pair(c, tight8(ref, w), tight8(dist, w), w, h, out_score);
 }
 
 int ssimu2_set_reference(ssimu2_ctx* c, const uint8_t* ref, uint32_t w, uint32_t h) {
     REMOTE(c, set_reference(c->remote, ref, w, h));
-    return set_reference_impl(c, ref, w, h, hipMemcpyHostToDevice);
+    const int rc = check_args(c, ref, ref, w, h);
+    return rc ? rc : feed_reference(c, tight8(ref, w), w, h);
 }
 
 int ssimu2_set_reference_device(ssimu2_ctx* c, const void* d_ref, uint32_t w, uint32_t h) {
     REMOTE_REFUSE(c, "ssimu2_set_reference_device");
-    return set_reference_impl(c, d_ref, w, h, hipMemcpyDeviceToDevice);
+    const int rc = check_args(c, d_ref, d_ref, w, h);
+    return rc ? rc : feed_reference(c, tight8(d_ref, w, hipMemcpyDeviceToDevice), w, h);
 }
 
 // What every against-reference call checks first, in this order; `pointers`: none of the call's pointers is null.
@@ -1727,30 +1834,20 @@ int ssimu2_enqueue_against_reference_device(ssimu2_ctx* c, const void* d_dist) {
     return enqueue_score(c, c->frame.ref_u8.as<uint8_t>(), (const uint8_t*)d_dist, c->ref.w, c->ref.h, true);
 }
 
-// The 8-bit frame now in frame.dist_u8 against the cached reference.
-static int score_against_reference8(ssimu2_ctx* c, double* out_score) {
-    int rc = enqueue_score(c, c->frame.ref_u8.as<uint8_t>(), c->frame.dist_u8.as<uint8_t>(), c->ref.w, c->ref.h, true);
-    if (rc) return rc;
-    return ssimu2_wait(c, out_score);
-}
-
-// One decoded frame into the staging buffer: one buffer for the 8-bit and the 16-bit strided call, with 16 bytes of
-// slack behind the frame.
-static int stage_upload(ssimu2_ctx* c, const void* pixels, size_t bytes) {
-    int rc = grow(c, c->stage, bytes + 16, "hipMalloc(staging frame)");
-    if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->stage.p, pixels, bytes, hipMemcpyHostToDevice, c->stream));
-    return SSIMU2_OK;
-}
-
 int ssimu2_score_against_reference(ssimu2_ctx* c, const uint8_t* dist, double* out_score) {
     REMOTE(c, score_against_reference(c->remote, dist, out_score));
-    int rc = check_against(c, dist && out_score);
-    if (rc) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)c->ref.w * c->ref.h * 3;
-    HIP_TRY(c, hipMemcpyAsync(c->frame.dist_u8.p, dist, bytes, hipMemcpyHostToDevice, c->stream));
-    return score_against_reference8(c, out_score);
+    const int rc = check_against(c, dist && out_score);
+    return rc ? rc : score_against(c, tight8(dist, c->ref.w), out_score);
+}
+
+// Decoded 8-bit rows in `stage` -> the tight RGB8 frame `dst` (Feed::unpack of the call below).
+static void unpack_rgb8(ssimu2_ctx* c, const Feed& f, uint32_t w, uint32_t h, void* dst) {
+    if (f.ch == 4 && w % 4 == 0 && f.row_bytes % 4 == 0)
+        launch(k_unpack_rgb<true>, dim3((w / 4 + 255) / 256, h), dim3(256), 0, c->stream, c->stage.as<uint8_t>(),
+               f.row_bytes, f.ch, w, h, (uint8_t*)dst);
+    else
+        launch(k_unpack_rgb<false>, dim3((w + 255) / 256, h), dim3(256), 0, c->stream, c->stage.as<uint8_t>(),
+               f.row_bytes, f.ch, w, h, (uint8_t*)dst);
 }
 
 int ssimu2_score_against_reference_strided(ssimu2_ctx* c, const uint8_t* pixels, uint32_t row_bytes,
@@ -1760,23 +1857,12 @@ int ssimu2_score_against_reference_strided(ssimu2_ctx* c, const uint8_t* pixels,
     if (rc) return rc;
     if (channels != 3 && channels != 4)
         return c->fail(SSIMU2_ERR_UNSUPPORTED, "channels must be 3 (RGB) or 4 (RGBA)");
-    const uint32_t w = c->ref.w, h = c->ref.h;
+    const uint32_t w = c->ref.w;
     if ((uint64_t)row_bytes < (uint64_t)w * channels)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "row_bytes smaller than one row of pixels");
-    if (channels == 3 && row_bytes == w * 3)  // already the scorer's layout
-        return ssimu2_score_against_reference(c, pixels, out_score);
-    HIP_TRY(c, hipSetDevice(c->device));
-    // the last row needs only its pixels, not its padding (libavif allocates rowBytes * height,
-    // a cropped view of a larger buffer may not)
-    const size_t bytes = (size_t)row_bytes * (h - 1) + (size_t)w * channels;
-    if ((rc = stage_upload(c, pixels, bytes))) return rc;
-    if (channels == 4 && w % 4 == 0 && row_bytes % 4 == 0)
-        launch(k_unpack_rgb<true>, dim3((w / 4 + 255) / 256, h), dim3(256), 0, c->stream,
-                           c->stage.as<uint8_t>(), row_bytes, channels, w, h, c->frame.dist_u8.as<uint8_t>());
-    else
-        launch(k_unpack_rgb<false>, dim3((w + 255) / 256, h), dim3(256), 0, c->stream,
-                           c->stage.as<uint8_t>(), row_bytes, channels, w, h, c->frame.dist_u8.as<uint8_t>());
-    return score_against_reference8(c, out_score);
+    if (channels == 3 && row_bytes == w * 3) return score_against(c, tight8(pixels, w), out_score);  // scorer's layout
+    const Feed f{pixels, hipMemcpyHostToDevice, row_bytes, channels, 1u, 0u, true, unpack_rgb8, -1};
+    return score_against(c, f, out_score);
 }
 
 int ssimu2_error_map_rgb8(ssimu2_ctx* c, const uint8_t* ref, const uint8_t* dist, uint32_t w, uint32_t h,
@@ -1804,10 +1890,7 @@ int ssimu2_error_map_against_reference(ssimu2_ctx* c, const uint8_t* dist, float
 int ssimu2_linear_table(uint32_t bit_depth, float* out) {
     if (!out) return SSIMU2_ERR_INVALID_ARG;
     if (bit_depth < 8 || bit_depth > 16) return SSIMU2_ERR_UNSUPPORTED;
-    const float* t = host_table(bit_depth);
-    if (!t) return SSIMU2_ERR_OOM;
-    memcpy(out, t, ((size_t)1 << bit_depth) * sizeof(float));
-    return SSIMU2_OK;
+    return copy_table(1u << bit_depth, (1u << bit_depth) - 1u, out);
 }
 
 int ssimu2_score_rgb16(ssimu2_ctx* c, const uint16_t* ref, const uint16_t* dist, uint32_t w, uint32_t h,
@@ -1818,75 +1901,21 @@ int ssimu2_score_rgb16(ssimu2_ctx* c, const uint16_t* ref, const uint16_t* dist,
     if ((rc = check16(c, ref, bit_depth)) || (rc = check16(c, dist, bit_depth))) return rc;
     if (channels != 3) return c->fail(SSIMU2_ERR_UNSUPPORTED, "channels must be 3");
     if (!out_score) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_score");
-    if (c->blur_mode != SSIMU2_BLUR_FIR && (rc = rg_check_size(c, w, h))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if ((rc = ensure_capacity(c, w, h))) return rc;
-    c->ref.drop();  // the lin_ref pyramid is overwritten
-    const size_t bytes = (size_t)w * h * 3 * sizeof(uint16_t);
-    const float* tab = nullptr;
-    if ((rc = grow(c, c->hbd.ref16, bytes, "hipMalloc(16-bit frames)")) ||
-        (rc = grow(c, c->hbd.dist16, bytes, "hipMalloc(16-bit frames)")) ||
-        (rc = hbd_prepare(c, w, h, true, bit_depth, &tab)))
-        return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->hbd.ref16.p, ref, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->hbd.dist16.p, dist, bytes, hipMemcpyHostToDevice, c->stream));
-    const Src16 r = tight16(c->hbd.ref16, w, tab, bit_depth);
-    if ((rc = enqueue_score16(c, &r, tight16(c->hbd.dist16, w, tab, bit_depth), w, h))) return rc;
-    return ssimu2_wait(c, out_score);
+    return score_pair(c, tight16(ref, w, bit_depth), tight16(dist, w, bit_depth), w, h, out_score);
 }
 
 int ssimu2_set_reference_rgb16(ssimu2_ctx* c, const uint16_t* ref, uint32_t w, uint32_t h, uint32_t bit_depth) {
     REMOTE(c, set_reference_rgb16(c->remote, ref, w, h, bit_depth));
     int rc = check_args(c, ref, ref, w, h);
-    if (rc) return rc;
-    if ((rc = check16(c, ref, bit_depth))) return rc;
-    const bool fir = c->blur_mode == SSIMU2_BLUR_FIR;
-    if (!fir && (rc = rg_check_size(c, w, h))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if ((rc = ensure_capacity(c, w, h))) return rc;
-    const Pyramid p = make_pyramid(w, h);
-    if (!fir && (rc = rg_ensure(c, p))) return rc;
-    c->ref.drop();  // the lin_ref pyramid and the cached planes are overwritten
-    const size_t bytes = (size_t)w * h * 3 * sizeof(uint16_t);
-    const float* tab = nullptr;
-    if ((rc = grow(c, c->hbd.ref16, bytes, "hipMalloc(16-bit frames)")) ||
-        (rc = hbd_prepare(c, w, h, true, bit_depth, &tab)))
-        return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->hbd.ref16.p, ref, bytes, hipMemcpyHostToDevice, c->stream));
-    const Src16 r = tight16(c->hbd.ref16, w, tab, bit_depth);
-    if (fir) {  // linear pyramid and scale-0 planes, then the same caches as an 8-bit reference's (required here)
-        const Src16* src[1] = {&r};
-        float* lin[1] = {c->frame.lin_ref.as<float>()};
-        float* lin0[1] = {c->hbd.lin0_ref.as<float>()};
-        launch_pyramid16(c, p, 1, src, lin, lin0);
-        if (p.nscales >= 1) note_lin0(c, 1, -1, w, h);
-        if ((rc = cache_reference_fir(c, p, c->hbd.lin0_ref.p, false, true))) return rc;
-    } else {
-        rg_enqueue_reference(c, p, nullptr, &r);
-    }
-    return reference_set(c, w, h, true);
-}
-
-// Score the 16-bit frame at `src.px` (already on the device) against the cached reference.
-static int score_against_reference16(ssimu2_ctx* c, const Src16& src, double* out_score) {
-    int rc = enqueue_score16(c, nullptr, src, c->ref.w, c->ref.h);
-    if (rc) return rc;
-    return ssimu2_wait(c, out_score);
+    if (rc || (rc = check16(c, ref, bit_depth))) return rc;
+    return feed_reference(c, tight16(ref, w, bit_depth), w, h);
 }
 
 int ssimu2_score_against_reference_rgb16(ssimu2_ctx* c, const uint16_t* dist, uint32_t bit_depth, double* out_score) {
     REMOTE(c, score_against_reference_rgb16(c->remote, dist, bit_depth, out_score));
     int rc = check_against(c, out_score != nullptr);
     if (rc || (rc = check16(c, dist, bit_depth))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const uint32_t w = c->ref.w, h = c->ref.h;
-    const size_t bytes = (size_t)w * h * 3 * sizeof(uint16_t);
-    const float* tab = nullptr;
-    if ((rc = grow(c, c->hbd.dist16, bytes, "hipMalloc(16-bit frames)")) ||
-        (rc = hbd_prepare(c, w, h, false, bit_depth, &tab)))
-        return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->hbd.dist16.p, dist, bytes, hipMemcpyHostToDevice, c->stream));
-    return score_against_reference16(c, tight16(c->hbd.dist16, w, tab, bit_depth), out_score);
+    return score_against(c, tight16(dist, c->ref.w, bit_depth), out_score);
 }
 
 int ssimu2_score_against_reference_strided16(ssimu2_ctx* c, const uint16_t* pixels, uint32_t row_bytes,
@@ -1896,15 +1925,11 @@ int ssimu2_score_against_reference_strided16(ssimu2_ctx* c, const uint16_t* pixe
     if (rc || (rc = check16(c, pixels, bit_depth))) return rc;
     if (channels != 3 && channels != 4)
         return c->fail(SSIMU2_ERR_UNSUPPORTED, "channels must be 3 (RGB) or 4 (RGBA)");
-    const uint32_t w = c->ref.w, h = c->ref.h;
-    if ((row_bytes & 1u) || (uint64_t)row_bytes < (uint64_t)w * channels * 2)
+    if ((row_bytes & 1u) || (uint64_t)row_bytes < (uint64_t)c->ref.w * channels * 2)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "row_bytes odd or smaller than one row of 16-bit pixels");
-    HIP_TRY(c, hipSetDevice(c->device));
-    // rows are read where they are, padding and alpha skipped by the front end; the last row needs only its pixels
-    const size_t bytes = (size_t)row_bytes * (h - 1) + (size_t)w * channels * 2;
-    const float* tab = nullptr;
-    if ((rc = hbd_prepare(c, w, h, false, bit_depth, &tab)) || (rc = stage_upload(c, pixels, bytes))) return rc;
-    return score_against_reference16(c, Src16{c->stage.p, row_bytes, channels, tab, (1u << bit_depth) - 1u}, out_score);
+    // rows are read where they are, in `stage`: padding and alpha skipped by the front end
+    const Feed f{pixels, hipMemcpyHostToDevice, row_bytes, channels, 2u, (1u << bit_depth) - 1u, true, nullptr, -1};
+    return score_against(c, f, out_score);
 }
 
 int ssimu2_last_averages(ssimu2_ctx* c, double* out, int* out_num_scales) {
@@ -1956,14 +1981,10 @@ int ssimu2_score_batch_rgb8(ssimu2_ctx* c, const uint8_t* const* refs, const uin
         if (!refs[i] || !dists[i]) return c->fail(SSIMU2_ERR_INVALID_ARG, "null image pointer in the batch");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)w * h * 3, stride = (bytes + 15) & ~(size_t)15;
-    if ((rc = batch_stage(c, c->batch.u8_ref, refs, n, bytes, stride)) ||
-        (rc = batch_stage(c, c->batch.u8_dist, dists, n, bytes, stride))) {
-        (void)hipStreamSynchronize(c->stream);  // the caller may free its frames after any return
-        return rc;
-    }
-    rc = batch_run(c, c->batch.u8_ref.as<uint8_t>(), c->batch.u8_dist.as<uint8_t>(), stride, n, w, h, out_scores);
-    if (rc) (void)hipStreamSynchronize(c->stream);
-    return rc;
+    if (!(rc = batch_stage(c, c->batch.u8_ref, refs, n, bytes, stride)) &&
+        !(rc = batch_stage(c, c->batch.u8_dist, dists, n, bytes, stride)))
+        rc = batch_run(c, c->batch.u8_ref.as<uint8_t>(), c->batch.u8_dist.as<uint8_t>(), stride, n, w, h, out_scores);
+    return leave(c, rc);
 }
 
 int ssimu2_score_batch_against_reference(ssimu2_ctx* c, const uint8_t* const* dists, uint32_t n, double* out_scores) {
@@ -1975,13 +1996,9 @@ int ssimu2_score_batch_against_reference(ssimu2_ctx* c, const uint8_t* const* di
         if (!dists[i]) return c->fail(SSIMU2_ERR_INVALID_ARG, "null image pointer in the batch");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)c->ref.w * c->ref.h * 3, stride = (bytes + 15) & ~(size_t)15;
-    if ((rc = batch_stage(c, c->batch.u8_dist, dists, n, bytes, stride))) {
-        (void)hipStreamSynchronize(c->stream);
-        return rc;
-    }
-    rc = batch_run(c, nullptr, c->batch.u8_dist.as<uint8_t>(), stride, n, c->ref.w, c->ref.h, out_scores);
-    if (rc) (void)hipStreamSynchronize(c->stream);
-    return rc;
+    if (!(rc = batch_stage(c, c->batch.u8_dist, dists, n, bytes, stride)))
+        rc = batch_run(c, nullptr, c->batch.u8_dist.as<uint8_t>(), stride, n, c->ref.w, c->ref.h, out_scores);
+    return leave(c, rc);
 }
 
 int ssimu2_last_batch_averages(ssimu2_ctx* c, uint32_t item, double* out, int* out_num_scales) {
