@@ -22,6 +22,10 @@ SOURCES = ["ssimu2_hip.hip", "tq.cpp", "png_ingest.cpp", "remote_client.cpp"]
 INSTR_SOURCES = ["ssimu2_instrument.hip", "tq.cpp", "png_ingest.cpp", "remote_client.cpp"]  # ssimu2_instrument.hip includes ssimu2_hip.hip
 EXT_SOURCES = ["ssimu2_ext.hip", "tq.cpp", "png_ingest.cpp", "remote_client.cpp"]  # ssimu2_ext.hip includes ssimu2_hip.hip
 _PROGRAMS = ("oavif_host.c", "oavif_scored.cpp")  # linked against the library, not into it
+# The flags that shape device code: the libraries' compile lines, the ISA tests and scripts/isa_ab.py all take them here.
+DEVICE_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17",
+                "-ffp-contract=off",    # arithmetic contract: every FMA is an explicit fmaf()
+                "-fno-slp-vectorize")   # v_pk_*_f32 + operand shuffles are slower than scalar VALU here
 
 
 def _hipcc() -> str:
@@ -79,9 +83,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         targets = ((LIB_PATH, SOURCES), (INSTR_LIB_PATH, INSTR_SOURCES), (EXT_LIB_PATH, EXT_SOURCES))
         for target, sources in targets if force or libs_need_build() else ():
             tmp = target + f".tmp{os.getpid()}"
-            cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                   "-ffp-contract=off",  # arithmetic contract: every FMA is an explicit fmaf()
-                   "-fno-slp-vectorize",  # v_pk_*_f32 + operand shuffles are slower than scalar VALU here
+            cmd = [_hipcc(), *DEVICE_FLAGS, "-fPIC", "-shared",
                    "-fvisibility=hidden", "-fvisibility-inlines-hidden",  # exports = the headers' functions
                    "-Wall", "-Wno-unused-function", "-o", tmp]
             cmd += os.environ.get("OAVIF_AMD_EXTRA_HIPCC_FLAGS", "").split()  # A/B builds of experiments

@@ -121,30 +121,6 @@ void gaussian_taps(double sigma, float taps[5], float n2_out[3], float d1_out[3]
     }
 }
 
-// host twin of the device cbrt_repro (same IEEE sequence; this file is built with
-// -ffp-contract=off, fmaf is the correctly rounded libm/hardware fma)
-float cbrt_repro_host(float x) {
-    if (!(x > 0.0f)) return 0.0f;
-    uint32_t i;
-    memcpy(&i, &x, 4);
-    i = 0x54A21D2Au - i / 3u;
-    float y;
-    memcpy(&y, &i, 4);
-    float t = x * y;
-    t = t * y;
-    t = t * y;
-    const float e = 1.0f - t;
-    float p = fmaf(e, 14.0f / 81.0f, 2.0f / 9.0f);
-    p = fmaf(p, e, 1.0f / 3.0f);
-    p = p * e;
-    y = fmaf(y, p, y);
-    const float y2 = y * y;
-    float c = x * y2;
-    const float r = fmaf(c * c, c, -x);
-    c = fmaf(r, y2 * (-1.0f / 3.0f), c);
-    return c;
-}
-
 thread_local std::string g_create_error;
 
 // One buffer of a context: device memory, or (`host`) page-locked host memory that a kernel writes.  `cap` is in
@@ -1620,7 +1596,7 @@ static int ctx_create_impl(int device, void* hip_stream, ssimu2_ctx** out_ctx) {
                 k->lut[i] = (float)(v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4));
             }
             gaussian_taps(1.5, k->taps, k->rg_n2, k->rg_d1);
-            k->cbrt_bias = cbrt_repro_host(kOpsinBias);
+            k->cbrt_bias = cbrt_repro<true>(kOpsinBias);
             memcpy(k->weights, kWeightsHost, sizeof kWeightsHost);
             hipError_t ec = hipMemcpyToSymbol(HIP_SYMBOL(c_k), k, sizeof(DevConst));
             delete k;

@@ -42,7 +42,7 @@ constexpr float kOpsinBias = 0.0037930732552754493f;
 struct DevConst {
     float lut[256];     // 8-bit sRGB -> linear, fp32(rounded from fp64)
     float taps[5];      // FIR taps |d| = 0..4 of the sigma-1.5 recursive Gaussian
-    float cbrt_bias;    // cbrt_repro(kOpsinBias)
+    float cbrt_bias;    // cbrt_repro<true>(kOpsinBias)
     float rg_n2[3];     // the recursion itself (ssimu2_recursive.h): input gains of the three sections
     float rg_d1[3];     // ... and their feedback coefficients -2 cos(omega_k)
     double weights[108];
@@ -53,13 +53,21 @@ __constant__ DevConst c_k;
 
 // Cube root from IEEE mul/fma only (arguments are in [0, 2)): bit-trick seed for y = x^(-1/3), one third-order step
 // y (1 + e/3 + 2e^2/9 + 14e^3/81) with e = 1 - x y^3, c = x y^2, one residual-corrected Newton
-// step on c.  17 operations, max error 0.76 ulp.
-__device__ __forceinline__ float cbrt_repro(float x) {
-    uint32_t i = __float_as_uint(x);
+// step on c.  17 operations, max error 0.76 ulp.  The one definition: the kernels run it, and the host forms
+// c_k.cbrt_bias with it (this file is built with -ffp-contract=off, the host's fmaf is the correctly rounded fma).
+// GUARD: 0 for x <= 0, for inputs that were clamped to >= 0; without it x must be positive.
+template <bool GUARD>
+__host__ __device__ __forceinline__ float cbrt_repro(float x) {
+    uint32_t i = __builtin_bit_cast(uint32_t, x);
+#ifdef __HIP_DEVICE_COMPILE__
     // i / 3 as one multiply-high: floor(i * 0x55555556 / 2^32) == i / 3 for every i < 2^31
     // (checked exhaustively), and the bits of a float below 2.0 are below 2^30
-    i = 0x54A21D2Au - __umulhi(i, 0x55555556u);
-    float y = __uint_as_float(i);
+    i = __umulhi(i, 0x55555556u);
+#else
+    i = i / 3u;
+#endif
+    i = 0x54A21D2Au - i;
+    float y = __builtin_bit_cast(float, i);
     float t = x * y;
     t = t * y;
     t = t * y;
@@ -72,60 +80,43 @@ __device__ __forceinline__ float cbrt_repro(float x) {
     float c = x * y2;
     const float r = fmaf(c * c, c, -x);
     c = fmaf(r, y2 * (-1.0f / 3.0f), c);
-    return x > 0.0f ? c : 0.0f;  // branch-free guard (inputs are clamped to >= 0)
+    return GUARD ? (x > 0.0f ? c : 0.0f) : c;  // branch-free guard
 }
 
-__device__ __forceinline__ void linear_to_xyb(float r, float g, float b, float& X, float& Y,
-                                              float& B) {
-    float l = fmaf(kM00, r, fmaf(kM01, g, fmaf(kM02, b, kOpsinBias)));
-    float m = fmaf(kM10, r, fmaf(kM11, g, fmaf(kM12, b, kOpsinBias)));
-    float s = fmaf(kM20, r, fmaf(kM21, g, fmaf(kM22, b, kOpsinBias)));
-    l = fmaxf(l, 0.0f);
-    m = fmaxf(m, 0.0f);
-    s = fmaxf(s, 0.0f);
+// Linear RGB -> positive XYB as two halves (the marching converters issue the sRGB LUT reads of their next row
+// between them): the opsin mix, then clamp, cube roots and the XYB sums.
+__device__ __forceinline__ void opsin_mix(float r, float g, float b, float (&lms)[3]) {
+    lms[0] = fmaf(kM00, r, fmaf(kM01, g, fmaf(kM02, b, kOpsinBias)));
+    lms[1] = fmaf(kM10, r, fmaf(kM11, g, fmaf(kM12, b, kOpsinBias)));
+    lms[2] = fmaf(kM20, r, fmaf(kM21, g, fmaf(kM22, b, kOpsinBias)));
+}
+// CLAMP: the published clamp of the mixed values to >= 0 and the guarded cube root.  The marching kernels go without:
+// all they ever see is non-negative linear input (LUT entries and their 2x2 averages are >= 0, so every opsin sum is
+// >= the bias), for which clamp and guard can never act -- the same values.
+template <bool CLAMP>
+__device__ __forceinline__ void mixed_to_xyb(const float (&lms)[3], float (&v)[3]) {
+    float l = lms[0], m = lms[1], s = lms[2];
+    if (CLAMP) {
+        l = fmaxf(l, 0.0f);
+        m = fmaxf(m, 0.0f);
+        s = fmaxf(s, 0.0f);
+    }
     const float cb = c_k.cbrt_bias;
-    l = cbrt_repro(l) - cb;
-    m = cbrt_repro(m) - cb;
-    s = cbrt_repro(s) - cb;
+    l = cbrt_repro<CLAMP>(l) - cb;
+    m = cbrt_repro<CLAMP>(m) - cb;
+    s = cbrt_repro<CLAMP>(s) - cb;
     const float x = 0.5f * (l - m), y = 0.5f * (l + m);
-    B = (s - y) + 0.55f;
-    X = fmaf(x, 14.0f, 0.42f);
-    Y = y + 0.01f;
+    v[2] = (s - y) + 0.55f;
+    v[0] = fmaf(x, 14.0f, 0.42f);
+    v[1] = y + 0.01f;
 }
-
-// Same values as linear_to_xyb for non-negative linear inputs, which is all the marching kernel
-// ever sees (LUT entries and their 2x2 averages are >= 0, so every opsin sum is >= the bias):
-// the published clamp to zero and cbrt_repro's x > 0 guard can never act and are left out.
-__device__ __forceinline__ float cbrt_repro_pos(float x) {
-    uint32_t i = __float_as_uint(x);
-    // i / 3 as one multiply-high: floor(i * 0x55555556 / 2^32) == i / 3 for every i < 2^31
-    // (checked exhaustively), and the bits of a float below 2.0 are below 2^30
-    i = 0x54A21D2Au - __umulhi(i, 0x55555556u);
-    float y = __uint_as_float(i);
-    float t = x * y;
-    t = t * y;
-    t = t * y;
-    const float e = 1.0f - t;
-    float p = fmaf(e, 14.0f / 81.0f, 2.0f / 9.0f);
-    p = fmaf(p, e, 1.0f / 3.0f);
-    p = p * e;
-    y = fmaf(y, p, y);
-    const float y2 = y * y;
-    float c = x * y2;
-    const float r = fmaf(c * c, c, -x);
-    return fmaf(r, y2 * (-1.0f / 3.0f), c);
-}
-
-__device__ __forceinline__ void linear_to_xyb_pos(float r, float g, float b, float& X, float& Y,
-                                                  float& B) {
-    const float cb = c_k.cbrt_bias;
-    const float l = cbrt_repro_pos(fmaf(kM00, r, fmaf(kM01, g, fmaf(kM02, b, kOpsinBias)))) - cb;
-    const float m = cbrt_repro_pos(fmaf(kM10, r, fmaf(kM11, g, fmaf(kM12, b, kOpsinBias)))) - cb;
-    const float s = cbrt_repro_pos(fmaf(kM20, r, fmaf(kM21, g, fmaf(kM22, b, kOpsinBias)))) - cb;
-    const float x = 0.5f * (l - m), y = 0.5f * (l + m);
-    B = (s - y) + 0.55f;
-    X = fmaf(x, 14.0f, 0.42f);
-    Y = y + 0.01f;
+__device__ __forceinline__ void linear_to_xyb(float r, float g, float b, float& X, float& Y, float& B) {
+    float lms[3], v[3];
+    opsin_mix(r, g, b, lms);
+    mixed_to_xyb<true>(lms, v);
+    B = v[2];
+    X = v[0];
+    Y = v[1];
 }
 
 // symmetric 9-tap in the contract's operation order: one mul, four FMAs.
@@ -153,6 +144,42 @@ __device__ __forceinline__ float div_rn(float a, float b) {
     q = fmaf(e1, r, q);
     const float e2 = fmaf(-b, q, a);
     return fmaf(e2, r, q);
+}
+
+// ---- the per-pixel terms ----------------------------------------------------------------------
+// What the score sums and the error map weighs, of one pixel of one channel: every kernel that forms them -- FIR or
+// recursive blur, score or map -- calls these three, so score and map cannot drift apart (the CPU checker mirrors them).
+// The SSIM term from the five blurred values.
+__device__ __forceinline__ float ssim_term(float mu1, float mu2, float s11, float s22, float s12) {
+    const float mu11 = mu1 * mu1, mu22 = mu2 * mu2, mu12 = mu1 * mu2;
+    const float dm = mu1 - mu2;
+    const float num_m = fmaf(-dm, dm, 1.0f);
+    const float num_s = fmaf(2.0f, s12 - mu12, kC2);
+    const float denom_s = ((s11 - mu11) + (s22 - mu22)) + kC2;
+    const float d = 1.0f - div_rn(num_m * num_s, denom_s);
+    return fmaxf(d, 0.0f);
+}
+// The edge-difference quotient (1+ea)/(1+eb) - 1, written without its cancellation, from the two blurred values and
+// the two frames' pixels.  RN: the correctly rounded quotient, the reference's bits (the recursive modes, whose map is
+// held to the checker bit for bit).  Otherwise one reciprocal times the difference (<= 1.5 ulp, the FIR kernels): the
+// checker evaluates the FIR map in fp64, so div_rn's rounding bought no agreement there.
+template <bool RN>
+__device__ __forceinline__ float edge_quotient(float mu1, float mu2, float r1, float r2) {
+    const float ea = fabsf(r2 - mu2), eb = fabsf(r1 - mu1);
+    return RN ? div_rn(ea - eb, 1.0f + eb) : (ea - eb) * __builtin_amdgcn_rcpf(1.0f + eb);
+}
+// The six terms d, d^4, art, art^4, det, det^4 in statistic order, handed to put(k, term) one by one: a score adds
+// them to its sums, a map collects them for map_density.
+template <typename Put>
+__device__ __forceinline__ void six_terms(float d, float e, Put put) {
+    const float art = fmaxf(e, 0.0f), det = fmaxf(-e, 0.0f);
+    const float d2 = d * d, a2 = art * art, t2 = det * det;
+    put(0, d);
+    put(1, d2 * d2);
+    put(2, art);
+    put(3, a2 * a2);
+    put(4, det);
+    put(5, t2 * t2);
 }
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -624,35 +651,17 @@ struct MapCoef {
 
 // The six per-pixel terms whose plane means / L4 norms are the averages, and the channel's
 // density from them: sum of mc[k] * term[k] in term order (the error map's definition).
-__device__ __forceinline__ float map_density(float d, float d4, float art, float a4, float det, float t4,
-                                             const float (&mc)[6]) {
-    float v = mc[0] * d;
-    v = fmaf(mc[1], d4, v);
-    v = fmaf(mc[2], art, v);
-    v = fmaf(mc[3], a4, v);
-    v = fmaf(mc[4], det, v);
-    return fmaf(mc[5], t4, v);
+__device__ __forceinline__ float map_density(const float (&t)[6], const float (&mc)[6]) {
+    float v = mc[0] * t[0];
+#pragma unroll
+    for (int k = 1; k < 6; ++k) v = fmaf(mc[k], t[k], v);
+    return v;
 }
+// Where term k of channel c sits among a scale's 18 statistics, as k_finalize reads them: 0..5 ssim (c*2 + n),
+// 6..17 edge (c*4 + j).
+__device__ __forceinline__ int term_stat(int c, int k) { return k < 2 ? c * 2 + k : 6 + c * 4 + (k - 2); }
 
 // ---- converter waves ------------------------------------------------------------------------------
-// opsin mix and the rest of linear_to_xyb_pos as two halves (same operations in the same order),
-// so that the sRGB LUT reads of the next row can be issued between them.
-__device__ __forceinline__ void opsin_mix(float r, float g, float b, float (&lms)[3]) {
-    lms[0] = fmaf(kM00, r, fmaf(kM01, g, fmaf(kM02, b, kOpsinBias)));
-    lms[1] = fmaf(kM10, r, fmaf(kM11, g, fmaf(kM12, b, kOpsinBias)));
-    lms[2] = fmaf(kM20, r, fmaf(kM21, g, fmaf(kM22, b, kOpsinBias)));
-}
-__device__ __forceinline__ void mixed_to_xyb_pos(const float (&lms)[3], float (&v)[3]) {
-    const float cb = c_k.cbrt_bias;
-    const float l = cbrt_repro_pos(lms[0]) - cb;
-    const float m = cbrt_repro_pos(lms[1]) - cb;
-    const float s = cbrt_repro_pos(lms[2]) - cb;
-    const float x = 0.5f * (l - m), y = 0.5f * (l + m);
-    v[2] = (s - y) + 0.55f;
-    v[0] = fmaf(x, 14.0f, 0.42f);
-    v[1] = y + 0.01f;
-}
-
 // Per-lane read cursor of a converter lane over one frame: address of this lane's
 // (column-clamped) pixel in the next row to load, advanced by one row pitch per load.
 //   u8 frames (scale 0): ONE unaligned dword load per pixel -- R | G << 8 | B << 16 | the next
@@ -798,9 +807,9 @@ __device__ __forceinline__ void march_convert_rows(f2 (*ring)[3][MRW], const flo
         if (CACHED) {                                                                          \
             _Pragma("unroll") for (int c_ = 0; c_ < 3; ++c_) a_[c_] = __uint_as_float(raw0[J][c_]); \
         } else {                                                                               \
-            mixed_to_xyb_pos(m0_, a_);                                                         \
+            mixed_to_xyb<false>(m0_, a_);                                                      \
         }                                                                                      \
-        if (TWO) mixed_to_xyb_pos(m1_, b_);                                                    \
+        if (TWO) mixed_to_xyb<false>(m1_, b_);                                                 \
         if (!(all_cols && rok_)) { /* uniform; the asm keeps it a branch, not 12 selects */    \
             asm volatile("; zero padding");                                                    \
             const bool keep_ = col_ok && rok_;                                                 \
@@ -955,35 +964,21 @@ __device__ __forceinline__ void march_v(const lds_vu64* rp, float (&win)[5][9], 
     const float r1 = ctr.x(), r2 = ctr.y();
     const float mu1 = v[0], mu2 = v[1];
     const float s11 = MODE == MARCH_REFBLUR ? c_s11 : v[2], s22 = v[3], s12 = v[4];
-    const float mu11 = mu1 * mu1, mu22 = mu2 * mu2, mu12 = mu1 * mu2;
-    const float dm = mu1 - mu2;
-    const float num_m = fmaf(-dm, dm, 1.0f);
-    const float num_s = fmaf(2.0f, s12 - mu12, kC2);
-    const float denom_s = ((s11 - mu11) + (s22 - mu22)) + kC2;
-    float d = 1.0f - div_rn(num_m * num_s, denom_s);
-    d = fmaxf(d, 0.0f);
-    const float ea = fabsf(r2 - mu2), eb = fabsf(r1 - mu1);
-    // == (1+ea)/(1+eb) - 1, no cancellation.  One reciprocal times the difference (<= 1.5 ulp): the checker
-    // evaluates this map in fp64, so the correctly rounded fp32 quotient of div_rn bought no agreement.
-    float e = (ea - eb) * __builtin_amdgcn_rcpf(1.0f + eb);
+    float d = ssim_term(mu1, mu2, s11, s22, s12);
+    float e = edge_quotient<false>(mu1, mu2, r1, r2);
     if (edge) {  // uniform; the asm keeps it a branch
         asm volatile("; right image edge");
         d = ok ? d : 0.0f;  // column inside the image?
         e = ok ? e : 0.0f;
     }
-    const float art = fmaxf(e, 0.0f), det = fmaxf(-e, 0.0f);
-    const float d2 = d * d, a2 = art * art, t2 = det * det;
     if (MODE == MARCH_MAP) {  // this channel's density, one row per step
-        if (ok && rb.active) *rb.s11 = map_density(d, d2 * d2, art, a2 * a2, det, t2 * t2, mc);
+        float tm[6];
+        six_terms(d, e, [&](int k, float term) { tm[k] = term; });
+        if (ok && rb.active) *rb.s11 = map_density(tm, mc);
         rb.s11 += rb.pitch;
         return;
     }
-    acc[0] += d;
-    acc[1] += d2 * d2;
-    acc[2] += art;
-    acc[3] += a2 * a2;
-    acc[4] += det;
-    acc[5] += t2 * t2;
+    six_terms(d, e, [&](int k, float term) { acc[k] += term; });
 }
 
 // XCD-aware tile order.  Workgroups are dealt to the eight XCDs round-robin by blockIdx (each XCD has its own
@@ -1068,11 +1063,8 @@ __device__ __forceinline__ void march_body(const MarchPlan& plan, const MapCoef*
     // MARCH_MAP: coefficients of this channel's six terms (d, d^4, art, art^4, det, det^4)
     float mc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (MODE == MARCH_MAP) {
-        const int cc = max(ch, 0);  // statistic index as k_finalize reads it: 0..5 ssim (c*2+n), 6..17 edge (c*4+k)
-        mc[0] = coef->c[sc][cc * 2];
-        mc[1] = coef->c[sc][cc * 2 + 1];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) mc[2 + k] = coef->c[sc][6 + cc * 4 + k];
+        for (int k = 0; k < 6; ++k) mc[k] = coef->c[sc][term_stat(max(ch, 0), k)];
     }
     {
         // this lane's pixel in output row y0 of its channel's planes (column clamped: lanes

@@ -382,52 +382,6 @@ __global__ __launch_bounds__(REF ? 128 : 192) __attribute__((amdgpu_waves_per_eu
 }
 
 // ---- vertical pass (+ maps) -----------------------------------------------------------------------
-// The SSIM and edge-difference terms of one pixel from its five blurred values and the two frames
-// (the expressions of march_v; products rounded as there).
-__device__ __forceinline__ void rg_maps_pixel(float mu1, float mu2, float s11, float s22, float s12, float r1,
-                                              float r2, double (&acc)[6]) {
-    const float mu11 = mu1 * mu1, mu22 = mu2 * mu2, mu12 = mu1 * mu2;
-    const float dm = mu1 - mu2;
-    const float num_m = fmaf(-dm, dm, 1.0f);
-    const float num_s = fmaf(2.0f, s12 - mu12, kC2);
-    const float denom_s = ((s11 - mu11) + (s22 - mu22)) + kC2;
-    float d = 1.0f - div_rn(num_m * num_s, denom_s);
-    d = fmaxf(d, 0.0f);
-    const float ea = fabsf(r2 - mu2), eb = fabsf(r1 - mu1);
-    const float e = div_rn(ea - eb, 1.0f + eb);  // == (1+ea)/(1+eb) - 1, no cancellation
-    const float art = fmaxf(e, 0.0f), det = fmaxf(-e, 0.0f);
-    const float d2 = d * d, a2 = art * art, t2 = det * det;
-    acc[0] += (double)d;
-    acc[1] += (double)(d2 * d2);
-    acc[2] += (double)art;
-    acc[3] += (double)(a2 * a2);
-    acc[4] += (double)det;
-    acc[5] += (double)(t2 * t2);
-}
-
-// The same expressions as rg_maps_pixel, the six terms returned in fp32 (the error-map pass; rg_maps_pixel is
-// left as it is so that the score kernels' code does not move).
-__device__ __forceinline__ void rg_map_terms(float mu1, float mu2, float s11, float s22, float s12, float r1,
-                                             float r2, float (&t)[6]) {
-    const float mu11 = mu1 * mu1, mu22 = mu2 * mu2, mu12 = mu1 * mu2;
-    const float dm = mu1 - mu2;
-    const float num_m = fmaf(-dm, dm, 1.0f);
-    const float num_s = fmaf(2.0f, s12 - mu12, kC2);
-    const float denom_s = ((s11 - mu11) + (s22 - mu22)) + kC2;
-    float d = 1.0f - div_rn(num_m * num_s, denom_s);
-    d = fmaxf(d, 0.0f);
-    const float ea = fabsf(r2 - mu2), eb = fabsf(r1 - mu1);
-    const float e = div_rn(ea - eb, 1.0f + eb);
-    const float art = fmaxf(e, 0.0f), det = fmaxf(-e, 0.0f);
-    const float d2 = d * d, a2 = art * art, t2 = det * det;
-    t[0] = d;
-    t[1] = d2 * d2;
-    t[2] = art;
-    t[3] = a2 * a2;
-    t[4] = det;
-    t[5] = t2 * t2;
-}
-
 // The recursion of one plane down this lane's column, PF batches of ten rows in a register queue
 // (three in flight under the one consumed).  Everything that counts in vmcnt is unconditional:
 // rows behind the image load the last row (and are replaced by the published zero padding in the
@@ -593,13 +547,11 @@ __device__ __forceinline__ void rg_v_body(const RgPlan& __restrict__ p, const Rg
             const float* g_r1 = p.xa[sc] + (size_t)ch * n + xc;
             const float* g_r2 = p.xb[sc] + (size_t)ch * n + xc;
             double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // !MAP
-            float mc[6];  // MAP; statistic index as k_finalize reads it: 0..5 ssim (c*2 + n), 6..17 edge (c*4 + j)
+            float mc[6];  // MAP: coefficients of this channel's six terms
             float* dens = nullptr;
             if constexpr (MAP) {
-                mc[0] = m->coef.c[sc][ch * 2];
-                mc[1] = m->coef.c[sc][ch * 2 + 1];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) mc[2 + k] = m->coef.c[sc][6 + ch * 4 + k];
+                for (int k = 0; k < 6; ++k) mc[k] = m->coef.c[sc][term_stat(ch, k)];
                 dens = m->dens[sc] + (size_t)ch * w * h + xc;
             }
             float g[RG_PF][2][4];
@@ -628,13 +580,16 @@ __device__ __forceinline__ void rg_v_body(const RgPlan& __restrict__ p, const Rg
                             const float mu2 = s_out[b & 1][0][j0 + jj][lane];
                             const float s22 = s_out[b & 1][1][j0 + jj][lane];
                             const float s12 = s_out[b & 1][2][j0 + jj][lane];
+                            const float d = ssim_term(g[u][jj][0], mu2, g[u][jj][1], s22, s12);
+                            const float e = edge_quotient<true>(g[u][jj][0], mu2, g[u][jj][2], g[u][jj][3]);
                             if constexpr (MAP) {
                                 float t[6];
-                                rg_map_terms(g[u][jj][0], mu2, g[u][jj][1], s22, s12, g[u][jj][2], g[u][jj][3], t);
-                                if (ok) dens[(size_t)r * w] = map_density(t[0], t[1], t[2], t[3], t[4], t[5], mc);
+                                six_terms(d, e, [&](int k, float term) { t[k] = term; });
+                                if (ok) dens[(size_t)r * w] = map_density(t, mc);
                             } else {
+                                // each fp32 term converted to fp64, per lane
                                 double z[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-                                rg_maps_pixel(g[u][jj][0], mu2, g[u][jj][1], s22, s12, g[u][jj][2], g[u][jj][3], z);
+                                six_terms(d, e, [&](int k, float term) { z[k] += (double)term; });
                                 if (ok) {
 #pragma unroll
                                     for (int k = 0; k < 6; ++k) acc[k] += z[k];
@@ -662,9 +617,7 @@ __device__ __forceinline__ void rg_v_body(const RgPlan& __restrict__ p, const Rg
                 double sum = s_part[0][k];
 #pragma unroll
                 for (int mw = 1; mw < RG_MAPS_WAVES; ++mw) sum += s_part[mw][k];
-                // statistic index as k_finalize reads it: 0..5 ssim (c*2 + n), 6..17 edge (c*4 + j)
-                const int stat = k < 2 ? ch * 2 + k : 6 + ch * 4 + (k - 2);
-                p.part[sc][(size_t)stat * p.vgroups[sc] + cg] = sum;
+                p.part[sc][(size_t)term_stat(ch, k) * p.vgroups[sc] + cg] = sum;
             }
         }
     }

@@ -129,7 +129,7 @@ def decoded_like(dist, channels, pad, seed):
 # * k_finalize: score = the published polynomial of sum_j w_j |avg_j| (oavif_amd/csrc/ssimu2_kernels.h).  Given the
 #   device's own averages, oracle.score_from_averages differs from it only in the order of that fp64 sum (a shuffle
 #   tree against a running sum: ~1e-16 relative) and in device against host pow(): FINALIZE_TOL.  No scale: 100 exactly.
-# * Recursive modes: k_rg_v sums each fp32 term converted to fp64 (rg_maps_pixel, ssimu2_recursive.h), per lane,
+# * Recursive modes: k_rg_v sums each fp32 term converted to fp64 (rg_v_body, ssimu2_recursive.h), per lane,
 #   then over lanes, waves and column groups, and k_finalize over the groups' partials, all in fp64; the reference
 #   takes the mean in extended precision.  A sum of n non-negative values in fp64, in any order, is within (n - 1) *
 #   2^-53 of the exact sum, relatively; the division by the pixel count and the two square roots of an L4 norm add a
@@ -249,7 +249,7 @@ def check_against_terms(oracle, score, avg, ns, ref, dist, mode, what, kavg=None
 
 # ---- the error map -----------------------------------------------------------------------------------------------
 #
-# Recursive modes: k_rg_vmap forms the reference's terms (rg_map_terms: div_rn for both quotients), map_density and
+# Recursive modes: k_rg_vmap forms the reference's terms (edge_quotient<true>: div_rn for both quotients), map_density and
 # k_map_compose restate compose()'s order, and the coefficients are the host's: the map equals the reference bit for
 # bit.  FIR: k_march_map shares march_v's edge quotient, (ea - eb) * rcp(1 + eb).  All terms and coefficients are
 # non-negative, so relative errors add without cancellation, per pixel, in units of 2^-24:

@@ -2,28 +2,20 @@
 cross-compiles without a GPU).  The occupancy arguments of DESIGN.md section 4 rest on them:
 the marching kernels need <= 80 VGPRs and ~50 KB of LDS for three 8-wave workgroups per CU (six
 waves per SIMD); the recursive horizontal pass needs its LDS under a third of the CU's 160 KB;
-nothing may spill.  CPU only (one device-only compile of the scorer translation unit, ~40 s)."""
+nothing may spill.  CPU only (the device-only compile of the scorer translation unit that isa_text.py shares, ~40 s)."""
 import os
 import re
-import shutil
-import subprocess
+import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "oavif_amd", "csrc", "ssimu2_hip.hip")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import isa_text  # noqa: E402
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc missing")
-    out = tmp_path_factory.mktemp("isa") / "scorer.s"
-    # the flags of oavif_amd/build.py that shape device code
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
-                    "-S", "--cuda-device-only", "-o", str(out), SRC], check=True, capture_output=True)
-    text = open(out).read()
+def kernels():
+    text = isa_text.scorer_asm()
     meta = {}
     for block in text.split("- .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)

@@ -1,5 +1,5 @@
 """Static instruction budget of k_march's two loops, read from the compiler's own assembly (hipcc cross-compiles
-without a GPU; CPU only, one device-only compile of the scorer translation unit).
+without a GPU; CPU only, the device-only compile of the scorer translation unit that isa_text.py shares).
 
 - The converter loops form no load address with VALU: the row base is uniform, so every global load takes the
   SGPR-base form with a 32-bit lane offset (global_load_dword v, v_off, s[base:base+1]); a 64-bit VALU add
@@ -9,13 +9,13 @@ without a GPU; CPU only, one device-only compile of the scorer translation unit)
 import collections
 import os
 import re
-import shutil
-import subprocess
+import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "oavif_amd", "csrc", "ssimu2_hip.hip")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import isa_text  # noqa: E402
+
 KERNEL = "_ZN6ssimu27k_marchENS_9MarchPlanE"
 # VALU instructions in the blur loop of k_march (nine unrolled steps) with the edge quotient computed by div_rn
 BLUR_LOOP_VALU_BEFORE = 1430
@@ -23,15 +23,8 @@ STEPS_PER_LOOP = 9
 
 
 @pytest.fixture(scope="module")
-def loops(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc missing")
-    out = tmp_path_factory.mktemp("isa") / "scorer.s"
-    # the flags of oavif_amd/build.py that shape device code
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
-                    "-S", "--cuda-device-only", "-o", str(out), SRC], check=True, capture_output=True)
-    body = open(out).read().split(KERNEL + ":")[1].split("s_endpgm")[0]
+def loops():
+    body = isa_text.scorer_asm().split(KERNEL + ":")[1].split("s_endpgm")[0]
     # instructions of each outermost loop, keyed by its header block (the compiler's loop annotations)
     found = collections.defaultdict(list)
     cur = None
