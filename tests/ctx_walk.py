@@ -15,8 +15,8 @@ from collections import namedtuple
 import numpy as np
 
 import gpu_cases
+from hbd_cases import hbd_distort, lift, rows16, to_depth
 from oavif_amd import _lib, synth
-from test_gpu_hbd import decoded_like16, hbd_distort, lift
 
 # ---- frames ----------------------------------------------------------------------------------------------------------
 # the smallest sizes at which each buffer rule and kernel shape changes
@@ -29,7 +29,7 @@ SIZES = {"N": (7, 7),        # no scale: score 100, zero map, nothing launched b
 SIZE_ORDER = sorted(SIZES, key=lambda z: SIZES[z][0] * SIZES[z][1])
 DEPTHS = (10, 12, 16)
 LAYOUTS8 = ((4, 0), (4, 3), (3, 5))      # (channels, pad bytes) of gpu_cases.decoded_like
-LAYOUTS16 = ((4, 0), (4, 2), (3, 3))     # (channels, pad samples) of decoded_like16: 0, 4 and 6 bytes, all even
+LAYOUTS16 = ((4, 0), (4, 2), (3, 3))     # (channels, pad samples) of hbd_cases.rows16: 0, 4 and 6 bytes, all even
 BATCH_N = (1, 3, 17)
 MODE_NAMES = ("fir", "recursive", "recursive_fma")
 MIXED = (12, 10)    # the mixed pair: the reference at depth 12, the distorted frame at depth 10
@@ -60,13 +60,10 @@ def frame16(size, k, depth):
     detail added, 1 hbd_distort of it, 2 the second 8-bit distortion lifted (257 u) and cut down to the depth."""
     def make():
         w, h = SIZES[size]
-        top = (1 << depth) - 1
         if k == 2:
             return np.ascontiguousarray(lift(frame8(size, 2)) >> np.uint16(16 - depth))
-        rng = np.random.default_rng(1000 * depth + w + h)
-        u = frame8(size, 0).astype(np.int64)
-        ref = np.clip(u * top // 255 + rng.integers(-(top // 255), top // 255 + 1, u.shape), 0, top).astype(np.uint16)
-        return np.ascontiguousarray(ref if k == 0 else hbd_distort(ref, depth, seed=depth + k))
+        ref = to_depth(frame8(size, 0), depth, 1000 * depth + w + h)
+        return ref if k == 0 else np.ascontiguousarray(hbd_distort(ref, depth, seed=depth + k))
     return _memo(_HOST, ("u16", size, k, depth), make)
 
 
@@ -78,7 +75,7 @@ def strided8(size, k, layout):
 def strided16(size, k, layout, depth):
     w, h = SIZES[size]
     return _memo(_HOST, ("s16", size, k, layout, depth),
-                 lambda: decoded_like16(frame16(size, k, depth), *layout, seed=w + h + depth))
+                 lambda: rows16(frame16(size, k, depth), *layout, seed=w + h + depth))
 
 
 def batch_pairs(size, n):

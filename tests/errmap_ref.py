@@ -4,7 +4,12 @@ multiply-add of fp32 operands is correctly rounded (`_fma`), and the map's coeff
 expression (`coefficients`).  `kernel_averages` are the 108 averages of those terms in fp64: what the kernels' sums
 of the same terms approach (the recursive modes exactly up to fp64 summation).  Given the
 segment rows of every scale, `kernel_averages`, `averages` and `reference_map` also return, from the same terms, the
-SSIM averages summed in k_march's own order (tests/fir_sums.py)."""
+SSIM averages summed in k_march's own order (tests/fir_sums.py).
+
+This module owns the fp32 checker route, stated once over scale-0 linear planes: the pyramid rule (`scales`), then XYB,
+`channel_terms` and the averages (`terms_lin`, `kernel_averages_lin`, which streams one channel at a time, and
+`score_lin`).  What makes the planes is a front end: `linear_planes` here for 8-bit frames (`terms`, `kernel_averages`,
+`reference_map`), tests/hbd_ref.py for 16-bit ones, tests/test_gpu_alpha.py for a composite's codes."""
 from __future__ import annotations
 
 import numpy as np
@@ -35,9 +40,14 @@ def _fma(a, b, c):
     return s.astype(F32)
 
 
-def _scales(orc, img):
-    """linear-light planes (3, h, w) of every scored scale (the scorer's pyramid rule)."""
-    lin = orc.srgb_lut()[img].transpose(2, 0, 1).copy()
+def linear_planes(orc, img):
+    """(3, h, w) float32 scale-0 linear planes of an (h, w, 3) uint8 frame: the checker's table."""
+    return orc.srgb_lut()[img].transpose(2, 0, 1).copy()
+
+
+def scales(orc, lin):
+    """The scorer's pyramid rule over (3, h, w) scale-0 linear planes: -> the linear planes of every scored scale.  Every
+    fp32 route starts here, whatever made the planes (8-bit frames above, hbd_ref.linear_planes, a composite's)."""
     out = []
     for s in range(6):
         h, w = lin.shape[1:]
@@ -66,15 +76,21 @@ def channel_terms(orc, a, b, blur):
     return np.stack([d, d2 * d2, art, a2 * a2, det, t2 * t2])
 
 
-def _xyb_pairs(orc, ref, dist):
-    for l1, l2 in zip(_scales(orc, ref), _scales(orc, dist)):
+def _xyb_pairs(orc, lin1, lin2):
+    for l1, l2 in zip(scales(orc, lin1), scales(orc, lin2)):
         yield orc.linear_to_xyb(l1), orc.linear_to_xyb(l2)
 
 
-def terms(orc, ref, dist, blur):
-    """-> per scale: (3, 6, h_s, w_s) float32 terms d, d^4, art, art^4, det, det^4."""
+def terms_lin(orc, lin1, lin2, blur):
+    """-> per scale: (3, 6, h_s, w_s) float32 terms d, d^4, art, art^4, det, det^4 of two frames given as scale-0 linear
+    planes (reference first)."""
     return [np.stack([channel_terms(orc, x1[c], x2[c], blur) for c in range(3)])
-            for x1, x2 in _xyb_pairs(orc, ref, dist)]
+            for x1, x2 in _xyb_pairs(orc, lin1, lin2)]
+
+
+def terms(orc, ref, dist, blur):
+    """terms_lin of two (h, w, 3) uint8 frames."""
+    return terms_lin(orc, linear_planes(orc, ref), linear_planes(orc, dist), blur)
 
 
 def _put(avg, s, c, m):
@@ -108,12 +124,12 @@ def _means(t):
     return [float(t[k].sum(dtype=np.longdouble) / n) for k in range(6)]
 
 
-def kernel_averages(orc, ref, dist, blur, seg_rows=None):
-    """-> ((6, 18) float64, nscales): averages(terms(orc, ref, dist, blur)), one channel's terms at a time (a 4K pair's
-    terms would take about 1 GB at once).  With `seg_rows` (by scale): -> (those, nscales, (6, 6) averages 0..5 in the
-    kernel's order), from the same pass over the terms."""
+def kernel_averages_lin(orc, lin1, lin2, blur, seg_rows=None):
+    """-> ((6, 18) float64, nscales): averages(terms_lin(orc, lin1, lin2, blur)), one channel's terms at a time (a 4K
+    pair's terms would take about 1 GB at once).  With `seg_rows` (by scale): -> (those, nscales, (6, 6) averages 0..5
+    in the kernel's order), from the same pass over the terms."""
     avg, kord, ns = np.zeros((6, 18)), np.zeros((6, 6)), 0
-    for s, (x1, x2) in enumerate(_xyb_pairs(orc, ref, dist)):
+    for s, (x1, x2) in enumerate(_xyb_pairs(orc, lin1, lin2)):
         for c in range(3):
             t = channel_terms(orc, x1[c], x2[c], blur)
             _put(avg, s, c, _means(t))
@@ -121,6 +137,18 @@ def kernel_averages(orc, ref, dist, blur, seg_rows=None):
                 _put_sums(kord, s, c, t, seg_rows[s])
         ns = s + 1
     return (avg, ns) if seg_rows is None else (avg, ns, kord)
+
+
+def kernel_averages(orc, ref, dist, blur, seg_rows=None):
+    """kernel_averages_lin of two (h, w, 3) uint8 frames."""
+    return kernel_averages_lin(orc, linear_planes(orc, ref), linear_planes(orc, dist), blur, seg_rows)
+
+
+def score_lin(orc, lin1, lin2, blur):
+    """-> (score, (6, 18) averages, nscales) of two frames given as scale-0 linear planes in the checker's blur mode
+    `blur`: the checker's score of kernel_averages_lin, 100 without a scale."""
+    avg, ns = kernel_averages_lin(orc, lin1, lin2, blur)
+    return (orc.score_from_averages(avg, ns) if ns else 100.0), avg, ns
 
 
 def weighted_terms(orc, avg, nscales):

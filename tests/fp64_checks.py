@@ -113,14 +113,8 @@ def check(score, avg, nscales, exp: dict, mode: str, what, kind: str = "natural"
 
 def reference_levels(ref, dist, scales):
     """-> {scale: (lin1, lin2, xyb1, xyb2)} fp64 (3, h_s, w_s) planes of the reference at the scales asked for."""
-    out = {}
     lin1, lin2 = ref64.srgb_to_linear(np.moveaxis(ref, 2, 0)), ref64.srgb_to_linear(np.moveaxis(dist, 2, 0))
-    for s in range(max(scales) + 1):
-        if s:
-            lin1, lin2 = ref64.downsample2(lin1), ref64.downsample2(lin2)
-        if s in scales:
-            out[s] = (lin1, lin2, ref64.to_xyb(lin1), ref64.to_xyb(lin2))
-    return out
+    return ref64.levels(lin1, lin2, scales)
 
 
 def lin_ulps(got, exp) -> float:

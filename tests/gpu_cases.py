@@ -1,20 +1,31 @@
-"""Test-side helpers shared by the GPU modules: the blur-mode table (scorer mode -> the checker's mode of the same
-blur), synthetic content kinds and the pairs that reach the clamps and the zero paths, libavif-like padded RGB(A)
-layouts, the hold of a score's averages and of k_finalize to the kernel-order terms (check_against_terms) and of the
-FIR d / d^4 averages to k_march's own summing order (check_fir_sums, tests/fir_sums.py), the error-map check against
-tests/errmap_ref.py (check_map), and
-what the batch modules share: the batch rule's rows and bound, seeded neighbours and the comparison of score and
-averages for bits; and what puts foreign content around a call: a stale pair score of a larger size (stale), the cached
-reference scored against itself (scrub) and device frames between margins of random bytes (in_margins)."""
+"""Test-side helpers shared by the GPU modules.  This module owns:
+
+* the blur-mode table (scorer mode -> the checker's mode of the same blur) and the per-mode context fixtures every GPU
+  module builds its `ctxs` / `ictxs` / `ictx` on (mode_contexts, contexts_fixture, ictx);
+* 8-bit content: the synthetic kinds, the pairs that reach the clamps and the zero paths, libavif-like padded RGB(A)
+  layouts (16-bit content and layouts: tests/hbd_cases.py);
+* the one hold of a score's averages to a reference (hold_averages) and the one bound of a FIR average
+  (averages_rtol), with their callers: check_against_terms (averages and k_finalize against the kernel-order terms),
+  check_fir_sums (the FIR d / d^4 averages against k_march's own summing order, tests/fir_sums.py) and
+  check_item_against_terms (a batch item); the error-map check against tests/errmap_ref.py (check_map);
+* what the batch modules share: the batch rule's rows, seeded neighbours, the comparison of score and averages for
+  bits, frames packed into one device buffer (on_device) and the golden pair's bits (golden_bits);
+* what puts foreign content around a call: a stale pair score of a larger size (stale), the cached reference scored
+  against itself (scrub) and device frames between margins of random bytes (in_margins).
+
+The references themselves live elsewhere: tests/errmap_ref.py (the fp32 checker route), tests/ssimu2_fp64.py (fp64;
+its scale_size is the one halving rule), tests/hbd_ref.py (their 16-bit front ends)."""
 from __future__ import annotations
 
 import numpy as np
+import pytest
 
-from oavif_amd import _lib, synth
+from oavif_amd import Ssimu2, _lib, synth
 from oracle import ssimu2_oracle as orc
 
 import errmap_ref
 import fir_sums
+from ssimu2_fp64 import scale_size
 
 # mode name -> (ssimu2_ctx_set_blur mode, the checker's OR_BLUR_* of the same blur)
 MODES = {"fir": (_lib.BLUR_FIR, orc.BLUR_FIR),
@@ -34,6 +45,33 @@ SIZES = [
     (333, 217), (513, 259), (1921, 1083),                        # ragged
     (9, 1000), (1000, 9), (4000, 8), (8, 4000),                  # very tall, very wide
 ]
+
+
+def mode_contexts(**kw):
+    """Yields {mode name: Ssimu2(0, blur=that mode, **kw)} over MODES and closes the contexts afterwards."""
+    out = {name: Ssimu2(0, blur=mode, **kw) for name, (mode, _) in MODES.items()}
+    yield out
+    for s in out.values():
+        s.close()
+
+
+def contexts_fixture(**kw):
+    """A module-scoped fixture of mode_contexts(**kw) (plain, instrumented=True or extended=True), to be bound to the
+    fixture's name in the module that uses it: `ctxs = contexts_fixture()`.  Each module gets contexts of its own."""
+    @pytest.fixture(scope="module")
+    def contexts(hip_lib):
+        yield from mode_contexts(**kw)
+    return contexts
+
+
+@pytest.fixture()
+def ictx(ictxs):
+    """The importing module's `ictxs` (contexts_fixture(instrumented=True)) for one test: the recursive contexts' debug
+    stop (rg_stop_after_scale) is cleared when the test ends, whatever its outcome, so a failure stays in its own test."""
+    yield ictxs
+    for m in MODES:
+        if m != "fir":
+            ictxs[m].rg_stop_after_scale(-1)
 
 
 def score_tol(exp: float) -> float:
@@ -162,18 +200,22 @@ def march_seg_rows(w: int, h: int, scale: int) -> int:
     return min(seg, 48) if scale > 0 else seg
 
 
+def averages_rtol(w_s: int, h_s: int, rows: int) -> float:
+    """The bound of a FIR average of a w_s x h_s scale whose lanes sum at most `rows` fp32 terms each (derivation
+    above): (rows + 3) * 2^-24 for the fp32 part, one unit of 2^-53 per pixel for the fp64 part."""
+    return (rows + 3) * 2.0 ** -24 + w_s * h_s * 2.0 ** -53
+
+
 def fir_rtol(w: int, h: int, scale: int) -> float:
-    """The bound of a FIR average at `scale` against the kernel-order terms (derivation above)."""
-    sw, sh = w, h
-    for _ in range(scale):
-        sw, sh = (sw + 1) // 2, (sh + 1) // 2
-    return (march_seg_rows(w, h, scale) + 3) * 2.0 ** -24 + sw * sh * 2.0 ** -53
+    """averages_rtol at `scale` of a w x h frame under the single-score rule (rows not clamped to the scale's height)."""
+    return averages_rtol(*scale_size(w, h, scale), march_seg_rows(w, h, scale))
 
 
-def scale_size(w: int, h: int, scale: int):
-    for _ in range(scale):
-        w, h = (w + 1) // 2, (h + 1) // 2
-    return w, h
+def rows_rtol(w: int, h: int, scale: int, rows: int) -> float:
+    """averages_rtol for segments of `rows` rows set by hand (ssimu2_instr_set_segment_rows): a lane sums at most
+    min(rows, rows of the scale) terms."""
+    sw, sh = scale_size(w, h, scale)
+    return averages_rtol(sw, sh, min(rows, sh))
 
 
 def seg_rows(w: int, h: int, rule=march_seg_rows):
@@ -187,32 +229,36 @@ def override_rows(rows_scale0: int, rows_other_scales: int):
     return [rows_scale0] + [rows_other_scales] * 5
 
 
+def hold_averages(avg, exp, ns, rtol_of, what, each_scale=False):
+    """The one hold of a score's averages `avg` (6, n) to a reference's `exp` over `ns` scales: 0 exactly where the
+    reference is 0 (at every scale, scored or not), and at each scored scale s the relative deviation within
+    rtol_of(s).  `each_scale`: print every scale's deviation and bound before asserting it.  -> the largest deviation
+    in units of its bound."""
+    assert avg.shape == exp.shape and len(avg) == 6, what
+    worst = 0.0
+    for s in range(6):
+        got, e = avg[s], exp[s]
+        assert np.array_equal(got == 0, e == 0), (what, s, got, e)
+        if s >= ns:
+            continue
+        rtol = rtol_of(s)
+        dev = np.abs(got - e) / np.where(e == 0, 1.0, e)
+        if each_scale:
+            print(f"measured: {what} scale {s}: {float(dev.max()):.3e} (bound {rtol:.3e})")
+        assert (dev <= rtol).all(), (what, s, int(np.argmax(dev)), float(dev.max()), rtol)
+        worst = max(worst, float(dev.max()) / rtol)
+    return worst
+
+
 def check_fir_sums(avg, ns, w, h, kord, rows, what):
     """FIR averages 0..5 (the d and d^4 statistics, whose terms are the reference's bits) of every scale of a w x h
     frame against `kord`, the same terms summed in k_march's own order at `rows` rows per segment (errmap_ref's
     seg_rows results): within fir_sums.rtol, the order of an fp64 sum, and 0 exactly where the reference is 0.  The edge
     statistics stay with check_against_terms.  -> the largest deviation in units of its bound."""
     assert avg.shape == (6, 18) and kord.shape == (6, 6), what
-    worst = 0.0
-    for s in range(6):
-        got, exp = avg[s, :6], kord[s]
-        assert np.array_equal(got == 0, exp == 0), (what, s, got, exp)
-        if s >= ns:
-            continue
-        sw, sh = scale_size(w, h, s)
-        rtol = fir_sums.rtol(sw, sh, rows[s])
-        dev = np.abs(got - exp) / np.where(exp == 0, 1.0, exp)
-        worst = max(worst, float(dev.max()) / rtol)
-        assert (dev <= rtol).all(), (what, s, int(np.argmax(dev)), float(dev.max()), rtol)
+    worst = hold_averages(avg[:, :6], kord, ns, lambda s: fir_sums.rtol(*scale_size(w, h, s), rows[s]), what)
     print(f"measured: {what}: kernel-order sums {worst:.3e} of the bound")
     return worst
-
-
-def rows_rtol(w: int, h: int, scale: int, rows: int) -> float:
-    """fir_rtol's formula for segments of `rows` rows set by hand (ssimu2_instr_set_segment_rows): a lane sums at
-    most min(rows, rows of the scale) terms."""
-    sw, sh = scale_size(w, h, scale)
-    return (min(rows, sh) + 3) * 2.0 ** -24 + sw * sh * 2.0 ** -53
 
 
 def check_against_terms(oracle, score, avg, ns, ref, dist, mode, what, kavg=None, rows=None):
@@ -232,16 +278,12 @@ def check_against_terms(oracle, score, avg, ns, ref, dist, mode, what, kavg=None
         kavg, ns_r = errmap_ref.kernel_averages(oracle, ref, dist, MODES[mode][1])
         assert ns_r == ns, what
     assert avg.shape == kavg.shape == (6, 18), what
-    worst = 0.0
-    for s in range(6):
-        got, exp = avg[s], kavg[s]
-        assert np.array_equal(got == 0, exp == 0), (what, s, got, exp)
-        if s >= ns:
-            continue
-        rtol = RTOL_RECURSIVE if mode != "fir" else fir_rtol(w, h, s) if rows is None else rows_rtol(w, h, s, rows[s])
-        dev = np.abs(got - exp) / np.where(exp == 0, 1.0, exp)
-        assert (dev <= rtol).all(), (what, s, int(np.argmax(dev)), float(dev.max()), rtol)
-        worst = max(worst, float(dev.max()) / rtol)
+
+    def rtol_of(s):
+        if mode != "fir":
+            return RTOL_RECURSIVE
+        return fir_rtol(w, h, s) if rows is None else rows_rtol(w, h, s, rows[s])
+    worst = hold_averages(avg, kavg, ns, rtol_of, what)
     print(f"measured: {what}: averages {worst:.3e} of the bound, finalize "
           f"{abs(score - host):.1e}")
     return worst
@@ -301,11 +343,8 @@ def batch_seg_rows(w, h, scale):
 
 
 def batch_rtol(w, h, scale):
-    """fir_rtol's formula at the batch rule's rows (derivation: tests/test_gpu_score_batch.py's docstring)."""
-    sw, sh = w, h
-    for _ in range(scale):
-        sw, sh = (sw + 1) // 2, (sh + 1) // 2
-    return (min(batch_seg_rows(w, h, scale), sh) + 3) * 2.0 ** -24 + sw * sh * 2.0 ** -53
+    """rows_rtol at the batch rule's rows (derivation: tests/test_gpu_score_batch.py's docstring)."""
+    return rows_rtol(w, h, scale, batch_seg_rows(w, h, scale))
 
 
 def bits_equal(score_a, avg_a, score_b, avg_b, what):
@@ -332,28 +371,42 @@ def neighbours(w, h, n, seed):
     return refs, dists
 
 
-def check_item_against_kavg(oracle, score, avg, ns, w, h, kavg, what):
-    """A batch item's score and averages over `ns` scales of a w x h frame: k_finalize_batch against
-    oracle.score_from_averages(avg) to FINALIZE_TOL, every average against the kernel-order averages `kavg` to
-    batch_rtol, exactly 0 where the reference is 0.  -> the largest deviation in units of its bound."""
+def check_item_against_terms(oracle, score, avg, ns, ref, dist, what, kavg=None):
+    """A batch item's score of (ref, dist) and its averages over `ns` scales: k_finalize_batch against
+    oracle.score_from_averages(avg) to FINALIZE_TOL, every average against errmap_ref.kernel_averages in FIR (or `kavg`,
+    the kernel-order averages computed by the caller) to batch_rtol, exactly 0 where the reference is 0.  -> the largest
+    deviation in units of its bound."""
+    h, w, _ = ref.shape
     if ns == 0:
         assert score == 100.0 and not avg.any(), what
         return 0.0
+    if kavg is None:
+        kavg, ns_r = errmap_ref.kernel_averages(oracle, ref, dist, MODES["fir"][1])
+        assert ns_r == ns, what
     host = oracle.score_from_averages(avg, ns)
     print(f"measured: {what}: finalize {abs(score - host):.1e}")
     assert abs(score - host) <= FINALIZE_TOL, (what, score, host)
     assert avg.shape == kavg.shape == (6, 18), what
-    worst = 0.0
-    for s in range(6):
-        got, exp = avg[s], kavg[s]
-        assert np.array_equal(got == 0, exp == 0), (what, s, got, exp)
-        if s >= ns:
-            continue
-        dev = np.abs(got - exp) / np.where(exp == 0, 1.0, exp)
-        print(f"measured: {what} scale {s}: {float(dev.max()):.3e} (bound {batch_rtol(w, h, s):.3e})")
-        assert (dev <= batch_rtol(w, h, s)).all(), (what, s, int(np.argmax(dev)), float(dev.max()), batch_rtol(w, h, s))
-        worst = max(worst, float(dev.max()) / batch_rtol(w, h, s))
-    return worst
+    return hold_averages(avg, kavg, ns, lambda s: batch_rtol(w, h, s), what, each_scale=True)
+
+
+def on_device(frames, stride):
+    """The uint8 frames in one device buffer (a torch tensor), frame k at byte k * stride, zeros between them."""
+    import torch
+    buf = torch.zeros(len(frames) * stride, dtype=torch.uint8)
+    for k, f in enumerate(frames):
+        buf[k * stride:k * stride + f.size] = torch.from_numpy(f.reshape(-1))
+    buf = buf.cuda()
+    torch.cuda.synchronize()
+    return buf
+
+
+def golden_bits(s, golden):
+    """(score, averages) of the golden fixture's blockq2 pair on context `s`: what a refused call must leave as it was."""
+    arrays, _ = golden
+    score = s.compute_ssimu2(arrays["ref"], arrays["blockq2"])
+    avg, _ns = s.last_averages()
+    return score, avg
 
 
 def rg_planes(oracle, blur, xa, xb):

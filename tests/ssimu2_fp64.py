@@ -190,32 +190,49 @@ def _linear_planes(img: np.ndarray) -> np.ndarray:
     return srgb_to_linear(np.moveaxis(img, 2, 0))
 
 
-def _pyramid_sizes(w: int, h: int):
-    sizes = []
-    for s in range(NUM_SCALES):
-        if w < MIN_SIZE or h < MIN_SIZE:
-            break
-        if s:
-            w, h = (w + 1) // 2, (h + 1) // 2
-        sizes.append((w, h))
-    return sizes
+def scale_size(w: int, h: int, scale: int):
+    """The size of `scale` of a w x h frame: halved `scale` times, rounding up.  The one halving rule of tests/."""
+    for _ in range(scale):
+        w, h = (w + 1) // 2, (h + 1) // 2
+    return w, h
 
 
 def nscales_of(w: int, h: int) -> int:
-    return len(_pyramid_sizes(w, h))
+    ns = 0
+    while ns < NUM_SCALES and min(scale_size(w, h, max(ns - 1, 0))) >= MIN_SIZE:
+        ns += 1
+    return ns
+
+
+def levels(lin1: np.ndarray, lin2: np.ndarray, scales) -> dict:
+    """-> {scale: (lin1, lin2, xyb1, xyb2)} fp64 (3, h_s, w_s) planes at the scales asked for, from the scale-0 linear
+    planes of both frames.  The front ends: fp64_checks.reference_levels (8-bit), hbd_ref.reference_levels (16-bit)."""
+    out = {}
+    for s in range(max(scales) + 1):
+        if s:
+            lin1, lin2 = downsample2(lin1), downsample2(lin2)
+        if s in scales:
+            out[s] = (lin1, lin2, to_xyb(lin1), to_xyb(lin2))
+    return out
 
 
 def evaluate(ref: np.ndarray, dist: np.ndarray, planes: bool = False) -> dict:
-    """Score `dist` ((h, w, 3) uint8) against `ref`.  -> {"score", "averages" (6, 18) in the checker's layout,
-    "nscales", "weighted_sum"} and, with `planes`, "planes": one dict per scale of (3, h_s, w_s) fp64 arrays
-    lin1, lin2, xyb1, xyb2, mu1, mu2, s11, s22, s12 (blurred products), d, artifact, detail_lost."""
-    h, w, _ = ref.shape
+    """Score `dist` ((h, w, 3) uint8) against `ref`: evaluate_linear of their linear planes."""
     assert dist.shape == ref.shape
+    return evaluate_linear(_linear_planes(ref), _linear_planes(dist), planes)
+
+
+def evaluate_linear(lin1: np.ndarray, lin2: np.ndarray, planes: bool = False) -> dict:
+    """Score two frames given as (3, h, w) fp64 linear planes, reference first.  -> {"score", "averages" (6, 18) in
+    the checker's layout, "nscales", "weighted_sum"} and, with `planes`, "planes": one dict per scale of
+    (3, h_s, w_s) fp64 arrays lin1, lin2, xyb1, xyb2, mu1, mu2, s11, s22, s12 (blurred products), d, artifact,
+    detail_lost.  The one body of the fp64 route; hbd_ref.compute_fp64 feeds it 16-bit frames."""
+    h, w = lin1.shape[1:]
+    assert lin2.shape == lin1.shape
     avg = np.zeros((NUM_SCALES, 18))
     per_scale = []
-    lin1, lin2 = _linear_planes(ref), _linear_planes(dist)
-    sizes = _pyramid_sizes(w, h)
-    for s in range(len(sizes)):
+    ns = nscales_of(w, h)
+    for s in range(ns):
         if s:
             lin1, lin2 = downsample2(lin1), downsample2(lin2)
         x1, x2 = to_xyb(lin1), to_xyb(lin2)
@@ -248,7 +265,6 @@ def evaluate(ref: np.ndarray, dist: np.ndarray, planes: bool = False) -> dict:
         del x1, x2
         if keep is not None:
             per_scale.append(keep)
-    ns = len(sizes)
     ws = weighted_sum(avg, ns)
     out = {"score": score_from_weighted_sum(ws), "averages": avg, "nscales": ns, "weighted_sum": ws}
     if planes:

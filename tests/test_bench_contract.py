@@ -107,10 +107,8 @@ def test_bench_byte_model_matches_survey():
     assert consts["ALGO_BYTES_PER_PX_SCORE"] == 85.97
     assert consts["HBM_PEAK_GBS"] == 8000.0
     # pyramid writes at 4K: 24 B per pixel of scales 1..5
-    w, h, px = 3840, 2160, 0
-    for _ in range(5):
-        w, h = (w + 1) // 2, (h + 1) // 2
-        px += w * h
+    from ssimu2_fp64 import scale_size
+    px = sum(w * h for w, h in (scale_size(3840, 2160, s) for s in range(1, 6)))
     assert abs((85.97 - consts["ALGO_BYTES_PER_PX_MARCH"]) - 24 * px / (3840 * 2160)) < 0.01
 
 

@@ -4,14 +4,13 @@ hidden under a = 0, alpha damage, genuine content against the checker, the conte
 RGBA calls, the scoring service's refusal, and the search.
 
 The expected values of genuine content come from numpy alone: codes n = a*c + (255 - a)*b -> T[n] as fp32 planes ->
-hbd_ref.terms -> errmap_ref.averages -> oracle.score_from_averages, held with the bounds tests/test_gpu_hbd.py holds
+errmap_ref.score_lin (the checker route over linear planes), held with the bounds tests/test_gpu_hbd.py holds
 16-bit content to (gpu_cases.score_tol, RTOL_AVG / ATOL_AVG, gpu_cases.check_against_terms), unchanged."""
 import numpy as np
 import pytest
 
 import errmap_ref
 import gpu_cases
-import hbd_ref
 from oavif_amd import Ssimu2, Ssimu2Error, _lib, scorer as scorer_mod, synth
 
 pytestmark = pytest.mark.gpu
@@ -20,14 +19,7 @@ MODES = list(gpu_cases.MODES)
 BACKGROUNDS = [0x000000, 0xFFFFFF, 0x1A80E6, int(np.random.default_rng(77).integers(0, 1 << 24))]
 
 
-@pytest.fixture(scope="module")
-def ctxs(hip_lib):
-    out = {}
-    for name, (mode, _) in gpu_cases.MODES.items():
-        out[name] = Ssimu2(0, blur=mode, extended=True)
-    yield out
-    for s in out.values():
-        s.close()
+ctxs = gpu_cases.contexts_fixture(extended=True)
 
 
 @pytest.fixture(scope="module")
@@ -198,9 +190,7 @@ def expected(oracle, table, key, cr, cd, blur):
     if (key, blur) not in _expected:
         lin_r = table[cr].transpose(2, 0, 1).copy()
         lin_d = table[cd].transpose(2, 0, 1).copy()
-        tm = hbd_ref.terms(oracle, lin_r, lin_d, blur)
-        avg, ns = errmap_ref.averages(tm), len(tm)
-        _expected[(key, blur)] = ((oracle.score_from_averages(avg, ns) if ns else 100.0), avg, ns)
+        _expected[(key, blur)] = errmap_ref.score_lin(oracle, lin_r, lin_d, blur)
     return _expected[(key, blur)]
 
 

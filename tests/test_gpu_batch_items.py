@@ -24,7 +24,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import errmap_ref  # noqa: E402
 import gpu_cases  # noqa: E402
 import hbd_ref  # noqa: E402
-from gpu_cases import KINDS, bits_equal, damaged  # noqa: E402
+from gpu_cases import KINDS, bits_equal, damaged, golden_bits, on_device  # noqa: E402
+from hbd_cases import lift, to_depth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -183,29 +184,12 @@ def test_every_item_of_the_device_forms_with_an_odd_item_stride(iscorer):
 
 
 # ---- B. the uncached-reference fallbacks --------------------------------------------------------------------------
-def golden_bits(s, golden):
-    arrays, _ = golden
-    score = s.compute_ssimu2(arrays["ref"], arrays["blockq2"])
-    avg, _ns = s.last_averages()
-    return score, avg
-
-
 def many_dists(ref, n):
     """n distinct damaged frames of `ref` from four distortions (rolled copies: cheap at full HD)."""
     base = [damaged(ref, k) for k in range(min(n, 4))]
     out = [np.ascontiguousarray(np.roll(base[k % 4], k // 4, axis=1)) for k in range(n)]
     assert distinct(out)
     return out
-
-
-def on_device(frames, stride):
-    import torch
-    buf = torch.zeros(len(frames) * stride, dtype=torch.uint8)
-    for k, f in enumerate(frames):
-        buf[k * stride:k * stride + f.size] = torch.from_numpy(f.reshape(-1))
-    buf = buf.cuda()
-    torch.cuda.synchronize()
-    return buf
 
 
 def against_reference_family(s, ref, dist, dists, expect):
@@ -392,17 +376,9 @@ def batch_single(s, w, h, ref, dist):
 
 
 # ---- C. a batch against a 16-bit reference ------------------------------------------------------------------------
-def lift(u8):
-    return u8.astype(np.uint16) * np.uint16(257)
-
-
 def hbd_reference(w, h, depth, seed):
     """A genuine `depth`-bit frame: 8-bit content scaled to the depth with low-order detail added."""
-    top = (1 << depth) - 1
-    rng = np.random.default_rng(seed)
-    u = synth.make_ref(w, h, seed=seed).astype(np.int64)
-    img = np.clip(u * top // 255 + rng.integers(-(top // 255), top // 255 + 1, u.shape), 0, top)
-    return np.ascontiguousarray(img.astype(np.uint16))
+    return to_depth(synth.make_ref(w, h, seed=seed), depth, seed)
 
 
 def to_8bit(img16, depth):
@@ -442,9 +418,9 @@ def test_batch_against_a_16bit_reference(iscorer, oracle, depth, w, h):
     for k in range(n):
         tm = hbd_ref.terms(oracle, lin_ref, hbd_ref.linear_planes(lift(d8[k]), 16), oracle.BLUR_FIR)
         assert len(tm) == got[k][2]
-        worst = max(worst, gpu_cases.check_item_against_kavg(oracle, got[k][0], got[k][1], got[k][2], w, h,
-                                                             errmap_ref.averages(tm),
-                                                             f"{depth}-bit reference {w}x{h} item {k}"))
+        worst = max(worst, gpu_cases.check_item_against_terms(oracle, got[k][0], got[k][1], got[k][2], r16, d8[k],
+                                                              f"{depth}-bit reference {w}x{h} item {k}",
+                                                              kavg=errmap_ref.averages(tm)))
     print(f"measured: batch against a {depth}-bit reference {w}x{h}: averages {worst:.3f} of batch_rtol")
     assert all(g[0] < 100.0 for g in got)
 

@@ -117,7 +117,7 @@ def test_fresh_results_match_the_checker(hip_lib, oracle, mode, size):
             kavg, ns_r = kavgs[key]
             avg, ns = got.items[i]
             assert ns == ns_r, (what, st.op, i)
-            gpu_cases.check_item_against_kavg(oracle, got.score[i], avg, ns, w, h, kavg, f"{what} {st.op} item {i}")
+            gpu_cases.check_item_against_terms(oracle, got.score[i], avg, ns, a, b, f"{what} {st.op} item {i}", kavg=kavg)
 
 
 # ---- four contexts side by side ------------------------------------------------------------------------------------------

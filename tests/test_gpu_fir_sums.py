@@ -25,6 +25,7 @@ import errmap_ref  # noqa: E402
 import gpu_cases  # noqa: E402
 import hbd_ref  # noqa: E402
 from gpu_cases import MW, bits_equal, check_against_terms, check_fir_sums  # noqa: E402
+from hbd_cases import hbd_content, hbd_distort  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -134,7 +135,7 @@ def test_segment_rows_set_by_hand(iscorer, oracle, seg, tail):
 @pytest.mark.parametrize("w,h", [(509, 131), (121, 40), (256, 192)])
 def test_batch_items_at_the_batch_rule_s_rows(scorer, oracle, w, h):
     """k_march_batch: 7 items of every content kind, one identical pair among them, each item's averages 0..5 against
-    its own terms summed at 96 / 48 rows, the rest as gpu_cases.check_item_against_kavg holds a batch item."""
+    its own terms summed at 96 / 48 rows, the rest as gpu_cases.check_item_against_terms holds a batch item."""
     refs, dists = gpu_cases.neighbours(w, h, 7, seed=w)
     rows = gpu_cases.seg_rows(w, h, gpu_cases.batch_seg_rows)
     assert rows == [96] + [48] * 5
@@ -148,13 +149,12 @@ def test_batch_items_at_the_batch_rule_s_rows(scorer, oracle, w, h):
         kavg, ns_r, kord = errmap_ref.kernel_averages(oracle, refs[k], dists[k], oracle.BLUR_FIR, seg_rows=rows)
         assert ns == ns_r >= 1, what
         worst = max(worst, check_fir_sums(avg, ns, w, h, kord, rows, what))
-        gpu_cases.check_item_against_kavg(oracle, scores[k], avg, ns, w, h, kavg, what)
+        gpu_cases.check_item_against_terms(oracle, scores[k], avg, ns, refs[k], dists[k], what, kavg=kavg)
     print(f"measured: batch {w}x{h}: kernel-order sums {worst:.3e} of the bound")
 
 
 def test_the_16_bit_front_end(scorer, oracle):
     """k_march_lin: scale 0 from the linear planes of a 12-bit pair; the terms are hbd_ref's."""
-    from test_gpu_hbd import hbd_content, hbd_distort
     w, h, depth = 333, 217, 12
     ref = hbd_content("text", w, h, depth, seed=12)
     dist = hbd_distort(ref, depth, seed=112)

@@ -19,7 +19,7 @@ from oavif_amd import _lib, synth
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fp64_checks as fc  # noqa: E402
 import ssimu2_fp64 as R  # noqa: E402
-from gpu_cases import MODES, SIZES, content  # noqa: E402
+from gpu_cases import MODES, SIZES, content, contexts_fixture  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -32,13 +32,7 @@ def _reference(key, ref, dist):
     return _REF[key]
 
 
-@pytest.fixture(scope="module")
-def ctxs(hip_lib):
-    from oavif_amd import Ssimu2
-    d = {m: Ssimu2(0, blur=b) for m, (b, _) in MODES.items()}
-    yield d
-    for s in d.values():
-        s.close()
+ctxs = contexts_fixture()
 
 
 def _cases(group):

@@ -12,6 +12,7 @@ import pytest
 import fp64_checks
 import gpu_cases
 import hbd_ref
+from hbd_cases import hbd_content, hbd_distort, lift, rows16
 from oavif_amd import Ssimu2, Ssimu2Error, _lib, synth
 
 pytestmark = pytest.mark.gpu
@@ -20,19 +21,7 @@ MODES = list(gpu_cases.MODES)
 KINDS = ["gradient", "primaries", "checker", "text", "noise"]
 
 
-@pytest.fixture(scope="module")
-def ctxs(hip_lib):
-    out = {}
-    for name, (mode, _) in gpu_cases.MODES.items():
-        out[name] = Ssimu2(0, blur=mode)
-    yield out
-    for s in out.values():
-        s.close()
-
-
-def lift(u8):
-    """8-bit samples u as the 16-bit samples 257 u (the same normalised values)."""
-    return u8.astype(np.uint16) * np.uint16(257)
+ctxs = gpu_cases.contexts_fixture()
 
 
 def pair_8(s, ref, dist):
@@ -64,45 +53,8 @@ def test_bit_identity_with_the_8bit_path(ctxs, mode):
         s.set_reference_hbd(lift(ref), 16)
         assert_same(s, s.score_against_reference_hbd(lift(dist), 16), exp_c, what + ("cached 16/16",))
         assert_same(s, s.score_against_reference_hbd(dist.astype(np.uint16), 8), exp_c, what + ("cached 16/d8",))
-        buf, view = decoded_like16(lift(dist), 4, 6, seed=k)
+        buf, view = rows16(lift(dist), 4, 6, seed=k)
         assert_same(s, s.score_decoded_against_reference_hbd(view, bit_depth=16), exp_c, what + ("strided16",))
-
-
-def decoded_like16(dist16, channels, pad_samples, seed):
-    """A uint16 frame laid out like libavif's avifRGBImage at depth > 8: `channels` samples per pixel (alpha random),
-    rows `pad_samples` samples longer than their pixels, padding filled with noise."""
-    h, w, _ = dist16.shape
-    rng = np.random.default_rng(seed)
-    pitch = w * channels + pad_samples
-    buf = rng.integers(0, 65536, (h, pitch), dtype=np.uint16)
-    view = np.lib.stride_tricks.as_strided(buf, (h, w, channels), (pitch * 2, channels * 2, 2))
-    view[..., :3] = dist16
-    return buf, view
-
-
-def hbd_content(kind, w, h, depth, seed):
-    """(h, w, 3) uint16 frames of `depth` bits: a smooth gradient over every code, noise, or a content kind lifted to
-    `depth` bits with low-order detail added."""
-    top = (1 << depth) - 1
-    rng = np.random.default_rng(seed)
-    if kind == "hgradient":
-        yy, xx = np.mgrid[0:h, 0:w]
-        img = np.stack([xx * top // max(w - 1, 1), yy * top // max(h - 1, 1), (xx + yy) * top // max(w + h - 2, 1)], -1)
-    elif kind == "hnoise":
-        img = rng.integers(0, top + 1, (h, w, 3))
-    else:
-        u = gpu_cases.content(kind, w, h, seed).astype(np.int64)
-        img = np.clip(u * top // 255 + rng.integers(-(top // 255), top // 255 + 1, (h, w, 3)), 0, top)
-    return np.ascontiguousarray(img.astype(np.uint16))
-
-
-def hbd_distort(img, depth, seed):
-    """A mild 16-bit distortion: quantise to 8 levels fewer bits and add noise (stays inside the depth's range)."""
-    top = (1 << depth) - 1
-    rng = np.random.default_rng(seed)
-    step = 1 << (depth - 6)
-    q = (img.astype(np.int64) // step) * step + step // 2
-    return np.clip(q + rng.integers(-step // 4, step // 4 + 1, img.shape), 0, top).astype(np.uint16)
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -142,7 +94,7 @@ def test_mixed_depths(ctxs, oracle, mode):
     exp = (s.compute_ssimu2_hbd(lift(ref8), d16, 16), s.last_averages())
     s.set_reference(ref8)
     assert_same(s, s.score_against_reference_hbd(d16, 16), exp, (mode, "8-bit ref, 16-bit frame"))
-    buf, view = decoded_like16(d16, 3, 5, seed=1)
+    buf, view = rows16(d16, 3, 5, seed=1)
     assert_same(s, s.score_decoded_against_reference_hbd(view, bit_depth=16), exp, (mode, "8-bit ref, strided"))
     # 16-bit reference, 8-bit frames: the pair score with the 8-bit frame as 257 u
     r16 = hbd_content("gradient", w, h, 16, seed=6)
@@ -182,7 +134,7 @@ def test_strided_hand_off_equals_the_tight_call(ctxs, oracle, mode):
             gpu_cases.check_against_terms(oracle, exp[0], exp[1][0], ns_r, ref, dist, mode,
                                           f"{mode} tight 10-bit call {w}x{h}", kavg=kavg)
         for ch, pad in ((3, 0), (3, 7), (4, 0), (4, 12)):
-            buf, view = decoded_like16(dist, ch, pad, seed=k + ch)
+            buf, view = rows16(dist, ch, pad, seed=k + ch)
             assert_same(s, s.score_decoded_against_reference_hbd(view, bit_depth=10), exp, (mode, w, h, ch, pad))
             flat = buf.reshape(-1)
             assert_same(s, s.score_decoded_against_reference_hbd(flat, row_bytes=buf.strides[0], channels=ch,

@@ -14,7 +14,8 @@ import fp64_checks as fc
 import gpu_cases
 import hbd_ref
 import ssimu2_fp64 as R
-from gpu_cases import check_rg, same_bits, scrub
+from gpu_cases import check_rg, ictx, same_bits, scrub  # noqa: F401  (ictx: a fixture)
+from hbd_cases import content16, lift, rows16
 from oavif_amd import Ssimu2, Ssimu2Error, _lib, synth
 
 pytestmark = pytest.mark.gpu
@@ -24,59 +25,8 @@ RECURSIVE = [m for m in gpu_cases.MODES if m != "fir"]
 DEPTHS = list(range(8, 17))
 
 
-@pytest.fixture(scope="module")
-def ictxs(hip_lib):
-    """Contexts of the instrumented build, one per blur mode."""
-    out = {name: Ssimu2(0, instrumented=True, blur=mode) for name, (mode, _) in gpu_cases.MODES.items()}
-    yield out
-    for s in out.values():
-        s.close()
-
-
-@pytest.fixture()
-def ictx(ictxs):
-    """ictxs for one test: the recursive contexts' debug stop (rg_stop_after_scale) is cleared when the test ends,
-    whatever its outcome, so that a failure stays in its own test."""
-    yield ictxs
-    for m in RECURSIVE:
-        ictxs[m].rg_stop_after_scale(-1)
-
-
-@pytest.fixture(scope="module")
-def ctxs(hip_lib):
-    out = {name: Ssimu2(0, blur=mode) for name, (mode, _) in gpu_cases.MODES.items()}
-    yield out
-    for s in out.values():
-        s.close()
-
-
-def lift(u8):
-    """8-bit samples u as the 16-bit samples 257 u (the same normalised values), one allocation."""
-    return np.multiply(u8, np.uint16(257), dtype=np.uint16)
-
-
-def content16(w, h, d, seed, distort=False):
-    """(h, w, 3) uint16 frames of d bits: a natural synthetic frame (or its blockq distortion) taken to d bits with
-    low-order noise, so that codes that are no multiple of 257 / 2^(16 - d) occur everywhere."""
-    u = synth.make_ref(w, h, seed)
-    if distort:
-        u = synth.distort(u, "blockq", 2, seed=seed)
-    top = (1 << d) - 1
-    rng = np.random.default_rng(seed + d)
-    step = top // 255
-    v = u.astype(np.int64) * top // 255 + rng.integers(-step, step + 1, u.shape)
-    return np.ascontiguousarray(np.clip(v, 0, top).astype(np.uint16))
-
-
-def rows16(img, channels, pad, fill):
-    """`img` in a libavif-like uint16 row buffer: `channels` samples per pixel, rows `pad` samples longer, alpha and
-    padding set to `fill`.  -> (buffer, (h, w, channels) view)."""
-    h, w, _ = img.shape
-    pitch = w * channels + pad
-    buf = np.full((h, pitch), fill, np.uint16)
-    view = np.lib.stride_tricks.as_strided(buf, (h, w, channels), (pitch * 2, channels * 2, 2))
-    view[..., :3] = img
-    return buf, view
+ictxs = gpu_cases.contexts_fixture(instrumented=True)
+ctxs = gpu_cases.contexts_fixture()
 
 
 # ---- the ssimu2_debug_download hook at scale 0 --------------------------------------------------------------------
@@ -172,7 +122,7 @@ def test_planes_on_the_size_grid_are_bit_identical(ictx, oracle, k):
     ref, dist = content16(w, h, d, 3 * k), content16(w, h, d, 3 * k + 1, distort=True)
     lv_r, lv_d = hbd_ref.levels(oracle, ref, d), hbd_ref.levels(oracle, dist, d)
     ns = len(lv_r)
-    buf, view = rows16(dist, 4, 6 + k, 0xFFFF)
+    buf, view = rows16(dist, 4, 6 + k, fill=0xFFFF)
 
     def score(s):
         if strided:
@@ -258,7 +208,7 @@ def test_mixed_depths_score_against_the_checker(ctxs, oracle, mode):
         frame = content16(w, h, dd, 7 * dr + dd, distort=True)
         exp, avg_r, ns_r = hbd_ref.compute(oracle, ref, frame, dr, blur, d_dist=dd)
         exp64 = hbd_ref.compute_fp64(ref, frame, dr, d_dist=dd)
-        buf, view = rows16(frame, 4, 10, 0xFFFF)
+        buf, view = rows16(frame, 4, 10, fill=0xFFFF)
         setters = [lambda: s.set_reference_hbd(ref, dr)]
         if dr == 8:
             setters.append(lambda: s.set_reference(ref.astype(np.uint8)))
@@ -312,7 +262,7 @@ def test_maximum_size_16bit_far_corner(hip_lib):
         same(s.compute_ssimu2_hbd(r16, d16, 16), "pair")
         s.set_reference_hbd(r16, 16)
         same(s.score_against_reference_hbd(d16, 16), "cached")
-        buf, view = rows16(d16, 4, 8, 0xFFFF)
+        buf, view = rows16(d16, 4, 8, fill=0xFFFF)
         assert buf.nbytes > 5 << 30
         same(s.score_decoded_against_reference_hbd(view, bit_depth=16), "strided rgba")
         del buf, view
@@ -407,6 +357,6 @@ def test_tall_frames_through_both_strided_hand_offs(ctxs, oracle, w, h):
     tight = s.score_against_reference_hbd(d16, 10)
     assert abs(tight - exp16) <= gpu_cases.score_tol(exp16)
     for ch, pad in ((3, 3), (4, 0), (4, 6)):
-        buf, view = rows16(d16, ch, pad, 0xFFFF)
+        buf, view = rows16(d16, ch, pad, fill=0xFFFF)
         assert scrub(s, r16, 10) != tight
         assert s.score_decoded_against_reference_hbd(view, bit_depth=10) == tight, (w, h, ch, pad)

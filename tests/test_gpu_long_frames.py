@@ -40,10 +40,10 @@ import pytest
 import errmap_ref
 import gpu_cases
 import hbd_ref
-from gpu_cases import (MODES, MW, bits_equal, check_against_terms, check_fir_sums, check_map, decoded_like, in_margins,
-                       same_bits, score_tol, scrub, stale, stale_pair)
-from oavif_amd import Ssimu2, synth
-from test_gpu_hbd_planes import content16, rows16
+from gpu_cases import (MODES, MW, bits_equal, check_against_terms, check_fir_sums, check_map, decoded_like,  # noqa: F401
+                       ictx, in_margins, same_bits, score_tol, scrub, stale, stale_pair)
+from hbd_cases import content16, rows16
+from oavif_amd import synth
 
 pytestmark = pytest.mark.gpu
 
@@ -118,29 +118,8 @@ def assert_regime(s, shape):
     assert -(-w // RG_VW) == {"W1": 1025, "W2": 1563}[shape]              # column groups = k_finalize's partials
 
 
-@pytest.fixture(scope="module")
-def ctxs(hip_lib):
-    out = {m: Ssimu2(0, blur=b) for m, (b, _) in MODES.items()}
-    yield out
-    for s in out.values():
-        s.close()
-
-
-@pytest.fixture(scope="module")
-def ictxs(hip_lib):
-    """Contexts of the instrumented build, one per blur mode."""
-    out = {m: Ssimu2(0, instrumented=True, blur=b) for m, (b, _) in MODES.items()}
-    yield out
-    for s in out.values():
-        s.close()
-
-
-@pytest.fixture()
-def ictx(ictxs):
-    """ictxs for one test; the recursive contexts' debug stop is cleared when the test ends, whatever its outcome."""
-    yield ictxs
-    for m in RECURSIVE:
-        ictxs[m].rg_stop_after_scale(-1)
+ctxs = gpu_cases.contexts_fixture()
+ictxs = gpu_cases.contexts_fixture(instrumented=True)
 
 
 def pair_score(s, shape, ref, dist):
@@ -247,7 +226,7 @@ def plane_levels(oracle, shape):
     """-> (linear levels, XYB levels) of both frames of the shape's pair, every scale; computed once."""
     if shape not in _LEVELS:
         ref, dist = frames(shape)
-        lin = errmap_ref._scales(oracle, ref), errmap_ref._scales(oracle, dist)
+        lin = [errmap_ref.scales(oracle, errmap_ref.linear_planes(oracle, f)) for f in (ref, dist)]
         assert len(lin[0]) == NSCALES[shape]
         _LEVELS[shape] = lin, tuple([oracle.linear_to_xyb(x) for x in levels] for levels in lin)
     return _LEVELS[shape]
@@ -348,7 +327,7 @@ def test_16bit_front_end_on_10bit_content(ctxs, oracle, shape, mode):
     assert scrub(s, r16, 10) != pair
     same("cached tight", s.score_against_reference_hbd(d16, 10))
     for ch, pad in ((3, 3), (4, 0)):
-        _buf, view = rows16(d16, ch, pad, 0xFFFF)
+        _buf, view = rows16(d16, ch, pad, fill=0xFFFF)
         assert scrub(s, r16, 10) != pair
         same(f"strided {ch} ch + {pad}", s.score_decoded_against_reference_hbd(view, bit_depth=10))
 

@@ -27,7 +27,7 @@ from oavif_amd import _lib, synth
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from gpu_cases import (ATOL_AVG, MODES, RTOL_AVG, SIZES, TOL_FAR_BELOW_ZERO, check_against_terms,  # noqa: E402
-                       check_fir_sums, check_map, content_pairs as _content_pairs, decoded_like,
+                       check_fir_sums, check_map, content_pairs as _content_pairs, contexts_fixture, decoded_like,
                        extreme_pairs as _extreme_pairs, flat_pairs as _flat_pairs, march_seg_rows, pseudo_codec,
                        score_tol, seg_rows)
 import errmap_ref  # noqa: E402
@@ -64,14 +64,7 @@ def _on_device(*frames):
     return ts
 
 
-@pytest.fixture(scope="module")
-def ctxs(hip_lib):
-    """One long-lived context per mode."""
-    from oavif_amd import Ssimu2
-    d = {m: Ssimu2(0, blur=b) for m, (b, _) in MODES.items()}
-    yield d
-    for s in d.values():
-        s.close()
+ctxs = contexts_fixture()   # one long-lived context per mode
 
 
 # ---- 1. sizes x modes x entry points ----------------------------------------------------------------------------

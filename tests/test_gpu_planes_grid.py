@@ -20,8 +20,8 @@ import pytest
 
 import errmap_ref
 import gpu_cases
-from gpu_cases import check_rg, in_margins, same_bits, stale
-from oavif_amd import Ssimu2, synth
+from gpu_cases import check_rg, ictx, in_margins, same_bits, stale  # noqa: F401  (ictx: a fixture)
+from oavif_amd import synth
 
 pytestmark = pytest.mark.gpu
 
@@ -32,21 +32,7 @@ KINDS = ["gradient", "primaries", "checker", "text", "noise"]
 DISTORTIONS = [("blockq", 2), ("noise", 2), ("blur", 1), ("band", 2)]
 
 
-@pytest.fixture(scope="module")
-def ictxs(hip_lib):
-    """Contexts of the instrumented build, one per blur mode."""
-    out = {name: Ssimu2(0, instrumented=True, blur=mode) for name, (mode, _) in gpu_cases.MODES.items()}
-    yield out
-    for s in out.values():
-        s.close()
-
-
-@pytest.fixture()
-def ictx(ictxs):
-    """ictxs for one test; the recursive contexts' debug stop is cleared when the test ends, whatever its outcome."""
-    yield ictxs
-    for m in RECURSIVE:
-        ictxs[m].rg_stop_after_scale(-1)
+ictxs = gpu_cases.contexts_fixture(instrumented=True)
 
 
 def frames(k):
@@ -61,7 +47,7 @@ def test_8bit_planes_on_the_size_grid_are_bit_identical(ictx, oracle, k):
     w, h = GRID[k]
     ref, dist = frames(k)
     off = k % 4
-    lin_r, lin_d = errmap_ref._scales(oracle, ref), errmap_ref._scales(oracle, dist)
+    lin_r, lin_d = [errmap_ref.scales(oracle, errmap_ref.linear_planes(oracle, f)) for f in (ref, dist)]
     ns = len(lin_r)
     xyb_r, xyb_d = [oracle.linear_to_xyb(x) for x in lin_r], [oracle.linear_to_xyb(x) for x in lin_d]
     _buf, view = gpu_cases.decoded_like(dist, 4, 5 + k, seed=k)

@@ -21,23 +21,12 @@ import pytest
 from oavif_amd import _lib, pam, scorepairs, synth
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import errmap_ref  # noqa: E402
 import gpu_cases  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-from gpu_cases import KINDS, batch_rtol, batch_seg_rows, bits_equal, damaged, neighbours  # noqa: E402
-
-
-def check_item_against_terms(oracle, score, avg, ns, ref, dist, what):
-    """gpu_cases.check_against_terms with the bound of the batch rule's rows (module docstring)."""
-    h, w, _ = ref.shape
-    if ns == 0:
-        assert score == 100.0 and not avg.any(), what
-        return
-    kavg, ns_r = errmap_ref.kernel_averages(oracle, ref, dist, gpu_cases.MODES["fir"][1])
-    assert ns_r == ns, what
-    gpu_cases.check_item_against_kavg(oracle, score, avg, ns, w, h, kavg, what)
+from gpu_cases import (KINDS, batch_rtol, batch_seg_rows, bits_equal, check_item_against_terms, damaged,  # noqa: E402
+                       golden_bits, neighbours)
 
 
 def item_in_batches(s, ref, dist, cached, placements=((0, 1), (3, 7), (31, 32), (5, 64))):
@@ -149,13 +138,6 @@ def test_sixteen_seeded_frames_against_the_kernel_order_terms(scorer, oracle, w,
 
 
 # ---- contract ----------------------------------------------------------------------------------------------------
-def _golden_bits(s, golden):
-    arrays, _ = golden
-    score = s.compute_ssimu2(arrays["ref"], arrays["blockq2"])
-    avg, _ns = s.last_averages()
-    return score, avg
-
-
 def _u8pp(frames):
     return (ctypes.POINTER(ctypes.c_uint8) * len(frames))(*[f.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if f is not None
                                                              else None for f in frames])
@@ -166,14 +148,14 @@ def test_refusals_leave_the_context_as_it_was(hip_lib, golden):
     L = hip_lib
     s = Ssimu2(0)
     try:
-        before = _golden_bits(s, golden)
+        before = golden_bits(s, golden)
         w, h = 64, 40
         refs, dists = neighbours(w, h, 3, seed=1)
         out = (ctypes.c_double * 4)(-1.0, -1.0, -1.0, -1.0)
         err = lambda: L.ssimu2_last_error(s._ctx).decode()   # noqa: E731
 
         def unchanged(what):
-            after = _golden_bits(s, golden)
+            after = golden_bits(s, golden)
             bits_equal(after[0], after[1], before[0], before[1], what)
 
         # n == 0: OK, nothing read, nothing written

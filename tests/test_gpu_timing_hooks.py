@@ -18,7 +18,7 @@ import pytest
 from oavif_amd import Ssimu2, _lib, synth
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from gpu_cases import bits_equal  # noqa: E402
+from gpu_cases import bits_equal, on_device  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -27,16 +27,11 @@ BLUR_BYTES = 2 * 4 * 3 * (136 * 24 + 68 * 12 + 34 * 6)  # every plane element of
 STAGES = (_lib.STAGE_PYRAMID, _lib.STAGE_MARCH, _lib.STAGE_FINALIZE)
 
 
-def on_device(frames):
-    """-> (the tensor that owns them, the device address of each frame)."""
-    import torch
-    buf = torch.from_numpy(np.concatenate([f.reshape(-1) for f in frames])).cuda()
-    torch.cuda.synchronize()
-    at, addrs = buf.data_ptr(), []
-    for f in frames:
-        addrs.append(at)
-        at += f.size
-    return buf, addrs
+def packed(frames):
+    """Same-size frames back to back on the device -> (the tensor that owns them, the device address of each frame)."""
+    size = frames[0].size
+    buf = on_device(frames, size)
+    return buf, [buf.data_ptr() + k * size for k in range(len(frames))]
 
 
 def duration(ms):
@@ -58,7 +53,7 @@ def hooks(hip_lib):
     finally:
         fresh.close()
     assert 0.0 < pair[0] < 100.0
-    buf, addrs = on_device(frames)
+    buf, addrs = packed(frames)
     s = Ssimu2(0, instrumented=True)
     yield s, frames, addrs, pair, cached
     s.close()
@@ -129,7 +124,7 @@ def test_hooks_on_a_frame_without_a_scale(hooks):
     s = hooks[0]
     ref = synth.make_ref(7, 7, 3)
     dist = synth.distort(ref, "noise", 3, seed=3)
-    buf, a = on_device([ref, dist])
+    buf, a = packed([ref, dist])
     for stage in STAGES:
         duration(s.time_stage(a[0], a[1], 7, 7, stage, 2))
     duration(s.time_march_rotating([a[0], a[1]], [a[1], a[0]], 7, 7, 3))
