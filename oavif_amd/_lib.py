@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("OAVIF_AMD_LIB") or os.path.join(_HERE, "lib", "liboav
 INSTR_LIB_PATH = os.environ.get("OAVIF_AMD_INSTR_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_instr.so")
 # the product library's sources plus the RGBA entry points of include/ssimu2_hip_ext.h (Ssimu2(..., extended=True))
 EXT_LIB_PATH = os.environ.get("OAVIF_AMD_EXT_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_ext.so")
+# the extension library's sources plus the YUV entry points of include/ssimu2_hip_yuv.h (Ssimu2(..., yuv=True))
+YUV_LIB_PATH = os.environ.get("OAVIF_AMD_YUV_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_yuv.so")
 
 OK = 0
 ERR_INVALID_ARG = -1
@@ -30,6 +32,7 @@ TQ_MAX_PASS = 12
 ALPHA_CODES = 65026   # SSIMU2_ALPHA_CODES (include/ssimu2_hip_ext.h): composite codes 0 .. 255 * 255
 MAX_BATCH = 4096   # SSIMU2_MAX_BATCH (include/ssimu2_hip.h): items of one ssimu2_score_batch_* call
 
+YUV_444, YUV_400 = 1, 4   # SSIMU2_YUV_* (include/ssimu2_hip_yuv.h): libavif's avifPixelFormat values
 BLUR_FIR, BLUR_RECURSIVE, BLUR_RECURSIVE_FMA = 0, 1, 2   # SSIMU2_BLUR_* (include/ssimu2_hip.h)
 
 
@@ -82,6 +85,12 @@ class DeviceInfo(ctypes.Structure):
                 "lds_bytes_per_cu": int(self.lds_bytes_per_cu), "lds_bytes_per_workgroup": int(self.lds_bytes_per_workgroup),
                 "wavefront_size": int(self.wavefront_size), "hbm_bytes": int(self.hbm_bytes),
                 "numa_node": int(self.numa_node), "usable": bool(self.usable)}
+
+
+class YuvFrameC(ctypes.Structure):
+    """ssimu2_yuv_frame (include/ssimu2_hip_yuv.h)."""
+    _fields_ = [("planes", ctypes.c_void_p * 3), ("row_bytes", ctypes.c_uint32 * 3), ("depth", ctypes.c_uint32),
+                ("format", ctypes.c_uint32), ("full_range", ctypes.c_uint32), ("matrix_coefficients", ctypes.c_uint32)]
 
 
 class TQSpecStats(ctypes.Structure):
@@ -179,13 +188,22 @@ EXT_FUNCTIONS = {      # include/ssimu2_hip_ext.h: only liboavif_hip_ext.so has 
     "ssimu2_score_against_reference_rgba8": (_ci, [_vp, _u8p, _u32, _f64p]),
 }
 
+YUV_FUNCTIONS = {      # include/ssimu2_hip_yuv.h: only liboavif_hip_yuv.so has these
+    "ssimu2_convert_yuv": (_ci, [_vp, _P(YuvFrameC), _u32, _u32, _u32, _u16p]),
+    "ssimu2_score_yuv": (_ci, [_vp, _P(YuvFrameC), _P(YuvFrameC), _u32, _u32, _u32, _f64p]),
+    "ssimu2_set_reference_yuv": (_ci, [_vp, _P(YuvFrameC), _u32, _u32, _u32]),
+    "ssimu2_score_against_reference_yuv": (_ci, [_vp, _P(YuvFrameC), _u32, _f64p]),
+}
+
 EXPORTED_SYMBOLS = tuple(PUBLIC_FUNCTIONS)
 INSTR_SYMBOLS = tuple(HOOK_FUNCTIONS)
 EXT_SYMBOLS = tuple(EXT_FUNCTIONS)
+YUV_SYMBOLS = tuple(YUV_FUNCTIONS)
 
 _lib = None
 _instr = None
 _ext = None
+_yuv = None
 
 
 def lib() -> ctypes.CDLL:
@@ -212,6 +230,14 @@ def ext_lib() -> ctypes.CDLL:
     return _ext
 
 
+def yuv_lib() -> ctypes.CDLL:
+    """The YUV build (include/ssimu2_hip_yuv.h): the extension library plus the YUV entry points."""
+    global _yuv
+    if _yuv is None:
+        _yuv = _load(YUV_LIB_PATH)
+    return _yuv
+
+
 def _load(path: str) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise ImportError(
@@ -227,7 +253,7 @@ def _load(path: str) -> ctypes.CDLL:
         except Exception:
             pass
     L = ctypes.CDLL(path)
-    for table in (PUBLIC_FUNCTIONS, HOOK_FUNCTIONS, EXT_FUNCTIONS):
+    for table in (PUBLIC_FUNCTIONS, HOOK_FUNCTIONS, EXT_FUNCTIONS, YUV_FUNCTIONS):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name, None)   # a build older than a symbol lacks it (scripts/gpu_ab.py loads such builds)
             if fn is not None:

@@ -42,7 +42,10 @@ _RESULT_OK = 0
 
 # offsets into the public structs of libavif 1.x (x86-64); verified by _check_layout()
 _IMG_WIDTH, _IMG_HEIGHT, _IMG_DEPTH, _IMG_YUVFORMAT, _IMG_YUVRANGE = 0, 4, 8, 12, 16
+_IMG_YUVPLANES, _IMG_YUVROWBYTES, _IMG_OWNSYUV = 24, 48, 60   # uint8_t* [3], uint32_t [3], avifBool
 _IMG_ALPHAPLANE = 64
+_PIXEL_FORMAT_YUV400 = 4
+_PLANES_YUV = 1
 _IMG_ICC = 88               # avifRWData {data, size}
 _IMG_CP, _IMG_TC, _IMG_MC = 104, 106, 108   # uint16_t each
 _RGB_SIZE = 64
@@ -88,6 +91,7 @@ def _bind(L) -> None:
     L.avifCodecVersions.argtypes, L.avifCodecVersions.restype = [ctypes.c_char_p], None
     L.avifImageCreate.argtypes, L.avifImageCreate.restype = [u32, u32, u32, ci], vp
     L.avifImageDestroy.argtypes, L.avifImageDestroy.restype = [vp], None
+    L.avifImageAllocatePlanes.argtypes, L.avifImageAllocatePlanes.restype = [vp, ci], ci
     L.avifImageSetProfileICC.argtypes, L.avifImageSetProfileICC.restype = [vp, ctypes.c_char_p, ctypes.c_size_t], ci
     L.avifRGBImageSetDefaults.argtypes, L.avifRGBImageSetDefaults.restype = [vp, vp], None
     L.avifRGBImageAllocatePixels.argtypes, L.avifRGBImageAllocatePixels.restype = [vp], ci
@@ -164,6 +168,16 @@ def _check_layout(L) -> Optional[str]:
         if head != (24, 16, 10, 1, 1) or cicp != (2, 2, 2) or _ptr(im, _IMG_ALPHAPLANE) != 0 \
                 or _ptr(im, _IMG_ICC) != 0:
             return f"avifImage fields {head} {cicp} do not match the 1.x layout"
+        # yuvPlanes / yuvRowBytes / imageOwnsYUVPlanes (decode_yuv reads the first two): empty, then allocated
+        yuv = lambda: ([_ptr(im, _IMG_YUVPLANES + 8 * k) for k in range(3)],
+                       [_u32(im, _IMG_YUVROWBYTES + 4 * k) for k in range(3)], _u32(im, _IMG_OWNSYUV))
+        if yuv() != ([0, 0, 0], [0, 0, 0], 0):
+            return f"avifImage YUV plane fields {yuv()} of a new image do not match the 1.x layout"
+        if L.avifImageAllocatePlanes(im, _PLANES_YUV) != _RESULT_OK:
+            return "avifImageAllocatePlanes failed"
+        planes, rows, owns = yuv()
+        if not all(planes) or len(set(planes)) != 3 or rows != [24 * 2] * 3 or owns != 1 or _ptr(im, _IMG_ALPHAPLANE) != 0:
+            return f"avifImage.yuvPlanes / yuvRowBytes ({planes}, {rows}, {owns}) are not where the 1.x layout puts them"
         icc = b"layout-check"
         if L.avifImageSetProfileICC(im, icc, len(icc)) != _RESULT_OK:
             return "avifImageSetProfileICC failed"
@@ -469,6 +483,76 @@ def decode_common(data: bytes, rgb_depth: int = 8) -> DecodedFrame:
         L.avifDecoderDestroy(dec)
         raise
     return DecodedFrame(L, dec, rgb, w, h, 4 if has_alpha else 3, depth, has_alpha, rgb_depth)
+
+
+class DecodedYuv:
+    """What the decoder itself leaves behind: views of avifImage.yuvPlanes, valid until close() (the decoder stays
+    open until then).  `planes`: (h, w) arrays, uint8 at depth 8 and uint16 above, rows yuvRowBytes apart -- three for
+    4:4:4, one for 4:0:0, subsampled chroma planes at their own size; `format` is libavif's avifPixelFormat
+    (1 = 4:4:4 ... 4 = 4:0:0), `full_range` its yuvRange, `matrix_coefficients` the CICP code.  `has_alpha`: the image
+    has an alpha plane too, which is not handed out: such frames go through decode_common."""
+
+    def __init__(self, L, dec, img):
+        self._L, self._dec = L, dec
+        self.width, self.height, self.depth = _u32(img, _IMG_WIDTH), _u32(img, _IMG_HEIGHT), _u32(img, _IMG_DEPTH)
+        self.format, self.full_range = _u32(img, _IMG_YUVFORMAT), _u32(img, _IMG_YUVRANGE) == 1
+        self.matrix_coefficients = _u16(img, _IMG_MC)
+        self.has_alpha = _ptr(img, _IMG_ALPHAPLANE) != 0
+        sample = ctypes.c_uint8 if self.depth == 8 else ctypes.c_uint16
+        size = ctypes.sizeof(sample)
+        self.planes, self.row_bytes = [], []
+        for k in range(1 if self.format == _PIXEL_FORMAT_YUV400 else 3):
+            ptr, row = _ptr(img, _IMG_YUVPLANES + 8 * k), _u32(img, _IMG_YUVROWBYTES + 4 * k)
+            w = self.width if k == 0 or self.format == _PIXEL_FORMAT_YUV444 else (self.width + 1) // 2      # 4:2:2, 4:2:0
+            h = self.height if k == 0 or self.format != 3 else (self.height + 1) // 2                       # 4:2:0
+            if not ptr or row < w * size or row % size:
+                raise AvifBridgeError("DecodeImageFailed", f"plane {k}: pointer {ptr:#x}, rowBytes {row}")
+            rows = np.ctypeslib.as_array((sample * (row // size * h)).from_address(ptr)).reshape(h, row // size)
+            self.planes.append(rows[:, :w])
+            self.row_bytes.append(row)
+
+    def close(self) -> None:
+        if getattr(self, "_dec", None) is not None:
+            self.planes = None
+            self._L.avifDecoderDestroy(self._dec)
+            self._dec = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def decode_yuv(data: bytes) -> DecodedYuv:
+    """decode_common's sequence up to avifDecoderNextImage, and no further: avifImageYUVToRGB never runs.  The planes
+    are the decoder's own (the YUV scorer input, include/ssimu2_hip_yuv.h)."""
+    L = _lib()
+    dec = L.avifDecoderCreate()
+    if not dec:
+        raise AvifBridgeError("OutOfMemory")
+    try:
+        if L.avifDecoderSetIOMemory(dec, data, len(data)) != _RESULT_OK:
+            raise AvifBridgeError("SetIOFailed")
+        rc = L.avifDecoderParse(dec)
+        if rc != _RESULT_OK:
+            _fail(L, "ParseFailed", rc)
+        rc = L.avifDecoderNextImage(dec)
+        if rc != _RESULT_OK:
+            _fail(L, "DecodeImageFailed", rc)
+        img = _ptr(dec, _DEC_IMAGE)
+        if not img:
+            raise AvifBridgeError("DecodeImageFailed", "decoder->image is null")
+        w, h, depth = _u32(img, _IMG_WIDTH), _u32(img, _IMG_HEIGHT), _u32(img, _IMG_DEPTH)
+        if not (0 < w <= 65536 and 0 < h <= 65536 and depth in (8, 10, 12)) or not 1 <= _u32(img, _IMG_YUVFORMAT) <= 4:
+            raise AvifBridgeError("DecodeImageFailed", f"implausible image header {w}x{h}, {depth}-bit")
+        return DecodedYuv(L, dec, img)
+    except BaseException:
+        L.avifDecoderDestroy(dec)
+        raise
 
 
 def decode_rgb8(data: bytes) -> np.ndarray:

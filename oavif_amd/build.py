@@ -16,11 +16,13 @@ LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip.so")              # the product: C ABI of include/ssimu2_hip.h, oavif_tq.h
 INSTR_LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip_instr.so")  # + include/ssimu2_hip_internal.h (bench / tests only)
 EXT_LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip_ext.so")      # + include/ssimu2_hip_ext.h (RGBA input)
+YUV_LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip_yuv.so")      # + include/ssimu2_hip_yuv.h (YUV input)
 HOST_PATH = os.path.join(LIB_DIR, "oavif_host")   # csrc/oavif_host.c: main.zig's flow in C over the two public headers + libavif
 SERVICE_PATH = os.path.join(LIB_DIR, "oavif_scored")  # csrc/oavif_scored.cpp: the resident scoring service
 SOURCES = ["ssimu2_hip.hip", "tq.cpp", "png_ingest.cpp", "remote_client.cpp"]
 INSTR_SOURCES = ["ssimu2_instrument.hip", "tq.cpp", "png_ingest.cpp", "remote_client.cpp"]  # ssimu2_instrument.hip includes ssimu2_hip.hip
 EXT_SOURCES = ["ssimu2_ext.hip", "tq.cpp", "png_ingest.cpp", "remote_client.cpp"]  # ssimu2_ext.hip includes ssimu2_hip.hip
+YUV_SOURCES = ["ssimu2_yuv.hip", "tq.cpp", "png_ingest.cpp", "remote_client.cpp"]  # ssimu2_yuv.hip includes ssimu2_ext.hip
 _PROGRAMS = ("oavif_host.c", "oavif_scored.cpp")  # linked against the library, not into it
 # The flags that shape device code: the libraries' compile lines, the ISA tests and scripts/isa_ab.py all take them here.
 DEVICE_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17",
@@ -45,7 +47,7 @@ def _headers():
 
 
 def libs_need_build() -> bool:
-    libs = (LIB_PATH, INSTR_LIB_PATH, EXT_LIB_PATH)
+    libs = (LIB_PATH, INSTR_LIB_PATH, EXT_LIB_PATH, YUV_LIB_PATH)
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
@@ -80,7 +82,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         fcntl.flock(lock, fcntl.LOCK_EX)
         if not force and not needs_build():
             return LIB_PATH
-        targets = ((LIB_PATH, SOURCES), (INSTR_LIB_PATH, INSTR_SOURCES), (EXT_LIB_PATH, EXT_SOURCES))
+        targets = ((LIB_PATH, SOURCES), (INSTR_LIB_PATH, INSTR_SOURCES), (EXT_LIB_PATH, EXT_SOURCES),
+                   (YUV_LIB_PATH, YUV_SOURCES))
         for target, sources in targets if force or libs_need_build() else ():
             tmp = target + f".tmp{os.getpid()}"
             cmd = [_hipcc(), *DEVICE_FLAGS, "-fPIC", "-shared",

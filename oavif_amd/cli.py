@@ -84,6 +84,9 @@ class AvifEncOptions:  # parse_args.zig:48-63
     color_primaries: int = 2
     transfer_characteristics: int = 2
     matrix_coefficients: int = 2
+    # not the reference's: probes hand the decoder's YUV planes to the scorer (avif_bridge.decode_yuv,
+    # include/ssimu2_hip_yuv.h) instead of libavif's 8-bit RGB; opt-in, --score-yuv 1
+    score_yuv: bool = False
 
 
 TUNE_MODES = ("ssim", "iq", "ssimulacra2")  # parse_args.zig:26-45
@@ -180,6 +183,8 @@ def parse_args(argv: List[str]) -> Tuple[AvifEncOptions, Optional[str], Optional
             o.transfer_characteristics = _int_arg(argv, i, 1, 18, a); i += 1
         elif a == "--matrix-coefficients":
             o.matrix_coefficients = _int_arg(argv, i, 0, 14, a); i += 1
+        elif a == "--score-yuv":   # this port's own; the usage text stays the reference's
+            o.score_yuv = _bool_arg(argv, i, a); i += 1
         elif inp is None:
             inp = a
         elif out is None:
@@ -422,7 +427,7 @@ def main(argv: Optional[List[str]] = None, scorer=None) -> int:
                 os.environ.setdefault("OAVIF_AMD_NO_TORCH", "1")  # a CLI run shares nothing with torch
             from . import _lib
             prefetched = int(os.environ.get("LOCAL_RANK", "0"))
-            _lib.lib().ssimu2_prefetch(prefetched)
+            (_lib.yuv_lib() if o.score_yuv else _lib.lib()).ssimu2_prefetch(prefetched)
         if inp is None or out is None:
             raise CliError("MissingInputOrOutput")
         src = load_source(inp)
@@ -447,7 +452,7 @@ def main(argv: Optional[List[str]] = None, scorer=None) -> int:
         from . import Ssimu2, search
         dev = int(os.environ.get("LOCAL_RANK", "0"))
         if scorer is None:
-            scorer = Ssimu2(dev, blur=blur_from_env())
+            scorer = Ssimu2(dev, blur=blur_from_env(), yuv=o.score_yuv)
             own_scorer = True
         fanned = []
         fan = int(os.environ.get("OAVIF_PROBE_FANOUT", "1") or 1)
@@ -458,7 +463,7 @@ def main(argv: Optional[List[str]] = None, scorer=None) -> int:
                 fanned = [Ssimu2(dev, blur=blur_from_env()) for _ in range(min(fan, 16) - 1)]
             r, data = search.search_image(
                 src, o, [scorer] + fanned, prepared,
-                found=lambda r: eprint(f"Found q{r.q} (score {r.score:.2f}, {r.num_pass} passes)"))
+                found=lambda r: eprint(f"Found q{r.q} (score {r.score:.2f}, {r.num_pass} passes)"), note=eprint)
         finally:
             for c in fanned:
                 c.close()
@@ -487,7 +492,7 @@ def main(argv: Optional[List[str]] = None, scorer=None) -> int:
             # context was created: let the background HIP start-up finish before the process
             # tears down under it
             from . import _lib
-            _lib.lib().ssimu2_prefetch_join(prefetched)
+            (_lib.yuv_lib() if o.score_yuv else _lib.lib()).ssimu2_prefetch_join(prefetched)
 
 
 if __name__ == "__main__":

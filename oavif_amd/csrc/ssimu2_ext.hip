@@ -77,13 +77,13 @@ int check_rgba(ssimu2_ctx* c, const void* a, const void* b, uint32_t row_bytes_a
 void composite(ssimu2_ctx* c, const Feed& f, uint32_t w, uint32_t h, void* dst) {
     const uint32_t groups = (w + 3) / 4;
     launch(k_composite_rgba8, dim3((groups + 255) / 256, h < 65535u ? h : 65535u), dim3(256), 0, c->stream,
-           c->stage.as<uint8_t>(), f.row_bytes, w, h, (uint32_t)f.bg, (uint16_t*)dst);
+           c->stage.as<uint8_t>(), f.plane[0].row_bytes, w, h, (uint32_t)f.bg, (uint16_t*)dst);
 }
 
 // One RGBA frame in host memory: its rows go through the staging buffer as they are, the front end reads the codes
 // through the composite table T (entry n: the 8-bit table's expression at n / 65025; entry 255 u is the 8-bit entry u).
 Feed rgba8(const uint8_t* pixels, uint32_t row_bytes, uint32_t bg) {
-    return {pixels, hipMemcpyHostToDevice, row_bytes, 4u, 1u, kAlphaTop, true, composite, (int64_t)bg};
+    return staged1(pixels, row_bytes, 4u, 1u, kAlphaTop, composite, (int64_t)bg);
 }
 
 }  // namespace

@@ -167,7 +167,7 @@ struct ssimu2_ctx {
         DevBuf xyb;   // positive-XYB planes of the reference, all scales
         DevBuf blur;  // blur(ref*ref) planes, all scales (null = not cached)
     } cache;
-    // stage: feed_reserve, for a frame whose rows are not the scorer's (the _strided, _strided16 and RGBA calls)
+    // stage: feed_reserve, for a frame whose rows are not the scorer's (the _strided, _strided16, RGBA and YUV calls)
     DevBuf stage;  // decoded avifRGBImage as uploaded (RGBA / padded rows)
     // rg: rg_ensure, SSIMU2_BLUR_RECURSIVE modes only (ssimu2_recursive.h); also released by ssimu2_ctx_set_blur(FIR)
     struct {
@@ -928,11 +928,17 @@ int device_table(ssimu2_ctx* c, uint32_t n, uint32_t top, const float** out) {
 // ---- a caller's frame onto the device ("One path for a frame") ---------------
 // How one frame of a call gets onto the device, for either slot of the context (the reference's or the distorted
 // frame's), and how the front end reads it there.
+struct Plane {
+    const void* px;      // the caller's rows
+    uint32_t row_bytes;  // bytes between them
+};
 struct Feed {
-    const void* px;      // the caller's frame
-    hipMemcpyKind kind;  // where that is: host memory, or an 8-bit frame already on the device
-    uint32_t row_bytes;  // bytes between its rows
-    uint32_t ch;         // samples per pixel there: 3, or 4 with the fourth skipped or composited away
+    // The caller's frame: one plane of interleaved pixels, or up to three planes of one sample per pixel (`unpack`
+    // makes the pixels of them); all `nplanes` of them of one layout (`ch`, `sample`) and in one place (`kind`)
+    Plane plane[3];
+    uint32_t nplanes;
+    hipMemcpyKind kind;  // where they are: host memory, or an 8-bit frame already on the device
+    uint32_t ch;         // samples per pixel there: 3, or 4 with the fourth skipped or composited away; 1 in a planar frame
     uint32_t sample;     // bytes per sample there: 1 or 2
     // 0: the front end reads an 8-bit RGB frame.  Else it reads u16 codes 0..top through the table of top + 1 entries:
     // 2^d - 1 for samples of depth d, 65025 for composite codes
@@ -943,14 +949,20 @@ struct Feed {
     bool staged;
     void (*unpack)(ssimu2_ctx* c, const Feed& f, uint32_t w, uint32_t h, void* dst);
     int64_t bg;  // 0xRRGGBB the unpacking composites over, which a reference keeps (ref.bg); -1: none
+    const void* aux = nullptr;  // what else `unpack` needs to know, the entry point's own; alive for the call
 };
 
+// A frame of one plane in host memory, staged: rows `row_bytes` apart of `ch` samples of `sample` bytes per pixel.
+Feed staged1(const void* px, uint32_t row_bytes, uint32_t ch, uint32_t sample, uint32_t top,
+             void (*unpack)(ssimu2_ctx*, const Feed&, uint32_t, uint32_t, void*), int64_t bg = -1) {
+    return {{{px, row_bytes}}, 1u, hipMemcpyHostToDevice, ch, sample, top, true, unpack, bg};
+}
 // Tight RGB frames of w pixels per row: 8-bit, and u16 samples of depth `bit_depth` in host memory.
 Feed tight8(const void* px, uint32_t w, hipMemcpyKind kind = hipMemcpyHostToDevice) {
-    return {px, kind, w * 3u, 3u, 1u, 0u, false, nullptr, -1};
+    return {{{px, w * 3u}}, 1u, kind, 3u, 1u, 0u, false, nullptr, -1};
 }
 Feed tight16(const void* px, uint32_t w, uint32_t bit_depth) {
-    return {px, hipMemcpyHostToDevice, w * 6u, 3u, 2u, (1u << bit_depth) - 1u, false, nullptr, -1};
+    return {{{px, w * 6u}}, 1u, hipMemcpyHostToDevice, 3u, 2u, (1u << bit_depth) - 1u, false, nullptr, -1};
 }
 
 // The slot's tight frame: ensure_capacity's 8-bit one, or the u16 one.
@@ -960,8 +972,17 @@ DevBuf& feed_frame(ssimu2_ctx* c, const Feed& f, bool ref) {
 
 // The last row needs only its pixels, not its padding (libavif allocates rowBytes * height, a cropped view of a larger
 // buffer may not).
+size_t plane_bytes(const Feed& f, uint32_t p, uint32_t w, uint32_t h) {
+    return (size_t)f.plane[p].row_bytes * (h - 1) + (size_t)w * f.ch * f.sample;
+}
+// Where plane `p` lies in `stage`: the planes back to back, each start 16-byte aligned (plane 0 at 0).
+size_t plane_off(const Feed& f, uint32_t p, uint32_t w, uint32_t h) {
+    size_t off = 0;
+    for (uint32_t q = 0; q < p; ++q) off += (plane_bytes(f, q, w, h) + 15) & ~(size_t)15;
+    return off;
+}
 size_t feed_bytes(const Feed& f, uint32_t w, uint32_t h) {
-    return (size_t)f.row_bytes * (h - 1) + (size_t)w * f.ch * f.sample;
+    return plane_off(f, f.nplanes - 1, w, h) + plane_bytes(f, f.nplanes - 1, w, h);
 }
 
 // Feeding a frame, first half: every buffer it needs beyond ensure_capacity's -- `stage` (16 bytes of slack behind the
@@ -986,10 +1007,12 @@ int feed_reserve(ssimu2_ctx* c, const Feed& f, bool ref, uint32_t w, uint32_t h,
 // context stream; *fed is what the front end reads.
 int feed_enqueue(ssimu2_ctx* c, const Feed& f, bool ref, uint32_t w, uint32_t h, Fed* fed) {
     void* const frame = feed_frame(c, f, ref).p;
-    HIP_TRY(c, hipMemcpyAsync(f.staged ? c->stage.p : frame, f.px, feed_bytes(f, w, h), f.kind, c->stream));
+    uint8_t* const to = (uint8_t*)(f.staged ? c->stage.p : frame);  // a frame that is not staged has one plane
+    for (uint32_t p = 0; p < f.nplanes; ++p)
+        HIP_TRY(c, hipMemcpyAsync(to + plane_off(f, p, w, h), f.plane[p].px, plane_bytes(f, p, w, h), f.kind, c->stream));
     if (f.unpack) f.unpack(c, f, w, h, frame);
     fed->u8 = f.top ? nullptr : (const uint8_t*)frame;
-    if (f.staged && !f.unpack) fed->s16 = {c->stage.p, f.row_bytes, f.ch, fed->s16.tab, f.top};
+    if (f.staged && !f.unpack) fed->s16 = {c->stage.p, f.plane[0].row_bytes, f.ch, fed->s16.tab, f.top};
     else fed->s16 = {frame, w * 6u, 3u, fed->s16.tab, f.top};
     return SSIMU2_OK;
 }
@@ -1818,12 +1841,13 @@ int ssimu2_score_against_reference(ssimu2_ctx* c, const uint8_t* dist, double* o
 
 // Decoded 8-bit rows in `stage` -> the tight RGB8 frame `dst` (Feed::unpack of the call below).
 static void unpack_rgb8(ssimu2_ctx* c, const Feed& f, uint32_t w, uint32_t h, void* dst) {
-    if (f.ch == 4 && w % 4 == 0 && f.row_bytes % 4 == 0)
+    const uint32_t row_bytes = f.plane[0].row_bytes;
+    if (f.ch == 4 && w % 4 == 0 && row_bytes % 4 == 0)
         launch(k_unpack_rgb<true>, dim3((w / 4 + 255) / 256, h), dim3(256), 0, c->stream, c->stage.as<uint8_t>(),
-               f.row_bytes, f.ch, w, h, (uint8_t*)dst);
+               row_bytes, f.ch, w, h, (uint8_t*)dst);
     else
         launch(k_unpack_rgb<false>, dim3((w + 255) / 256, h), dim3(256), 0, c->stream, c->stage.as<uint8_t>(),
-               f.row_bytes, f.ch, w, h, (uint8_t*)dst);
+               row_bytes, f.ch, w, h, (uint8_t*)dst);
 }
 
 int ssimu2_score_against_reference_strided(ssimu2_ctx* c, const uint8_t* pixels, uint32_t row_bytes,
@@ -1837,8 +1861,7 @@ int ssimu2_score_against_reference_strided(ssimu2_ctx* c, const uint8_t* pixels,
     if ((uint64_t)row_bytes < (uint64_t)w * channels)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "row_bytes smaller than one row of pixels");
     if (channels == 3 && row_bytes == w * 3) return score_against(c, tight8(pixels, w), out_score);  // scorer's layout
-    const Feed f{pixels, hipMemcpyHostToDevice, row_bytes, channels, 1u, 0u, true, unpack_rgb8, -1};
-    return score_against(c, f, out_score);
+    return score_against(c, staged1(pixels, row_bytes, channels, 1u, 0u, unpack_rgb8), out_score);
 }
 
 int ssimu2_error_map_rgb8(ssimu2_ctx* c, const uint8_t* ref, const uint8_t* dist, uint32_t w, uint32_t h,
@@ -1904,8 +1927,7 @@ int ssimu2_score_against_reference_strided16(ssimu2_ctx* c, const uint16_t* pixe
     if ((row_bytes & 1u) || (uint64_t)row_bytes < (uint64_t)c->ref.w * channels * 2)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "row_bytes odd or smaller than one row of 16-bit pixels");
     // rows are read where they are, in `stage`: padding and alpha skipped by the front end
-    const Feed f{pixels, hipMemcpyHostToDevice, row_bytes, channels, 2u, (1u << bit_depth) - 1u, true, nullptr, -1};
-    return score_against(c, f, out_score);
+    return score_against(c, staged1(pixels, row_bytes, channels, 2u, (1u << bit_depth) - 1u, nullptr), out_score);
 }
 
 int ssimu2_last_averages(ssimu2_ctx* c, double* out, int* out_num_scales) {

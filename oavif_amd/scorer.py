@@ -113,6 +113,47 @@ def _check_rgba8(a, name: str) -> np.ndarray:
     return a
 
 
+MATRIX_COEFFICIENTS = (1, 2, 5, 6, 9)   # the CICP codes include/ssimu2_hip_yuv.h converts
+
+
+class YuvFrame:
+    """A decoder's planes as the YUV calls take them (ssimu2_yuv_frame, include/ssimu2_hip_yuv.h): `planes` is (Y, U, V)
+    for format _lib.YUV_444 or (Y,) for _lib.YUV_400, each an (h, w) array -- uint8 at depth 8, uint16 at depth 10 and
+    12 -- whose rows may be any distance apart (a strided view of libavif's yuvPlanes goes through as it is; a view
+    whose samples are not adjacent within a row is copied).  `full_range` and `matrix_coefficients` are the image's
+    yuvRange and CICP matrix code."""
+
+    def __init__(self, planes, depth: int = 8, format: int = _lib.YUV_444, full_range: bool = True,
+                 matrix_coefficients: int = 6):
+        self.depth, self.format = int(depth), int(format)
+        self.full_range, self.matrix_coefficients = int(full_range), int(matrix_coefficients)
+        dtype = np.uint8 if self.depth == 8 else np.uint16
+        need = 1 if self.format == _lib.YUV_400 else 3
+        planes = list(planes)[:need]
+        if len(planes) < need:
+            raise ValueError(f"format {self.format} needs {need} plane(s), got {len(planes)}")
+        self.planes = []
+        for k, a in enumerate(planes):
+            a = np.asarray(a)
+            if a.dtype != dtype:
+                raise TypeError(f"plane {k} of a {self.depth}-bit frame must be {np.dtype(dtype).name}, got {a.dtype}")
+            if a.ndim != 2 or a.shape != np.asarray(planes[0]).shape:
+                raise ValueError(f"plane {k} must be (h, w) like plane 0, got {a.shape}")
+            if a.strides[1] != a.itemsize or (a.shape[0] > 1 and a.strides[0] < a.shape[1] * a.itemsize):
+                a = np.ascontiguousarray(a)
+            self.planes.append(a)
+        self.height, self.width = self.planes[0].shape
+
+    def as_c(self) -> "_lib.YuvFrameC":
+        """The C struct; it points into self.planes, which must stay alive for the call."""
+        c = _lib.YuvFrameC()
+        for k, a in enumerate(self.planes):
+            c.planes[k] = a.ctypes.data
+            c.row_bytes[k] = a.strides[0] if a.shape[0] > 1 else a.shape[1] * a.itemsize
+        c.depth, c.format, c.full_range, c.matrix_coefficients = self.depth, self.format, self.full_range, self.matrix_coefficients
+        return c
+
+
 def query_device(device: int = 0, instrumented: bool = False) -> dict:
     """ssimu2_query_device: what the library reads off HIP device `device` without creating a context
     (`usable` False = ssimu2_ctx_create would refuse it: not gfx950, or less than 160 KB of LDS per CU)."""
@@ -180,9 +221,10 @@ class Ssimu2:
     _ref_shape = None
 
     extended = False   # bound to liboavif_hip_ext.so (the RGBA calls of include/ssimu2_hip_ext.h)
+    yuv = False        # bound to liboavif_hip_yuv.so (the YUV calls of include/ssimu2_hip_yuv.h, and the RGBA calls)
 
     def __init__(self, device: int = 0, stream: int | None = None, instrumented: bool = False,
-                 blur: int | None = None, service: str | None = None, extended: bool = False):
+                 blur: int | None = None, service: str | None = None, extended: bool = False, yuv: bool = False):
         """`service`: socket path of a running scoring service (oavif_amd.service): the context lives there, and this
         process makes no HIP call for it (OAVIF_SCORER_SOCKET set around ssimu2_ctx_create, then restored; None = the
         environment as it is).  `instrumented=True` binds liboavif_hip_instr.so (the hooks of
@@ -190,11 +232,17 @@ class Ssimu2:
         default is the product library, which has none of them.  `blur`: _lib.BLUR_FIR /
         _lib.BLUR_RECURSIVE (ssimu2_ctx_set_blur); None = FIR.  `extended=True` binds liboavif_hip_ext.so instead: the
         product library plus the RGBA calls of include/ssimu2_hip_ext.h (composite_rgba, compute_ssimu2_rgba,
-        set_reference_rgba, score_against_reference_rgba); not together with `instrumented`."""
+        set_reference_rgba, score_against_reference_rgba); not together with `instrumented`.  `yuv=True` binds
+        liboavif_hip_yuv.so: the YUV calls of include/ssimu2_hip_yuv.h (convert_yuv, compute_ssimu2_yuv,
+        set_reference_yuv, score_against_reference_yuv); that library has the RGBA calls too, so `extended=True` may be
+        given as well; not together with `instrumented`."""
         if instrumented and extended:
             raise ValueError("instrumented=True and extended=True are different libraries: choose one")
-        self.instrumented, self.extended = bool(instrumented), bool(extended)
-        self._L = _lib.instr_lib() if instrumented else _lib.ext_lib() if extended else _lib.lib()
+        if instrumented and yuv:
+            raise ValueError("instrumented=True and yuv=True are different libraries: choose one")
+        self.instrumented, self.extended, self.yuv = bool(instrumented), bool(extended), bool(yuv)
+        self._L = (_lib.instr_lib() if instrumented else _lib.yuv_lib() if yuv else _lib.ext_lib() if extended
+                   else _lib.lib())
         self._ctx = ctypes.c_void_p()
         self._holder = None
         if service is None:
@@ -464,6 +512,51 @@ class Ssimu2:
         elif a.ndim != 1 or row_bytes is None or not a.flags.c_contiguous:
             raise ValueError("pixels must be (h, w, 4), libavif's (h, rowBytes) rows, or a flat buffer with row_bytes")
         return self._score(self._L.ssimu2_score_against_reference_rgba8, _u8p(a), int(row_bytes))
+
+    # -- YUV input (include/ssimu2_hip_yuv.h): the YUV library only ---------------
+    def _need_yuv(self):
+        if not self.yuv:
+            raise Ssimu2Error(_lib.ERR_UNSUPPORTED, "YUV input needs Ssimu2(..., yuv=True) (liboavif_hip_yuv.so)")
+
+    @staticmethod
+    def _yuv_frame(frame, name: str) -> YuvFrame:
+        if not isinstance(frame, YuvFrame):
+            raise TypeError(f"{name} must be a YuvFrame, got {type(frame).__name__}")
+        return frame
+
+    def convert_yuv(self, frame: YuvFrame, rgb_depth: int = 16) -> np.ndarray:
+        """ssimu2_convert_yuv: the (h, w, 3) uint16 RGB codes of depth `rgb_depth` the scorer makes of `frame`."""
+        self._need_yuv()
+        f = self._yuv_frame(frame, "frame")
+        out = np.empty((f.height, f.width, 3), np.uint16)
+        c = f.as_c()
+        self._call(self._L.ssimu2_convert_yuv, ctypes.byref(c), f.width, f.height, int(rgb_depth), _u16p(out))
+        return out
+
+    def compute_ssimu2_yuv(self, ref: YuvFrame, dist: YuvFrame, rgb_depth: int = 16) -> float:
+        """ssimu2_score_yuv: two YUV frames of one size, each converted with its own depth, range and matrix."""
+        self._need_yuv()
+        r, d = self._yuv_frame(ref, "ref"), self._yuv_frame(dist, "dist")
+        if (r.height, r.width) != (d.height, d.width):
+            raise ValueError("ref and dist must have the same shape")
+        cr, cd = r.as_c(), d.as_c()
+        return self._score(self._L.ssimu2_score_yuv, ctypes.byref(cr), ctypes.byref(cd), r.width, r.height, int(rgb_depth))
+
+    def set_reference_yuv(self, ref: YuvFrame, rgb_depth: int = 16) -> None:
+        """ssimu2_set_reference_yuv; later 8-bit, 16-bit and YUV frames can all be scored against it."""
+        self._need_yuv()
+        r = self._yuv_frame(ref, "ref")
+        c = r.as_c()
+        self._call(self._L.ssimu2_set_reference_yuv, ctypes.byref(c), r.width, r.height, int(rgb_depth))
+        self._ref_shape = (r.height, r.width, 3)
+
+    def score_against_reference_yuv(self, frame: YuvFrame, rgb_depth: int = 16) -> float:
+        """ssimu2_score_against_reference_yuv against the reference of any set_reference* call."""
+        self._need_yuv()
+        f = self._yuv_frame(frame, "frame")
+        self._check_ref_shape((f.height, f.width), "frame size")
+        c = f.as_c()
+        return self._score(self._L.ssimu2_score_against_reference_yuv, ctypes.byref(c), int(rgb_depth))
 
     # -- device-resident entry points (pointers are raw device addresses) -------------------
     # The per-frame ones make their C call in their own body, not through _call / _score / _scores: a 512x512 score is

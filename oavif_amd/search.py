@@ -3,7 +3,7 @@ driver both run between loading an image and writing its AVIF."""
 from __future__ import annotations
 
 
-def search_image(src, o, scorers, prepared, found=None):
+def search_image(src, o, scorers, prepared, found=None, note=None):
     """Find the quantizer of `src` (cli.Source) under the options `o` (cli.AvifEncOptions) and return
     (tq.TQResult, the AVIF bytes at its q).
 
@@ -17,7 +17,12 @@ def search_image(src, o, scorers, prepared, found=None):
     The bytes of the last probe are reused only when its quantizer is the chosen one (EncBuffer, tq.zig:31-35;
     main.zig:109-113), otherwise the image is encoded once more at the chosen q.  With fan-out every probe is kept:
     any of a wave may be the answer.  `found(result)`, when given, runs once the search has ended and before that
-    encode: the CLI reports the quantizer there, as main.zig:106 does, so the line is out when the encode fails."""
+    encode: the CLI reports the quantizer there, as main.zig:106 does, so the line is out when the encode fails.
+
+    `o.score_yuv` (--score-yuv 1; needs the bridge, one scorer, and that scorer an Ssimu2(..., yuv=True)): a probe hands
+    over the decoder's own Y, U and V planes (avif_bridge.decode_yuv) and avifImageYUVToRGB never runs on the host.  An
+    image with an alpha plane, subsampled chroma or a matrix the scorer does not convert goes through the RGB path as
+    before, with one line to `note` saying so."""
     from . import cli, tq
     fanout = len(scorers) > 1
     cache = {}
@@ -40,8 +45,26 @@ def search_image(src, o, scorers, prepared, found=None):
     elif prepared is not None:
         from . import avif_bridge
 
+        yuv = {"on": bool(getattr(o, "score_yuv", False))}
+
+        def fall_back(why: str):
+            yuv["on"] = False
+            if note is not None:
+                note(f"note: --score-yuv: {why}; scoring libavif's 8-bit RGB instead")
+
+        if yuv["on"] and not getattr(scorers[0], "yuv", False):
+            fall_back("the scorer context was not created with yuv=True")
+
         def codec_frame(q: int):
             data = encode(q)
+            if yuv["on"]:
+                from .scorer import MATRIX_COEFFICIENTS
+                f = avif_bridge.decode_yuv(data)
+                if not f.has_alpha and f.format in (1, 4) and f.matrix_coefficients in MATRIX_COEFFICIENTS:
+                    return f, len(data)
+                f.close()
+                fall_back("the decoded image has an alpha plane" if f.has_alpha else
+                          f"pixel format {f.format} / matrix {f.matrix_coefficients} is not converted on the device")
             return avif_bridge.decode_common(data), len(data)
         r = tq.search_hip_frames(scorers[0], src.rgb, codec_frame, **how)
     else:

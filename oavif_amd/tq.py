@@ -205,7 +205,10 @@ def search_hip_frames(scorer: Ssimu2, ref_rgb: np.ndarray, codec_frame, score_tg
     search_hip (the device unpacks to the same tight RGB8).
     A frame decoded at rgb_depth > 8 (avif_bridge.decode_common(data, rgb_depth)) is scored at that depth
     (`ssimu2_score_against_reference_strided16`).  A uint16 `ref_rgb` is a high-bit-depth source and needs its
-    `ref_bit_depth` (8..16); the default, a uint8 source, is the reference's search exactly."""
+    `ref_bit_depth` (8..16); the default, a uint8 source, is the reference's search exactly.
+    A frame of the decoder's own planes (avif_bridge.decode_yuv: `planes`, `depth`, `format`, `full_range`,
+    `matrix_coefficients`) is converted on the device at full precision and scored
+    (`ssimu2_score_against_reference_yuv`, rgb_depth 16); the scorer must be an Ssimu2(..., yuv=True)."""
     if ref_bit_depth is None:
         if np.asarray(ref_rgb).dtype == np.uint16:
             raise ValueError("a uint16 ref_rgb needs ref_bit_depth")
@@ -222,7 +225,11 @@ def search_hip_frames(scorer: Ssimu2, ref_rgb: np.ndarray, codec_frame, score_tg
             if (frame.height, frame.width) != ref.shape[:2]:
                 raise ValueError(f"codec returned {frame.width}x{frame.height}, expected {ref.shape[1]}x{ref.shape[0]}")
             depth = getattr(frame, "rgb_depth", 8)
-            if depth > 8:
+            if hasattr(frame, "matrix_coefficients"):
+                from .scorer import YuvFrame
+                score = scorer.score_against_reference_yuv(
+                    YuvFrame(frame.planes, frame.depth, frame.format, frame.full_range, frame.matrix_coefficients), 16)
+            elif depth > 8:
                 score = scorer.score_decoded_against_reference_hbd(frame.rows.reshape(-1), frame.row_bytes,
                                                                    frame.channels, depth)
             else:

@@ -1,0 +1,94 @@
+"""SSIMULACRA2 of an AVIF from the decoder's own Y, U and V planes, converted to RGB on the device with the exact colour
+matrix at full precision (include/ssimu2_hip_yuv.h).
+
+    python -m oavif_amd.yuvscore REF.png|REF.avif DIST.avif [--rgb-depth N] [--blur fir|recursive|recursive_fma] [--compare]
+
+prints the score of DIST against REF through the YUV path.  A PNG reference is taken as 8-bit RGB (alpha dropped, 16
+bits truncated, as the search takes its source); an AVIF reference goes through the YUV path too.  `--compare` adds
+the score of libavif's 8-bit RGB output of DIST (avifImageYUVToRGB at depth 8: libyuv's fixed-point conversion), which
+is what the reference program scores.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+
+from . import _lib
+from .scorer import MATRIX_COEFFICIENTS, Ssimu2, YuvFrame
+
+BLUR_MODES = {"fir": _lib.BLUR_FIR, "recursive": _lib.BLUR_RECURSIVE, "recursive_fma": _lib.BLUR_RECURSIVE_FMA}
+
+
+def rgb_depth_arg(text: str) -> int:
+    try:
+        v = int(text, 10)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--rgb-depth must be an integer 8..16, got {text!r}")
+    if not 8 <= v <= 16:
+        raise argparse.ArgumentTypeError(f"--rgb-depth must be 8..16, got {v}")
+    return v
+
+
+def parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(prog="python -m oavif_amd.yuvscore",
+                                 description="SSIMULACRA2 of an AVIF scored from its decoded YUV planes")
+    ap.add_argument("ref", help="reference: a PNG, or an AVIF (scored from its YUV planes too)")
+    ap.add_argument("dist", help="distorted image: an AVIF")
+    ap.add_argument("--rgb-depth", type=rgb_depth_arg, default=16, metavar="N",
+                    help="depth of the RGB codes the planes are converted to, 8..16 (default 16: full precision)")
+    ap.add_argument("--blur", choices=sorted(BLUR_MODES), default="fir")
+    ap.add_argument("--compare", action="store_true", help="also print the score of libavif's 8-bit RGB output")
+    ap.add_argument("--device", type=int, default=0)
+    return ap
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    ap = parser()
+    a = ap.parse_args(argv)
+    if not a.dist.lower().endswith(".avif"):
+        ap.error(f"DIST must be an AVIF, got {a.dist!r}")
+    if not a.ref.lower().endswith((".png", ".avif")):
+        ap.error(f"REF must be a PNG or an AVIF, got {a.ref!r}")
+    return a
+
+
+def frame_of(decoded) -> YuvFrame:
+    """avif_bridge.DecodedYuv -> YuvFrame (views: valid while `decoded` is open); ValueError for what the scorer does
+    not convert."""
+    if decoded.has_alpha:
+        raise ValueError("the image has an alpha plane: score it with python -m oavif_amd.alpha")
+    if decoded.format not in (_lib.YUV_444, _lib.YUV_400):
+        raise ValueError("subsampled chroma (4:2:0 / 4:2:2) is not converted on the device")
+    if decoded.matrix_coefficients not in MATRIX_COEFFICIENTS:
+        raise ValueError(f"matrix coefficients {decoded.matrix_coefficients} are not converted on the device")
+    return YuvFrame(decoded.planes, decoded.depth, decoded.format, decoded.full_range, decoded.matrix_coefficients)
+
+
+def main(argv=None) -> int:
+    a = parse_args(argv)
+    from . import avif_bridge as ab, cli
+    try:
+        dist_data = open(a.dist, "rb").read()
+        with Ssimu2(a.device, blur=BLUR_MODES[a.blur], yuv=True) as s, ab.decode_yuv(dist_data) as dist:
+            if a.ref.lower().endswith(".avif"):
+                with ab.decode_yuv(open(a.ref, "rb").read()) as ref:
+                    if (ref.width, ref.height) != (dist.width, dist.height):
+                        raise ValueError(f"{a.ref} is {ref.width}x{ref.height}, {a.dist} is {dist.width}x{dist.height}")
+                    s.set_reference_yuv(frame_of(ref), a.rgb_depth)
+            else:
+                rgb = cli.load_source(a.ref).rgb
+                if rgb.shape[:2] != (dist.height, dist.width):
+                    raise ValueError(f"{a.ref} is {rgb.shape[1]}x{rgb.shape[0]}, {a.dist} is {dist.width}x{dist.height}")
+                s.set_reference(rgb)
+            print(f"yuv {s.score_against_reference_yuv(frame_of(dist), a.rgb_depth):.6f}")
+            if a.compare:
+                with ab.decode_common(dist_data) as rgb8:
+                    print(f"rgb8 {s.score_decoded_against_reference(rgb8.rows.reshape(-1), rgb8.row_bytes, rgb8.channels):.6f}")
+    except (ValueError, OSError, ab.AvifBridgeError, cli.CliError) as e:
+        print(f"Error: {e}", file=sys.stderr)
+        return 1
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
