@@ -1,10 +1,11 @@
-"""Build the gfx950 shared library in-tree (oavif_amd/lib/liboavif_hip.so).
+"""Build the gfx950 shared libraries in-tree (oavif_amd/lib/liboavif_hip.so and its three siblings).
 
-hipcc cross-compiles without a GPU; the built .so travels to the GPU box with the
-repo snapshot (it is git-ignored, not gpurun-ignored).
+Every source is compiled once, to an object under oavif_amd/lib/obj; the four libraries are links of those objects
+(LIBRARIES).  hipcc cross-compiles without a GPU; the built libraries are git-ignored.
 """
 from __future__ import annotations
 
+import concurrent.futures
 import os
 import shutil
 import subprocess
@@ -19,10 +20,18 @@ EXT_LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip_ext.so")      # + include/ssi
 YUV_LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip_yuv.so")      # + include/ssimu2_hip_yuv.h (YUV input)
 HOST_PATH = os.path.join(LIB_DIR, "oavif_host")   # csrc/oavif_host.c: main.zig's flow in C over the two public headers + libavif
 SERVICE_PATH = os.path.join(LIB_DIR, "oavif_scored")  # csrc/oavif_scored.cpp: the resident scoring service
-SOURCES = ["ssimu2_hip.hip", "tq.cpp", "png_ingest.cpp", "remote_client.cpp"]
-INSTR_SOURCES = ["ssimu2_instrument.hip", "tq.cpp", "png_ingest.cpp", "remote_client.cpp"]  # ssimu2_instrument.hip includes ssimu2_hip.hip
-EXT_SOURCES = ["ssimu2_ext.hip", "tq.cpp", "png_ingest.cpp", "remote_client.cpp"]  # ssimu2_ext.hip includes ssimu2_hip.hip
-YUV_SOURCES = ["ssimu2_yuv.hip", "tq.cpp", "png_ingest.cpp", "remote_client.cpp"]  # ssimu2_yuv.hip includes ssimu2_ext.hip
+OBJ_DIR = os.path.join(LIB_DIR, "obj")  # one object per source, whichever libraries it is linked into
+# Library -> the units linked into it.  A front end (csrc/ssimu2_host.h is what it may use) is a unit of its own on top of
+# the objects of the library below it: the same scorer object, not the same text compiled again.  The instrumented
+# library is another build of the scorer (ssimu2_instrument.hip includes ssimu2_hip.hip under its macro), so it shares
+# only the support objects.
+SUPPORT_SOURCES = ["tq.cpp", "png_ingest.cpp", "remote_client.cpp"]
+SOURCES = ["ssimu2_hip.hip", *SUPPORT_SOURCES]
+EXT_SOURCES = [*SOURCES, "ssimu2_ext.hip"]
+YUV_SOURCES = [*EXT_SOURCES, "ssimu2_yuv.hip"]
+INSTR_SOURCES = ["ssimu2_instrument.hip", *SUPPORT_SOURCES]
+LIBRARIES = {LIB_PATH: SOURCES, INSTR_LIB_PATH: INSTR_SOURCES, EXT_LIB_PATH: EXT_SOURCES, YUV_LIB_PATH: YUV_SOURCES}
+MAX_COMPILES = 6  # compiles in flight; never the machine's CPU count
 _PROGRAMS = ("oavif_host.c", "oavif_scored.cpp")  # linked against the library, not into it
 # The flags that shape device code: the libraries' compile lines, the ISA tests and scripts/isa_ab.py all take them here.
 DEVICE_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17",
@@ -46,8 +55,13 @@ def _headers():
     return [os.path.join(inc, s) for s in os.listdir(inc)]
 
 
+def compile_units():
+    """Every source of LIBRARIES, once, in the table's order: what build() compiles."""
+    return list(dict.fromkeys(s for sources in LIBRARIES.values() for s in sources))
+
+
 def libs_need_build() -> bool:
-    libs = (LIB_PATH, INSTR_LIB_PATH, EXT_LIB_PATH, YUV_LIB_PATH)
+    libs = tuple(LIBRARIES)
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
@@ -82,27 +96,42 @@ def build(force: bool = False, verbose: bool = False) -> str:
         fcntl.flock(lock, fcntl.LOCK_EX)
         if not force and not needs_build():
             return LIB_PATH
-        targets = ((LIB_PATH, SOURCES), (INSTR_LIB_PATH, INSTR_SOURCES), (EXT_LIB_PATH, EXT_SOURCES),
-                   (YUV_LIB_PATH, YUV_SOURCES))
-        for target, sources in targets if force or libs_need_build() else ():
-            tmp = target + f".tmp{os.getpid()}"
-            cmd = [_hipcc(), *DEVICE_FLAGS, "-fPIC", "-shared",
-                   "-fvisibility=hidden", "-fvisibility-inlines-hidden",  # exports = the headers' functions
-                   "-Wall", "-Wno-unused-function", "-o", tmp]
-            cmd += os.environ.get("OAVIF_AMD_EXTRA_HIPCC_FLAGS", "").split()  # A/B builds of experiments
-            cmd += [os.path.join(CSRC, s) for s in sources]
-            cmd += ["-lz"]  # png_ingest.cpp inflates with zlib
-            if verbose:
-                print(" ".join(cmd), file=sys.stderr)
-            try:
-                subprocess.run(cmd, check=True)
-                os.replace(tmp, target)
-            finally:
-                if os.path.exists(tmp):
-                    os.unlink(tmp)
+        if force or libs_need_build():
+            _build_libs(verbose)
         build_host(verbose)
         build_service(verbose)
     return LIB_PATH
+
+
+def _run_to(target: str, cmd, verbose: bool) -> None:
+    """Run cmd + ["-o", a temporary name], then put the result at `target` atomically."""
+    tmp = target + f".tmp{os.getpid()}"
+    cmd = [*cmd, "-o", tmp]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    try:
+        subprocess.run(cmd, check=True)
+        os.replace(tmp, target)
+    finally:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+
+
+def _build_libs(verbose: bool) -> None:
+    """Objects, then links: each unit of compile_units() to OBJ_DIR (MAX_COMPILES at a time), each library from its own."""
+    os.makedirs(OBJ_DIR, exist_ok=True)
+    flags = [*DEVICE_FLAGS, "-fPIC",
+             "-fvisibility=hidden", "-fvisibility-inlines-hidden",  # exports = the headers' functions
+             "-Wall", "-Wno-unused-function"]
+    flags += os.environ.get("OAVIF_AMD_EXTRA_HIPCC_FLAGS", "").split()  # A/B builds of experiments
+    hipcc = _hipcc()
+    obj = {s: os.path.join(OBJ_DIR, s + ".o") for s in compile_units()}
+    with concurrent.futures.ThreadPoolExecutor(MAX_COMPILES) as pool:
+        jobs = [pool.submit(_run_to, o, [hipcc, *flags, "-c", os.path.join(CSRC, s)], verbose) for s, o in obj.items()]
+    for job in jobs:
+        job.result()  # the first failed compile raises here
+    for target, sources in LIBRARIES.items():
+        _run_to(target, [hipcc, *flags, "-shared", *(obj[s] for s in sources), "-lz"], verbose)  # -lz: png_ingest.cpp
 
 
 def build_host(verbose: bool = False) -> str:

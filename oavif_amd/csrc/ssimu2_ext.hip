@@ -1,16 +1,18 @@
 // RGBA input of the MI355X SSIMULACRA2 scorer: the entry points of include/ssimu2_hip_ext.h.
 //
-// This translation unit is the product translation unit (ssimu2_hip.hip, included below: same kernels, same host
-// code, same flags) plus one kernel and five functions.  It is built into liboavif_hip_ext.so; liboavif_hip.so and
-// liboavif_hip_instr.so contain none of this, and their exports are what they were.
+// A translation unit of its own: one kernel, one Feed constructor, one check and five functions over ssimu2_host.h, the
+// list of what a front end may use of the scorer.  Its object is linked with the product library's objects into
+// liboavif_hip_ext.so (and liboavif_hip_yuv.so); liboavif_hip.so and liboavif_hip_instr.so contain none of this, and
+// their exports are what they were.
 //
 // An RGBA frame becomes a u16 frame of exact integer codes n = a * c + (255 - a) * b (k_composite_rgba8) that the
 // 16-bit front end reads through a table of its own: Src16{codes, w * 6, 3, T, 65025}.  No pyramid, marching,
 // recursive or finalize kernel knows about alpha.  To the host code an RGBA frame is one more Feed (rgba8 below): the
 // three shapes of a call -- score_pair, feed_reference, score_against -- are the product's.
-#include "ssimu2_hip.hip"
-
 #include "../../include/ssimu2_hip_ext.h"
+#include "ssimu2_host.h"
+
+using namespace ssimu2h;
 
 namespace ssimu2 {
 
@@ -58,6 +60,8 @@ __global__ __launch_bounds__(256) void k_composite_rgba8(const uint8_t* __restri
 
 }  // namespace ssimu2
 
+using namespace ssimu2;
+
 namespace {
 
 constexpr uint32_t kAlphaTop = SSIMU2_ALPHA_CODES - 1;  // 65025 = 255 * 255, the largest code
@@ -95,19 +99,9 @@ int ssimu2_alpha_table(float* out) { return copy_table(SSIMU2_ALPHA_CODES, kAlph
 int ssimu2_composite_rgba8(ssimu2_ctx* c, const uint8_t* pixels, uint32_t row_bytes, uint32_t w, uint32_t h,
                            uint32_t background_rgb, uint16_t* out_codes) {
     REMOTE_REFUSE(c, "ssimu2_composite_rgba8");
-    int rc = check_rgba(c, pixels, out_codes, row_bytes, row_bytes, w, h, background_rgb);
+    const int rc = check_rgba(c, pixels, out_codes, row_bytes, row_bytes, w, h, background_rgb);
     if (rc) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const Feed f = rgba8(pixels, row_bytes, background_rgb);
-    Fed codes{};
-    if ((rc = feed_reserve(c, f, false, w, h, &codes))) return rc;
-    hipError_t e = hipSuccess;
-    if (!(rc = feed_enqueue(c, f, false, w, h, &codes)) &&  // the download is this diagnostic's alone
-        ((e = hipGetLastError()) != hipSuccess ||
-         (e = hipMemcpyAsync(out_codes, codes.s16.px, (size_t)w * h * 6, hipMemcpyDeviceToHost, c->stream)) ||
-         (e = hipStreamSynchronize(c->stream)) != hipSuccess))
-        rc = c->fail(SSIMU2_ERR_HIP, "ssimu2_composite_rgba8", e);
-    return leave(c, rc);
+    return feed_codes(c, rgba8(pixels, row_bytes, background_rgb), w, h, out_codes, "ssimu2_composite_rgba8");
 }
 
 int ssimu2_score_rgba8(ssimu2_ctx* c, const uint8_t* ref, uint32_t ref_row_bytes, const uint8_t* dist,

@@ -27,11 +27,6 @@
 // k_finalize launch that writes its 880 bytes into the host mirror itself (recursive modes: conversion, horizontal
 // pass, vertical pass + maps, k_finalize); everything on the ctx stream, no host sync inside (enqueue / wait
 // split).  Streams the library creates are placed on distinct hardware queues ("stream placement").
-#include <hip/hip_runtime.h>
-#ifdef SSIMU2_INSTRUMENTED_BUILD
-#include <hip/hip_ext.h>
-#endif
-
 #include <ctype.h>
 #include <math.h>
 #include <stdint.h>
@@ -46,13 +41,14 @@
 #include <string>
 #include <type_traits>
 
-#include "../../include/ssimu2_hip.h"
 #include "../../include/ssimu2_hip_internal.h"  // SSIMU2_MARCH_*
-#include "remote_client.h"
+#define SSIMU2_CORE_UNIT 1  // the unit whose ssimu2_ctx the instrumented build may lay out differently
+#include "ssimu2_host.h"    // ssimu2_ctx, DevBuf, launch, Feed: what this unit shares with the front ends
 #include "ssimu2_kernels.h"
 #include "ssimu2_recursive.h"
 
 using namespace ssimu2;
+using namespace ssimu2h;  // this unit defines every function ssimu2_host.h declares, each as ssimu2h::name
 
 namespace {
 
@@ -122,168 +118,6 @@ void gaussian_taps(double sigma, float taps[5], float n2_out[3], float d1_out[3]
 }
 
 thread_local std::string g_create_error;
-
-// One buffer of a context: device memory, or (`host`) page-locked host memory that a kernel writes.  `cap` is in
-// bytes, always; p is null exactly when cap is 0.  grow() is the one place that allocates.
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    bool host = false;
-    template <class T>
-    T* as() const { return (T*)p; }
-    void release() {
-        (void)(host ? hipHostFree(p) : hipFree(p));
-        p = nullptr;
-        cap = 0;
-    }
-};
-
-}  // namespace
-
-struct ssimu2_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;   // created here, destroyed with the ctx
-    bool pool_stream = false;  // borrowed from the process-wide set of streams on distinct hardware queues
-    std::string err;
-    // set: the context lives in a scoring service (OAVIF_SCORER_SOCKET at ssimu2_ctx_create, remote_client.h); nothing
-    // below is used then, and every entry point hands over to it on its first line (REMOTE)
-    ssimu2r::Remote* remote = nullptr;
-
-    int blur_mode = SSIMU2_BLUR_FIR;
-    ssimu2_device_info dev{};  // what ctx_create saw of the device (and checked: gfx950, 160 KB of LDS per CU)
-
-    // The buffers, grouped by who releases them: the rows of DESIGN.md section 3, "Which call touches which buffer".
-    // A group is a struct of DevBuf members and nothing else, so that release(group) finds every one of them.
-    // Every group from `frame` to `hbd` is released when the frame buffers regrow (release_frame_groups).
-    // frame: ensure_capacity grows all five or none
-    struct {
-        DevBuf ref_u8, dist_u8;    // interleaved RGB8
-        DevBuf lin_ref, lin_dist;  // fp32, scales 1..5 packed
-        DevBuf partials;           // fp64 [scale][18][workgroups]
-    } frame;
-    // cache: cache_reference_fir, for a reference set in FIR mode
-    struct {
-        DevBuf xyb;   // positive-XYB planes of the reference, all scales
-        DevBuf blur;  // blur(ref*ref) planes, all scales (null = not cached)
-    } cache;
-    // stage: feed_reserve, for a frame whose rows are not the scorer's (the _strided, _strided16, RGBA and YUV calls)
-    DevBuf stage;  // decoded avifRGBImage as uploaded (RGBA / padded rows)
-    // rg: rg_ensure, SSIMU2_BLUR_RECURSIVE modes only (ssimu2_recursive.h); also released by ssimu2_ctx_set_blur(FIR)
-    struct {
-        DevBuf planes;  // fp32, every scale packed: XYB planes of both frames [3], the reference's cached mu1 / s11
-                        // planes [6], the horizontal pass of a pass's planes [9]
-        DevBuf part;    // fp64 [scale][18][column groups]
-        DevBuf dbg;     // instrumented builds: 15 + 15 raw fp32 planes of scale rg_dbg_scale
-    } rg;
-    unsigned* d_rg_q = nullptr;  // job cursor of the persistent vertical pass (RgPlan::q, 4 words); released with `rg`
-    int num_cus = 0;             // workgroups of that kernel: one per CU
-    unsigned rg_v_pad = 0;       // unused dynamic LDS of k_rg_v's launch: rg_v_pad_bytes(dev.lds_bytes_per_cu)
-    // map: map_ensure, by the first ssimu2_error_map_* call
-    struct {
-        DevBuf dens;  // fp32 per-(scale, channel) density planes [scale][3][h_s][w_s]
-        DevBuf out;   // the full-resolution fp32 map [h][w]
-    } map;
-    // hbd: the first 16-bit call (ssimu2_*_rgb16 / _strided16)
-    struct {
-        DevBuf ref16, dist16;        // the tight u16 frames
-        DevBuf lin0_ref, lin0_dist;  // FIR: the frames' scale-0 linear planes, fp32 [3][h][w]
-    } hbd;
-    // tab: device_table; released by ssimu2_ctx_destroy only.  The sRGB -> linear tables of depths 8..16: depth d at
-    // float offset 2^d - 256, uploaded by the first call at that depth
-    DevBuf tab;
-    // alpha: device_table, by the first RGBA call (the extension library's: ssimu2_ext.hip, include/ssimu2_hip_ext.h;
-    // nothing in the product library feeds RGBA); released by ssimu2_ctx_destroy only.  The table of the 65,026
-    // composite codes
-    DevBuf alpha_tab;
-    uint32_t tab_ready = 0;  // bit d: the depth-d table is in `tab`; bit 0: the composite table is in `alpha_tab`
-    // batch: batch_run / batch_stage (ssimu2_score_batch_*), each buffer when too small; released by ssimu2_ctx_destroy
-    // only.  Scratch of its own, so a batch leaves the single-score buffers and a cached reference alone: the staged
-    // 8-bit frames of the host-pointer forms, the linear pyramids (scales 1..5) and partial sums of every item, and the
-    // page-locked result block k_finalize_batch writes (110 doubles per item)
-    struct {
-        DevBuf u8_ref, u8_dist, lin_ref, lin_dist, part;
-        DevBuf result{nullptr, 0, true};
-    } batch;
-    uint32_t batch_n = 0;  // items of the last finished batch (ssimu2_last_batch_averages)
-    // result: ssimu2_ctx_create; ssimu2_ctx_destroy
-    double* d_result = nullptr;         // 110 doubles in device memory: the stage timing of the instrumented build only
-    DevBuf h_result{nullptr, 0, true};  // page-locked host memory k_finalize writes the result into (110 doubles)
-
-    // The cached reference: set by reference_set, dropped where its storage is released or overwritten
-    struct {
-        bool have = false, hbd = false;  // hbd: set from 16-bit samples (its 8-bit frame buffer is not it)
-        uint32_t w = 0, h = 0;
-        int64_t bg = -1;  // 0xRRGGBB the reference was composited over (ssimu2_set_reference_rgba8); -1: none recorded
-        void drop() { have = hbd = false, w = h = 0, bg = -1; }
-        void set(uint32_t w_, uint32_t h_, bool hbd_, int64_t bg_) {
-            have = true, hbd = hbd_, w = w_, h = h_, bg = bg_;
-        }
-    } ref;
-    bool pending = false;
-
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // measurement builds only (ssimu2_instrument.hip); always 0 / true in the product library
-    int seg_rows_override = 0;
-    int seg_rows_tail_override = 0;
-    int batch_seg_override = 0;  // scale-0 rows of a batch item: 0 = the rule, -1 = the single-score rule, 8..160 fixed
-    bool cache_ref_blur = true;
-    int rg_dbg_scale = -1;  // recursive mode: keep that scale's 15 raw planes (after each pass) downloadable
-#ifdef SSIMU2_INSTRUMENTED_BUILD
-    // the frame size whose scale-0 planes hbd.lin0_ref / hbd.lin0_dist hold for the last score or reference (0: none;
-    // for ssimu2_debug_download at scale 0)
-    uint32_t lin0_ref_w = 0, lin0_ref_h = 0, lin0_dist_w = 0, lin0_dist_h = 0;
-    int last_march = 0;  // SSIMU2_MARCH_* of the last score or batch (ssimu2_instr_last_march)
-#endif
-
-    int fail(int code, const char* what, hipError_t e = hipSuccess) {
-        char buf[256];
-        if (e != hipSuccess) snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-        else snprintf(buf, sizeof buf, "%s", what);
-        err = buf;
-        return code;
-    }
-};
-
-#define REMOTE(c, call) \
-    if ((c) && (c)->remote) return ssimu2r::call
-#define REMOTE_REFUSE(c, name) REMOTE(c, unsupported((c)->remote, name))
-
-namespace {
-
-#define HIP_TRY(ctx, call)                                                   \
-    do {                                                                     \
-        hipError_t e_ = (call);                                              \
-        if (e_ != hipSuccess) return (ctx)->fail(SSIMU2_ERR_HIP, #call, e_); \
-    } while (0)
-
-// Every kernel of a score goes through launch().  Product build: hipLaunchKernelGGL, nothing else.  Instrumented build
-// (ssimu2_instrument.hip): while a timing scope is open on the calling thread the same launch is made with
-// hipExtLaunchKernelGGL and a start / stop event pair, so the duration of each kernel comes from its own dispatch packet
-// (what rocprofv3's kernel trace reads) with no marker or barrier packet added between the launches of a score.
-template <class T>
-struct arg_of { using type = T; };
-#ifdef SSIMU2_INSTRUMENTED_BUILD
-struct LaunchTimer {
-    hipEvent_t* ev;  // cap events: launch k of the scope uses ev[2k] (start) and ev[2k + 1] (stop)
-    int n, cap;
-};
-thread_local LaunchTimer* g_launch_timer = nullptr;
-#endif
-template <typename... KArgs>
-inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, unsigned lds, hipStream_t stream,
-                   typename arg_of<KArgs>::type... args) {
-#ifdef SSIMU2_INSTRUMENTED_BUILD
-    if (LaunchTimer* t = g_launch_timer) {
-        if (t->n + 2 <= t->cap) {
-            hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, t->ev[t->n], t->ev[t->n + 1], 0, args...);
-            t->n += 2;
-            return;
-        }
-    }
-#endif
-    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
-}
 
 // Instrumented build: record whether hbd.lin0_ref / hbd.lin0_dist hold the w x h scale-0 planes of the last score or
 // reference (1: they do from now on, 0: they do not, -1: unchanged).  Nothing in the product library.
@@ -545,16 +379,7 @@ void launch_pyramid(ssimu2_ctx* c, const Pyramid& p, int nframes, const uint8_t*
     launch(k_pyramid_bands, dim3(a.bands_x * a.bands_y * nframes), dim3(PYR_THREADS), 0, c->stream, a);
 }
 
-// ---- 16-bit input ----------------------------------------------------------
-// One 16-bit frame on the device: rows `pitch` bytes apart, `ch` = 3 (RGB) or 4 (RGBA) samples per pixel, read through
-// the table of its depth.
-struct Src16 {
-    const void* px;
-    uint32_t pitch, ch;
-    const float* tab;
-    uint32_t maxv;
-};
-
+// ---- 16-bit input (Src16: ssimu2_host.h) ------------------------------------
 PyrHbdArgs hbd_args(int nframes, const Src16* const* src, float* const* lin0) {
     PyrHbdArgs hb{};
     for (int f = 0; f < nframes; ++f) {
@@ -808,12 +633,6 @@ int rg_prepare(ssimu2_ctx* c, const Pyramid& p, uint32_t w, uint32_t h, bool nee
     return SSIMU2_OK;
 }
 
-// A frame where the front end reads it: an 8-bit RGB frame (`u8`), or with `u8` null 16-bit codes (`s16`).
-struct Fed {
-    const uint8_t* u8;
-    Src16 s16;
-};
-
 // What a pass against the cached reference is refused for once its arguments are in order, before anything of it is
 // enqueued.  FIR: a 16-bit scale 0 (`hbd`) cannot be paired with an 8-bit reference frame in one marching kernel, so it
 // needs the reference's cached planes.  Recursive modes: rg_prepare.
@@ -892,14 +711,18 @@ const float* host_table(uint32_t n, uint32_t top) {
     return t;
 }
 
+}  // namespace
+
 // The tables as the exported functions hand them out.
-int copy_table(uint32_t n, uint32_t top, float* out) {
+int ssimu2h::copy_table(uint32_t n, uint32_t top, float* out) {
     if (!out) return SSIMU2_ERR_INVALID_ARG;
     const float* t = host_table(n, top);
     if (!t) return SSIMU2_ERR_OOM;
     memcpy(out, t, (size_t)n * sizeof(float));
     return SSIMU2_OK;
 }
+
+namespace {
 
 size_t table_off(uint32_t d) { return ((size_t)1 << d) - 256; }
 
@@ -925,38 +748,7 @@ int device_table(ssimu2_ctx* c, uint32_t n, uint32_t top, const float** out) {
     return SSIMU2_OK;
 }
 
-// ---- a caller's frame onto the device ("One path for a frame") ---------------
-// How one frame of a call gets onto the device, for either slot of the context (the reference's or the distorted
-// frame's), and how the front end reads it there.
-struct Plane {
-    const void* px;      // the caller's rows
-    uint32_t row_bytes;  // bytes between them
-};
-struct Feed {
-    // The caller's frame: one plane of interleaved pixels, or up to three planes of one sample per pixel (`unpack`
-    // makes the pixels of them); all `nplanes` of them of one layout (`ch`, `sample`) and in one place (`kind`)
-    Plane plane[3];
-    uint32_t nplanes;
-    hipMemcpyKind kind;  // where they are: host memory, or an 8-bit frame already on the device
-    uint32_t ch;         // samples per pixel there: 3, or 4 with the fourth skipped or composited away; 1 in a planar frame
-    uint32_t sample;     // bytes per sample there: 1 or 2
-    // 0: the front end reads an 8-bit RGB frame.  Else it reads u16 codes 0..top through the table of top + 1 entries:
-    // 2^d - 1 for samples of depth d, 65025 for composite codes
-    uint32_t top;
-    // The rows go into the slot's tight frame as they are (`staged` false: they are tight RGB), or into `stage`.  From
-    // there `unpack` launches what makes the slot's tight frame `dst` of them; with none the front end reads them in
-    // `stage`, pitch, fourth sample and all (16-bit samples only)
-    bool staged;
-    void (*unpack)(ssimu2_ctx* c, const Feed& f, uint32_t w, uint32_t h, void* dst);
-    int64_t bg;  // 0xRRGGBB the unpacking composites over, which a reference keeps (ref.bg); -1: none
-    const void* aux = nullptr;  // what else `unpack` needs to know, the entry point's own; alive for the call
-};
-
-// A frame of one plane in host memory, staged: rows `row_bytes` apart of `ch` samples of `sample` bytes per pixel.
-Feed staged1(const void* px, uint32_t row_bytes, uint32_t ch, uint32_t sample, uint32_t top,
-             void (*unpack)(ssimu2_ctx*, const Feed&, uint32_t, uint32_t, void*), int64_t bg = -1) {
-    return {{{px, row_bytes}}, 1u, hipMemcpyHostToDevice, ch, sample, top, true, unpack, bg};
-}
+// ---- a caller's frame onto the device ("One path for a frame"; Feed: ssimu2_host.h) ----
 // Tight RGB frames of w pixels per row: 8-bit, and u16 samples of depth `bit_depth` in host memory.
 Feed tight8(const void* px, uint32_t w, hipMemcpyKind kind = hipMemcpyHostToDevice) {
     return {{{px, w * 3u}}, 1u, kind, 3u, 1u, 0u, false, nullptr, -1};
@@ -975,20 +767,32 @@ DevBuf& feed_frame(ssimu2_ctx* c, const Feed& f, bool ref) {
 size_t plane_bytes(const Feed& f, uint32_t p, uint32_t w, uint32_t h) {
     return (size_t)f.plane[p].row_bytes * (h - 1) + (size_t)w * f.ch * f.sample;
 }
+
+}  // namespace
+
+// A frame of one plane in host memory, staged: rows `row_bytes` apart of `ch` samples of `sample` bytes per pixel.
+Feed ssimu2h::staged1(const void* px, uint32_t row_bytes, uint32_t ch, uint32_t sample, uint32_t top,
+                      void (*unpack)(ssimu2_ctx*, const Feed&, uint32_t, uint32_t, void*), int64_t bg) {
+    return {{{px, row_bytes}}, 1u, hipMemcpyHostToDevice, ch, sample, top, true, unpack, bg};
+}
+
 // Where plane `p` lies in `stage`: the planes back to back, each start 16-byte aligned (plane 0 at 0).
-size_t plane_off(const Feed& f, uint32_t p, uint32_t w, uint32_t h) {
+size_t ssimu2h::plane_off(const Feed& f, uint32_t p, uint32_t w, uint32_t h) {
     size_t off = 0;
     for (uint32_t q = 0; q < p; ++q) off += (plane_bytes(f, q, w, h) + 15) & ~(size_t)15;
     return off;
 }
+
+namespace {
 size_t feed_bytes(const Feed& f, uint32_t w, uint32_t h) {
     return plane_off(f, f.nplanes - 1, w, h) + plane_bytes(f, f.nplanes - 1, w, h);
 }
+}  // namespace
 
 // Feeding a frame, first half: every buffer it needs beyond ensure_capacity's -- `stage` (16 bytes of slack behind the
 // frame), and for u16 codes the slot's tight frame, in FIR mode its scale-0 linear planes, the table (fed->s16.tab).
 // Enqueues nothing that reads the caller's memory, so a failure needs no wait.
-int feed_reserve(ssimu2_ctx* c, const Feed& f, bool ref, uint32_t w, uint32_t h, Fed* fed) {
+int ssimu2h::feed_reserve(ssimu2_ctx* c, const Feed& f, bool ref, uint32_t w, uint32_t h, Fed* fed) {
     int rc;
     if (f.staged && (rc = grow(c, c->stage, feed_bytes(f, w, h) + 16, "hipMalloc(staging frame)"))) return rc;
     if (!f.top) return SSIMU2_OK;
@@ -1005,7 +809,7 @@ int feed_reserve(ssimu2_ctx* c, const Feed& f, bool ref, uint32_t w, uint32_t h,
 
 // Second half, after every feed_reserve of the call: the copy from the caller's memory and the unpacking, on the
 // context stream; *fed is what the front end reads.
-int feed_enqueue(ssimu2_ctx* c, const Feed& f, bool ref, uint32_t w, uint32_t h, Fed* fed) {
+int ssimu2h::feed_enqueue(ssimu2_ctx* c, const Feed& f, bool ref, uint32_t w, uint32_t h, Fed* fed) {
     void* const frame = feed_frame(c, f, ref).p;
     uint8_t* const to = (uint8_t*)(f.staged ? c->stage.p : frame);  // a frame that is not staged has one plane
     for (uint32_t p = 0; p < f.nplanes; ++p)
@@ -1019,10 +823,28 @@ int feed_enqueue(ssimu2_ctx* c, const Feed& f, bool ref, uint32_t w, uint32_t h,
 
 // The one way out of a call from its first copy out of the caller's memory onwards: a failed call waits for the
 // stream, so that the caller may free its frames after any return (a call that succeeds has waited for its result).
-int leave(ssimu2_ctx* c, int rc) {
+int ssimu2h::leave(ssimu2_ctx* c, int rc) {
     if (rc) (void)hipStreamSynchronize(c->stream);
     return rc;
 }
+
+// The body of the front ends' diagnostics (ssimu2_composite_rgba8, ssimu2_convert_yuv), after their argument checks:
+// the frame `f` of u16 codes goes into the distorted slot as in a score, and its w * h * 3 codes come back.
+int ssimu2h::feed_codes(ssimu2_ctx* c, const Feed& f, uint32_t w, uint32_t h, uint16_t* out_codes, const char* what) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    Fed codes{};
+    int rc = feed_reserve(c, f, false, w, h, &codes);
+    if (rc) return rc;
+    hipError_t e = hipSuccess;
+    if (!(rc = feed_enqueue(c, f, false, w, h, &codes)) &&  // the download is the diagnostics' alone
+        ((e = hipGetLastError()) != hipSuccess ||
+         (e = hipMemcpyAsync(out_codes, codes.s16.px, (size_t)w * h * 6, hipMemcpyDeviceToHost, c->stream)) ||
+         (e = hipStreamSynchronize(c->stream)) != hipSuccess))
+        rc = c->fail(SSIMU2_ERR_HIP, what, e);
+    return leave(c, rc);
+}
+
+namespace {
 
 // Argument checks of the 16-bit calls (the ctx is not null).
 int check16(ssimu2_ctx* c, const void* px, uint32_t bit_depth) {
@@ -1114,7 +936,9 @@ int map_pass(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, uint32_
     return SSIMU2_OK;
 }
 
-int check_args(ssimu2_ctx* c, const void* a, const void* b, uint32_t w, uint32_t h) {
+}  // namespace
+
+int ssimu2h::check_args(ssimu2_ctx* c, const void* a, const void* b, uint32_t w, uint32_t h) {
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     if (!a || !b) return c->fail(SSIMU2_ERR_INVALID_ARG, "null image pointer");
     if (w == 0 || h == 0) return c->fail(SSIMU2_ERR_INVALID_ARG, "zero image dimension");
@@ -1122,6 +946,8 @@ int check_args(ssimu2_ctx* c, const void* a, const void* b, uint32_t w, uint32_t
         return c->fail(SSIMU2_ERR_INVALID_ARG, "image larger than 2^31/3 pixels");
     return SSIMU2_OK;
 }
+
+namespace {
 
 // ---- batch scoring (include/ssimu2_hip.h "Batch scoring") -------------------
 constexpr size_t kResultDoubles = kNumScales * kStats + 2;  // one item's block of the result mirror
@@ -1728,13 +1554,15 @@ static int reference_set(ssimu2_ctx* c, uint32_t w, uint32_t h, bool hbd, int64_
     return SSIMU2_OK;
 }
 
+}  // extern "C"
+
 // ---- the three shapes of a call that feeds frames, each once ----------------
 // Every one of them, after the entry point's own argument checks: what can be refused without the device; the buffers
 // (nothing enqueued yet that reads the caller's memory, so a failure returns as it is); then the copies and launches,
 // from where leave() is the only way out.
 
 // The pair score: `dist` against `ref`, two frames of one kind.
-static int score_pair(ssimu2_ctx* c, const Feed& ref, const Feed& dist, uint32_t w, uint32_t h, double* out_score) {
+int ssimu2h::score_pair(ssimu2_ctx* c, const Feed& ref, const Feed& dist, uint32_t w, uint32_t h, double* out_score) {
     const bool recursive = c->blur_mode != SSIMU2_BLUR_FIR;
     int rc;
     if (recursive && (rc = rg_check_size(c, w, h))) return rc;
@@ -1752,7 +1580,7 @@ static int score_pair(ssimu2_ctx* c, const Feed& ref, const Feed& dist, uint32_t
 }
 
 // Set-reference: the frame, then everything that depends on the reference alone.
-static int feed_reference(ssimu2_ctx* c, const Feed& ref, uint32_t w, uint32_t h) {
+int ssimu2h::feed_reference(ssimu2_ctx* c, const Feed& ref, uint32_t w, uint32_t h) {
     const bool fir = c->blur_mode == SSIMU2_BLUR_FIR;
     int rc;
     if (!fir && (rc = rg_check_size(c, w, h))) return rc;
@@ -1784,7 +1612,7 @@ static int feed_reference(ssimu2_ctx* c, const Feed& ref, uint32_t w, uint32_t h
 }
 
 // The pass against the cached reference.
-static int score_against(ssimu2_ctx* c, const Feed& dist, double* out_score) {
+int ssimu2h::score_against(ssimu2_ctx* c, const Feed& dist, double* out_score) {
     const uint32_t w = c->ref.w, h = c->ref.h;
     HIP_TRY(c, hipSetDevice(c->device));
     Fed d{};
@@ -1794,6 +1622,16 @@ static int score_against(ssimu2_ctx* c, const Feed& dist, double* out_score) {
         rc = ssimu2_wait(c, out_score);
     return leave(c, rc);
 }
+
+// What every against-reference call checks first, in this order; `pointers`: none of the call's pointers is null.
+int ssimu2h::check_against(ssimu2_ctx* c, bool pointers) {
+    if (!c) return SSIMU2_ERR_INVALID_ARG;
+    if (!c->ref.have) return c->fail(SSIMU2_ERR_NO_REFERENCE, "no reference set");
+    if (!pointers) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
+    return SSIMU2_OK;
+}
+
+extern "C" {
 
 int ssimu2_score_rgb8(ssimu2_ctx* c, const uint8_t* ref, const uint8_t* dist, uint32_t w,
                       uint32_t h, uint32_t channels, double* out_score) {
@@ -1815,14 +1653,6 @@ int ssimu2_set_reference_device(ssimu2_ctx* c, const void* d_ref, uint32_t w, ui
     REMOTE_REFUSE(c, "ssimu2_set_reference_device");
     const int rc = check_args(c, d_ref, d_ref, w, h);
     return rc ? rc : feed_reference(c, tight8(d_ref, w, hipMemcpyDeviceToDevice), w, h);
-}
-
-// What every against-reference call checks first, in this order; `pointers`: none of the call's pointers is null.
-static int check_against(ssimu2_ctx* c, bool pointers) {
-    if (!c) return SSIMU2_ERR_INVALID_ARG;
-    if (!c->ref.have) return c->fail(SSIMU2_ERR_NO_REFERENCE, "no reference set");
-    if (!pointers) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
-    return SSIMU2_OK;
 }
 
 int ssimu2_enqueue_against_reference_device(ssimu2_ctx* c, const void* d_dist) {

@@ -1,0 +1,272 @@
+// What a front end of the MI355X SSIMULACRA2 scorer may use of its host code: the interface between ssimu2_hip.hip
+// (which defines everything declared here) and the translation units that add an input form -- ssimu2_ext.hip (RGBA),
+// ssimu2_yuv.hip (YUV).  Private to oavif_amd/csrc: nothing here is exported, and a caller sees include/*.h only.
+//
+// A front end turns a caller's frame into a Feed -- where its rows are, how they get onto the device, what kernel of
+// the front end's own makes tight u16 codes of them (Feed::unpack) and through which table the scorer reads those --
+// and hands it to one of the three shapes of a call: score_pair, feed_reference, score_against.  Everything else of
+// ssimu2_hip.hip (plans, pyramids, the recursive path, batch, map, the stream pool) is that unit's own.
+//
+// No kernel and no __constant__ lives here or in anything this header includes (ssimu2_kernels.h and
+// ssimu2_recursive.h are ssimu2_hip.hip's alone): the units that include it are linked into one library, where a
+// second definition of a kernel is a clash and a second c_k a constant block nobody uploads.
+#pragma once
+
+// ssimu2_ctx ends in fields that only the instrumented build has, so every unit of a library must agree on the macro.
+// The instrumented library is one unit, ssimu2_instrument.hip, which includes ssimu2_hip.hip: nothing else may see it.
+#if defined(SSIMU2_INSTRUMENTED_BUILD) && !defined(SSIMU2_CORE_UNIT)
+#error "ssimu2_host.h under SSIMU2_INSTRUMENTED_BUILD: only ssimu2_instrument.hip (through ssimu2_hip.hip) is built with it"
+#endif
+
+#include <hip/hip_runtime.h>
+#ifdef SSIMU2_INSTRUMENTED_BUILD
+#include <hip/hip_ext.h>
+#endif
+
+#include <stdint.h>
+#include <stdio.h>
+
+#include <string>
+
+#include "../../include/ssimu2_hip.h"
+#include "remote_client.h"
+
+namespace ssimu2h {
+
+// One buffer of a context: device memory, or (`host`) page-locked host memory that a kernel writes.  `cap` is in
+// bytes, always; p is null exactly when cap is 0.  grow() is the one place that allocates.
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    bool host = false;
+    template <class T>
+    T* as() const { return (T*)p; }
+    void release() {
+        (void)(host ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+}  // namespace ssimu2h
+
+struct ssimu2_ctx {
+    using DevBuf = ssimu2h::DevBuf;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;   // created here, destroyed with the ctx
+    bool pool_stream = false;  // borrowed from the process-wide set of streams on distinct hardware queues
+    std::string err;
+    // set: the context lives in a scoring service (OAVIF_SCORER_SOCKET at ssimu2_ctx_create, remote_client.h); nothing
+    // below is used then, and every entry point hands over to it on its first line (REMOTE)
+    ssimu2r::Remote* remote = nullptr;
+
+    int blur_mode = SSIMU2_BLUR_FIR;
+    ssimu2_device_info dev{};  // what ctx_create saw of the device (and checked: gfx950, 160 KB of LDS per CU)
+
+    // The buffers, grouped by who releases them: the rows of DESIGN.md section 3, "Which call touches which buffer".
+    // A group is a struct of DevBuf members and nothing else, so that release(group) finds every one of them.
+    // Every group from `frame` to `hbd` is released when the frame buffers regrow (release_frame_groups).
+    // frame: ensure_capacity grows all five or none
+    struct {
+        DevBuf ref_u8, dist_u8;    // interleaved RGB8
+        DevBuf lin_ref, lin_dist;  // fp32, scales 1..5 packed
+        DevBuf partials;           // fp64 [scale][18][workgroups]
+    } frame;
+    // cache: cache_reference_fir, for a reference set in FIR mode
+    struct {
+        DevBuf xyb;   // positive-XYB planes of the reference, all scales
+        DevBuf blur;  // blur(ref*ref) planes, all scales (null = not cached)
+    } cache;
+    // stage: feed_reserve, for a frame whose rows are not the scorer's (the _strided, _strided16, RGBA and YUV calls)
+    DevBuf stage;  // decoded avifRGBImage as uploaded (RGBA / padded rows)
+    // rg: rg_ensure, SSIMU2_BLUR_RECURSIVE modes only (ssimu2_recursive.h); also released by ssimu2_ctx_set_blur(FIR)
+    struct {
+        DevBuf planes;  // fp32, every scale packed: XYB planes of both frames [3], the reference's cached mu1 / s11
+                        // planes [6], the horizontal pass of a pass's planes [9]
+        DevBuf part;    // fp64 [scale][18][column groups]
+        DevBuf dbg;     // instrumented builds: 15 + 15 raw fp32 planes of scale rg_dbg_scale
+    } rg;
+    unsigned* d_rg_q = nullptr;  // job cursor of the persistent vertical pass (RgPlan::q, 4 words); released with `rg`
+    int num_cus = 0;             // workgroups of that kernel: one per CU
+    unsigned rg_v_pad = 0;       // unused dynamic LDS of k_rg_v's launch: rg_v_pad_bytes(dev.lds_bytes_per_cu)
+    // map: map_ensure, by the first ssimu2_error_map_* call
+    struct {
+        DevBuf dens;  // fp32 per-(scale, channel) density planes [scale][3][h_s][w_s]
+        DevBuf out;   // the full-resolution fp32 map [h][w]
+    } map;
+    // hbd: the first 16-bit call (ssimu2_*_rgb16 / _strided16)
+    struct {
+        DevBuf ref16, dist16;        // the tight u16 frames
+        DevBuf lin0_ref, lin0_dist;  // FIR: the frames' scale-0 linear planes, fp32 [3][h][w]
+    } hbd;
+    // tab: device_table; released by ssimu2_ctx_destroy only.  The sRGB -> linear tables of depths 8..16: depth d at
+    // float offset 2^d - 256, uploaded by the first call at that depth
+    DevBuf tab;
+    // alpha: device_table, by the first RGBA call (the extension library's: ssimu2_ext.hip, include/ssimu2_hip_ext.h;
+    // nothing in the product library feeds RGBA); released by ssimu2_ctx_destroy only.  The table of the 65,026
+    // composite codes
+    DevBuf alpha_tab;
+    uint32_t tab_ready = 0;  // bit d: the depth-d table is in `tab`; bit 0: the composite table is in `alpha_tab`
+    // batch: batch_run / batch_stage (ssimu2_score_batch_*), each buffer when too small; released by ssimu2_ctx_destroy
+    // only.  Scratch of its own, so a batch leaves the single-score buffers and a cached reference alone: the staged
+    // 8-bit frames of the host-pointer forms, the linear pyramids (scales 1..5) and partial sums of every item, and the
+    // page-locked result block k_finalize_batch writes (110 doubles per item)
+    struct {
+        DevBuf u8_ref, u8_dist, lin_ref, lin_dist, part;
+        DevBuf result{nullptr, 0, true};
+    } batch;
+    uint32_t batch_n = 0;  // items of the last finished batch (ssimu2_last_batch_averages)
+    // result: ssimu2_ctx_create; ssimu2_ctx_destroy
+    double* d_result = nullptr;         // 110 doubles in device memory: the stage timing of the instrumented build only
+    DevBuf h_result{nullptr, 0, true};  // page-locked host memory k_finalize writes the result into (110 doubles)
+
+    // The cached reference: set by reference_set, dropped where its storage is released or overwritten
+    struct {
+        bool have = false, hbd = false;  // hbd: set from 16-bit samples (its 8-bit frame buffer is not it)
+        uint32_t w = 0, h = 0;
+        int64_t bg = -1;  // 0xRRGGBB the reference was composited over (ssimu2_set_reference_rgba8); -1: none recorded
+        void drop() { have = hbd = false, w = h = 0, bg = -1; }
+        void set(uint32_t w_, uint32_t h_, bool hbd_, int64_t bg_) {
+            have = true, hbd = hbd_, w = w_, h = h_, bg = bg_;
+        }
+    } ref;
+    bool pending = false;
+
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // measurement builds only (ssimu2_instrument.hip); always 0 / true in the product library
+    int seg_rows_override = 0;
+    int seg_rows_tail_override = 0;
+    int batch_seg_override = 0;  // scale-0 rows of a batch item: 0 = the rule, -1 = the single-score rule, 8..160 fixed
+    bool cache_ref_blur = true;
+    int rg_dbg_scale = -1;  // recursive mode: keep that scale's 15 raw planes (after each pass) downloadable
+#ifdef SSIMU2_INSTRUMENTED_BUILD
+    // the frame size whose scale-0 planes hbd.lin0_ref / hbd.lin0_dist hold for the last score or reference (0: none;
+    // for ssimu2_debug_download at scale 0)
+    uint32_t lin0_ref_w = 0, lin0_ref_h = 0, lin0_dist_w = 0, lin0_dist_h = 0;
+    int last_march = 0;  // SSIMU2_MARCH_* of the last score or batch (ssimu2_instr_last_march)
+#endif
+
+    int fail(int code, const char* what, hipError_t e = hipSuccess) {
+        char buf[256];
+        if (e != hipSuccess) snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
+        else snprintf(buf, sizeof buf, "%s", what);
+        err = buf;
+        return code;
+    }
+};
+
+#define REMOTE(c, call) \
+    if ((c) && (c)->remote) return ssimu2r::call
+#define REMOTE_REFUSE(c, name) REMOTE(c, unsupported((c)->remote, name))
+
+#define HIP_TRY(ctx, call)                                                   \
+    do {                                                                     \
+        hipError_t e_ = (call);                                              \
+        if (e_ != hipSuccess) return (ctx)->fail(SSIMU2_ERR_HIP, #call, e_); \
+    } while (0)
+
+namespace ssimu2h {
+
+// Every kernel of a score goes through launch().  Product build: hipLaunchKernelGGL, nothing else.  Instrumented build
+// (ssimu2_instrument.hip): while a timing scope is open on the calling thread the same launch is made with
+// hipExtLaunchKernelGGL and a start / stop event pair, so the duration of each kernel comes from its own dispatch packet
+// (what rocprofv3's kernel trace reads) with no marker or barrier packet added between the launches of a score.
+template <class T>
+struct arg_of { using type = T; };
+#ifdef SSIMU2_INSTRUMENTED_BUILD
+struct LaunchTimer {
+    hipEvent_t* ev;  // cap events: launch k of the scope uses ev[2k] (start) and ev[2k + 1] (stop)
+    int n, cap;
+};
+inline thread_local LaunchTimer* g_launch_timer = nullptr;
+#endif
+template <typename... KArgs>
+inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, unsigned lds, hipStream_t stream,
+                   typename arg_of<KArgs>::type... args) {
+#ifdef SSIMU2_INSTRUMENTED_BUILD
+    if (LaunchTimer* t = g_launch_timer) {
+        if (t->n + 2 <= t->cap) {
+            hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, t->ev[t->n], t->ev[t->n + 1], 0, args...);
+            t->n += 2;
+            return;
+        }
+    }
+#endif
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+}
+
+// ---- 16-bit input ----------------------------------------------------------
+// One 16-bit frame on the device: rows `pitch` bytes apart, `ch` = 3 (RGB) or 4 (RGBA) samples per pixel, read through
+// the table of its depth.
+struct Src16 {
+    const void* px;
+    uint32_t pitch, ch;
+    const float* tab;
+    uint32_t maxv;
+};
+
+// A frame where the front end reads it: an 8-bit RGB frame (`u8`), or with `u8` null 16-bit codes (`s16`).
+struct Fed {
+    const uint8_t* u8;
+    Src16 s16;
+};
+
+// ---- a caller's frame onto the device ("One path for a frame") ---------------
+// How one frame of a call gets onto the device, for either slot of the context (the reference's or the distorted
+// frame's), and how the front end reads it there.
+struct Plane {
+    const void* px;      // the caller's rows
+    uint32_t row_bytes;  // bytes between them
+};
+struct Feed {
+    // The caller's frame: one plane of interleaved pixels, or up to three planes of one sample per pixel (`unpack`
+    // makes the pixels of them); all `nplanes` of them of one layout (`ch`, `sample`) and in one place (`kind`)
+    Plane plane[3];
+    uint32_t nplanes;
+    hipMemcpyKind kind;  // where they are: host memory, or an 8-bit frame already on the device
+    uint32_t ch;         // samples per pixel there: 3, or 4 with the fourth skipped or composited away; 1 in a planar frame
+    uint32_t sample;     // bytes per sample there: 1 or 2
+    // 0: the front end reads an 8-bit RGB frame.  Else it reads u16 codes 0..top through the table of top + 1 entries:
+    // 2^d - 1 for samples of depth d, 65025 for composite codes
+    uint32_t top;
+    // The rows go into the slot's tight frame as they are (`staged` false: they are tight RGB), or into `stage`.  From
+    // there `unpack` launches what makes the slot's tight frame `dst` of them; with none the front end reads them in
+    // `stage`, pitch, fourth sample and all (16-bit samples only)
+    bool staged;
+    void (*unpack)(ssimu2_ctx* c, const Feed& f, uint32_t w, uint32_t h, void* dst);
+    int64_t bg;  // 0xRRGGBB the unpacking composites over, which a reference keeps (ref.bg); -1: none
+    const void* aux = nullptr;  // what else `unpack` needs to know, the entry point's own; alive for the call
+};
+
+// A frame of one plane in host memory, staged: rows `row_bytes` apart of `ch` samples of `sample` bytes per pixel.
+Feed staged1(const void* px, uint32_t row_bytes, uint32_t ch, uint32_t sample, uint32_t top,
+             void (*unpack)(ssimu2_ctx*, const Feed&, uint32_t, uint32_t, void*), int64_t bg = -1);
+// Where plane `p` lies in `stage`: the planes back to back, each start 16-byte aligned (plane 0 at 0).
+size_t plane_off(const Feed& f, uint32_t p, uint32_t w, uint32_t h);
+
+// Feeding a frame in two halves (every feed_reserve of a call before its first feed_enqueue), and the one way out of a
+// call from its first copy out of the caller's memory onwards.  The three shapes below do all of it; a front end calls
+// these itself only for a diagnostic (feed_codes).
+int feed_reserve(ssimu2_ctx* c, const Feed& f, bool ref, uint32_t w, uint32_t h, Fed* fed);
+int feed_enqueue(ssimu2_ctx* c, const Feed& f, bool ref, uint32_t w, uint32_t h, Fed* fed);
+int leave(ssimu2_ctx* c, int rc);
+// The diagnostics of the front ends (ssimu2_composite_rgba8, ssimu2_convert_yuv): feed one frame of u16 codes and
+// download its w * h * 3 codes into `out_codes`; `what` names the entry point in a HIP error.
+int feed_codes(ssimu2_ctx* c, const Feed& f, uint32_t w, uint32_t h, uint16_t* out_codes, const char* what);
+
+// Argument checks: of a call that names a frame size (the ctx may be null); of an against-reference call, in this
+// order: the ctx, the reference, `pointers` (none of the call's pointers is null).
+int check_args(ssimu2_ctx* c, const void* a, const void* b, uint32_t w, uint32_t h);
+int check_against(ssimu2_ctx* c, bool pointers);
+
+// The table of the `n` codes 0..top as the exported functions hand it out.
+int copy_table(uint32_t n, uint32_t top, float* out);
+
+// The three shapes of a call that feeds frames, after the entry point's own argument checks: the
+// pair score of two frames of one kind, set-reference, the pass against the cached reference.
+int score_pair(ssimu2_ctx* c, const Feed& ref, const Feed& dist, uint32_t w, uint32_t h, double* out_score);
+int feed_reference(ssimu2_ctx* c, const Feed& ref, uint32_t w, uint32_t h);
+int score_against(ssimu2_ctx* c, const Feed& dist, double* out_score);
+
+}  // namespace ssimu2h

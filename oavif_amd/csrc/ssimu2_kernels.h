@@ -1,4 +1,6 @@
-// Device code of the MI355X (gfx950) SSIMULACRA2 scorer: included only by ssimu2_hip.hip.
+// Device code of the MI355X (gfx950) SSIMULACRA2 scorer: every kernel and the constant block c_k that ssimu2_hip.hip
+// launches and uploads.  Included by ssimu2_hip.hip and by no other unit of a library (a second copy is a link clash and
+// a second c_k); the front ends' kernels are in their own units, and what they share with these is ssimu2_div_rn.h.
 //
 // Kernels (wave64; VALU + LDS work, no MFMA: stencil and pointwise arithmetic):
 //   k_pyramid_bands : linear-light 2x2 box pyramid, all five levels in one launch from one read
@@ -25,6 +27,7 @@
 #include <stdint.h>
 
 #include "../../include/ssimu2_hip.h"
+#include "ssimu2_div_rn.h"  // div_rn: correctly rounded division (shared with ssimu2_yuv.hip)
 
 namespace ssimu2 {
 
@@ -128,22 +131,6 @@ __device__ __forceinline__ float fir9(float c, float s1, float s2, float s3, flo
     acc = fmaf(w3, s3, acc);
     acc = fmaf(w4, s4, acc);
     return acc;
-}
-
-// Correctly rounded a / b for operands that need no exponent scaling (here b is in
-// [9e-4, 4], |a| < 4): v_rcp_f32 seed, one Newton step on the reciprocal, two fused
-// residual corrections of the quotient -- the sequence hipcc emits for `a / b` minus
-// v_div_scale / v_div_fixup, which only act on out-of-range exponents.  Same bits as the
-// IEEE division the CPU checker performs.
-__device__ __forceinline__ float div_rn(float a, float b) {
-    float r = __builtin_amdgcn_rcpf(b);
-    const float e0 = fmaf(-b, r, 1.0f);
-    r = fmaf(e0, r, r);
-    float q = a * r;
-    const float e1 = fmaf(-b, q, a);
-    q = fmaf(e1, r, q);
-    const float e2 = fmaf(-b, q, a);
-    return fmaf(e2, r, q);
 }
 
 // ---- the per-pixel terms ----------------------------------------------------------------------

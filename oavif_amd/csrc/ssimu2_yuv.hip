@@ -1,17 +1,19 @@
 // YUV input of the MI355X SSIMULACRA2 scorer: the entry points of include/ssimu2_hip_yuv.h.
 //
-// This translation unit is the extension translation unit (ssimu2_ext.hip, included below, which includes the product's:
-// same kernels, same host code, same flags) plus one kernel and four functions.  It is built into liboavif_hip_yuv.so;
-// the other three libraries contain none of this, and their exports are what they were.
+// A translation unit of its own: one kernel template, one Feed constructor, one check and four functions over
+// ssimu2_host.h, the list of what a front end may use of the scorer.  Its object is linked with the extension library's
+// objects into liboavif_hip_yuv.so; the other three libraries contain none of this, and their exports are what they were.
 //
 // A decoder's Y, U and V planes become a u16 frame of RGB codes of the caller's depth (k_yuv_to_codes: the colour matrix
 // in fp32, operation for operation the header's definition) that the 16-bit front end reads through that depth's
 // table: Src16{codes, w * 6, 3, table, 2^rgb_depth - 1}.  No pyramid, marching, recursive or finalize kernel knows about
 // YUV.  To the host code a YUV frame is one more Feed, of three planes (yuv below): the three shapes of a call --
 // score_pair, feed_reference, score_against -- are the product's.
-#include "ssimu2_ext.hip"
-
 #include "../../include/ssimu2_hip_yuv.h"
+#include "ssimu2_div_rn.h"
+#include "ssimu2_host.h"
+
+using namespace ssimu2h;
 
 namespace ssimu2 {
 
@@ -116,6 +118,8 @@ __global__ __launch_bounds__(256) void k_yuv_to_codes(const uint8_t* __restrict_
 
 }  // namespace ssimu2
 
+using namespace ssimu2;
+
 namespace {
 
 // What a YUV Feed's unpacking needs beyond the planes (Feed::aux).
@@ -204,18 +208,8 @@ int ssimu2_convert_yuv(ssimu2_ctx* c, const ssimu2_yuv_frame* frame, uint32_t w,
     REMOTE_REFUSE(c, "ssimu2_convert_yuv");
     int rc = check_args(c, frame, out_codes, w, h);
     if (rc || (rc = check_yuv(c, frame, w, rgb_depth))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
     YuvAux aux;
-    const Feed f = yuv(*frame, rgb_depth, &aux);
-    Fed codes{};
-    if ((rc = feed_reserve(c, f, false, w, h, &codes))) return rc;
-    hipError_t e = hipSuccess;
-    if (!(rc = feed_enqueue(c, f, false, w, h, &codes)) &&  // the download is this diagnostic's alone
-        ((e = hipGetLastError()) != hipSuccess ||
-         (e = hipMemcpyAsync(out_codes, codes.s16.px, (size_t)w * h * 6, hipMemcpyDeviceToHost, c->stream)) ||
-         (e = hipStreamSynchronize(c->stream)) != hipSuccess))
-        rc = c->fail(SSIMU2_ERR_HIP, "ssimu2_convert_yuv", e);
-    return leave(c, rc);
+    return feed_codes(c, yuv(*frame, rgb_depth, &aux), w, h, out_codes, "ssimu2_convert_yuv");
 }
 
 int ssimu2_score_yuv(ssimu2_ctx* c, const ssimu2_yuv_frame* ref_frame, const ssimu2_yuv_frame* dist_frame, uint32_t w,

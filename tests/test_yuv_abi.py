@@ -84,8 +84,13 @@ def test_the_other_libraries_have_none_of_it(hip_lib):
 def test_build_knows_the_fourth_library(hip_lib):
     from oavif_amd import _lib, build
     assert os.path.samefile(os.path.dirname(build.YUV_LIB_PATH), os.path.dirname(_lib.YUV_LIB_PATH))
-    assert os.path.basename(build.YUV_LIB_PATH) == "liboavif_hip_yuv.so" and build.YUV_SOURCES[0] == "ssimu2_yuv.hip"
-    assert build.YUV_SOURCES[1:] == build.EXT_SOURCES[1:] == build.SOURCES[1:]
+    assert os.path.basename(build.YUV_LIB_PATH) == "liboavif_hip_yuv.so" and build.YUV_SOURCES[-1] == "ssimu2_yuv.hip"
+    assert build.LIBRARIES[build.YUV_LIB_PATH] is build.YUV_SOURCES  # the table is what build() links
+    assert build.LIBRARIES[build.EXT_LIB_PATH] is build.EXT_SOURCES and build.LIBRARIES[build.LIB_PATH] is build.SOURCES
+    # its other inputs are exactly the extension library's, and that library's other inputs exactly the product's
+    assert build.YUV_SOURCES[:-1] == build.EXT_SOURCES and "ssimu2_yuv.hip" not in build.EXT_SOURCES
+    assert build.EXT_SOURCES[:-1] == build.SOURCES and build.EXT_SOURCES[-1] == "ssimu2_ext.hip"
+    assert "ssimu2_ext.hip" not in build.SOURCES
     assert os.path.exists(build.YUV_LIB_PATH)
 
 
