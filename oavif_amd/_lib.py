@@ -16,6 +16,9 @@ INSTR_LIB_PATH = os.environ.get("OAVIF_AMD_INSTR_LIB") or os.path.join(_HERE, "l
 EXT_LIB_PATH = os.environ.get("OAVIF_AMD_EXT_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_ext.so")
 # the extension library's sources plus the YUV entry points of include/ssimu2_hip_yuv.h (Ssimu2(..., yuv=True))
 YUV_LIB_PATH = os.environ.get("OAVIF_AMD_YUV_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_yuv.so")
+# the YUV library's objects plus the error maps of 16-bit, RGBA and YUV frames of include/ssimu2_hip_map.h
+# (Ssimu2(..., maps=True))
+MAP_LIB_PATH = os.environ.get("OAVIF_AMD_MAP_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_map.so")
 
 OK = 0
 ERR_INVALID_ARG = -1
@@ -195,15 +198,26 @@ YUV_FUNCTIONS = {      # include/ssimu2_hip_yuv.h: only liboavif_hip_yuv.so has 
     "ssimu2_score_against_reference_yuv": (_ci, [_vp, _P(YuvFrameC), _u32, _f64p]),
 }
 
+MAP_FUNCTIONS = {      # include/ssimu2_hip_map.h: only liboavif_hip_map.so has these
+    "ssimu2_error_map_rgb16": (_ci, [_vp, _u16p, _u16p, _u32, _u32, _u32, _f32p, _f64p]),
+    "ssimu2_error_map_against_reference_rgb16": (_ci, [_vp, _u16p, _u32, _f32p, _f64p]),
+    "ssimu2_error_map_rgba8": (_ci, [_vp, _u8p, _u32, _u8p, _u32, _u32, _u32, _u32, _f32p, _f64p]),
+    "ssimu2_error_map_against_reference_rgba8": (_ci, [_vp, _u8p, _u32, _f32p, _f64p]),
+    "ssimu2_error_map_yuv": (_ci, [_vp, _P(YuvFrameC), _P(YuvFrameC), _u32, _u32, _u32, _f32p, _f64p]),
+    "ssimu2_error_map_against_reference_yuv": (_ci, [_vp, _P(YuvFrameC), _u32, _f32p, _f64p]),
+}
+
 EXPORTED_SYMBOLS = tuple(PUBLIC_FUNCTIONS)
 INSTR_SYMBOLS = tuple(HOOK_FUNCTIONS)
 EXT_SYMBOLS = tuple(EXT_FUNCTIONS)
 YUV_SYMBOLS = tuple(YUV_FUNCTIONS)
+MAP_SYMBOLS = tuple(MAP_FUNCTIONS)
 
 _lib = None
 _instr = None
 _ext = None
 _yuv = None
+_map = None
 
 
 def lib() -> ctypes.CDLL:
@@ -238,6 +252,14 @@ def yuv_lib() -> ctypes.CDLL:
     return _yuv
 
 
+def map_lib() -> ctypes.CDLL:
+    """The map build (include/ssimu2_hip_map.h): the YUV library plus the error maps of 16-bit, RGBA and YUV frames."""
+    global _map
+    if _map is None:
+        _map = _load(MAP_LIB_PATH)
+    return _map
+
+
 def _load(path: str) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise ImportError(
@@ -253,7 +275,7 @@ def _load(path: str) -> ctypes.CDLL:
         except Exception:
             pass
     L = ctypes.CDLL(path)
-    for table in (PUBLIC_FUNCTIONS, HOOK_FUNCTIONS, EXT_FUNCTIONS, YUV_FUNCTIONS):
+    for table in (PUBLIC_FUNCTIONS, HOOK_FUNCTIONS, EXT_FUNCTIONS, YUV_FUNCTIONS, MAP_FUNCTIONS):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name, None)   # a build older than a symbol lacks it (scripts/gpu_ab.py loads such builds)
             if fn is not None:

@@ -1,7 +1,7 @@
-"""Build the gfx950 shared libraries in-tree (oavif_amd/lib/liboavif_hip.so and its three siblings).
+"""Build the gfx950 shared libraries in-tree (oavif_amd/lib/liboavif_hip.so and its four siblings).
 
-Every source is compiled once, to an object under oavif_amd/lib/obj; the four libraries are links of those objects
-(LIBRARIES).  hipcc cross-compiles without a GPU; the built libraries are git-ignored.
+Every source is compiled once, to an object under oavif_amd/lib/obj; the libraries are links of those objects
+(LIBRARIES, and MAP_LIBRARIES beside it).  hipcc cross-compiles without a GPU; the built libraries are git-ignored.
 """
 from __future__ import annotations
 
@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip.so")              # the product: 
 INSTR_LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip_instr.so")  # + include/ssimu2_hip_internal.h (bench / tests only)
 EXT_LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip_ext.so")      # + include/ssimu2_hip_ext.h (RGBA input)
 YUV_LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip_yuv.so")      # + include/ssimu2_hip_yuv.h (YUV input)
+MAP_LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip_map.so")      # + include/ssimu2_hip_map.h (error maps of every input, section 15)
 HOST_PATH = os.path.join(LIB_DIR, "oavif_host")   # csrc/oavif_host.c: main.zig's flow in C over the two public headers + libavif
 SERVICE_PATH = os.path.join(LIB_DIR, "oavif_scored")  # csrc/oavif_scored.cpp: the resident scoring service
 OBJ_DIR = os.path.join(LIB_DIR, "obj")  # one object per source, whichever libraries it is linked into
@@ -31,6 +32,10 @@ EXT_SOURCES = [*SOURCES, "ssimu2_ext.hip"]
 YUV_SOURCES = [*EXT_SOURCES, "ssimu2_yuv.hip"]
 INSTR_SOURCES = ["ssimu2_instrument.hip", *SUPPORT_SOURCES]
 LIBRARIES = {LIB_PATH: SOURCES, INSTR_LIB_PATH: INSTR_SOURCES, EXT_LIB_PATH: EXT_SOURCES, YUV_LIB_PATH: YUV_SOURCES}
+# The fifth library, in a table of its own beside LIBRARIES: the YUV library's objects plus one unit over ssimu2_host.h.
+# build() compiles the units it adds (map_units()) with the others and links it after them.
+MAP_SOURCES = [*YUV_SOURCES, "ssimu2_map.hip"]
+MAP_LIBRARIES = {MAP_LIB_PATH: MAP_SOURCES}
 MAX_COMPILES = 6  # compiles in flight; never the machine's CPU count
 _PROGRAMS = ("oavif_host.c", "oavif_scored.cpp")  # linked against the library, not into it
 # The flags that shape device code: the libraries' compile lines, the ISA tests and scripts/isa_ab.py all take them here.
@@ -60,8 +65,14 @@ def compile_units():
     return list(dict.fromkeys(s for sources in LIBRARIES.values() for s in sources))
 
 
+def map_units():
+    """The sources of MAP_LIBRARIES that no library of LIBRARIES has: compiled once each, like compile_units()."""
+    have = set(compile_units())
+    return list(dict.fromkeys(s for sources in MAP_LIBRARIES.values() for s in sources if s not in have))
+
+
 def libs_need_build() -> bool:
-    libs = tuple(LIBRARIES)
+    libs = (*LIBRARIES, *MAP_LIBRARIES)
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
@@ -118,19 +129,20 @@ def _run_to(target: str, cmd, verbose: bool) -> None:
 
 
 def _build_libs(verbose: bool) -> None:
-    """Objects, then links: each unit of compile_units() to OBJ_DIR (MAX_COMPILES at a time), each library from its own."""
+    """Objects, then links: each unit of compile_units() and map_units() to OBJ_DIR (MAX_COMPILES at a time), each
+    library of LIBRARIES and MAP_LIBRARIES from its own."""
     os.makedirs(OBJ_DIR, exist_ok=True)
     flags = [*DEVICE_FLAGS, "-fPIC",
              "-fvisibility=hidden", "-fvisibility-inlines-hidden",  # exports = the headers' functions
              "-Wall", "-Wno-unused-function"]
     flags += os.environ.get("OAVIF_AMD_EXTRA_HIPCC_FLAGS", "").split()  # A/B builds of experiments
     hipcc = _hipcc()
-    obj = {s: os.path.join(OBJ_DIR, s + ".o") for s in compile_units()}
+    obj = {s: os.path.join(OBJ_DIR, s + ".o") for s in (*compile_units(), *map_units())}
     with concurrent.futures.ThreadPoolExecutor(MAX_COMPILES) as pool:
         jobs = [pool.submit(_run_to, o, [hipcc, *flags, "-c", os.path.join(CSRC, s)], verbose) for s, o in obj.items()]
     for job in jobs:
         job.result()  # the first failed compile raises here
-    for target, sources in LIBRARIES.items():
+    for target, sources in (*LIBRARIES.items(), *MAP_LIBRARIES.items()):
         _run_to(target, [hipcc, *flags, "-shared", *(obj[s] for s in sources), "-lz"], verbose)  # -lz: png_ingest.cpp
 
 

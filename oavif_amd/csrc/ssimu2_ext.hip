@@ -66,9 +66,11 @@ namespace {
 
 constexpr uint32_t kAlphaTop = SSIMU2_ALPHA_CODES - 1;  // 65025 = 255 * 255, the largest code
 
+}  // namespace
+
 // Argument checks of the RGBA calls that name a frame size (the ctx may be null).
-int check_rgba(ssimu2_ctx* c, const void* a, const void* b, uint32_t row_bytes_a, uint32_t row_bytes_b, uint32_t w,
-               uint32_t h, uint32_t background_rgb) {
+int ssimu2h::check_rgba(ssimu2_ctx* c, const void* a, const void* b, uint32_t row_bytes_a, uint32_t row_bytes_b,
+                        uint32_t w, uint32_t h, uint32_t background_rgb) {
     int rc = check_args(c, a, b, w, h);
     if (rc) return rc;
     if ((uint64_t)row_bytes_a < (uint64_t)w * 4 || (uint64_t)row_bytes_b < (uint64_t)w * 4)
@@ -77,6 +79,8 @@ int check_rgba(ssimu2_ctx* c, const void* a, const void* b, uint32_t row_bytes_a
     return SSIMU2_OK;
 }
 
+namespace {
+
 // RGBA rows in `stage` composited over f.bg -> the tight u16 frame of codes `dst`.
 void composite(ssimu2_ctx* c, const Feed& f, uint32_t w, uint32_t h, void* dst) {
     const uint32_t groups = (w + 3) / 4;
@@ -84,13 +88,13 @@ void composite(ssimu2_ctx* c, const Feed& f, uint32_t w, uint32_t h, void* dst) 
            c->stage.as<uint8_t>(), f.plane[0].row_bytes, w, h, (uint32_t)f.bg, (uint16_t*)dst);
 }
 
+}  // namespace
+
 // One RGBA frame in host memory: its rows go through the staging buffer as they are, the front end reads the codes
 // through the composite table T (entry n: the 8-bit table's expression at n / 65025; entry 255 u is the 8-bit entry u).
-Feed rgba8(const uint8_t* pixels, uint32_t row_bytes, uint32_t bg) {
+Feed ssimu2h::rgba8_feed(const uint8_t* pixels, uint32_t row_bytes, uint32_t bg) {
     return staged1(pixels, row_bytes, 4u, 1u, kAlphaTop, composite, (int64_t)bg);
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -101,7 +105,7 @@ int ssimu2_composite_rgba8(ssimu2_ctx* c, const uint8_t* pixels, uint32_t row_by
     REMOTE_REFUSE(c, "ssimu2_composite_rgba8");
     const int rc = check_rgba(c, pixels, out_codes, row_bytes, row_bytes, w, h, background_rgb);
     if (rc) return rc;
-    return feed_codes(c, rgba8(pixels, row_bytes, background_rgb), w, h, out_codes, "ssimu2_composite_rgba8");
+    return feed_codes(c, rgba8_feed(pixels, row_bytes, background_rgb), w, h, out_codes, "ssimu2_composite_rgba8");
 }
 
 int ssimu2_score_rgba8(ssimu2_ctx* c, const uint8_t* ref, uint32_t ref_row_bytes, const uint8_t* dist,
@@ -111,14 +115,14 @@ int ssimu2_score_rgba8(ssimu2_ctx* c, const uint8_t* ref, uint32_t ref_row_bytes
     if (rc) return rc;
     if (!out_score) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_score");
     const uint32_t bg = background_rgb;
-    return score_pair(c, rgba8(ref, ref_row_bytes, bg), rgba8(dist, dist_row_bytes, bg), w, h, out_score);
+    return score_pair(c, rgba8_feed(ref, ref_row_bytes, bg), rgba8_feed(dist, dist_row_bytes, bg), w, h, out_score);
 }
 
 int ssimu2_set_reference_rgba8(ssimu2_ctx* c, const uint8_t* ref, uint32_t row_bytes, uint32_t w, uint32_t h,
                                uint32_t background_rgb) {
     REMOTE_REFUSE(c, "ssimu2_set_reference_rgba8");
     const int rc = check_rgba(c, ref, ref, row_bytes, row_bytes, w, h, background_rgb);
-    return rc ? rc : feed_reference(c, rgba8(ref, row_bytes, background_rgb), w, h);
+    return rc ? rc : feed_reference(c, rgba8_feed(ref, row_bytes, background_rgb), w, h);
 }
 
 int ssimu2_score_against_reference_rgba8(ssimu2_ctx* c, const uint8_t* pixels, uint32_t row_bytes, double* out_score) {
@@ -129,7 +133,7 @@ int ssimu2_score_against_reference_rgba8(ssimu2_ctx* c, const uint8_t* pixels, u
         return c->fail(SSIMU2_ERR_INVALID_ARG, "the reference was not set by ssimu2_set_reference_rgba8: no background recorded");
     if ((uint64_t)row_bytes < (uint64_t)c->ref.w * 4)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "row_bytes smaller than one row of RGBA pixels");
-    return score_against(c, rgba8(pixels, row_bytes, (uint32_t)c->ref.bg), out_score);
+    return score_against(c, rgba8_feed(pixels, row_bytes, (uint32_t)c->ref.bg), out_score);
 }
 
 }  // extern "C"

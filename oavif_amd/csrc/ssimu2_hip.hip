@@ -749,12 +749,9 @@ int device_table(ssimu2_ctx* c, uint32_t n, uint32_t top, const float** out) {
 }
 
 // ---- a caller's frame onto the device ("One path for a frame"; Feed: ssimu2_host.h) ----
-// Tight RGB frames of w pixels per row: 8-bit, and u16 samples of depth `bit_depth` in host memory.
+// Tight RGB frames of w pixels per row: 8-bit (u16 samples: ssimu2h::tight16 below).
 Feed tight8(const void* px, uint32_t w, hipMemcpyKind kind = hipMemcpyHostToDevice) {
     return {{{px, w * 3u}}, 1u, kind, 3u, 1u, 0u, false, nullptr, -1};
-}
-Feed tight16(const void* px, uint32_t w, uint32_t bit_depth) {
-    return {{{px, w * 6u}}, 1u, hipMemcpyHostToDevice, 3u, 2u, (1u << bit_depth) - 1u, false, nullptr, -1};
 }
 
 // The slot's tight frame: ensure_capacity's 8-bit one, or the u16 one.
@@ -769,6 +766,19 @@ size_t plane_bytes(const Feed& f, uint32_t p, uint32_t w, uint32_t h) {
 }
 
 }  // namespace
+
+// A tight frame of u16 samples of depth `bit_depth` in host memory.
+Feed ssimu2h::tight16(const void* px, uint32_t w, uint32_t bit_depth) {
+    return {{{px, w * 6u}}, 1u, hipMemcpyHostToDevice, 3u, 2u, (1u << bit_depth) - 1u, false, nullptr, -1};
+}
+
+// Argument checks of the 16-bit calls (the ctx is not null).
+int ssimu2h::check16(ssimu2_ctx* c, const void* px, uint32_t bit_depth) {
+    if (!px) return c->fail(SSIMU2_ERR_INVALID_ARG, "null image pointer");
+    if ((uintptr_t)px & 1u) return c->fail(SSIMU2_ERR_INVALID_ARG, "16-bit image pointer not 2-byte aligned");
+    if (bit_depth < 8 || bit_depth > 16) return c->fail(SSIMU2_ERR_UNSUPPORTED, "bit_depth must be 8..16");
+    return SSIMU2_OK;
+}
 
 // A frame of one plane in host memory, staged: rows `row_bytes` apart of `ch` samples of `sample` bytes per pixel.
 Feed ssimu2h::staged1(const void* px, uint32_t row_bytes, uint32_t ch, uint32_t sample, uint32_t top,
@@ -846,14 +856,6 @@ int ssimu2h::feed_codes(ssimu2_ctx* c, const Feed& f, uint32_t w, uint32_t h, ui
 
 namespace {
 
-// Argument checks of the 16-bit calls (the ctx is not null).
-int check16(ssimu2_ctx* c, const void* px, uint32_t bit_depth) {
-    if (!px) return c->fail(SSIMU2_ERR_INVALID_ARG, "null image pointer");
-    if ((uintptr_t)px & 1u) return c->fail(SSIMU2_ERR_INVALID_ARG, "16-bit image pointer not 2-byte aligned");
-    if (bit_depth < 8 || bit_depth > 16) return c->fail(SSIMU2_ERR_UNSUPPORTED, "bit_depth must be 8..16");
-    return SSIMU2_OK;
-}
-
 // ---- error map --------------------------------------------------------------
 // Coefficients of the map's terms from the averages of the score that just finished (h_result): the weight of
 // every average by the score's contiguous walk (k_finalize, or_score_from_averages), w for an L1 term and
@@ -886,10 +888,13 @@ int map_ensure(ssimu2_ctx* c, const Pyramid& p, uint32_t w, uint32_t h) {
     return rc;
 }
 
-// The map pass after a finished score of (d_ref, d_dist) (its planes still in place): densities of every scale from
-// the same per-pixel terms, composed into the w x h map, downloaded into `out_map`.  Reads the score's buffers and
-// writes only the map's own: the averages, partial sums and a cached reference are left as the score left them.
-int map_pass(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, uint32_t w, uint32_t h, float* out_map) {
+// The map pass after a finished score (its planes still in place): densities of every scale from the same per-pixel
+// terms, composed into the w x h map, downloaded into `out_map`.  `hbd` says what the score read at scale 0, which the
+// FIR pass reads again: two 8-bit frames (the context's ref_u8 / dist_u8), or the 16-bit path's linear planes
+// hbd.lin0_ref / hbd.lin0_dist; the scales below come from the lin_ref / lin_dist pyramids either way, and the
+// recursive modes read the planes of rg.planes, whatever made them.  Reads the score's buffers and writes only the
+// map's own: the averages, partial sums and a cached reference are left as the score left them.
+int map_pass(ssimu2_ctx* c, bool hbd, uint32_t w, uint32_t h, float* out_map) {
     const Pyramid p = make_pyramid(w, h);
     int rc = map_ensure(c, p, w, h);
     if (rc) return rc;
@@ -903,10 +908,11 @@ int map_pass(ssimu2_ctx* c, const uint8_t* d_ref, const uint8_t* d_dist, uint32_
         if (c->blur_mode == SSIMU2_BLUR_FIR) {
             MarchPlan mp;
             FinalizeArgs fa;
-            PlanSources src = score_sources(c, d_ref, d_dist, false);
+            PlanSources src = hbd ? score_sources(c, c->hbd.lin0_ref.p, c->hbd.lin0_dist.p, false)
+                                  : score_sources(c, c->frame.ref_u8.p, c->frame.dist_u8.p, false);
             src.ref_s11 = dens;  // the output planes
             const int blocks = build_plans(c, p, march_seg_rows, src, &mp, &fa);
-            launch(k_march_map, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp, mc);
+            launch(hbd ? k_march_map_lin : k_march_map, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp, mc);
         } else {
             RgPlan rp;
             int hblocks, vblocks;
@@ -1607,6 +1613,7 @@ int ssimu2h::feed_reference(ssimu2_ctx* c, const Feed& ref, uint32_t w, uint32_t
             rc = cache_reference_fir(c, p, lin0[0], false, true);
         }
         if (!rc) rc = reference_set(c, w, h, !r.u8, ref.bg);
+        if (!rc) c->ref.lin0 = fir && !r.u8 && p.nscales >= 1;  // launch_pyramid16 above wrote hbd.lin0_ref
     }
     return leave(c, rc);
 }
@@ -1629,6 +1636,44 @@ int ssimu2h::check_against(ssimu2_ctx* c, bool pointers) {
     if (!c->ref.have) return c->fail(SSIMU2_ERR_NO_REFERENCE, "no reference set");
     if (!pointers) return c->fail(SSIMU2_ERR_INVALID_ARG, "null pointer");
     return SSIMU2_OK;
+}
+
+// ---- the two shapes that add the error map (include/ssimu2_hip_map.h) --------
+void (*ssimu2h::map_lin0_of_u8)(ssimu2_ctx*, const uint8_t*, const float*, size_t, float*) = nullptr;
+
+// The pair score, then the map pass over the planes it left.
+int ssimu2h::map_pair(ssimu2_ctx* c, const Feed& ref, const Feed& dist, uint32_t w, uint32_t h, float* out_map,
+                      double* out_score) {
+    const int rc = score_pair(c, ref, dist, w, h, out_score);
+    return rc ? rc : map_pass(c, dist.top != 0, w, h, out_map);
+}
+
+// The pass against the cached reference, then the map pass.  What the FIR pass reads of the reference at scale 0:
+// an 8-bit frame of u8 feeds against an 8-bit reference (ssimu2_error_map_against_reference's case, and its refusal
+// of a 16-bit one: no 8-bit frame is kept of that); of u16 codes, hbd.lin0_ref, which feed_reference wrote of a
+// 16-bit reference and nothing has touched since (ref.lin0: every call that regrows, rewrites or releases the plane
+// drops the reference), and which is made here, once, of an 8-bit reference's frame.
+int ssimu2h::map_against(ssimu2_ctx* c, const Feed& dist, float* out_map, double* out_score) {
+    const bool hbd = dist.top != 0;
+    if (!hbd && c->ref.hbd)
+        return c->fail(SSIMU2_ERR_UNSUPPORTED, "no error map of an 8-bit frame against a reference set from 16-bit samples");
+    int rc = score_against(c, dist, out_score);
+    if (rc) return rc;
+    const uint32_t w = c->ref.w, h = c->ref.h;
+    if (hbd && c->blur_mode == SSIMU2_BLUR_FIR && !c->ref.lin0 && w >= 8 && h >= 8) {
+        if (c->ref.hbd || !map_lin0_of_u8)  // neither happens: feed_reference sets lin0, the map unit the pointer
+            return c->fail(SSIMU2_ERR_UNSUPPORTED, "error map: the reference's scale-0 linear planes are missing");
+        const size_t n = (size_t)w * h;
+        const float* tab8 = nullptr;
+        if ((rc = grow(c, c->hbd.lin0_ref, n * 3 * sizeof(float), "hipMalloc(16-bit scale-0 planes)")) ||
+            (rc = device_table(c, 256u, 255u, &tab8)))
+            return rc;
+        map_lin0_of_u8(c, c->frame.ref_u8.as<uint8_t>(), tab8, n, c->hbd.lin0_ref.as<float>());
+        HIP_TRY(c, hipGetLastError());
+        note_lin0(c, 1, -1, w, h);
+        c->ref.lin0 = true;
+    }
+    return map_pass(c, hbd, w, h, out_map);
 }
 
 extern "C" {
@@ -1701,7 +1746,7 @@ int ssimu2_error_map_rgb8(ssimu2_ctx* c, const uint8_t* ref, const uint8_t* dist
     if (!out_map) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_map");
     int rc = ssimu2_score_rgb8(c, ref, dist, w, h, channels, out_score);
     if (rc) return rc;
-    return map_pass(c, c->frame.ref_u8.as<uint8_t>(), c->frame.dist_u8.as<uint8_t>(), w, h, out_map);
+    return map_pass(c, false, w, h, out_map);
 }
 
 int ssimu2_error_map_against_reference(ssimu2_ctx* c, const uint8_t* dist, float* out_map, double* out_score) {
@@ -1712,7 +1757,7 @@ int ssimu2_error_map_against_reference(ssimu2_ctx* c, const uint8_t* dist, float
         return c->fail(SSIMU2_ERR_UNSUPPORTED, "no error map against a reference set from 16-bit samples");
     int rc = ssimu2_score_against_reference(c, dist, out_score);
     if (rc) return rc;
-    return map_pass(c, c->frame.ref_u8.as<uint8_t>(), c->frame.dist_u8.as<uint8_t>(), c->ref.w, c->ref.h, out_map);
+    return map_pass(c, false, c->ref.w, c->ref.h, out_map);
 }
 
 // ---- 16-bit input ----------------------------------------------------------

@@ -1,11 +1,14 @@
 // What a front end of the MI355X SSIMULACRA2 scorer may use of its host code: the interface between ssimu2_hip.hip
-// (which defines everything declared here) and the translation units that add an input form -- ssimu2_ext.hip (RGBA),
-// ssimu2_yuv.hip (YUV).  Private to oavif_amd/csrc: nothing here is exported, and a caller sees include/*.h only.
+// (which defines everything declared here but the front ends' own feed builders, marked below) and the translation
+// units that add an input form -- ssimu2_ext.hip (RGBA), ssimu2_yuv.hip (YUV) -- or a call over those forms --
+// ssimu2_map.hip (error maps of 16-bit, RGBA and YUV frames).  Private to oavif_amd/csrc: nothing here is exported,
+// and a caller sees include/*.h only.
 //
 // A front end turns a caller's frame into a Feed -- where its rows are, how they get onto the device, what kernel of
 // the front end's own makes tight u16 codes of them (Feed::unpack) and through which table the scorer reads those --
-// and hands it to one of the three shapes of a call: score_pair, feed_reference, score_against.  Everything else of
-// ssimu2_hip.hip (plans, pyramids, the recursive path, batch, map, the stream pool) is that unit's own.
+// and hands it to one of the three shapes of a call: score_pair, feed_reference, score_against, or to the two that
+// add the error map (map_pair, map_against).  Everything else of ssimu2_hip.hip (plans, pyramids, the recursive path,
+// batch, the map pass, the stream pool) is that unit's own.
 //
 // No kernel and no __constant__ lives here or in anything this header includes (ssimu2_kernels.h and
 // ssimu2_recursive.h are ssimu2_hip.hip's alone): the units that include it are linked into one library, where a
@@ -49,6 +52,8 @@ struct DevBuf {
 };
 
 }  // namespace ssimu2h
+
+struct ssimu2_yuv_frame;  // include/ssimu2_hip_yuv.h
 
 struct ssimu2_ctx {
     using DevBuf = ssimu2h::DevBuf;
@@ -124,11 +129,13 @@ struct ssimu2_ctx {
     // The cached reference: set by reference_set, dropped where its storage is released or overwritten
     struct {
         bool have = false, hbd = false;  // hbd: set from 16-bit samples (its 8-bit frame buffer is not it)
+        bool lin0 = false;  // FIR: hbd.lin0_ref holds its scale-0 linear planes (feed_reference of 16-bit samples, or
+                            // map_against, which makes them of an 8-bit reference's frame on its first call)
         uint32_t w = 0, h = 0;
         int64_t bg = -1;  // 0xRRGGBB the reference was composited over (ssimu2_set_reference_rgba8); -1: none recorded
-        void drop() { have = hbd = false, w = h = 0, bg = -1; }
+        void drop() { have = hbd = lin0 = false, w = h = 0, bg = -1; }
         void set(uint32_t w_, uint32_t h_, bool hbd_, int64_t bg_) {
-            have = true, hbd = hbd_, w = w_, h = h_, bg = bg_;
+            have = true, hbd = hbd_, lin0 = false, w = w_, h = h_, bg = bg_;
         }
     } ref;
     bool pending = false;
@@ -268,5 +275,46 @@ int copy_table(uint32_t n, uint32_t top, float* out);
 int score_pair(ssimu2_ctx* c, const Feed& ref, const Feed& dist, uint32_t w, uint32_t h, double* out_score);
 int feed_reference(ssimu2_ctx* c, const Feed& ref, uint32_t w, uint32_t h);
 int score_against(ssimu2_ctx* c, const Feed& dist, double* out_score);
+
+// ---- error maps of any feed (include/ssimu2_hip_map.h) ----------------------
+// score_pair / score_against, then the map pass over what that score left in place: the w * h floats of section 9's
+// map into `out_map`.  One path for every kind of frame; out_map and out_score are not null.
+int map_pair(ssimu2_ctx* c, const Feed& ref, const Feed& dist, uint32_t w, uint32_t h, float* out_map, double* out_score);
+int map_against(ssimu2_ctx* c, const Feed& dist, float* out_map, double* out_score);
+// FIR, a frame of u16 codes against a reference set from 8-bit samples: the marching map reads scale 0 of both frames
+// as linear planes, which such a reference does not have.  map_against makes them once per reference, of its retained
+// 8-bit frame through the 8-bit table `tab` (entry 257 u of the depth-16 table is that entry u: the planes of the
+// codes 257 u), with this launch: n pixels of interleaved RGB8 -> fp32 [3][n].  The kernel is ssimu2_map.hip's, which
+// sets the pointer when its library is loaded; null in a library without that unit, where nothing calls map_against.
+extern void (*map_lin0_of_u8)(ssimu2_ctx* c, const uint8_t* rgb8, const float* tab, size_t n, float* lin0);
+
+// ---- what the front ends build their feeds with, for the units above them -------------------------
+// A tight frame of u16 samples of depth `bit_depth` in host memory, and the 16-bit calls' argument checks (the ctx is
+// not null).  Defined in ssimu2_hip.hip.
+Feed tight16(const void* px, uint32_t w, uint32_t bit_depth);
+int check16(ssimu2_ctx* c, const void* px, uint32_t bit_depth);
+// RGBA (defined in ssimu2_ext.hip; in the libraries that link it): the argument checks of the calls that name a frame
+// size (the ctx may be null), and one RGBA frame in host memory composited over `bg`.
+int check_rgba(ssimu2_ctx* c, const void* a, const void* b, uint32_t row_bytes_a, uint32_t row_bytes_b, uint32_t w,
+               uint32_t h, uint32_t background_rgb);
+Feed rgba8_feed(const uint8_t* pixels, uint32_t row_bytes, uint32_t bg);
+// YUV (defined in ssimu2_yuv.hip; in the libraries that link it): the constants of one conversion, formed on the host
+// in fp32 exactly as include/ssimu2_hip_yuv.h writes them; what a YUV Feed's unpacking needs beyond the planes
+// (Feed::aux, which outlives the call); the argument checks of one frame for a call of `w` columns (the ctx is not
+// null); the frame's Feed.
+struct YuvK {
+    float bias_y, range_y, bias_uv, range_uv;
+    float r_cr, b_cb;    // 2 (1 - kr), 2 (1 - kb)
+    float g_cr, g_cb;    // kr (1 - kr), kb (1 - kb)
+    float kg;
+    float top;           // (float)(2^rgb_depth - 1)
+    uint32_t max_code;   // m = 2^depth - 1: a 16-bit sample above it is read as m
+};
+struct YuvAux {
+    YuvK k;
+    bool mono;
+};
+int check_yuv(ssimu2_ctx* c, const ssimu2_yuv_frame* f, uint32_t w, uint32_t rgb_depth);
+Feed yuv_feed(const ssimu2_yuv_frame& f, uint32_t rgb_depth, YuvAux* aux);
 
 }  // namespace ssimu2h

@@ -1223,6 +1223,12 @@ __global__ __launch_bounds__(MARCH_THREADS, 6) void k_march_map(MarchPlan plan, 
     march_body<MARCH_MAP>(plan, &coef);
 }
 
+// The same pass after a 16-bit score (include/ssimu2_hip_map.h): scale 0 comes from the linear planes of the two
+// frames, as in k_march_lin.  An entry of its own; k_march_map's code is what it was.
+__global__ __launch_bounds__(MARCH_THREADS, 6) void k_march_map_lin(MarchPlan plan, MapCoef coef) {
+    march_body<MARCH_MAP, true>(plan, &coef);
+}
+
 // The full-resolution map: map(x, y) = sum over scales s (ascending) of
 // (dens_s[X] + dens_s[Y]) + dens_s[B] at (x >> s, y >> s).  One thread per pixel, fixed order.
 struct MapComposeArgs {

@@ -7,7 +7,7 @@
 // A decoder's Y, U and V planes become a u16 frame of RGB codes of the caller's depth (k_yuv_to_codes: the colour matrix
 // in fp32, operation for operation the header's definition) that the 16-bit front end reads through that depth's
 // table: Src16{codes, w * 6, 3, table, 2^rgb_depth - 1}.  No pyramid, marching, recursive or finalize kernel knows about
-// YUV.  To the host code a YUV frame is one more Feed, of three planes (yuv below): the three shapes of a call --
+// YUV.  To the host code a YUV frame is one more Feed, of three planes (yuv_feed below): the three shapes of a call --
 // score_pair, feed_reference, score_against -- are the product's.
 #include "../../include/ssimu2_hip_yuv.h"
 #include "ssimu2_div_rn.h"
@@ -17,15 +17,7 @@ using namespace ssimu2h;
 
 namespace ssimu2 {
 
-// The constants of one conversion, formed on the host in fp32 exactly as the header writes them (yuv_constants).
-struct YuvK {
-    float bias_y, range_y, bias_uv, range_uv;
-    float r_cr, b_cb;    // 2 (1 - kr), 2 (1 - kb)
-    float g_cr, g_cb;    // kr (1 - kr), kb (1 - kb)
-    float kg;
-    float top;           // (float)(2^rgb_depth - 1)
-    uint32_t max_code;   // m = 2^depth - 1: a 16-bit sample above it is read as m
-};
+// YuvK, the constants of one conversion (formed on the host: yuv_constants), is ssimu2_host.h's.
 
 __device__ __forceinline__ uint32_t yuv_code(float c, float top) {
     return (uint32_t)(0.5f + fminf(fmaxf(c, 0.0f), 1.0f) * top);
@@ -122,12 +114,6 @@ using namespace ssimu2;
 
 namespace {
 
-// What a YUV Feed's unpacking needs beyond the planes (Feed::aux).
-struct YuvAux {
-    YuvK k;
-    bool mono;
-};
-
 // The header's constants, each operation in fp32 and rounded once (the host code is built with -ffp-contract=off too).
 YuvK yuv_constants(const ssimu2_yuv_frame& f, uint32_t rgb_depth) {
     float kr = 0.299f, kb = 0.114f;  // 5, 6 and 2 (unspecified)
@@ -150,8 +136,10 @@ YuvK yuv_constants(const ssimu2_yuv_frame& f, uint32_t rgb_depth) {
     return k;
 }
 
+}  // namespace
+
 // Argument checks of one frame for a w x h call (the ctx is not null).
-int check_yuv(ssimu2_ctx* c, const ssimu2_yuv_frame* f, uint32_t w, uint32_t rgb_depth) {
+int ssimu2h::check_yuv(ssimu2_ctx* c, const ssimu2_yuv_frame* f, uint32_t w, uint32_t rgb_depth) {
     if (!f) return c->fail(SSIMU2_ERR_INVALID_ARG, "null frame");
     if (f->depth != 8 && f->depth != 10 && f->depth != 12) return c->fail(SSIMU2_ERR_UNSUPPORTED, "depth must be 8, 10 or 12");
     if (rgb_depth < 8 || rgb_depth > 16) return c->fail(SSIMU2_ERR_UNSUPPORTED, "rgb_depth must be 8..16");
@@ -172,6 +160,8 @@ int check_yuv(ssimu2_ctx* c, const ssimu2_yuv_frame* f, uint32_t w, uint32_t rgb
     return SSIMU2_OK;
 }
 
+namespace {
+
 // The planes in `stage` (plane_off) -> the tight u16 frame of codes `dst`.
 void convert(ssimu2_ctx* c, const Feed& f, uint32_t w, uint32_t h, void* dst) {
     const YuvAux& a = *(const YuvAux*)f.aux;
@@ -185,9 +175,11 @@ void convert(ssimu2_ctx* c, const Feed& f, uint32_t w, uint32_t h, void* dst) {
     launch(kernel, grid, dim3(256), 0, c->stream, p[0], p[1], p[2], pitch[0], pitch[1], pitch[2], w, h, a.k, (uint16_t*)dst);
 }
 
+}  // namespace
+
 // One YUV frame in host memory: its planes go through the staging buffer as they are, the front end reads the codes
 // through the table of depth rgb_depth.  `aux` outlives the call.
-Feed yuv(const ssimu2_yuv_frame& f, uint32_t rgb_depth, YuvAux* aux) {
+Feed ssimu2h::yuv_feed(const ssimu2_yuv_frame& f, uint32_t rgb_depth, YuvAux* aux) {
     *aux = {yuv_constants(f, rgb_depth), f.format == SSIMU2_YUV_400};
     Feed feed = staged1(f.planes[0], f.row_bytes[0], 1u, f.depth > 8 ? 2u : 1u, (1u << rgb_depth) - 1u, convert);
     if (!aux->mono) {
@@ -199,8 +191,6 @@ Feed yuv(const ssimu2_yuv_frame& f, uint32_t rgb_depth, YuvAux* aux) {
     return feed;
 }
 
-}  // namespace
-
 extern "C" {
 
 int ssimu2_convert_yuv(ssimu2_ctx* c, const ssimu2_yuv_frame* frame, uint32_t w, uint32_t h, uint32_t rgb_depth,
@@ -209,7 +199,7 @@ int ssimu2_convert_yuv(ssimu2_ctx* c, const ssimu2_yuv_frame* frame, uint32_t w,
     int rc = check_args(c, frame, out_codes, w, h);
     if (rc || (rc = check_yuv(c, frame, w, rgb_depth))) return rc;
     YuvAux aux;
-    return feed_codes(c, yuv(*frame, rgb_depth, &aux), w, h, out_codes, "ssimu2_convert_yuv");
+    return feed_codes(c, yuv_feed(*frame, rgb_depth, &aux), w, h, out_codes, "ssimu2_convert_yuv");
 }
 
 int ssimu2_score_yuv(ssimu2_ctx* c, const ssimu2_yuv_frame* ref_frame, const ssimu2_yuv_frame* dist_frame, uint32_t w,
@@ -219,7 +209,7 @@ int ssimu2_score_yuv(ssimu2_ctx* c, const ssimu2_yuv_frame* ref_frame, const ssi
     if (rc || (rc = check_yuv(c, ref_frame, w, rgb_depth)) || (rc = check_yuv(c, dist_frame, w, rgb_depth))) return rc;
     if (!out_score) return c->fail(SSIMU2_ERR_INVALID_ARG, "null out_score");
     YuvAux ra, da;
-    return score_pair(c, yuv(*ref_frame, rgb_depth, &ra), yuv(*dist_frame, rgb_depth, &da), w, h, out_score);
+    return score_pair(c, yuv_feed(*ref_frame, rgb_depth, &ra), yuv_feed(*dist_frame, rgb_depth, &da), w, h, out_score);
 }
 
 int ssimu2_set_reference_yuv(ssimu2_ctx* c, const ssimu2_yuv_frame* frame, uint32_t w, uint32_t h, uint32_t rgb_depth) {
@@ -227,7 +217,7 @@ int ssimu2_set_reference_yuv(ssimu2_ctx* c, const ssimu2_yuv_frame* frame, uint3
     int rc = check_args(c, frame, frame, w, h);
     if (rc || (rc = check_yuv(c, frame, w, rgb_depth))) return rc;
     YuvAux aux;
-    return feed_reference(c, yuv(*frame, rgb_depth, &aux), w, h);
+    return feed_reference(c, yuv_feed(*frame, rgb_depth, &aux), w, h);
 }
 
 int ssimu2_score_against_reference_yuv(ssimu2_ctx* c, const ssimu2_yuv_frame* frame, uint32_t rgb_depth,
@@ -236,7 +226,7 @@ int ssimu2_score_against_reference_yuv(ssimu2_ctx* c, const ssimu2_yuv_frame* fr
     int rc = check_against(c, frame && out_score);
     if (rc || (rc = check_yuv(c, frame, c->ref.w, rgb_depth))) return rc;
     YuvAux aux;
-    return score_against(c, yuv(*frame, rgb_depth, &aux), out_score);
+    return score_against(c, yuv_feed(*frame, rgb_depth, &aux), out_score);
 }
 
 }  // extern "C"

@@ -1,11 +1,13 @@
 """Per-pixel SSIMULACRA2 error map of a pair of images on the MI355X.
 
-    python -m oavif_amd.errmap REF DIST OUT [--blur fir|recursive|recursive_fma]
+    python -m oavif_amd.errmap REF DIST OUT [--blur fir|recursive|recursive_fma] [--full-depth]
 
 Loads both images the way the CLI loads its source (cli.load_source), scores DIST against REF
 and writes where it is damaged (ssimu2_error_map_rgb8; the map's definition is in
-include/ssimu2_hip.h and DESIGN.md section 9).  The score is the one line on stdout.  OUT by
-its extension:
+include/ssimu2_hip.h and DESIGN.md section 9).  With --full-depth a 16-bit PNG keeps its 16-bit
+samples (ssimu2_error_map_rgb16 at depth 16, include/ssimu2_hip_map.h; an 8-bit image counts as
+the samples 257 u); without it every input is reduced to 8 bits.  The score is the one line on
+stdout.  OUT by its extension:
   .pfm  the map itself, 32-bit float (greyscale "Pf", little-endian, rows bottom to top)
   .pam  8-bit greyscale, normalised to the map's maximum
   .png  the same as PNG
@@ -63,7 +65,7 @@ def encode(m: np.ndarray, ext: str):
     return png_bytes(g), peak
 
 
-def main(argv=None) -> int:
+def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m oavif_amd.errmap",
                                  description="Per-pixel SSIMULACRA2 error map of DIST against REF (MI355X).")
     ap.add_argument("ref")
@@ -71,7 +73,34 @@ def main(argv=None) -> int:
     ap.add_argument("out", help="output map: .pfm (float), .pam or .png (8-bit, normalised to the maximum)")
     ap.add_argument("--blur", choices=sorted(BLURS), default="fir", help="blur mode of the scorer (default fir)")
     ap.add_argument("--device", type=int, default=0)
-    a = ap.parse_args(argv)
+    ap.add_argument("--full-depth", action="store_true",
+                    help="score a 16-bit PNG's 16-bit samples (ssimu2_error_map_rgb16 at depth 16; an 8-bit image "
+                         "counts as the samples 257 u) instead of reducing every input to 8 bits")
+    return ap
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    return parser().parse_args(argv)
+
+
+def load_rgb16(path: str) -> np.ndarray:
+    """(h, w, 3) uint16 samples of depth 16 of an image: a 16-bit PNG's own (grey replicated, alpha dropped), any other
+    image's 8-bit samples u as 257 u (the same normalised values)."""
+    from .cli import CliError, load_source
+    if os.path.splitext(path)[1].lower() == ".png":
+        from .png import PngError, load_png
+        try:
+            arr = load_png(open(path, "rb").read())[0]
+        except PngError as e:
+            raise CliError(e.name)
+        if arr.dtype == np.uint16:
+            rgb = np.repeat(arr[..., :1], 3, axis=2) if arr.shape[2] < 3 else arr[..., :3]
+            return np.ascontiguousarray(rgb)
+    return np.multiply(load_source(path).rgb, np.uint16(257), dtype=np.uint16)
+
+
+def main(argv=None) -> int:
+    a = parse_args(argv)
     ext = os.path.splitext(a.out)[1].lower()
     if ext not in FORMATS:
         print(f"errmap: output must end in one of {', '.join(FORMATS)}", file=sys.stderr)
@@ -82,7 +111,10 @@ def main(argv=None) -> int:
             return 1
     from .cli import CliError, load_source
     try:
-        ref, dist = load_source(a.ref).rgb, load_source(a.dist).rgb
+        if a.full_depth:
+            ref, dist = load_rgb16(a.ref), load_rgb16(a.dist)
+        else:
+            ref, dist = load_source(a.ref).rgb, load_source(a.dist).rgb
     except CliError as e:
         print(f"errmap: {e.name}", file=sys.stderr)
         return 1
@@ -91,8 +123,8 @@ def main(argv=None) -> int:
         return 1
     try:
         from .scorer import Ssimu2
-        with Ssimu2(a.device, blur=BLURS[a.blur]) as s:
-            score, m = s.error_map(ref, dist)
+        with Ssimu2(a.device, blur=BLURS[a.blur], maps=a.full_depth) as s:
+            score, m = s.error_map_hbd(ref, dist, 16) if a.full_depth else s.error_map(ref, dist)
     except Exception as e:   # no library, no usable device, a HIP error: the library's message
         print(f"errmap: {e}", file=sys.stderr)
         return 1

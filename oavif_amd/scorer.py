@@ -222,9 +222,11 @@ class Ssimu2:
 
     extended = False   # bound to liboavif_hip_ext.so (the RGBA calls of include/ssimu2_hip_ext.h)
     yuv = False        # bound to liboavif_hip_yuv.so (the YUV calls of include/ssimu2_hip_yuv.h, and the RGBA calls)
+    maps = False       # bound to liboavif_hip_map.so (the error maps of include/ssimu2_hip_map.h, and the RGBA and YUV calls)
 
     def __init__(self, device: int = 0, stream: int | None = None, instrumented: bool = False,
-                 blur: int | None = None, service: str | None = None, extended: bool = False, yuv: bool = False):
+                 blur: int | None = None, service: str | None = None, extended: bool = False, yuv: bool = False,
+                 maps: bool = False):
         """`service`: socket path of a running scoring service (oavif_amd.service): the context lives there, and this
         process makes no HIP call for it (OAVIF_SCORER_SOCKET set around ssimu2_ctx_create, then restored; None = the
         environment as it is).  `instrumented=True` binds liboavif_hip_instr.so (the hooks of
@@ -235,14 +237,19 @@ class Ssimu2:
         set_reference_rgba, score_against_reference_rgba); not together with `instrumented`.  `yuv=True` binds
         liboavif_hip_yuv.so: the YUV calls of include/ssimu2_hip_yuv.h (convert_yuv, compute_ssimu2_yuv,
         set_reference_yuv, score_against_reference_yuv); that library has the RGBA calls too, so `extended=True` may be
-        given as well; not together with `instrumented`."""
+        given as well; not together with `instrumented`.  `maps=True` binds liboavif_hip_map.so: the error maps of
+        16-bit, RGBA and YUV frames of include/ssimu2_hip_map.h (error_map_hbd, error_map_rgba, error_map_yuv and their
+        against-reference forms); that library has the RGBA and YUV calls too, so `extended=True` / `yuv=True` may be
+        given with it; not together with `instrumented`."""
+        if instrumented and maps:
+            raise ValueError("instrumented=True and maps=True are different libraries: choose one")
         if instrumented and extended:
             raise ValueError("instrumented=True and extended=True are different libraries: choose one")
         if instrumented and yuv:
             raise ValueError("instrumented=True and yuv=True are different libraries: choose one")
-        self.instrumented, self.extended, self.yuv = bool(instrumented), bool(extended), bool(yuv)
-        self._L = (_lib.instr_lib() if instrumented else _lib.yuv_lib() if yuv else _lib.ext_lib() if extended
-                   else _lib.lib())
+        self.instrumented, self.extended, self.yuv, self.maps = bool(instrumented), bool(extended), bool(yuv), bool(maps)
+        self._L = (_lib.instr_lib() if instrumented else _lib.map_lib() if maps else _lib.yuv_lib() if yuv
+                   else _lib.ext_lib() if extended else _lib.lib())
         self._ctx = ctypes.c_void_p()
         self._holder = None
         if service is None:
@@ -557,6 +564,74 @@ class Ssimu2:
         self._check_ref_shape((f.height, f.width), "frame size")
         c = f.as_c()
         return self._score(self._L.ssimu2_score_against_reference_yuv, ctypes.byref(c), int(rgb_depth))
+
+    # -- error maps of 16-bit, RGBA and YUV frames (include/ssimu2_hip_map.h): the map library only
+    def _need_maps(self):
+        if not self.maps:
+            raise Ssimu2Error(_lib.ERR_UNSUPPORTED, "error maps of 16-bit, RGBA and YUV frames need Ssimu2(..., maps=True) "
+                                                    "(liboavif_hip_map.so)")
+
+    def _map(self, fn, h: int, w: int, *args):
+        """A call whose last two parameters are `float* out_map, double* out_score` -> (score, (h, w) float32 map)."""
+        out = np.empty((h, w), np.float32)
+        return self._score(fn, *args, _f32p(out)), out
+
+    def error_map_hbd(self, ref, dist, bit_depth: int):
+        """ssimu2_error_map_rgb16 -> (score, (h, w) float32 map) of two (h, w, 3) uint16 frames of `bit_depth` bits: the
+        score bit for bit as compute_ssimu2_hbd, the map of DESIGN.md section 9 from the 16-bit pipeline's terms."""
+        self._need_maps()
+        ref, dist = _check_pair(ref, dist, _check_rgb16)
+        h, w, _ = ref.shape
+        return self._map(self._L.ssimu2_error_map_rgb16, h, w, _u16p(ref), _u16p(dist), w, h, int(bit_depth))
+
+    def error_map_against_reference_hbd(self, dist, bit_depth: int):
+        """ssimu2_error_map_against_reference_rgb16 -> (score, map) against the reference of any set_reference* call."""
+        self._need_maps()
+        dist = _check_rgb16(dist, "dist")
+        self._check_ref_shape(dist.shape)
+        h, w, _ = dist.shape
+        return self._map(self._L.ssimu2_error_map_against_reference_rgb16, h, w, _u16p(dist), int(bit_depth))
+
+    def error_map_rgba(self, ref, dist, background):
+        """ssimu2_error_map_rgba8 -> (score, map) of two (h, w, 4) uint8 frames (rows may be padded), each composited
+        over `background`."""
+        self._need_maps()
+        ref, dist = _check_pair(ref, dist, _check_rgba8)
+        h, w, _ = ref.shape
+        tight = 4 * w
+        return self._map(self._L.ssimu2_error_map_rgba8, h, w, _u8p(ref), ref.strides[0] if h > 1 else tight, _u8p(dist),
+                         dist.strides[0] if h > 1 else tight, w, h, background_rgb(background))
+
+    def error_map_against_reference_rgba(self, pixels, row_bytes: int | None = None):
+        """ssimu2_error_map_against_reference_rgba8 -> (score, map): an (h, w, 4) uint8 array or view whose rows are
+        `row_bytes` apart (None: its own stride) against the reference of set_reference_rgba, over its background."""
+        self._need_maps()
+        a = np.asarray(pixels)
+        if a.dtype != np.uint8:
+            raise TypeError(f"pixels must be uint8 RGBA, got {a.dtype}")
+        a = _check_rgba8(a, "pixels")
+        self._check_ref_shape(a.shape[:2], "frame size")
+        h, w, _ = a.shape
+        row_bytes = (a.strides[0] if h > 1 else 4 * w) if row_bytes is None else row_bytes
+        return self._map(self._L.ssimu2_error_map_against_reference_rgba8, h, w, _u8p(a), int(row_bytes))
+
+    def error_map_yuv(self, ref: YuvFrame, dist: YuvFrame, rgb_depth: int = 16):
+        """ssimu2_error_map_yuv -> (score, map) of two YUV frames of one size, converted to codes of `rgb_depth` bits."""
+        self._need_maps()
+        r, d = self._yuv_frame(ref, "ref"), self._yuv_frame(dist, "dist")
+        if (r.height, r.width) != (d.height, d.width):
+            raise ValueError("ref and dist must have the same shape")
+        cr, cd = r.as_c(), d.as_c()
+        return self._map(self._L.ssimu2_error_map_yuv, r.height, r.width, ctypes.byref(cr), ctypes.byref(cd), r.width,
+                         r.height, int(rgb_depth))
+
+    def error_map_against_reference_yuv(self, frame: YuvFrame, rgb_depth: int = 16):
+        """ssimu2_error_map_against_reference_yuv -> (score, map) against the reference of any set_reference* call."""
+        self._need_maps()
+        f = self._yuv_frame(frame, "frame")
+        self._check_ref_shape((f.height, f.width), "frame size")
+        c = f.as_c()
+        return self._map(self._L.ssimu2_error_map_against_reference_yuv, f.height, f.width, ctypes.byref(c), int(rgb_depth))
 
     # -- device-resident entry points (pointers are raw device addresses) -------------------
     # The per-frame ones make their C call in their own body, not through _call / _score / _scores: a 512x512 score is

@@ -2,8 +2,10 @@
 matrix at full precision (include/ssimu2_hip_yuv.h).
 
     python -m oavif_amd.yuvscore REF.png|REF.avif DIST.avif [--rgb-depth N] [--blur fir|recursive|recursive_fma] [--compare]
+                                 [--map OUT.png|.pam|.pfm]
 
-prints the score of DIST against REF through the YUV path.  A PNG reference is taken as 8-bit RGB (alpha dropped, 16
+prints the score of DIST against REF through the YUV path; `--map` also writes where DIST is damaged, the error map of
+that very score (ssimu2_error_map_against_reference_yuv, include/ssimu2_hip_map.h), in errmap's formats.  A PNG reference is taken as 8-bit RGB (alpha dropped, 16
 bits truncated, as the search takes its source); an AVIF reference goes through the YUV path too.  `--compare` adds
 the score of libavif's 8-bit RGB output of DIST (avifImageYUVToRGB at depth 8: libyuv's fixed-point conversion), which
 is what the reference program scores.
@@ -11,12 +13,14 @@ is what the reference program scores.
 from __future__ import annotations
 
 import argparse
+import os
 import sys
 
 from . import _lib
 from .scorer import MATRIX_COEFFICIENTS, Ssimu2, YuvFrame
 
 BLUR_MODES = {"fir": _lib.BLUR_FIR, "recursive": _lib.BLUR_RECURSIVE, "recursive_fma": _lib.BLUR_RECURSIVE_FMA}
+MAP_FORMATS = (".pfm", ".pam", ".png")   # errmap.FORMATS
 
 
 def rgb_depth_arg(text: str) -> int:
@@ -39,6 +43,9 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--blur", choices=sorted(BLUR_MODES), default="fir")
     ap.add_argument("--compare", action="store_true", help="also print the score of libavif's 8-bit RGB output")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--map", default=None, metavar="OUT",
+                    help="also write the error map of the YUV-path score: OUT.pfm (float), .pam or .png (8-bit, "
+                         "normalised to the maximum), as python -m oavif_amd.errmap writes it")
     return ap
 
 
@@ -49,6 +56,8 @@ def parse_args(argv=None) -> argparse.Namespace:
         ap.error(f"DIST must be an AVIF, got {a.dist!r}")
     if not a.ref.lower().endswith((".png", ".avif")):
         ap.error(f"REF must be a PNG or an AVIF, got {a.ref!r}")
+    if a.map is not None and not a.map.lower().endswith(MAP_FORMATS):
+        ap.error(f"--map must end in one of {', '.join(MAP_FORMATS)}, got {a.map!r}")
     return a
 
 
@@ -69,7 +78,8 @@ def main(argv=None) -> int:
     from . import avif_bridge as ab, cli
     try:
         dist_data = open(a.dist, "rb").read()
-        with Ssimu2(a.device, blur=BLUR_MODES[a.blur], yuv=True) as s, ab.decode_yuv(dist_data) as dist:
+        with Ssimu2(a.device, blur=BLUR_MODES[a.blur], yuv=True, maps=a.map is not None) as s, \
+                ab.decode_yuv(dist_data) as dist:
             if a.ref.lower().endswith(".avif"):
                 with ab.decode_yuv(open(a.ref, "rb").read()) as ref:
                     if (ref.width, ref.height) != (dist.width, dist.height):
@@ -80,7 +90,17 @@ def main(argv=None) -> int:
                 if rgb.shape[:2] != (dist.height, dist.width):
                     raise ValueError(f"{a.ref} is {rgb.shape[1]}x{rgb.shape[0]}, {a.dist} is {dist.width}x{dist.height}")
                 s.set_reference(rgb)
-            print(f"yuv {s.score_against_reference_yuv(frame_of(dist), a.rgb_depth):.6f}")
+            if a.map is None:
+                print(f"yuv {s.score_against_reference_yuv(frame_of(dist), a.rgb_depth):.6f}")
+            else:
+                from . import errmap
+                score, m = s.error_map_against_reference_yuv(frame_of(dist), a.rgb_depth)
+                data, peak = errmap.encode(m, os.path.splitext(a.map)[1].lower())
+                with open(a.map, "wb") as f:
+                    f.write(data)
+                if peak is not None:
+                    print(f"yuvscore: map maximum {peak!r} (= 255)", file=sys.stderr)
+                print(f"yuv {score:.6f}")
             if a.compare:
                 with ab.decode_common(dist_data) as rgb8:
                     print(f"rgb8 {s.score_decoded_against_reference(rgb8.rows.reshape(-1), rgb8.row_bytes, rgb8.channels):.6f}")
