@@ -33,7 +33,11 @@ enum { SSIMU2_DEBUG_LIN_REF = 0, SSIMU2_DEBUG_LIN_DIST = 1, SSIMU2_DEBUG_XYB_REF
        /* SSIMU2_BLUR_RECURSIVE: the FIFTEEN planes (5 * channel + {x, y, xx, yy, xy}) after the
           horizontal / after both passes, of the scale chosen with ssimu2_instr_rg_stop_after_scale
           (`out`: 15 planes) */
-       SSIMU2_DEBUG_RG_H = 4, SSIMU2_DEBUG_RG_V = 5 };
+       SSIMU2_DEBUG_RG_H = 4, SSIMU2_DEBUG_RG_V = 5,
+       /* the linear-light pyramid level `scale` (1..5) of item i of the last batch (ssimu2_score_batch_*), reference /
+          distorted frame: `what` = SSIMU2_DEBUG_BATCH_LIN_REF / _DIST + SSIMU2_DEBUG_BATCH_ITEM * i; `w`, `h` must be
+          that batch's frame size (a batch against the cached reference has no reference pyramids of its own) */
+       SSIMU2_DEBUG_BATCH_LIN_REF = 6, SSIMU2_DEBUG_BATCH_LIN_DIST = 7, SSIMU2_DEBUG_BATCH_ITEM = 8 };
 int ssimu2_debug_download(ssimu2_ctx* ctx, int what, int scale, uint32_t w, uint32_t h, float* out,
                           uint32_t* out_w, uint32_t* out_h);
 

@@ -124,6 +124,16 @@ int ssimu2_debug_download(ssimu2_ctx* c, int what, int scale, uint32_t w, uint32
     } else if (what == SSIMU2_DEBUG_LIN_REF || what == SSIMU2_DEBUG_LIN_DIST) {
         if (scale < 1 || scale >= p.nscales || !c->frame.lin_ref.p) return c->fail(SSIMU2_ERR_INVALID_ARG, "no such level");
         src = (what == SSIMU2_DEBUG_LIN_REF ? c->frame.lin_ref : c->frame.lin_dist).as<float>() + p.lin_off[scale];
+    } else if (what >= SSIMU2_DEBUG_BATCH_LIN_REF) {
+        // a level of one item of the last batch: item i's pyramid lies i * lin_stride floats into the batch buffer (batch_run)
+        const int kind = SSIMU2_DEBUG_BATCH_LIN_REF + (what - SSIMU2_DEBUG_BATCH_LIN_REF) % SSIMU2_DEBUG_BATCH_ITEM;
+        const size_t item = (size_t)(what - SSIMU2_DEBUG_BATCH_LIN_REF) / SSIMU2_DEBUG_BATCH_ITEM;
+        const DevBuf& buf = kind == SSIMU2_DEBUG_BATCH_LIN_REF ? c->batch.lin_ref : c->batch.lin_dist;
+        const size_t lin_stride = (p.lin_total + 3) & ~(size_t)3;
+        if (kind > SSIMU2_DEBUG_BATCH_LIN_DIST || scale < 1 || scale >= p.nscales || item >= c->batch_n || !buf.p ||
+            (size_t)c->batch_n * lin_stride * sizeof(float) > buf.cap)
+            return c->fail(SSIMU2_ERR_INVALID_ARG, "no such level of such an item of the last batch");
+        src = buf.as<float>() + item * lin_stride + p.lin_off[scale];
     } else if (what == SSIMU2_DEBUG_XYB_REF) {
         if (scale < 0 || scale >= p.nscales || !c->cache.xyb.p || !c->ref.have || c->ref.w != w || c->ref.h != h)
             return c->fail(SSIMU2_ERR_INVALID_ARG, "no cached reference XYB for that level");

@@ -226,15 +226,26 @@ __device__ __forceinline__ float box4(float p00, float p01, float p10, float p11
     return sum * 0.25f;
 }
 
+// Addresses of the pyramid kernels: a WAVE-UNIFORM pointer (a row of a plane or of a frame, formed on the scalar
+// unit) plus a per-lane 32-bit BYTE offset -- global_load / global_store v_off, s[base:base+1], no 64-bit VALU
+// arithmetic.  The empty asm gives every access an offset register of its own (one v_mov_b32; march_load does the
+// same for its cursor): with one offset shared by the planes of a row the compiler adds it to the row pointer
+// first and carries the sum through per-lane 64-bit additions.
+template <typename T>
+__device__ __forceinline__ T* pyr_at(T* row, uint32_t at) {
+    asm volatile("" : "+v"(at));
+    return (T*)((const char*)row + at);
+}
+
 // XYB variant (the recursive blur modes, which read nothing but XYB planes): the positive-XYB
 // value of a linear-light pixel goes out instead of the pixel; the linear values stay in
 // registers / LDS for the next level.  linear_to_xyb is what k_rg_xyb applies to the same values.
-__device__ __forceinline__ void pyr_store_xyb(float* out, size_t n, size_t at, const float (&lin)[3]) {
+__device__ __forceinline__ void pyr_store_xyb(float* row, size_t n, uint32_t at, const float (&lin)[3]) {
     float X, Y, B;
     linear_to_xyb(lin[0], lin[1], lin[2], X, Y, B);
-    out[at] = X;
-    out[n + at] = Y;
-    out[2 * n + at] = B;
+    *pyr_at(row, at) = X;
+    *pyr_at(row + n, at) = Y;
+    *pyr_at(row + 2 * n, at) = B;
 }
 
 // One level from an LDS tile of the level above: `src` is [3][sh][sw] (tile origin = global
@@ -249,13 +260,15 @@ __device__ __forceinline__ void pyr_lds_level(const float* src, int sw, int sh, 
         const int xa = 2 * lx, xb = min(2 * ox + 1, wa - 1) - 2 * ox0;
         const int ya = 2 * ly, yb = min(2 * oy + 1, ha - 1) - 2 * oy0;
         const size_t n = (size_t)po * ho;
+        float* origin = out + (size_t)oy0 * po + ox0;              // the tile's first output: the same for every lane
+        const uint32_t at = 4u * (uint32_t)(ly * po + lx);         // ly < 4: a few rows of bytes, far inside 32 bits
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float* p = src + c * sw * sh;
             v[c] = box4(p[ya * sw + xa], p[ya * sw + xb], p[yb * sw + xa], p[yb * sw + xb]);
-            if (!XYB) out[c * n + (size_t)oy * po + ox] = v[c];
+            if (!XYB) *pyr_at(origin + c * n, at) = v[c];
         }
-        if (XYB) pyr_store_xyb(out, n, (size_t)oy * po + ox, v);
+        if (XYB) pyr_store_xyb(origin, n, at, v);
     }
     if (dst_tile) {
 #pragma unroll
@@ -310,13 +323,16 @@ __device__ __forceinline__ void pyr_load16(const PyrHbdArgs& hb, int f, int w0, 
             for (int c = 0; c < 3; ++c) lin[j][i][c] = tab[min(s[j][i][c], maxv)];
 }
 
-// `lut`: the sRGB table in LDS; `lds`: PYR_BAND_LDS_FLOATS floats of scratch; 512 threads, all of
-// which must call (barriers inside).  `band` < bands_x * bands_y * nframes.
+// `lut`: 256 floats of LDS that receive the sRGB table here; `lds`: PYR_BAND_LDS_FLOATS floats of scratch; 512
+// threads, all of which must call (barriers inside).  `band` < bands_x * bands_y * nframes.
 // CH16 = 0: 8-bit frames through the LDS table `lut`; 3 / 4: 16-bit RGB / RGBA frames of `hb`.
 // BATCH (k_pyramid_bands_batch): `in_off` (bytes) / `out_off` (floats) are added to the frame's input and to each of
-// its output levels -- item i of a batch.  An instantiation of its own: the code of the other kernels is as it was.
+// its output levels -- item i of a batch.
+// Addresses: a wave is one thread row (PYR_TX = 64 lanes), so the thread row, every pixel row and every output row
+// are the same for all its lanes.  Each row's address is formed once, on the scalar unit, from the band's first
+// column; a lane adds a 32-bit byte offset inside the band (< 256 pixels * 16 bytes).
 template <bool XYB, int CH16 = 0, bool BATCH = false>
-__device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, const float* lut, float* lds,
+__device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, float* lut, float* lds,
                                              const PyrHbdArgs* hb = nullptr, size_t in_off = 0, size_t out_off = 0) {
     const int t = threadIdx.x;
     const int per_frame = a.bands_x * a.bands_y;
@@ -325,96 +341,119 @@ __device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, con
     const int by = r / a.bands_x, bx = r - by * a.bands_x;
     const int w0 = a.w[0], h0 = a.h[0], w1 = a.w[1], h1 = a.h[1];
     constexpr int TX = PYR_TX;
+    static_assert(TX == 64, "one thread row per wave: ty below is read from lane 0");
     float* s2 = lds;                       // [3][8][TX]
     float* s3 = s2 + 3 * 8 * TX;           // [3][4][TX/2]
     float* s4 = s3 + 3 * 4 * (TX / 2);     // [3][2][TX/4]
-    const int tx = t % TX, ty = t / TX;
-    const int X0 = bx * PYR_BAND_W + 4 * tx, Y0 = by * PYR_BAND_H + 4 * ty;
-    // ---- levels 1 and 2 in registers
-    float l1[2][2][3];  // [row][col][channel] of this thread's 2 x 2 level-1 outputs
+    const int tx = t % TX, ty = __builtin_amdgcn_readfirstlane(t / TX);
+    const int XB = bx * PYR_BAND_W;        // the band's first column
+    const int X0 = XB + 4 * tx, Y0 = by * PYR_BAND_H + 4 * ty;
+    const bool work = X0 < w0 && Y0 < h0;
+    const bool inside = X0 + 3 < w0 && Y0 + 3 < h0;
+    uint32_t raw[4][3];  // CH16 = 0: this thread's four rows of 12 bytes
+    if constexpr (CH16 == 0) {
+        // The table entry and the frame bytes are requested together, before the table is stored and the barrier
+        // passed: one memory latency, not two in a row.
+        const float entry = c_k.lut[t & 255];
+        if (work) {
+            const uint8_t* base = a.in[f];
+            if constexpr (BATCH) base += in_off;
+            if (inside) {  // four rows of 12 contiguous bytes
+                // X0 + 3 < w0 and Y0 + j <= Y0 + 3 < h0: bytes 3 * ((Y0 + j) * w0 + X0) + 0..11 are pixels X0..X0+3
+                // of row Y0 + j, the last of them at most byte 3 * w0 * h0 - 1, the frame's last.
+                const uint8_t* row0 = base + ((size_t)Y0 * w0 + XB) * 3;
+                const uint32_t at = 12u * tx;
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+                for (int j = 0; j < 4; ++j) {
+                    const uint8_t* p = pyr_at(row0 + (size_t)j * w0 * 3, at);
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) l1[j][i][c] = 0.f;
-    if (X0 < w0 && Y0 < h0) {
-        const uint8_t* base = a.in[f];
-        if constexpr (BATCH) base += in_off;
-        uint32_t raw[4][3];
-        float lin16[4][4][3];  // CH16: linear values of this thread's 4 x 4 pixels
-        const bool inside = X0 + 3 < w0 && Y0 + 3 < h0;
-        if constexpr (CH16 != 0) {
-            pyr_load16<CH16>(*hb, f, w0, h0, X0, Y0, inside, lin16);
-        } else if (inside) {  // four rows of 12 contiguous bytes
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint8_t* p = base + ((size_t)(Y0 + j) * w0 + X0) * 3;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) __builtin_memcpy(&raw[j][k], p + 4 * k, 4);
-            }
-        } else {  // frame border: clamped coordinates, byte by byte
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int y = min(Y0 + j, h0 - 1);
-                uint8_t b[12];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const uint8_t* p = base + ((size_t)y * w0 + min(X0 + i, w0 - 1)) * 3;
-                    b[3 * i] = p[0];
-                    b[3 * i + 1] = p[1];
-                    b[3 * i + 2] = p[2];
+                    for (int k = 0; k < 3; ++k) __builtin_memcpy(&raw[j][k], p + 4 * k, 4);
                 }
+            } else {  // frame border: clamped coordinates (row <= h0 - 1, column <= w0 - 1), byte by byte
 #pragma unroll
-                for (int k = 0; k < 3; ++k)
-                    raw[j][k] = (uint32_t)b[4 * k] | ((uint32_t)b[4 * k + 1] << 8) | ((uint32_t)b[4 * k + 2] << 16) |
-                                ((uint32_t)b[4 * k + 3] << 24);
+                for (int j = 0; j < 4; ++j) {
+                    const uint8_t* row = base + ((size_t)min(Y0 + j, h0 - 1) * w0 + XB) * 3;
+                    uint8_t b[12];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const uint8_t* p = pyr_at(row, 3u * (uint32_t)(min(X0 + i, w0 - 1) - XB));
+                        b[3 * i] = p[0];
+                        b[3 * i + 1] = p[1];
+                        b[3 * i + 2] = p[2];
+                    }
+#pragma unroll
+                    for (int k = 0; k < 3; ++k)
+                        raw[j][k] = (uint32_t)b[4 * k] | ((uint32_t)b[4 * k + 1] << 8) | ((uint32_t)b[4 * k + 2] << 16) |
+                                    ((uint32_t)b[4 * k + 3] << 24);
+                }
             }
         }
+        if (t < 256) lut[t] = entry;
+        __syncthreads();
+    }
+    // ---- levels 1 and 2 in registers
+    float v2[3] = {0.f, 0.f, 0.f};  // this thread's level-2 output
+    if (work) {
+        float lin16[4][4][3];  // CH16: linear values of this thread's 4 x 4 pixels
+        if constexpr (CH16 != 0) pyr_load16<CH16>(*hb, f, w0, h0, X0, Y0, inside, lin16);
         // byte 3*i + c of a row = channel c of pixel i
 #define PYR_LIN(j, i, c) \
     (CH16 ? lin16[j][i][c] : lut[(raw[j][(3 * (i) + (c)) >> 2] >> (8 * ((3 * (i) + (c)) & 3))) & 255u])
+        float l1[2][2][3];  // [row][col][channel] of this thread's 2 x 2 level-1 outputs
         const int p1 = a.opitch[1];
         const size_t n1 = (size_t)p1 * h1;
+        float* o1 = a.out[f][0];
+        if constexpr (BATCH) o1 += out_off;
+        const int ox1 = X0 >> 1, oy1 = Y0 >> 1;
+        // the two floats of a row go out as one 8-byte store where every such pair is 8-byte aligned: plane, pitch
+        // (hence plane size) and the lane's offset 8 * tx all even in floats
+        const bool pairs = !XYB && (p1 & 1) == 0 && ((uintptr_t)o1 & 7) == 0;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int ox = (X0 >> 1) + i, oy = (Y0 >> 1) + j;
+            for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int c = 0; c < 3; ++c)
                     l1[j][i][c] = box4(PYR_LIN(2 * j, 2 * i, c), PYR_LIN(2 * j, 2 * i + 1, c),
                                        PYR_LIN(2 * j + 1, 2 * i, c), PYR_LIN(2 * j + 1, 2 * i + 1, c));
-                if (ox < w1 && oy < h1 && (!XYB || a.nlevels >= 1)) {
-                    float* o = a.out[f][0];
-                    if constexpr (BATCH) o += out_off;
-                    if (XYB) {
-                        pyr_store_xyb(o, n1, (size_t)oy * p1 + ox, l1[j][i]);
-                    } else {
+            if (oy1 + j < h1 && (!XYB || a.nlevels >= 1)) {
+                float* row = o1 + (size_t)(oy1 + j) * p1 + (XB >> 1);
+                const uint32_t at = 8u * tx;
+                if (XYB) {
 #pragma unroll
-                        for (int c = 0; c < 3; ++c) o[c * n1 + (size_t)oy * p1 + ox] = l1[j][i][c];
-                    }
+                    for (int i = 0; i < 2; ++i)
+                        if (ox1 + i < w1) pyr_store_xyb(row, n1, at + 4 * i, l1[j][i]);
+                } else if (pairs && ox1 + 1 < w1) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) *(float2*)pyr_at(row + c * n1, at) = make_float2(l1[j][0][c], l1[j][1][c]);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+                        if (ox1 + i < w1) {
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) *pyr_at(row + c * n1, at + 4 * i) = l1[j][i][c];
+                        }
                 }
             }
         }
         if constexpr (CH16 != 0 && !XYB) {  // FIR: the frame's scale-0 linear planes, a row of four pixels at a time
             const size_t n0 = (size_t)w0 * h0;
-            float* o = hb->lin0[f];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
+                float* row = hb->lin0[f] + (size_t)(Y0 + j) * w0 + XB;
+                const uint32_t at = 16u * tx;
                 if (inside) {
-                    const size_t at = (size_t)(Y0 + j) * w0 + X0;
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
                         const float px[4] = {lin16[j][0][c], lin16[j][1][c], lin16[j][2][c], lin16[j][3][c]};
-                        __builtin_memcpy(o + c * n0 + at, px, 16);
+                        __builtin_memcpy(pyr_at(row + c * n0, at), px, 16);
                     }
                 } else if (Y0 + j < h0) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
                         if (X0 + i < w0) {
 #pragma unroll
-                            for (int c = 0; c < 3; ++c) o[c * n0 + (size_t)(Y0 + j) * w0 + X0 + i] = lin16[j][i][c];
+                            for (int c = 0; c < 3; ++c) *pyr_at(row + c * n0, at + 4 * i) = lin16[j][i][c];
                         }
                 }
             }
@@ -422,7 +461,6 @@ __device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, con
         if (XYB) {  // the frame's own XYB planes: this thread's 4 x 4 pixels, a row of four at a time
             const int p0 = a.opitch[0];
             const size_t n0 = (size_t)p0 * h0;
-            float* o = a.xyb0[f];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float px[3][4];
@@ -430,47 +468,48 @@ __device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, con
                 for (int i = 0; i < 4; ++i) {
                     linear_to_xyb(PYR_LIN(j, i, 0), PYR_LIN(j, i, 1), PYR_LIN(j, i, 2), px[0][i], px[1][i], px[2][i]);
                 }
+                float* row = a.xyb0[f] + (size_t)(Y0 + j) * p0 + XB;
+                const uint32_t at = 16u * tx;
                 if (inside) {
-                    const size_t at = (size_t)(Y0 + j) * p0 + X0;
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) __builtin_memcpy(o + c * n0 + at, px[c], 16);
+                    for (int c = 0; c < 3; ++c) __builtin_memcpy(pyr_at(row + c * n0, at), px[c], 16);
                 } else if (Y0 + j < h0) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
                         if (X0 + i < w0) {
 #pragma unroll
-                            for (int c = 0; c < 3; ++c) o[c * n0 + (size_t)(Y0 + j) * p0 + X0 + i] = px[c][i];
+                            for (int c = 0; c < 3; ++c) *pyr_at(row + c * n0, at + 4 * i) = px[c][i];
                         }
                 }
             }
         }
 #undef PYR_LIN
-    }
-    if (a.nlevels < 2) return;
-    {
         const int w2 = a.w[2], h2 = a.h[2];
         const int ox = X0 >> 2, oy = Y0 >> 2;  // = 64 bx + tx, 8 by + ty
-        float v[3] = {0.f, 0.f, 0.f};
-        if (ox < w2 && oy < h2) {
+        if (a.nlevels >= 2 && ox < w2 && oy < h2) {
             // the level-1 column / row 2*ox+1, 2*oy+1 may not exist: the published clamp repeats the last one
             const int ib = min(2 * ox + 1, w1 - 1) - 2 * ox, jb = min(2 * oy + 1, h1 - 1) - 2 * oy;
             const int p2 = a.opitch[2];
             const size_t n2 = (size_t)p2 * h2;
-            float* o = a.out[f][1];
-            if constexpr (BATCH) o += out_off;
+            float* row = a.out[f][1] + (size_t)oy * p2 + (XB >> 2);
+            if constexpr (BATCH) row += out_off;
+            const uint32_t at = 4u * tx;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float p01 = ib ? l1[0][1][c] : l1[0][0][c];
                 const float p10 = jb ? l1[1][0][c] : l1[0][0][c];
                 const float p11 = jb ? (ib ? l1[1][1][c] : l1[1][0][c]) : (ib ? l1[0][1][c] : l1[0][0][c]);
-                v[c] = box4(l1[0][0][c], p01, p10, p11);
-                if (!XYB) o[c * n2 + (size_t)oy * p2 + ox] = v[c];
+                v2[c] = box4(l1[0][0][c], p01, p10, p11);
+                if (!XYB) *pyr_at(row + c * n2, at) = v2[c];
             }
-            if (XYB) pyr_store_xyb(o, n2, (size_t)oy * p2 + ox, v);
+            if (XYB) pyr_store_xyb(row, n2, at, v2);
         }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) s2[(c * 8 + ty) * TX + tx] = v[c];
     }
+    if (a.nlevels < 2) return;
+    // a thread outside the frame (no `work`) has X0 / 4 >= w[2] or Y0 / 4 >= h[2] and stores 0, as one whose level-2
+    // output does not exist always did
+#pragma unroll
+    for (int c = 0; c < 3; ++c) s2[(c * 8 + ty) * TX + tx] = v2[c];
     if (a.nlevels < 3) return;
     __syncthreads();
     if (t < 4 * (TX / 2))
@@ -487,11 +526,16 @@ __device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, con
         pyr_lds_level<XYB>(s4, TX / 4, 2, a.w[4], a.h[4], nullptr, 0, 0, BATCH ? a.out[f][4] + out_off : a.out[f][4], a.w[5], a.h[5], a.opitch[5], bx * (TX / 8), by, t, 0);
 }
 
+// The pair score's pyramid runs beside the other context's marching kernel, in the slot a marching workgroup has left
+// ("Two scores in flight"): it holds that slot for as long as it lives.  Its few instructions
+// would wait their turn behind the marching waves that saturate the SIMD's issue; at a higher issue priority they go
+// first and the slot is back sooner.
+__device__ __forceinline__ void pyr_issue_first() { __builtin_amdgcn_s_setprio(3); }
+
 __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_bands(PyrBandArgs a) {
     __shared__ float s_lut[256];
     __shared__ float s_tiles[PYR_BAND_LDS_FLOATS];
-    if (threadIdx.x < 256) s_lut[threadIdx.x] = c_k.lut[threadIdx.x];
-    __syncthreads();
+    pyr_issue_first();
     pyramid_band<false>(a, (int)blockIdx.x, s_lut, s_tiles);
 }
 
@@ -506,8 +550,7 @@ struct PyrBatchArgs {
 __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_bands_batch(PyrBatchArgs b) {
     __shared__ float s_lut[256];
     __shared__ float s_tiles[PYR_BAND_LDS_FLOATS];
-    if (threadIdx.x < 256) s_lut[threadIdx.x] = c_k.lut[threadIdx.x];
-    __syncthreads();
+    pyr_issue_first();
     const int per_item = b.a.bands_x * b.a.bands_y * b.a.nframes;
     const int item = (int)blockIdx.x / per_item;
     pyramid_band<false, 0, true>(b.a, (int)blockIdx.x - item * per_item, s_lut, s_tiles, nullptr, (size_t)item * b.in_stride,
@@ -519,9 +562,7 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_bands_batch(PyrBatchArg
 __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_bands_xyb(PyrBandArgs a) {
     __shared__ float s_lut[256];
     __shared__ float s_tiles[PYR_BAND_LDS_FLOATS];
-    if (threadIdx.x < 256) s_lut[threadIdx.x] = c_k.lut[threadIdx.x];
     if (blockIdx.x == 0 && threadIdx.x < 4 && a.zero4) a.zero4[threadIdx.x] = 0u;  // k_rg_v starts after this launch has ended
-    __syncthreads();
     pyramid_band<true>(a, (int)blockIdx.x, s_lut, s_tiles);
 }
 
