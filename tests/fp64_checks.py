@@ -61,8 +61,46 @@ for _m in ("recursive", "recursive_fma"):
 MAP_PIXEL_REL = {"fir": 5e-3, "recursive": 6e-2}
 MAP_MEAN_REL = {"fir": 5e-5, "recursive": 1e-3}
 
+# the same two measures for maps of 9- to 16-bit frames (hbd_cases.content16 pairs: MAP_HBD_CASES below and a dozen more
+# at depths 9..16, sizes up to 640 x 352; cpu_fp64_campaign.py's "error map, 16-bit" section), fp32 (device /
+# errmap_ref over hbd_ref.linear_planes) against hbd_ref.error_map_fp64.  content16's low-order noise makes these maps
+# rougher than the 8-bit campaign's, so they get bounds of their own: campaign max x 2.
+#   pixel: campaign max FIR 3.18e-3 (174 x 207, 12-bit), RECURSIVE 4.13e-2 (192 x 224, 9-bit);
+#   mean (tiling sizes): 1.02e-4 (160 x 128, 13-bit) / 1.97e-3 (192 x 224, 9-bit)
+MAP_PIXEL_REL_HBD = {"fir": 6.4e-3, "recursive": 8.3e-2}
+MAP_MEAN_REL_HBD = {"fir": 2.1e-4, "recursive": 4e-3}
+MAP_HBD_CASES = [(128, 96, 10), (131, 173, 12), (640, 352, 9)]   # (w, h, depth); pairs: map_hbd_pair
+
 # a structural variant of a stage must miss at least one FIR check (natural frames) by this factor
 DISCRIMINATION_FACTOR = 2.0
+
+
+def map_hbd_pair(w: int, h: int, d: int, seed=None):
+    """The content16 pair of a 16-bit map case: (reference, distorted), seeded by the size unless `seed` is given."""
+    from hbd_cases import content16
+    seed = w * h if seed is None else seed
+    return content16(w, h, d, seed), content16(w, h, d, seed, distort=True)
+
+
+def map_tiles(w: int, h: int, nscales: int) -> bool:
+    """Every scale tiles the frame (w, h multiples of 2^(nscales - 1)): only then is the map's mean sum w_i |a_i|."""
+    return nscales >= 1 and w % (1 << (nscales - 1)) == 0 and h % (1 << (nscales - 1)) == 0
+
+
+def map_deviation(m, m64, e: dict) -> dict:
+    """An fp32 map `m` against the fp64 map `m64` of the result `e`: -> {"pixel": max |delta| / the fp64 map's peak,
+    "mean": |mean - sum w_i |a_i|| / that sum where every scale tiles the frame, else None}."""
+    assert m.shape == m64.shape
+    h, w = m64.shape
+    out = {"pixel": float(np.abs(m - m64).max() / m64.max()), "mean": None}
+    if map_tiles(w, h, e["nscales"]):
+        out["mean"] = abs(float(m.mean(dtype=np.float64)) - e["weighted_sum"]) / e["weighted_sum"]
+    return out
+
+
+def map_deviation_text(dev: dict, pixel_bound: float, mean_bound: float) -> str:
+    mean = "not measured (a scale does not tile the frame)" if dev["mean"] is None else f"{dev['mean']:.3e}"
+    return f"pixel {dev['pixel']:.3e} (bound {pixel_bound:.1e}), mean {mean} (bound {mean_bound:.1e})"
 
 
 def deviation(score, avg, nscales, exp: dict) -> dict:

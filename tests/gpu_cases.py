@@ -7,7 +7,8 @@
 * the one hold of a score's averages to a reference (hold_averages) and the one bound of a FIR average
   (averages_rtol), with their callers: check_against_terms (averages and k_finalize against the kernel-order terms),
   check_fir_sums (the FIR d / d^4 averages against k_march's own summing order, tests/fir_sums.py) and
-  check_item_against_terms (a batch item); the error-map check against tests/errmap_ref.py (check_map);
+  check_item_against_terms (a batch item); the error-map check against tests/errmap_ref.py (check_map; the same rule
+  for maps of 16-bit, RGBA and YUV frames: tests/map_cases.py);
 * what the batch modules share: the batch rule's rows, seeded neighbours, the comparison of score and averages for
   bits, frames packed into one device buffer (on_device) and the golden pair's bits (golden_bits);
 * what puts foreign content around a call: a stale pair score of a larger size (stale), the cached reference scored

@@ -5,7 +5,8 @@ planes (scales, terms_lin, kernel_averages_lin, score_lin), tests/ssimu2_fp64.py
 `table(d)` restates the library's sRGB -> linear table of d-bit samples and `linear_planes` builds the scale-0 fp32
 linear planes of a uint16 frame from it; `compute`, `terms` and `levels` hand those to errmap_ref: the checker's
 arithmetic, fed 16-bit planes.  `linear_planes_fp64` is the counterpart in fp64 (linear values never rounded to fp32),
-which `compute_fp64` and `reference_levels` hand to ssimu2_fp64.  `every_code_frame` is a frame that holds every 16-bit
+which `compute_fp64`, `reference_levels` and `error_map_fp64` hand to ssimu2_fp64; `error_map_fp32` is the fp32 route's
+map of the same frames.  `every_code_frame` is a frame that holds every 16-bit
 code once per channel."""
 from __future__ import annotations
 
@@ -58,6 +59,16 @@ def compute(orc, ref: np.ndarray, dist: np.ndarray, d: int, blur: int, d_dist: i
     return errmap_ref.score_lin(orc, linear_planes(ref, d), linear_planes(dist, d if d_dist is None else d_dist), blur)
 
 
+def error_map_fp32(orc, ref: np.ndarray, dist: np.ndarray, d: int, blur: int):
+    """The numpy fp32 map of two uint16 frames of d bits, its coefficients from the averages of its own terms (a device
+    map takes the device's): -> (map (h, w) float32, the terms per scale, the (6, 18) averages).  Bit for bit the device
+    map in the recursive modes, within gpu_cases.MAP_K * 2^-24 of it in FIR."""
+    h, w, _ = ref.shape
+    tm = errmap_ref.terms_lin(orc, linear_planes(ref, d), linear_planes(dist, d), blur)
+    avg = errmap_ref.averages(tm)
+    return errmap_ref.compose(tm, errmap_ref.coefficients(orc, avg, len(tm)), w, h), tm, avg
+
+
 def linear_planes_fp64(img: np.ndarray, d: int) -> np.ndarray:
     v = np.moveaxis(_clamped(img, d), 2, 0).astype(np.float64) / float((1 << d) - 1)
     return np.where(v <= ref64.SRGB_THRESHOLD, v / ref64.SRGB_SLOPE,
@@ -74,3 +85,10 @@ def compute_fp64(ref: np.ndarray, dist: np.ndarray, d: int, d_dist: int | None =
     """ssimu2_fp64.evaluate for uint16 frames of d bits (`d_dist`: the distorted frame's own depth):
     {"score", "averages", "nscales", "weighted_sum"}."""
     return ref64.evaluate_linear(linear_planes_fp64(ref, d), linear_planes_fp64(dist, d if d_dist is None else d_dist))
+
+
+def error_map_fp64(ref: np.ndarray, dist: np.ndarray, d: int):
+    """ssimu2_fp64.error_map for uint16 frames of d bits: -> (map (h, w) fp64, evaluate_linear's result with planes).
+    Shares no code with the kernels or the checker beyond the weight table."""
+    result = ref64.evaluate_linear(linear_planes_fp64(ref, d), linear_planes_fp64(dist, d), planes=True)
+    return ref64.error_map(None, None, result, size=ref.shape[:2])

@@ -272,11 +272,17 @@ def evaluate_linear(lin1: np.ndarray, lin2: np.ndarray, planes: bool = False) ->
     return out
 
 
-def error_map(ref: np.ndarray, dist: np.ndarray, result: dict | None = None):
+def error_map(ref: np.ndarray | None, dist: np.ndarray | None, result: dict | None = None, size=None):
     """The per-pixel error map of DESIGN.md section 9 in fp64: -> (map (h, w), evaluate()'s result).  Each average
     a_i of the walk is spread over its scale as w_i t for an L1 term and w_i t^4 / a_i^3 for an L4 term (0 when
-    a_i == 0); map(x, y) = sum over scales of the scale's density at (x >> s, y >> s)."""
-    h, w, _ = ref.shape
+    a_i == 0); map(x, y) = sum over scales of the scale's density at (x >> s, y >> s).  Without 8-bit frames (ref and
+    dist None): `result` is evaluate_linear(..., planes=True) of any front end (hbd_ref.error_map_fp64) and `size` the
+    frame's (h, w), all the map needs of the frames."""
+    if ref is None:
+        assert result is not None and "planes" in result and size is not None
+        h, w = size
+    else:
+        h, w, _ = ref.shape
     if result is None or "planes" not in result:
         result = evaluate(ref, dist, planes=True)
     avg, ns = result["averages"], result["nscales"]

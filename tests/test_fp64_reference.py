@@ -217,6 +217,67 @@ def test_reference_error_map_against_the_fp32_map(oracle, golden):
             assert abs(m32.mean(dtype=np.float64) - e["weighted_sum"]) <= fc.MAP_MEAN_REL["fir"] * e["weighted_sum"]
 
 
+def _scale_parts(oracle, tm, coef, w, h):
+    """errmap_ref.compose scale by scale: -> each scale's density at full resolution (their sum in order is compose's
+    map: 0 + x is x exactly)."""
+    parts = []
+    for s in range(len(tm)):
+        only = np.zeros_like(coef)
+        only[s] = coef[s]
+        parts.append(errmap_ref.compose(tm, only, w, h))
+    return parts
+
+
+def _wrong_maps(oracle, tm, avg, e, w, h):
+    """Two structurally wrong fp32 FIR maps: -> {name: map}.  "shifted": the density of scale 1 taken at (x >> 1) + 1,
+    clamped to the scale's last column (an off-by-one in k_map_compose's gather).  "dropped": the artifact L4
+    coefficient of one channel at one scale left 0 -- the one whose term w_i a_i weighs most in the reference's sum, so
+    that the variant is a wrong map and not the drop of a zero weight."""
+    ns = len(tm)
+    coef = errmap_ref.coefficients(oracle, avg, ns)
+    parts = _scale_parts(oracle, tm, coef, w, h)
+    xs = np.arange(w)
+    w1 = (w + 1) // 2
+    src = np.minimum((xs >> 1) + 1, w1 - 1) << 1
+    shifted = np.zeros((h, w), np.float32)
+    for s, p in enumerate(parts):
+        shifted = shifted + (p[:, src] if s == 1 else p)
+    art_l4 = [(wt * abs(e["averages"][s, st]), s, st) for wt, s, st in R.weight_walk(ns) if st >= 6 and (st - 6) % 4 == 1]
+    _top, s_drop, st_drop = max(art_l4)
+    less = coef.copy()
+    less[s_drop, st_drop] = 0
+    return {"shifted": shifted, "dropped": errmap_ref.compose(tm, less, w, h)}
+
+
+def test_reference_error_map_of_16_bit_frames_against_the_fp32_map(oracle):
+    """hbd_ref.error_map_fp32 (the 16-bit device map's own reference: bit for bit in the recursive modes, within 48 *
+    2^-24 in FIR) against hbd_ref.error_map_fp64 on fc.MAP_HBD_CASES, inside fc.MAP_PIXEL_REL_HBD / MAP_MEAN_REL_HBD;
+    and those bounds still tell a wrong map from rounding: each structural variant of the FIR map misses the pixel
+    bound by fc.DISCRIMINATION_FACTOR on every case.  Measured: FIR pixel 1.1e-3 .. 2.8e-3 of the peak, recursive
+    2.1e-2 .. 2.8e-2; the shifted scale misses the FIR pixel bound 9 to 51 times over, the dropped coefficient 28 to
+    82 times."""
+    import hbd_ref
+    for w, h, d in fc.MAP_HBD_CASES:
+        ref, dist = fc.map_hbd_pair(w, h, d)
+        m64, e = hbd_ref.error_map_fp64(ref, dist, d)
+        assert m64.shape == (h, w) and e["nscales"] == R.nscales_of(w, h)
+        if fc.map_tiles(w, h, e["nscales"]):
+            assert abs(m64.mean() - e["weighted_sum"]) <= 1e-12 * e["weighted_sum"]
+        for mode, blur in (("fir", oracle.BLUR_FIR), ("recursive", oracle.BLUR_IIR)):
+            m32, tm, avg = hbd_ref.error_map_fp32(oracle, ref, dist, d, blur)
+            assert len(tm) == e["nscales"]
+            dev = fc.map_deviation(m32, m64, e)
+            print(f"measured: {w}x{h} {d}-bit {mode}: " + fc.map_deviation_text(dev, fc.MAP_PIXEL_REL_HBD[mode],
+                                                                                 fc.MAP_MEAN_REL_HBD[mode]))
+            assert dev["pixel"] <= fc.MAP_PIXEL_REL_HBD[mode], (w, h, d, mode, dev)
+            assert dev["mean"] is None or dev["mean"] <= fc.MAP_MEAN_REL_HBD[mode], (w, h, d, mode, dev)
+            if mode == "fir":
+                for name, wrong in _wrong_maps(oracle, tm, avg, e, w, h).items():
+                    miss = fc.map_deviation(wrong, m64, e)["pixel"] / fc.MAP_PIXEL_REL_HBD["fir"]
+                    print(f"measured: {w}x{h} {d}-bit variant {name}: {miss:.1f} x the pixel bound")
+                    assert miss >= fc.DISCRIMINATION_FACTOR, (w, h, d, name, miss)
+
+
 # ---- discrimination: the bounds tell a wrong operation from fp32 rounding --------------------------------------------
 
 STRUCTURAL = {"edge_clamp": 0x1, "edge_mirror": 0x2, "gauss9": 0x4, "gauss11": 0x8, "downsample_xyb": 0x10,

@@ -112,7 +112,45 @@ def test_noise_frames_at_every_width_pitch_and_alignment(ctxs, h):
             k += 1
 
 
+@pytest.mark.parametrize("w,h", [(1027, 5), (4100, 3), (8, 65_600)])
+def test_codes_past_one_block_in_x_and_past_the_grid_s_rows(ctxs, w, h):
+    """A block of k_composite_rgba8 takes 1,024 pixels of a row: 1027 = 1,024 + 3 has a second block that is a tail
+    alone, 4100 = 4 * 1,024 + 4 a fifth block of one whole group.  gridDim.y ends at 65,535: 8 x 65,600 is the smallest
+    frame whose last 65 rows are taken in the kernel's second round (y += gridDim.y)."""
+    s = ctxs["fir"]
+    assert w > 1024 or h > 65_535
+    frame = np.random.default_rng(1000 * h + w).integers(0, 256, (h, w, 4), dtype=np.uint8)
+    for k, pad in enumerate((0, 1, 3, 64)):
+        bg = BACKGROUNDS[k % 4]
+        exp = codes_of(frame, bg)
+        buf, view = laid_out(frame, 4 * w + pad, k % 4, seed=k)
+        assert view.ctypes.data % 4 == (buf.ctypes.data + k % 4) % 4
+        got = s.composite_rgba(view, bg)
+        assert got.dtype == np.uint16 and got.shape == exp.shape
+        assert np.array_equal(got, exp), (w, h, pad, k % 4, np.argwhere(got != exp)[:4].tolist())
+
+
 # ---- (b) opaque frames are the 8-bit path ------------------------------------------------------------------------
+def test_opaque_frame_of_65600_rows_scores_as_its_rgb_bit_for_bit(ctxs):
+    """9 x 65,600 (FIR): the composite's second row round in front of the pair score and the cached score."""
+    s = ctxs["fir"]
+    w, h = 9, 65_600
+    ref = synth.make_ref(w, h, seed=17 * w + h)
+    dist = synth.distort(ref, "noise", 2, seed=w + 3 * h)
+    exp = results(s, s.compute_ssimu2(ref, dist))
+    assert 0.0 < exp[0] < 100.0 and exp[2] == 2
+    s.set_reference(ref)
+    exp_c = results(s, s.score_against_reference(dist))
+    _br, r4 = laid_out(rgba_of(ref, 255), 4 * w + 5, 1, seed=1)
+    _bd, d4 = laid_out(rgba_of(dist, 255), 4 * w + 12, 2, seed=2)
+    gpu_cases.stale(s, w, h, 1)
+    assert_bits(results(s, s.compute_ssimu2_rgba(r4, d4, 0xE680FF)), exp, "9x65600 pair")
+    s.set_reference_rgba(r4, 0xE680FF)
+    assert s.score_against_reference_rgba(r4) == 100.0
+    assert_bits(results(s, s.score_against_reference_rgba(d4)), exp_c, "9x65600 cached")
+
+
+
 @pytest.mark.parametrize("mode", MODES)
 def test_opaque_frames_score_as_their_rgb_bit_for_bit(ctxs, mode):
     s = ctxs[mode]

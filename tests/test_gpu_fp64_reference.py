@@ -132,3 +132,28 @@ def test_error_map_against_the_fp64_map(ctxs, mode, w, h):
     ns = e["nscales"]
     if w % (1 << (ns - 1)) == 0 and h % (1 << (ns - 1)) == 0:
         assert abs(m.mean(dtype=np.float64) - e["weighted_sum"]) <= fc.MAP_MEAN_REL[mode] * e["weighted_sum"]
+
+
+mctxs = contexts_fixture(maps=True, extended=True, yuv=True)
+_REF_MAP16 = {}
+
+
+@pytest.mark.parametrize("w,h,d", fc.MAP_HBD_CASES, ids=[f"{w}x{h}-{d}bit" for w, h, d in fc.MAP_HBD_CASES])
+@pytest.mark.parametrize("mode", ["fir", "recursive"])
+def test_error_map_of_16_bit_frames_against_the_fp64_map(mctxs, mode, w, h, d):
+    """error_map_hbd against hbd_ref.error_map_fp64, which shares no code with the kernels or with tests/errmap_ref.py:
+    per pixel relative to the fp64 map's peak, and the mean against sum w_i |a_i| where every scale tiles the frame, in
+    the 16-bit bounds of tests/fp64_checks.py (tests/test_fp64_reference.py shows that they tell a wrong map from
+    rounding).  The fp64 map is computed once per case."""
+    import hbd_ref
+    ref, dist = fc.map_hbd_pair(w, h, d)
+    if (w, h, d) not in _REF_MAP16:
+        _REF_MAP16[w, h, d] = hbd_ref.error_map_fp64(ref, dist, d)
+    m64, e = _REF_MAP16[w, h, d]
+    _score, m = mctxs[mode].error_map_hbd(ref, dist, d)
+    assert mctxs[mode].last_averages()[1] == e["nscales"]
+    dev = fc.map_deviation(m, m64, e)
+    print(f"measured: {mode} {w}x{h} {d}-bit: " + fc.map_deviation_text(dev, fc.MAP_PIXEL_REL_HBD[mode],
+                                                                         fc.MAP_MEAN_REL_HBD[mode]))
+    assert dev["pixel"] <= fc.MAP_PIXEL_REL_HBD[mode], (mode, w, h, d, dev)
+    assert dev["mean"] is None or dev["mean"] <= fc.MAP_MEAN_REL_HBD[mode], (mode, w, h, d, dev)

@@ -162,6 +162,29 @@ def test_scores_equal_the_16bit_calls_on_the_restated_codes(ctxs, mode):
             k += 1
 
 
+def test_frame_of_65600_rows_scores_as_the_16bit_calls_on_the_restated_codes(ctxs):
+    """9 x 65,600 (FIR): k_yuv_to_codes' second row round (gridDim.y ends at 65,535) in front of the pair score and the
+    cached score, which (8, 65600) of SIZES holds as codes only."""
+    s = ctxs["fir"]
+    w, h, depth, full_range, mc = 9, 65_600, 10, False, 1
+    rp, dp = yuv_pair(w, h, depth, full_range, mc, 4)
+    rf, _rb = frame_of(rp, depth, full_range, mc, yuv_ref.YUV_444, 4)
+    df, _db = frame_of(dp, depth, full_range, mc, yuv_ref.YUV_444, 5)
+    for rgb_depth in (depth, 16):
+        what = (w, h, depth, rgb_depth)
+        cr = yuv_ref.codes(*rp, depth, full_range, mc, rgb_depth)
+        cd = yuv_ref.codes(*dp, depth, full_range, mc, rgb_depth)
+        exp = results(s, s.compute_ssimu2_hbd(cr, cd, rgb_depth))
+        assert 0.0 < exp[0] < 100.0 and exp[2] == 2, what
+        s.set_reference_hbd(cr, rgb_depth)
+        exp_c = results(s, s.score_against_reference_hbd(cd, rgb_depth))
+        gpu_cases.stale(s, w, h, 2)
+        assert_bits(results(s, s.compute_ssimu2_yuv(rf, df, rgb_depth)), exp, what + ("pair",))
+        s.set_reference_yuv(rf, rgb_depth)
+        assert s.score_against_reference_yuv(rf, rgb_depth) == 100.0, what
+        assert_bits(results(s, s.score_against_reference_yuv(df, rgb_depth)), exp_c, what + ("cached",))
+
+
 @pytest.mark.parametrize("mode", MODES)
 def test_grey_frames_score_as_their_rgb8_bit_for_bit(ctxs, mode):
     s = ctxs[mode]

@@ -7,7 +7,7 @@ Stages: the sRGB table (all 256 codes), linear_to_xyb (all 2^24 colours), downsa
 per side, the five content kinds of tests/gpu_cases.py plus synth.make_ref, four distortion kinds, strengths 1..3)
 and 1080p / 4K pairs, each in FIR, EXACT, IIR and IIR_FMA.  The recursive modes are also reported by frame size.
 
-Usage: cpu_fp64_campaign.py [N_CASES] [--no-large] [--no-stages] [--seed S]
+Usage: cpu_fp64_campaign.py [N_CASES] [--no-large] [--no-stages] [--seed S] [--hbd-maps]
 """
 import argparse
 import os
@@ -143,6 +143,39 @@ def map_campaign():
     return out
 
 
+def hbd_map_cases():
+    """fc.MAP_HBD_CASES (the frames of the tests) and a dozen more content16 pairs at depths 9..16, sizes up to
+    640 x 352, every other one a multiple of 32 both ways so that the mean is measured too: -> [(w, h, depth, seed or
+    None)]."""
+    rng = np.random.default_rng(1016)
+    more = []
+    for i in range(12):
+        w, h = int(rng.integers(8, 641)), int(rng.integers(8, 353))
+        if i % 2 == 0:
+            w, h = max(32, w // 32 * 32), max(32, h // 32 * 32)
+        more.append((w, h, 9 + i % 8, 500 + i))
+    return [c + (None,) for c in fc.MAP_HBD_CASES] + more
+
+
+def hbd_map_campaign():
+    """The fp32 map of 9- to 16-bit frames (hbd_ref.error_map_fp32: bit for bit the device map in the recursive modes,
+    within MAP_K * 2^-24 of it in FIR) against hbd_ref.error_map_fp64, in fc.map_deviation's measures.  -> (per case,
+    {(measure, mode): maximum}); fc.MAP_PIXEL_REL_HBD / MAP_MEAN_REL_HBD are the maxima times 2."""
+    import hbd_ref
+    out, worst = {}, {}
+    for w, h, d, seed in hbd_map_cases():
+        ref, dist = fc.map_hbd_pair(w, h, d, seed)
+        m64, e = hbd_ref.error_map_fp64(ref, dist, d)
+        for mode, blur in (("fir", orc.BLUR_FIR), ("recursive", orc.BLUR_IIR)):
+            r = fc.map_deviation(hbd_ref.error_map_fp32(orc, ref, dist, d, blur)[0], m64, e)
+            out[f"{w}x{h} {d}-bit {mode}"] = {k: v for k, v in r.items() if v is not None}
+            for k, v in r.items():
+                if v is not None:
+                    worst[k, mode] = max(worst.get((k, mode), 0.0), v)
+        print(f"  16-bit map {w}x{h} {d}-bit done", file=sys.stderr)
+    return out, worst
+
+
 def random_case(rng, i):
     w, h = (int(x) for x in rng.integers(1, 601, 2))
     kind = KINDS[i % len(KINDS)]
@@ -196,9 +229,10 @@ def main():
     ap.add_argument("--no-large", action="store_true")
     ap.add_argument("--no-stages", action="store_true")
     ap.add_argument("--seed", type=int, default=2026)
+    ap.add_argument("--hbd-maps", action="store_true", help="only the 16-bit error-map section")
     a = ap.parse_args()
     orc.build()
-    if not a.no_stages:
+    if not a.no_stages and not a.hbd_maps:
         print("== stages: checker vs fp64 reference")
         for k, v in stage_campaign().items():
             print(f"  {k}: {v}")
@@ -208,6 +242,15 @@ def main():
         print("== error map: fp32 map vs fp64 map")
         for k, v in map_campaign().items():
             print(f"  {k}: " + ", ".join(f"{m} {x:.3g}" for m, x in v.items()))
+    if not a.no_stages or a.hbd_maps:
+        print("== error map, 16-bit: fp32 map vs fp64 map")
+        per_case, worst = hbd_map_campaign()
+        for k, v in per_case.items():
+            print(f"  {k}: " + ", ".join(f"{m} {x:.3g}" for m, x in v.items()))
+        for (meas, mode), x in sorted(worst.items()):
+            print(f"  maximum {meas} {mode}: {x:.3e}")
+    if a.hbd_maps:
+        return
     rng = np.random.default_rng(a.seed)
     cases = [random_case(rng, i) for i in range(a.cases)]
     if not a.no_large:
