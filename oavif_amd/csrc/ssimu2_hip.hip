@@ -182,8 +182,11 @@ Pyramid make_pyramid(uint32_t w, uint32_t h) {
 // best at ~512 workgroups (two thirds of the 768 resident slots, 6 % halo), the smaller scales
 // at ~48 rows -- their few, long workgroups overlap the tail of scale 0 and, with two
 // streams, the next score.  Bounds: >= 8 rows, <= 160 rows (fp32 partial sums per lane).
+// kSegRuleCols is the rule's own column unit, not a kernel's strip width: the rows a lane sums in fp32 are part of a
+// score's bits (tests/gpu_cases.py restates the rule), so they stay what they were when the strips became wider.
+constexpr int kSegRuleCols = 120;
 int march_seg_rule(const Pyramid& p, int scale) {
-    const int nstrips = (p.w[0] + MW - 1) / MW;
+    const int nstrips = (p.w[0] + kSegRuleCols - 1) / kSegRuleCols;
     int nsegs = (512 + nstrips / 2) / nstrips;
     if (nsegs < 1) nsegs = 1;
     int seg = (p.h[0] + nsegs - 1) / nsegs;  // full-resolution scale: ~512 workgroups
@@ -217,6 +220,12 @@ int batch_seg_rows(const ssimu2_ctx* c, const Pyramid& p, int scale) {
 
 using SegRows = int (*)(const ssimu2_ctx*, const Pyramid&, int);
 
+// Output columns per strip of the marching kernel a plan is built for -- the one place that knows which entry point
+// has which geometry (ssimu2_kernels.h, MarchGeo): the kernels that leave partial sums (pair, cached reference, 16-bit,
+// batch) march wide strips, the ones that write planes (k_ref_blur, the map kernels) narrow ones.
+enum MarchOut { MARCH_OUT_SUMS, MARCH_OUT_PLANES };
+constexpr int strip_cols(MarchOut out) { return out == MARCH_OUT_SUMS ? MarchWide::MW : MarchNarrow::MW; }
+
 // What the final reduction needs of the frame size alone; `part` and `nblocks` are the caller's.
 FinalizeArgs finalize_args(const Pyramid& p) {
     FinalizeArgs fa;
@@ -245,16 +254,17 @@ struct PlanSources {
 // A marching plan and its final reduction under a segment-rows rule (march_seg_rows or batch_seg_rows).  The one place
 // for the sizes -- per scale w, h, segment rows, strips, workgroups and their running total, 1 / pixels -- and the one
 // place that writes the per-scale pointers, from `src`.  Returns the workgroups of one pair's marching launch (none
-// for a frame below 8 x 8), each with kStats doubles of partial sums.
+// for a frame below 8 x 8), each with kStats doubles of partial sums.  `out`: what the kernel that will run the plan
+// leaves behind, which fixes its strip width (strip_cols).
 int build_plans(const ssimu2_ctx* c, const Pyramid& p, SegRows seg_rows, const PlanSources& src, MarchPlan* mp,
-                FinalizeArgs* fa) {
+                FinalizeArgs* fa, MarchOut out = MARCH_OUT_SUMS) {
     memset(mp, 0, sizeof *mp);
     *fa = finalize_args(p);
     mp->nscales = p.nscales;
     int blocks = 0;
     for (int s = 0; s < p.nscales; ++s) {
         const int seg = seg_rows(c, p, s);
-        const int nstrips = (p.w[s] + MW - 1) / MW;
+        const int nstrips = (p.w[s] + strip_cols(out) - 1) / strip_cols(out);
         const int nb = nstrips * ((p.h[s] + seg - 1) / seg);
         mp->blk_end[s] = blocks + nb;
         mp->w[s] = p.w[s];
@@ -911,7 +921,7 @@ int map_pass(ssimu2_ctx* c, bool hbd, uint32_t w, uint32_t h, float* out_map) {
             PlanSources src = hbd ? score_sources(c, c->hbd.lin0_ref.p, c->hbd.lin0_dist.p, false)
                                   : score_sources(c, c->frame.ref_u8.p, c->frame.dist_u8.p, false);
             src.ref_s11 = dens;  // the output planes
-            const int blocks = build_plans(c, p, march_seg_rows, src, &mp, &fa);
+            const int blocks = build_plans(c, p, march_seg_rows, src, &mp, &fa, MARCH_OUT_PLANES);
             launch(hbd ? k_march_map_lin : k_march_map, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp, mc);
         } else {
             RgPlan rp;
@@ -1540,7 +1550,7 @@ static int cache_reference_fir(ssimu2_ctx* c, const Pyramid& p, const void* scal
             FinalizeArgs fa;
             PlanSources src = score_sources(c, scale0, scale0, true);  // XYB planes in, blur(x*x) out
             src.lin_dist = src.lin_ref;                                // second frame unused
-            const int blocks = build_plans(c, p, march_seg_rows, src, &mp, &fa);
+            const int blocks = build_plans(c, p, march_seg_rows, src, &mp, &fa, MARCH_OUT_PLANES);
             if (blocks > 0)
                 launch(k_ref_blur, dim3(blocks), dim3(MARCH_THREADS), 0, c->stream, mp);
         }

@@ -358,7 +358,7 @@ int ssimu2_time_blur_stage_rotating(ssimu2_ctx* c, const void* const* d_frames, 
         src.lin_dist = src.lin_ref;  // second frame unused
         src.ref_xyb = xyb;
         src.ref_s11 = xyb + planes;
-        blocks = build_plans(c, p, march_seg_rows, src, &plans[i], &fa);
+        blocks = build_plans(c, p, march_seg_rows, src, &plans[i], &fa, MARCH_OUT_PLANES);
     }
     float ms = 0.f;
     hipError_t e = hipSuccess;

@@ -5,7 +5,7 @@
 // Kernels (wave64; VALU + LDS work, no MFMA: stencil and pointwise arithmetic):
 //   k_pyramid_bands : linear-light 2x2 box pyramid, all five levels in one launch from one read
 //                  of the u8 sRGB frames (through the LUT)
-//   k_march      : ONE launch for all scales: per workgroup, a strip of 120 output columns of
+//   k_march      : ONE launch for all scales: per workgroup, a strip of 128 output columns of
 //                  one scale is marched top to bottom: sRGB LUT -> opsin -> cbrt -> positive
 //                  XYB (converter waves, LDS ring of (ref, dist) pair rows), horizontal 9-tap of
 //                  {x, y, xx, yy, xy} in registers, vertical 9-tap from a 9-row register
@@ -584,9 +584,9 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_bands_xyb16(PyrBandArgs
 }
 
 // ---- fused per-scale kernel, marching form, all scales in one launch ----------------------------
-// One workgroup (8 waves) owns a strip of MW output columns of ONE scale and marches down
+// One workgroup (8 waves) owns a strip of MW output columns (MarchGeo below) of ONE scale and marches down
 // `seg` output rows, one image row per step.
-//   waves 0-1 (converters): lane = one staged column (MW + 8 halo = 128), both frames.  Each
+//   waves 0-1 (converters): lane = one staged column (of MW + 8; the wide geometry's last eight: halo pass), both frames.  Each
 //     step they convert one input row (sRGB LUT at scale 0 -> opsin -> cbrt -> positive XYB)
 //     into an LDS ring of raw rows, one barrier group ahead of the blur waves; their global
 //     loads run one more group ahead, so HBM latency is off the critical path.  At scale 0 a
@@ -614,9 +614,6 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_bands_xyb16(PyrBandArgs
 // Scales are laid out largest first in the grid, so the short workgroups of the small scales
 // fill the tail of the big ones instead of running as five latency-bound launches.
 constexpr int RAD = 4;
-constexpr int MW = 120;        // output columns per strip
-constexpr int MRW = MW + 8;    // staged columns (4 px halo each side) = 128 = 2 waves per frame
-constexpr int MHALF = MW / 2;  // output columns per blur wave (lanes 0..59 active)
 constexpr int RING = 16;       // raw-row ring depth (power of two >= 13: rows t-4 .. t+8)
 constexpr int AHEAD = 3;       // rows the converters run ahead of the blur waves (1 group)
 constexpr int GROUP = 3;       // rows per barrier interval (divides the 9-phase unroll)
@@ -628,7 +625,26 @@ constexpr int CONV_WAVES = 2;  // each converter lane handles one staged column 
 // waves one naturally aligned ds_read_b64 (256 B/clk/CU; the planar layout needed
 // ds_read2_b32, 128 B/clk/CU) and every converter store one ds_write_b64.
 typedef float f2 __attribute__((ext_vector_type(2)));
-constexpr int RING_ROW = 3 * MRW;  // f2 elements per ring row: [channel][column]
+
+// Strip geometry of a marching kernel (a template parameter of the marching body: each entry point names its own).
+//   MarchNarrow  120 output columns, 128 staged: one staged column per converter lane; lanes 60..63 of every blur wave
+//                idle.  The kernels that write planes (k_ref_blur, the map kernels).
+//   MarchWide    128 output columns, 136 staged: every blur-wave lane owns a column.  The converter lanes stage columns
+//                0..127 as before; the 8 columns behind them are converted six rows at a time, once per pair of barrier
+//                groups (march_convert_rows, "halo pass").  Every kernel whose partial sums k_finalize reads: the fp64
+//                part of a sum is grouped by wave and tile, so those kernels share one geometry and a pair score, a
+//                pass against the cached reference, a batch item and a 16-bit score of the same pixels keep equal bits.
+template <int W>
+struct MarchGeo {
+    static constexpr int MW = W;              // output columns per strip
+    static constexpr int MRW = W + 2 * RAD;   // staged columns (4 px halo each side)
+    static constexpr int MHALF = W / 2;       // output columns per blur wave
+    static constexpr int HALO = MRW - 128;    // staged columns behind the 128 converter lanes
+    static constexpr int RING_ROW = 3 * MRW;  // f2 elements per ring row: [channel][column]
+    static_assert(MHALF <= 64 && (HALO == 0 || HALO == 8), "two blur waves per channel, 128 converter lanes");
+};
+typedef MarchGeo<120> MarchNarrow;
+typedef MarchGeo<128> MarchWide;
 
 struct MarchPlan {
     int nscales;
@@ -667,7 +683,7 @@ struct MarchRefBlur {
     float* s11;
     int pitch;       // elements per row
     int rows_left;   // rows of this segment not loaded yet
-    bool active;     // lane owns an output column (lanes >= MHALF of a blur wave only shadow lane 0)
+    bool active;     // lane owns an output column (lanes >= MarchNarrow::MHALF of a blur wave only shadow lane 0)
     float ps11[9];  // slot = phase of the consuming step; RB_AHEAD of them are live
 };
 
@@ -762,8 +778,16 @@ __device__ __forceinline__ void march_lut(const float* lut, uint32_t d, uint32_t
 // channel.  The LUT reads therefore land under ~100 arithmetic instructions.
 // LIN0: instantiated for the kernels of march_body<MODE, true> (same code; an instantiation of their own leaves the
 // code generated for the 8-bit kernels as it was).
-template <bool U8, int MODE, bool LIN0 = false, bool BATCH = false>
-__device__ __forceinline__ void march_convert_rows(f2 (*ring)[3][MRW], const float* lut,
+// G::HALO (MarchWide): the halo pass.  Staged columns 128..135 have no converter lane of their own; wave f converts
+// them for frame f alone, six rows at a time: lane L takes row L >> 3 of the six and column 128 + (L & 7) and writes
+// the frame's 4-byte half of the ring element (lanes 48..63 repeat lanes 40..47: the same value to the same
+// address, so nothing is masked).  The pass for rows 3g .. 3g+5 runs at the head of even group g, so rows 3g+3 ..
+// 3g+5 of those columns are written one group early, into slots that held rows <= 3g-11 while the oldest row the
+// blur waves still read is 3g-8: the ring depth holds.  Its loads go out one pass (six rows) ahead, unconditional
+// and in the SGPR-base form like the others; clamping rows into the image and the zero padding sit behind uniform
+// branches that only the first and last segment and the image's last strips take.
+template <typename G, bool U8, int MODE, bool LIN0 = false, bool BATCH = false>
+__device__ __forceinline__ void march_convert_rows(f2 (*ring)[3][G::MRW], const float* lut,
                                                    const MarchPlan& plan, int sc, int w, int h, int x0,
                                                    int y0, int steps, int ngroups, int col, size_t off0 = 0,
                                                    size_t off1 = 0) {
@@ -774,7 +798,7 @@ __device__ __forceinline__ void march_convert_rows(f2 (*ring)[3][MRW], const flo
     constexpr bool LUT0 = U8 && !CACHED;  // frame 0 goes through the sRGB LUT
     const int gx = x0 - RAD + col;
     const bool col_ok = gx >= 0 && gx < w;
-    const bool all_cols = x0 - RAD >= 0 && x0 - RAD + MRW <= w;  // uniform: no lane outside the image
+    const bool all_cols = x0 - RAD >= 0 && x0 - RAD + G::MRW <= w;  // uniform: no lane outside the image
     const int gxc = min(max(gx, 0), w - 1);  // clamped: the value is discarded when gx is outside
     MarchCursor c0 = CACHED ? march_cursor<false>(plan.ref_xyb[sc], w, h, gxc)
                             : march_cursor<U8>(plan.ref[sc], w, h, gxc);
@@ -849,6 +873,85 @@ __device__ __forceinline__ void march_convert_rows(f2 (*ring)[3][MRW], const flo
         _Pragma("unroll") for (int c_ = 0; c_ < 3; ++c_)                                       \
             ring[(R) & (RING - 1)][c_][col] = f2{a_[c_], b_[c_]};                              \
     }
+    // ---- halo pass (G::HALO): this wave's frame, staged columns 128 .. 135, QD rows per pass
+    constexpr bool HALO = G::HALO > 0;
+    static_assert(!HALO || (TWO && QD * G::HALO <= 64), "halo pass: one wave per frame, one lane per row and column");
+    constexpr int HN = U8 && !CACHED ? 1 : 3;  // dwords of a halo pixel: one of a u8 frame, three of fp32 planes
+    const int hf = HALO ? __builtin_amdgcn_readfirstlane(col >> 6) : 0;  // this wave and its frame
+    const bool hcopy = CACHED && hf == 0;                                // cached XYB planes: no arithmetic
+    const bool hu8 = U8 && !hcopy;                                       // this wave's frame goes through the LUT
+    const int hrow = min((col & 63) >> 3, QD - 1), hcol = 128 + (col & 7);
+    const bool hcol_ok = x0 - RAD + hcol < w;
+    MarchCursor hc = hf ? c1 : c0;  // base, pitch, plane of the frame; the lane's offset is set below
+    uint32_t hoff = 0;              // row `hrow` of a pass, column `hcol`: loop-invariant
+    size_t hplane = 0;              // bytes between the three loads (a u8 pixel among fp32 ones: loaded three times)
+    uint32_t hnext[HN] = {};        // the next pass's pixel
+    if constexpr (HALO) {
+        const int hgxc = min(x0 - RAD + hcol, w - 1);
+        const MarchCursor at = hu8 ? march_cursor<true>(nullptr, w, h, hgxc) : march_cursor<false>(nullptr, w, h, hgxc);
+        hc.off = at.off;
+        hc.shift = at.shift;
+        hoff = (uint32_t)hrow * (uint32_t)hc.pitch + hc.off;
+        hplane = hu8 ? 0 : hc.plane;
+    }
+    // pixels of pass b (ring rows QD b .. QD b + QD - 1) into q
+    const auto halo_load = [&](uint32_t (&q)[HN], int b) {
+        const int r0 = y0 - RAD + QD * b;  // image row of the pass's first row (uniform)
+        int rbase = r0;
+        uint32_t off = hoff;
+        if (r0 < 0 || r0 + QD > h) {  // uniform; the asm keeps it a branch
+            asm volatile("; halo rows clamped into the image");
+            rbase = min(max(r0, 0), h - 1);
+            off = (uint32_t)(min(max(r0 + hrow, 0), h - 1) - rbase) * (uint32_t)hc.pitch;
+            asm volatile("" : "+v"(off));  // a 32-bit product and a 32-bit sum, not one 64-bit multiply-add
+            off += hc.off;
+        }
+        const uint8_t* p = hc.base + (size_t)(uint32_t)rbase * (uint32_t)hc.pitch;
+        asm volatile("" : "+v"(off));  // as in march_load: the zero extension stays with the loads
+        __builtin_memcpy(&q[0], p + off, 4);
+        if constexpr (HN == 3) {
+            __builtin_memcpy(&q[1], (p + hplane) + off, 4);
+            __builtin_memcpy(&q[2], (p + 2 * hplane) + off, 4);
+        }
+    };
+    // ... converted and stored: this frame's half of the ring elements
+    const auto halo_put = [&](const uint32_t (&q)[HN], int b) {
+        float v[3];
+        if (hcopy) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v[k] = __uint_as_float(q[k % HN]);
+        } else {
+            float lin[3], m[3];
+            if (hu8) {
+                march_lut(lut, q[0], hc.shift, lin);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) lin[k] = __uint_as_float(q[k % HN]);
+            }
+            opsin_mix(lin[0], lin[1], lin[2], m);
+            mixed_to_xyb<false>(m, v);
+        }
+        const int r0 = y0 - RAD + QD * b;
+        if (!(all_cols && r0 >= 0 && r0 + QD <= h)) {  // uniform; the asm keeps it a branch
+            asm volatile("; halo zero padding");
+            const bool keep = hcol_ok && (unsigned)(r0 + hrow) < (unsigned)h;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v[k] = keep ? v[k] : 0.0f;
+        }
+        float* dst = (float*)&ring[(QD * b + hrow) & (RING - 1)][0][hcol] + hf;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) dst[k * 2 * G::MRW] = v[k];
+    };
+#define MARCH_HALO(G_)                                        \
+    if constexpr (HALO) {                                     \
+        uint32_t hcur_[HN];                                   \
+        _Pragma("unroll") for (int k_ = 0; k_ < HN; ++k_) hcur_[k_] = hnext[k_]; \
+        halo_load(hnext, ((G_) >> 1) + 1);                    \
+        halo_put(hcur_, (G_) >> 1);                           \
+    }
+    // first of all loads, as in the loop a pass's load precedes the QD rows' own: the wait before its use then counts
+    // the same loads behind it on both ways into the loop
+    if constexpr (HALO) halo_load(hnext, 0);
 #pragma unroll
     for (int j = 0; j < QD; ++j) MARCH_LOAD(j)  // rows 0 .. QD-1
     MARCH_LUT(0)
@@ -858,6 +961,7 @@ __device__ __forceinline__ void march_convert_rows(f2 (*ring)[3][MRW], const flo
     // into ring slots nobody reads any more.
 #define MARCH_GROUP(G, J0)                                   \
     if ((G) * GROUP < steps) {                               \
+        if ((J0) == 0) MARCH_HALO(G) /* even groups */       \
         MARCH_PUT(J0 + 0, (G) * GROUP + 0)                   \
         MARCH_LOAD(J0 + 0)                                   \
         MARCH_PUT(J0 + 1, (G) * GROUP + 1)                   \
@@ -876,6 +980,7 @@ __device__ __forceinline__ void march_convert_rows(f2 (*ring)[3][MRW], const flo
         }
     }
 #undef MARCH_GROUP
+#undef MARCH_HALO
 #undef MARCH_LOAD
 #undef MARCH_LUT
 #undef MARCH_PUT
@@ -920,8 +1025,9 @@ struct MarchPair {
 // ds_read2_b64, which the LDS serves at half the rate of two ds_read_b64 (measured: +3 %).
 typedef __attribute__((address_space(3))) volatile unsigned long long lds_vu64;
 
+template <typename G>
 __device__ __forceinline__ const lds_vu64* march_row(const lds_vu64* rp, int t) {
-    return rp + (t & (RING - 1)) * RING_ROW;
+    return rp + (t & (RING - 1)) * G::RING_ROW;
 }
 
 // Horizontal pass of ring row t into window slot P: the lane's 9-wide window of (x, y) pairs
@@ -929,10 +1035,10 @@ __device__ __forceinline__ const lds_vu64* march_row(const lds_vu64* rp, int t) 
 // plain planes: pair sums of the taps; product planes: the products are formed inside the
 // pair sums as fma(a-, b-, a+ * b+) -- one rounding and one operation fewer than two
 // products and an add (arithmetic contract, mirrored by the CPU checker)
-template <int P, int MODE>
+template <int P, int MODE, typename G>
 __device__ __forceinline__ void march_h(const lds_vu64* rp, float (&win)[5][9], int t, float w0,
                                         float w1, float w2, float w3, float w4) {
-    const lds_vu64* row = march_row(rp, t);
+    const lds_vu64* row = march_row<G>(rp, t);
     MarchPair v[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) v[q].u = row[q];
@@ -957,7 +1063,7 @@ __device__ __forceinline__ void march_h(const lds_vu64* rp, float (&win)[5][9], 
 // Second half of step t: vertical pass and maps of output row t - 4 (window slot of row t - j
 // is (P - j) mod 9).  `edge`: the strip reaches past the image's right edge, so lanes whose
 // column is outside (`!ok`) must not contribute (uniform; interior strips skip the selects).
-template <int P, int MODE>
+template <int P, int MODE, typename G>
 __device__ __forceinline__ void march_v(const lds_vu64* rp, float (&win)[5][9], float (&acc)[6], int t,
                                         bool ok, bool edge, float w0, float w1, float w2, float w3,
                                         float w4, MarchRefBlur& rb, const float (&mc)[6]) {
@@ -988,7 +1094,7 @@ __device__ __forceinline__ void march_v(const lds_vu64* rp, float (&win)[5][9], 
         return;
     }
     MarchPair ctr;
-    ctr.u = march_row(rp, t - 4)[RAD];  // centre pixel of the output row
+    ctr.u = march_row<G>(rp, t - 4)[RAD];  // centre pixel of the output row
     const float r1 = ctr.x(), r2 = ctr.y();
     const float mu1 = v[0], mu2 = v[1];
     const float s11 = MODE == MARCH_REFBLUR ? c_s11 : v[2], s22 = v[3], s12 = v[4];
@@ -1039,11 +1145,11 @@ struct MarchItem {
 
 // LIN0: scale 0 is fp32 linear planes [3][h][w] like the smaller scales (the 16-bit front end's), not 8-bit frames.
 // BATCH: `it` says where the workgroup works; otherwise blockIdx.x does and `it` is not read.
-template <int MODE, bool LIN0 = false, bool BATCH = false>
+template <int MODE, typename G, bool LIN0 = false, bool BATCH = false>
 __device__ __forceinline__ void march_body(const MarchPlan& plan, const MapCoef* coef = nullptr,
                                            const MarchItem* it = nullptr) {
     // [row slot][channel][column] of (ref, dist) pairs
-    __shared__ __attribute__((aligned(16))) f2 s_ring[RING][3][MRW];
+    __shared__ __attribute__((aligned(16))) f2 s_ring[RING][3][G::MRW];
     __shared__ float s_lut[256];
     __shared__ double s_part[6][6];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1063,7 +1169,7 @@ __device__ __forceinline__ void march_body(const MarchPlan& plan, const MapCoef*
     const int nstrips = plan.nstrips[sc];
     const int by = blk / nstrips, bx = blk - by * nstrips;
     const bool u8 = !LIN0 && sc == 0;
-    const int x0 = bx * MW;
+    const int x0 = bx * G::MW;
     const int y0 = by * seg_rows;
     const int rows_out = min(seg_rows, h - y0);
     const int steps = rows_out + 2 * RAD;  // input rows y0-4 .. y0+rows_out+3
@@ -1079,8 +1185,8 @@ __device__ __forceinline__ void march_body(const MarchPlan& plan, const MapCoef*
     float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const int hw = wave - CONV_WAVES;
     const int ch = hw >> 1;
-    const bool hv_active = lane < MHALF;
-    const int o = (hw & 1) * MHALF + (hv_active ? lane : 0);
+    const bool hv_active = G::MHALF == 64 || lane < G::MHALF;  // MarchWide: every lane owns a column
+    const int o = (hw & 1) * G::MHALF + (hv_active ? lane : 0);
     const bool ok = x0 + o < w;
     MarchRefBlur rb;
     rb.pitch = w;
@@ -1113,25 +1219,25 @@ __device__ __forceinline__ void march_body(const MarchPlan& plan, const MapCoef*
         // on its SIMDs (profiles/r07_placement.txt), so which wave converts is left as it is.
         const int col = (wave << 6) + lane;  // staged column; this lane converts both frames
         if constexpr (BATCH) {
-            if (u8) march_convert_rows<true, MODE, LIN0, true>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col, it->off_ref, it->off_dist);
-            else march_convert_rows<false, MODE, LIN0, true>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col, it->off_ref, it->off_dist);
+            if (u8) march_convert_rows<G, true, MODE, LIN0, true>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col, it->off_ref, it->off_dist);
+            else march_convert_rows<G, false, MODE, LIN0, true>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col, it->off_ref, it->off_dist);
         } else {
-            if (u8) march_convert_rows<true, MODE, LIN0>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col);
-            else march_convert_rows<false, MODE, LIN0>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col);
+            if (u8) march_convert_rows<G, true, MODE, LIN0>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col);
+            else march_convert_rows<G, false, MODE, LIN0>(s_ring, s_lut, plan, sc, w, h, x0, y0, steps, ngroups, col);
         }
     } else {
         float win[5][9];
         const lds_vu64* rp = (const lds_vu64*)&s_ring[0][ch][o];  // staged columns o .. o+8, centre o+4
-        const bool edge = x0 + MW > w;  // uniform: some lanes of this strip are outside the image
+        const bool edge = x0 + G::MW > w;  // uniform: some lanes of this strip are outside the image
         __syncthreads();
         // step t: horizontal pass of ring row t; [barrier after the group's last row]; vertical
         // pass + maps of output row t - 4
 #define MARCH_STEP(P)                                                                          \
     {                                                                                          \
         const int t = t0 + P;                                                                  \
-        if (t < steps) march_h<P, MODE>(rp, win, t, w0, w1, w2, w3, w4);                       \
+        if (t < steps) march_h<P, MODE, G>(rp, win, t, w0, w1, w2, w3, w4);                       \
         if ((P % GROUP) == GROUP - 1 && t - (GROUP - 1) < steps) __syncthreads();              \
-        if (t < steps) march_v<P, MODE>(rp, win, acc, t, ok, edge, w0, w1, w2, w3, w4, rb, mc);    \
+        if (t < steps) march_v<P, MODE, G>(rp, win, acc, t, ok, edge, w0, w1, w2, w3, w4, rb, mc);    \
     }
 #pragma unroll 1
         for (int t0 = 0; t0 < steps; t0 += 9) {
@@ -1220,32 +1326,32 @@ __device__ __forceinline__ void march_batch_body(const MarchBatchPlan& bp) {
     it.off_ref = (size_t)item * (sc == 0 ? bp.ref_stride0 : bp.ref_stride);
     it.off_dist = (size_t)item * (sc == 0 ? bp.dist_stride0 : bp.dist_stride);
     it.off_part = (size_t)item * bp.part_stride;
-    march_body<MODE, false, true>(bp.item, nullptr, &it);
+    march_body<MODE, MarchWide, false, true>(bp.item, nullptr, &it);
 }
 
 // launch bound: 3 workgroups of 8 waves per CU = 6 waves per SIMD (<= 80 VGPRs)
 __global__ __launch_bounds__(MARCH_THREADS, 6) void k_march(MarchPlan plan) {
-    march_body<MARCH_PAIR>(plan);
+    march_body<MARCH_PAIR, MarchWide>(plan);
 }
 
 // the per-pass kernel of a search: reference XYB and blur(ref*ref) planes cached
 __global__ __launch_bounds__(MARCH_THREADS, 6) void k_march_refblur(MarchPlan plan) {
-    march_body<MARCH_REFBLUR>(plan);
+    march_body<MARCH_REFBLUR, MarchWide>(plan);
 }
 
 // once per search: blur(ref*ref) of every scale into plan.ref_s11
 __global__ __launch_bounds__(MARCH_THREADS, 6) void k_ref_blur(MarchPlan plan) {
-    march_body<MARCH_EMIT>(plan);
+    march_body<MARCH_EMIT, MarchNarrow>(plan);
 }
 
 // The same two kernels for 16-bit frames: scale 0 comes from the linear planes k_pyramid_bands16 wrote
 // (ssimu2_score_rgb16, ssimu2_score_against_reference_rgb16 / _strided16).
 __global__ __launch_bounds__(MARCH_THREADS, 6) void k_march_lin(MarchPlan plan) {
-    march_body<MARCH_PAIR, true>(plan);
+    march_body<MARCH_PAIR, MarchWide, true>(plan);
 }
 
 __global__ __launch_bounds__(MARCH_THREADS, 6) void k_march_refblur_lin(MarchPlan plan) {
-    march_body<MARCH_REFBLUR, true>(plan);
+    march_body<MARCH_REFBLUR, MarchWide, true>(plan);
 }
 
 // The batch forms of k_march and k_march_refblur: entries of their own (own register allocation; the single-score
@@ -1261,13 +1367,13 @@ __global__ __launch_bounds__(MARCH_THREADS, 6) void k_march_refblur_batch(MarchB
 // error-map pass (ssimu2_error_map_*): per-pixel densities of every scale into plan.ref_s11.  Its own entry and
 // register allocation; the score kernels above are not touched by it.
 __global__ __launch_bounds__(MARCH_THREADS, 6) void k_march_map(MarchPlan plan, MapCoef coef) {
-    march_body<MARCH_MAP>(plan, &coef);
+    march_body<MARCH_MAP, MarchNarrow>(plan, &coef);
 }
 
 // The same pass after a 16-bit score (include/ssimu2_hip_map.h): scale 0 comes from the linear planes of the two
 // frames, as in k_march_lin.  An entry of its own; k_march_map's code is what it was.
 __global__ __launch_bounds__(MARCH_THREADS, 6) void k_march_map_lin(MarchPlan plan, MapCoef coef) {
-    march_body<MARCH_MAP, true>(plan, &coef);
+    march_body<MARCH_MAP, MarchNarrow, true>(plan, &coef);
 }
 
 // The full-resolution map: map(x, y) = sum over scales s (ascending) of
