@@ -41,7 +41,8 @@ TOL_FAR_BELOW_ZERO = 5e-4   # test_extreme_frames' bound for frames that score f
 SIZES = [
     (1, 1), (7, 7), (7, 100), (100, 7), (8, 8),                  # at and below 8 px: no scale, one scale
     (15, 9), (16, 16), (112, 112), (113, 113), (127, 300),       # scale-count transitions
-    (119, 40), (120, 40), (121, 40), (241, 33),                  # FIR strip edges (120 columns)
+    (119, 40), (120, 40), (121, 40), (241, 33),                  # strip edges of k_ref_blur and the map kernels (120 columns;
+                                                                 # the summing kernels' 128: tests/wide_cases.py and its modules)
     (64, 20), (65, 21), (128, 19), (129, 41),                    # recursive tile (64 columns) and batch edges
     (333, 217), (513, 259), (1921, 1083),                        # ragged
     (9, 1000), (1000, 9), (4000, 8), (8, 4000),                  # very tall, very wide
@@ -189,7 +190,8 @@ def decoded_like(dist, channels, pad, seed):
 FINALIZE_TOL = 1e-11
 RTOL_RECURSIVE = 1e-9
 MAX_TERMS = 3840 * 2160
-MW = 120   # output columns per k_march strip (ssimu2_kernels.h)
+MW = 120        # the segment rule's column unit (kSegRuleCols) and the strip width of k_ref_blur and the map kernels
+WIDE_MW = 128   # output columns per strip of the kernels that leave partial sums (ssimu2_kernels.h, MarchWide)
 
 
 def march_seg_rows(w: int, h: int, scale: int) -> int:

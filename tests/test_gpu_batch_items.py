@@ -30,11 +30,13 @@ from hbd_cases import lift, to_depth  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 RESIDUES = list(range(1, 18)) + [31, 33]
-#                (w, h)      scales and blocks per item (batch rule: 96 rows at scale 0, 48 below; strips of 120 columns)
+#                (w, h)      scales and blocks per item (batch rule: 96 rows at scale 0, 48 below; strips of 128 columns:
+#                            tests/test_wide_cases.py asserts these counts, tests/wide_cases.py::TILES; the sizes with
+#                            three strips and with two strips at scale 1: WIDE_RESIDUE_SIZES, tests/test_gpu_wide_batch.py)
 RESIDUE_SIZES = [(24, 17),   # 3 scales of 1 block
-                 (121, 40),  # 2 strips at scale 0
-                 (241, 100),  # 3 strips x 2 segments at scale 0, 2 x 2 at scale 1 (50 rows)
-                 (130, 200)]  # 2 strips x 3 segments at scale 0, 1 x 3 at scale 1
+                 (121, 40),  # 1 strip: 4 scales of 1 block
+                 (241, 100),  # 2 strips x 2 segments at scale 0, 1 x 2 at scale 1 (50 rows)
+                 (130, 200)]  # 2 strips x 3 segments at scale 0, 1 x 3 at scale 1, 1 x 2 at scale 2
 
 
 def seed_of(w, h, n, k):
@@ -85,11 +87,12 @@ def run_batch(s, refs, dists, cached):
     return [(scores[k],) + s.last_batch_averages(k) for k in range(len(dists))]
 
 
-def check_against_singles(s, w, h, batches):
+def check_against_singles(s, w, h, batches, rows=None):
     """`batches`: [(refs, dists, cached, results of run_batch)].  Every item of every batch against the single score of
-    its pair on `s` at the batch rule's rows.  -> the single scores of the last batch."""
+    its pair on `s` at the batch rule's rows (`rows`: the rows by scale that an override of
+    ssimu2_instr_set_batch_segment_rows must give instead).  -> the single scores of the last batch."""
     rule = [s.batch_segment_rows(w, h, 0), s.batch_segment_rows(w, h, 1)]
-    assert rule == [gpu_cases.batch_seg_rows(w, h, 0), gpu_cases.batch_seg_rows(w, h, 1)]
+    assert rule == (list(rows[:2]) if rows else [gpu_cases.batch_seg_rows(w, h, 0), gpu_cases.batch_seg_rows(w, h, 1)])
     singles = []
     try:
         s.set_segment_rows(rule[0], rule[1])
@@ -157,13 +160,12 @@ def test_every_item_of_the_largest_batch(iscorer, w, h, cached):
     bits_equal(got[-1][0], avg_last, singles[-1][0], singles[-1][1], f"{w}x{h} item {n - 1} read again")
 
 
-def test_every_item_of_the_device_forms_with_an_odd_item_stride(iscorer):
-    """33 items of 121 x 40 on the device, item stride = frame + 52 bytes (no multiple of 16), noise between frames."""
+def device_forms_against_singles(s, w, h, n, gap):
+    """n items of w x h on the device, item stride = frame + `gap` bytes, noise between frames: both device forms
+    against the single scores."""
     import torch
-    s = iscorer
-    w, h, n = 121, 40, 33
     frame = w * h * 3
-    stride = frame + 52
+    stride = frame + gap
     for cached in (False, True):
         refs, dists = batch_items(w, h, n, cached)
         g = torch.Generator().manual_seed(seed_of(w, h, n, int(cached)))
@@ -181,6 +183,11 @@ def test_every_item_of_the_device_forms_with_an_odd_item_stride(iscorer):
             scores = s.score_batch_device(bufs[0].data_ptr(), bufs[1].data_ptr(), stride, n, w, h)
         got = [(scores[k],) + s.last_batch_averages(k) for k in range(n)]
         check_against_singles(s, w, h, [(refs, dists, cached, got)])
+
+
+def test_every_item_of_the_device_forms_with_an_odd_item_stride(iscorer):
+    """33 items of 121 x 40 on the device, item stride = frame + 52 bytes (no multiple of 16), noise between frames."""
+    device_forms_against_singles(iscorer, 121, 40, 33, 52)
 
 
 # ---- B. the uncached-reference fallbacks --------------------------------------------------------------------------
@@ -385,10 +392,8 @@ def to_8bit(img16, depth):
     return np.ascontiguousarray((img16.astype(np.int64) * 255 // ((1 << depth) - 1)).astype(np.uint8))
 
 
-@pytest.mark.parametrize("w,h", [(333, 217), (121, 40)])
-@pytest.mark.parametrize("depth", [10, 12, 16])
-def test_batch_against_a_16bit_reference(iscorer, oracle, depth, w, h):
-    s = iscorer
+def hold_batch_against_a_16bit_reference(s, oracle, depth, w, h):
+    """Part C at one size and depth, on the instrumented context `s`."""
     n = 9
     r16 = hbd_reference(w, h, depth, seed=seed_of(w, h, n, depth))
     low = to_8bit(r16, depth)
@@ -423,6 +428,12 @@ def test_batch_against_a_16bit_reference(iscorer, oracle, depth, w, h):
                                                               kavg=errmap_ref.averages(tm)))
     print(f"measured: batch against a {depth}-bit reference {w}x{h}: averages {worst:.3f} of batch_rtol")
     assert all(g[0] < 100.0 for g in got)
+
+
+@pytest.mark.parametrize("w,h", [(333, 217), (121, 40)])
+@pytest.mark.parametrize("depth", [10, 12, 16])
+def test_batch_against_a_16bit_reference(iscorer, oracle, depth, w, h):
+    hold_batch_against_a_16bit_reference(iscorer, oracle, depth, w, h)
 
 
 def test_an_8bit_reference_after_a_16bit_one(scorer):

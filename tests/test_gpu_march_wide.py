@@ -29,27 +29,13 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import errmap_ref  # noqa: E402
 import gpu_cases  # noqa: E402
 from gpu_cases import bits_equal, check_against_terms, check_fir_sums, in_margins  # noqa: E402
+from wide_cases import HEIGHT_ROWS, TAIL_ROWS, WIDTHS, _pair, _steps  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-WIDTHS = [120, 123, 124, 127, 128, 129, 131, 132, 135, 136,   # the right edge on every halo column
-          255, 256, 257, 260, 264,                            # two and three wide strips
-          8, 9]                                               # narrower than the halo
-HEIGHT_ROWS = [(8, 8), (9, 9), (13, 13), (26, 10), (41, 11)]
-TAIL_ROWS = 8
-
-
-def _steps(h, rows):
-    return {min(rows, h - y0) + 8 for y0 in range(0, h, rows)}
 
 
 def test_the_heights_cover_every_residue_of_the_six_row_batches():
     assert {s % 6 for h, rows in HEIGHT_ROWS for s in _steps(h, rows)} == set(range(6))
-
-
-def _pair(w, h, seed):
-    ref = gpu_cases.content(gpu_cases.KINDS[seed % 5], w, h, seed)
-    return ref, synth.distort(ref, "noise", 2, seed=seed + 1)
 
 
 def _hold(s, oracle, ref, dist, rows, what):

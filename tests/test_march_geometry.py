@@ -14,6 +14,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gpu_cases  # noqa: E402
 from ssimu2_fp64 import scale_size  # noqa: E402
+from wide_cases import nscales, plan  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WIDE, NARROW = 128, 120
@@ -24,28 +25,6 @@ PINNED_ROWS = {(3840, 2160): 135, (1921, 1083): 37, (1000, 700): 13}
 def _source(name):
     with open(os.path.join(ROOT, "oavif_amd", "csrc", name)) as f:
         return f.read()
-
-
-def nscales(w, h):
-    """make_pyramid: scale s is scored iff scale s - 1 is at least 8 x 8."""
-    n = 0
-    while n < 6 and min(scale_size(w, h, max(n - 1, 0))) >= 8:
-        n += 1
-    return n
-
-
-def plan(w, h, cols):
-    """build_plans under march_seg_rows for a kernel with strips of `cols` columns: per scale (seg, nstrips, tiles)
-    and the running block ranges."""
-    out, first = [], 0
-    for s in range(nscales(w, h)):
-        sw, sh = scale_size(w, h, s)
-        seg = gpu_cases.march_seg_rows(w, h, s)
-        nstrips = (sw + cols - 1) // cols
-        nb = nstrips * ((sh + seg - 1) // seg)
-        out.append((seg, nstrips, nb, first, first + nb))
-        first += nb
-    return out
 
 
 def tile_of_block(b, first, end):
