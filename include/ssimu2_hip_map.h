@@ -2,8 +2,8 @@
    of the score, for every kind of input the scorer takes and in every blur mode.
 
    These functions live in liboavif_hip_map.so, which is liboavif_hip_yuv.so -- the same objects, the same kernels,
-   every function of ssimu2_hip.h, oavif_tq.h, ssimu2_hip_ext.h and ssimu2_hip_yuv.h -- plus the six below.  The other
-   four libraries have none of them.
+   every function of ssimu2_hip.h, oavif_tq.h, ssimu2_hip_ext.h and ssimu2_hip_yuv.h -- plus the six below.  Of the
+   other libraries only liboavif_hip_chroma.so (ssimu2_hip_chroma.h), which is this one plus six more, has them.
 
    Definition.  The map is the map of ssimu2_hip.h ("Error map"), unchanged: per scale and channel
    the density  sum_k coef_k * term_k  over the six per-pixel terms d, d^4, art, art^4, det, det^4 (one product, then

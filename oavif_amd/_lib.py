@@ -19,6 +19,8 @@ YUV_LIB_PATH = os.environ.get("OAVIF_AMD_YUV_LIB") or os.path.join(_HERE, "lib",
 # the YUV library's objects plus the error maps of 16-bit, RGBA and YUV frames of include/ssimu2_hip_map.h
 # (Ssimu2(..., maps=True))
 MAP_LIB_PATH = os.environ.get("OAVIF_AMD_MAP_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_map.so")
+# the map library's objects plus the 4:2:2 / 4:2:0 YUV calls of include/ssimu2_hip_chroma.h (Ssimu2(..., chroma=True))
+CHROMA_LIB_PATH = os.environ.get("OAVIF_AMD_CHROMA_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_chroma.so")
 
 OK = 0
 ERR_INVALID_ARG = -1
@@ -36,6 +38,8 @@ ALPHA_CODES = 65026   # SSIMU2_ALPHA_CODES (include/ssimu2_hip_ext.h): composite
 MAX_BATCH = 4096   # SSIMU2_MAX_BATCH (include/ssimu2_hip.h): items of one ssimu2_score_batch_* call
 
 YUV_444, YUV_400 = 1, 4   # SSIMU2_YUV_* (include/ssimu2_hip_yuv.h): libavif's avifPixelFormat values
+YUV_422, YUV_420 = 2, 3   # SSIMU2_YUV_* (include/ssimu2_hip_chroma.h): subsampled chroma, the chroma library only
+CHROMA_BILINEAR, CHROMA_NEAREST = 0, 1   # SSIMU2_CHROMA_* (include/ssimu2_hip_chroma.h)
 BLUR_FIR, BLUR_RECURSIVE, BLUR_RECURSIVE_FMA = 0, 1, 2   # SSIMU2_BLUR_* (include/ssimu2_hip.h)
 
 
@@ -207,17 +211,28 @@ MAP_FUNCTIONS = {      # include/ssimu2_hip_map.h: only liboavif_hip_map.so has 
     "ssimu2_error_map_against_reference_yuv": (_ci, [_vp, _P(YuvFrameC), _u32, _f32p, _f64p]),
 }
 
+CHROMA_FUNCTIONS = {   # include/ssimu2_hip_chroma.h: only liboavif_hip_chroma.so has these
+    "ssimu2_convert_yuv_chroma": (_ci, [_vp, _P(YuvFrameC), _u32, _u32, _u32, _u32, _u16p]),
+    "ssimu2_score_yuv_chroma": (_ci, [_vp, _P(YuvFrameC), _P(YuvFrameC), _u32, _u32, _u32, _u32, _f64p]),
+    "ssimu2_set_reference_yuv_chroma": (_ci, [_vp, _P(YuvFrameC), _u32, _u32, _u32, _u32]),
+    "ssimu2_score_against_reference_yuv_chroma": (_ci, [_vp, _P(YuvFrameC), _u32, _u32, _f64p]),
+    "ssimu2_error_map_yuv_chroma": (_ci, [_vp, _P(YuvFrameC), _P(YuvFrameC), _u32, _u32, _u32, _u32, _f32p, _f64p]),
+    "ssimu2_error_map_against_reference_yuv_chroma": (_ci, [_vp, _P(YuvFrameC), _u32, _u32, _f32p, _f64p]),
+}
+
 EXPORTED_SYMBOLS = tuple(PUBLIC_FUNCTIONS)
 INSTR_SYMBOLS = tuple(HOOK_FUNCTIONS)
 EXT_SYMBOLS = tuple(EXT_FUNCTIONS)
 YUV_SYMBOLS = tuple(YUV_FUNCTIONS)
 MAP_SYMBOLS = tuple(MAP_FUNCTIONS)
+CHROMA_SYMBOLS = tuple(CHROMA_FUNCTIONS)
 
 _lib = None
 _instr = None
 _ext = None
 _yuv = None
 _map = None
+_chroma = None
 
 
 def lib() -> ctypes.CDLL:
@@ -260,6 +275,14 @@ def map_lib() -> ctypes.CDLL:
     return _map
 
 
+def chroma_lib() -> ctypes.CDLL:
+    """The chroma build (include/ssimu2_hip_chroma.h): the map library plus the calls that take 4:2:2 and 4:2:0 frames."""
+    global _chroma
+    if _chroma is None:
+        _chroma = _load(CHROMA_LIB_PATH)
+    return _chroma
+
+
 def _load(path: str) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise ImportError(
@@ -275,7 +298,7 @@ def _load(path: str) -> ctypes.CDLL:
         except Exception:
             pass
     L = ctypes.CDLL(path)
-    for table in (PUBLIC_FUNCTIONS, HOOK_FUNCTIONS, EXT_FUNCTIONS, YUV_FUNCTIONS, MAP_FUNCTIONS):
+    for table in (PUBLIC_FUNCTIONS, HOOK_FUNCTIONS, EXT_FUNCTIONS, YUV_FUNCTIONS, MAP_FUNCTIONS, CHROMA_FUNCTIONS):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name, None)   # a build older than a symbol lacks it (scripts/gpu_ab.py loads such builds)
             if fn is not None:

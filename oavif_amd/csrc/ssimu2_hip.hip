@@ -770,9 +770,10 @@ DevBuf& feed_frame(ssimu2_ctx* c, const Feed& f, bool ref) {
 }
 
 // The last row needs only its pixels, not its padding (libavif allocates rowBytes * height, a cropped view of a larger
-// buffer may not).
+// buffer may not).  A plane with a size of its own (Plane::w, Plane::h) is that many rows of that many pixels.
 size_t plane_bytes(const Feed& f, uint32_t p, uint32_t w, uint32_t h) {
-    return (size_t)f.plane[p].row_bytes * (h - 1) + (size_t)w * f.ch * f.sample;
+    const Plane& pl = f.plane[p];
+    return (size_t)pl.row_bytes * ((pl.h ? pl.h : h) - 1) + (size_t)(pl.w ? pl.w : w) * f.ch * f.sample;
 }
 
 }  // namespace

@@ -1,7 +1,7 @@
 // What a front end of the MI355X SSIMULACRA2 scorer may use of its host code: the interface between ssimu2_hip.hip
 // (which defines everything declared here but the front ends' own feed builders, marked below) and the translation
-// units that add an input form -- ssimu2_ext.hip (RGBA), ssimu2_yuv.hip (YUV) -- or a call over those forms --
-// ssimu2_map.hip (error maps of 16-bit, RGBA and YUV frames).  Private to oavif_amd/csrc: nothing here is exported,
+// units that add an input form -- ssimu2_ext.hip (RGBA), ssimu2_yuv.hip (YUV), ssimu2_chroma.hip (4:2:2 and 4:2:0
+// YUV) -- or a call over those forms -- ssimu2_map.hip (error maps of 16-bit, RGBA and YUV frames).  Private to oavif_amd/csrc: nothing here is exported,
 // and a caller sees include/*.h only.
 //
 // A front end turns a caller's frame into a Feed -- where its rows are, how they get onto the device, what kernel of
@@ -225,6 +225,7 @@ struct Fed {
 struct Plane {
     const void* px;      // the caller's rows
     uint32_t row_bytes;  // bytes between them
+    uint32_t w = 0, h = 0;  // its own size in pixels where it is not the frame's (subsampled chroma); 0 = the frame's
 };
 struct Feed {
     // The caller's frame: one plane of interleaved pixels, or up to three planes of one sample per pixel (`unpack`

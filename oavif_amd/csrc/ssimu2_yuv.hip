@@ -10,37 +10,25 @@
 // YUV.  To the host code a YUV frame is one more Feed, of three planes (yuv_feed below): the three shapes of a call --
 // score_pair, feed_reference, score_against -- are the product's.
 #include "../../include/ssimu2_hip_yuv.h"
-#include "ssimu2_div_rn.h"
 #include "ssimu2_host.h"
+#include "ssimu2_yuv_pixel.h"
 
 using namespace ssimu2h;
 
 namespace ssimu2 {
 
-// YuvK, the constants of one conversion (formed on the host: yuv_constants), is ssimu2_host.h's.
+// YuvK, the constants of one conversion (formed on the host: yuv_constants), is ssimu2_host.h's; the two halves of the
+// arithmetic -- yuv_unorm, yuv_codes -- are ssimu2_yuv_pixel.h's, shared with the subsampled formats' unit.
 
-__device__ __forceinline__ uint32_t yuv_code(float c, float top) {
-    return (uint32_t)(0.5f + fminf(fmaxf(c, 0.0f), 1.0f) * top);
-}
-
-// One pixel: the samples y, u, v -> its three codes.  Every operation rounded once (-ffp-contract=off), the three
-// divisions correctly rounded (div_rn: the divisors are 219..4095 and 0.587..0.7152, the quotients within +-1.3 -- no
-// operand needs exponent scaling).  MONO: Cb = Cr = 0, which leaves R = G = B = Y in the same bits.
+// One pixel: the samples y, u, v -> its three codes.  MONO: Cb = Cr = 0, which leaves R = G = B = Y in the same bits.
 template <bool MONO>
 __device__ __forceinline__ void yuv_pixel(uint32_t y, uint32_t u, uint32_t v, const YuvK& k, uint32_t* code) {
-    const float Y = div_rn((float)min(y, k.max_code) - k.bias_y, k.range_y);
+    const float Y = yuv_unorm(y, k.max_code, k.bias_y, k.range_y);
     if (MONO) {
         code[0] = code[1] = code[2] = yuv_code(Y, k.top);
         return;
     }
-    const float Cb = div_rn((float)min(u, k.max_code) - k.bias_uv, k.range_uv);
-    const float Cr = div_rn((float)min(v, k.max_code) - k.bias_uv, k.range_uv);
-    const float R = Y + k.r_cr * Cr;
-    const float B = Y + k.b_cb * Cb;
-    const float G = Y - div_rn(2.0f * (k.g_cr * Cr + k.g_cb * Cb), k.kg);
-    code[0] = yuv_code(R, k.top);
-    code[1] = yuv_code(G, k.top);
-    code[2] = yuv_code(B, k.top);
+    yuv_codes(Y, yuv_unorm(u, k.max_code, k.bias_uv, k.range_uv), yuv_unorm(v, k.max_code, k.bias_uv, k.range_uv), k, code);
 }
 
 // ---------------------------------------------------------------------------------------------

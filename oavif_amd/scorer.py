@@ -120,13 +120,16 @@ class YuvFrame:
     """A decoder's planes as the YUV calls take them (ssimu2_yuv_frame, include/ssimu2_hip_yuv.h): `planes` is (Y, U, V)
     for format _lib.YUV_444 or (Y,) for _lib.YUV_400, each an (h, w) array -- uint8 at depth 8, uint16 at depth 10 and
     12 -- whose rows may be any distance apart (a strided view of libavif's yuvPlanes goes through as it is; a view
-    whose samples are not adjacent within a row is copied).  `full_range` and `matrix_coefficients` are the image's
+    whose samples are not adjacent within a row is copied).  For the subsampled formats _lib.YUV_422 and _lib.YUV_420
+    (include/ssimu2_hip_chroma.h, a chroma=True context) U and V are (ch, cw) with cw = (w + 1) // 2 and ch = h (4:2:2)
+    or (h + 1) // 2 (4:2:0); `width` and `height` are plane 0's.  `full_range` and `matrix_coefficients` are the image's
     yuvRange and CICP matrix code."""
 
     def __init__(self, planes, depth: int = 8, format: int = _lib.YUV_444, full_range: bool = True,
                  matrix_coefficients: int = 6):
         self.depth, self.format = int(depth), int(format)
         self.full_range, self.matrix_coefficients = int(full_range), int(matrix_coefficients)
+        self.subsampled = self.format in (_lib.YUV_422, _lib.YUV_420)
         dtype = np.uint8 if self.depth == 8 else np.uint16
         need = 1 if self.format == _lib.YUV_400 else 3
         planes = list(planes)[:need]
@@ -137,7 +140,13 @@ class YuvFrame:
             a = np.asarray(a)
             if a.dtype != dtype:
                 raise TypeError(f"plane {k} of a {self.depth}-bit frame must be {np.dtype(dtype).name}, got {a.dtype}")
-            if a.ndim != 2 or a.shape != np.asarray(planes[0]).shape:
+            if k and self.subsampled:   # plane 0 has passed: (ch, cw) of its (h, w)
+                h0, w0 = self.planes[0].shape
+                want = ((h0 + 1) // 2 if self.format == _lib.YUV_420 else h0, (w0 + 1) // 2)
+                if a.shape != want:
+                    raise ValueError(f"plane {k} of a subsampled frame (format {self.format}) must be (ch, cw) = {want} "
+                                     f"for a {w0} x {h0} plane 0, got {a.shape}")
+            elif a.ndim != 2 or a.shape != np.asarray(planes[0]).shape:
                 raise ValueError(f"plane {k} must be (h, w) like plane 0, got {a.shape}")
             if a.strides[1] != a.itemsize or (a.shape[0] > 1 and a.strides[0] < a.shape[1] * a.itemsize):
                 a = np.ascontiguousarray(a)
@@ -223,10 +232,11 @@ class Ssimu2:
     extended = False   # bound to liboavif_hip_ext.so (the RGBA calls of include/ssimu2_hip_ext.h)
     yuv = False        # bound to liboavif_hip_yuv.so (the YUV calls of include/ssimu2_hip_yuv.h, and the RGBA calls)
     maps = False       # bound to liboavif_hip_map.so (the error maps of include/ssimu2_hip_map.h, and the RGBA and YUV calls)
+    chroma = False     # bound to liboavif_hip_chroma.so (4:2:2 / 4:2:0 frames, include/ssimu2_hip_chroma.h, and all of the above)
 
     def __init__(self, device: int = 0, stream: int | None = None, instrumented: bool = False,
                  blur: int | None = None, service: str | None = None, extended: bool = False, yuv: bool = False,
-                 maps: bool = False):
+                 maps: bool = False, chroma: bool = False):
         """`service`: socket path of a running scoring service (oavif_amd.service): the context lives there, and this
         process makes no HIP call for it (OAVIF_SCORER_SOCKET set around ssimu2_ctx_create, then restored; None = the
         environment as it is).  `instrumented=True` binds liboavif_hip_instr.so (the hooks of
@@ -240,16 +250,22 @@ class Ssimu2:
         given as well; not together with `instrumented`.  `maps=True` binds liboavif_hip_map.so: the error maps of
         16-bit, RGBA and YUV frames of include/ssimu2_hip_map.h (error_map_hbd, error_map_rgba, error_map_yuv and their
         against-reference forms); that library has the RGBA and YUV calls too, so `extended=True` / `yuv=True` may be
-        given with it; not together with `instrumented`."""
+        given with it; not together with `instrumented`.  `chroma=True` binds liboavif_hip_chroma.so: everything
+        `maps=True` has, the YUV calls included, and YuvFrames of the subsampled formats 4:2:2 and 4:2:0 in every YUV
+        method (include/ssimu2_hip_chroma.h); not together with `instrumented`."""
+        if instrumented and chroma:
+            raise ValueError("instrumented=True and chroma=True are different libraries: choose one")
         if instrumented and maps:
             raise ValueError("instrumented=True and maps=True are different libraries: choose one")
         if instrumented and extended:
             raise ValueError("instrumented=True and extended=True are different libraries: choose one")
         if instrumented and yuv:
             raise ValueError("instrumented=True and yuv=True are different libraries: choose one")
-        self.instrumented, self.extended, self.yuv, self.maps = bool(instrumented), bool(extended), bool(yuv), bool(maps)
-        self._L = (_lib.instr_lib() if instrumented else _lib.map_lib() if maps else _lib.yuv_lib() if yuv
-                   else _lib.ext_lib() if extended else _lib.lib())
+        self.chroma = bool(chroma)
+        self.instrumented, self.extended = bool(instrumented), bool(extended)
+        self.yuv, self.maps = bool(yuv or chroma), bool(maps or chroma)
+        self._L = (_lib.instr_lib() if instrumented else _lib.chroma_lib() if chroma else _lib.map_lib() if maps
+                   else _lib.yuv_lib() if yuv else _lib.ext_lib() if extended else _lib.lib())
         self._ctx = ctypes.c_void_p()
         self._holder = None
         if service is None:
@@ -531,39 +547,64 @@ class Ssimu2:
             raise TypeError(f"{name} must be a YuvFrame, got {type(frame).__name__}")
         return frame
 
-    def convert_yuv(self, frame: YuvFrame, rgb_depth: int = 16) -> np.ndarray:
-        """ssimu2_convert_yuv: the (h, w, 3) uint16 RGB codes of depth `rgb_depth` the scorer makes of `frame`."""
-        self._need_yuv()
+    _CHROMA_UPSAMPLING = {"bilinear": _lib.CHROMA_BILINEAR, "nearest": _lib.CHROMA_NEAREST}
+
+    def _chroma_args(self, chroma_upsampling, *frames) -> tuple:
+        """What follows `rgb_depth` in a YUV call: nothing on a context of another library (which refuses a subsampled
+        frame here, before any C call), the upsampling code on a chroma=True context, whose calls take it."""
+        try:
+            up = self._CHROMA_UPSAMPLING[chroma_upsampling]
+        except (KeyError, TypeError):
+            raise ValueError(f"chroma_upsampling must be 'bilinear' or 'nearest', got {chroma_upsampling!r}") from None
+        if not self.chroma and any(f.subsampled for f in frames):
+            raise Ssimu2Error(_lib.ERR_UNSUPPORTED, "subsampled chroma (4:2:2 / 4:2:0) needs Ssimu2(..., chroma=True) "
+                                                    "(liboavif_hip_chroma.so)")
+        return (up,) if self.chroma else ()
+
+    def _yuv_fn(self, name: str):
+        """The C function of a YUV method: ssimu2_<name>, or on a chroma=True context ssimu2_<name>_chroma."""
+        return getattr(self._L, f"ssimu2_{name}_chroma" if self.chroma else f"ssimu2_{name}")
+
+    def convert_yuv(self, frame: YuvFrame, rgb_depth: int = 16, chroma_upsampling: str = "bilinear") -> np.ndarray:
+        """ssimu2_convert_yuv: the (h, w, 3) uint16 RGB codes of depth `rgb_depth` the scorer makes of `frame`.
+        `chroma_upsampling` ("bilinear" or "nearest", here and in the other YUV methods) is how a 4:2:2 or 4:2:0
+        frame's chroma is upsampled (include/ssimu2_hip_chroma.h); a 4:4:4 or 4:0:0 frame does not depend on it."""
         f = self._yuv_frame(frame, "frame")
+        up = self._chroma_args(chroma_upsampling, f)
+        self._need_yuv()
         out = np.empty((f.height, f.width, 3), np.uint16)
         c = f.as_c()
-        self._call(self._L.ssimu2_convert_yuv, ctypes.byref(c), f.width, f.height, int(rgb_depth), _u16p(out))
+        self._call(self._yuv_fn("convert_yuv"), ctypes.byref(c), f.width, f.height, int(rgb_depth), *up, _u16p(out))
         return out
 
-    def compute_ssimu2_yuv(self, ref: YuvFrame, dist: YuvFrame, rgb_depth: int = 16) -> float:
-        """ssimu2_score_yuv: two YUV frames of one size, each converted with its own depth, range and matrix."""
-        self._need_yuv()
+    def compute_ssimu2_yuv(self, ref: YuvFrame, dist: YuvFrame, rgb_depth: int = 16,
+                           chroma_upsampling: str = "bilinear") -> float:
+        """ssimu2_score_yuv: two YUV frames of one size, each converted with its own format, depth, range and matrix."""
         r, d = self._yuv_frame(ref, "ref"), self._yuv_frame(dist, "dist")
+        up = self._chroma_args(chroma_upsampling, r, d)
+        self._need_yuv()
         if (r.height, r.width) != (d.height, d.width):
             raise ValueError("ref and dist must have the same shape")
         cr, cd = r.as_c(), d.as_c()
-        return self._score(self._L.ssimu2_score_yuv, ctypes.byref(cr), ctypes.byref(cd), r.width, r.height, int(rgb_depth))
+        return self._score(self._yuv_fn("score_yuv"), ctypes.byref(cr), ctypes.byref(cd), r.width, r.height, int(rgb_depth), *up)
 
-    def set_reference_yuv(self, ref: YuvFrame, rgb_depth: int = 16) -> None:
+    def set_reference_yuv(self, ref: YuvFrame, rgb_depth: int = 16, chroma_upsampling: str = "bilinear") -> None:
         """ssimu2_set_reference_yuv; later 8-bit, 16-bit and YUV frames can all be scored against it."""
-        self._need_yuv()
         r = self._yuv_frame(ref, "ref")
+        up = self._chroma_args(chroma_upsampling, r)
+        self._need_yuv()
         c = r.as_c()
-        self._call(self._L.ssimu2_set_reference_yuv, ctypes.byref(c), r.width, r.height, int(rgb_depth))
+        self._call(self._yuv_fn("set_reference_yuv"), ctypes.byref(c), r.width, r.height, int(rgb_depth), *up)
         self._ref_shape = (r.height, r.width, 3)
 
-    def score_against_reference_yuv(self, frame: YuvFrame, rgb_depth: int = 16) -> float:
+    def score_against_reference_yuv(self, frame: YuvFrame, rgb_depth: int = 16, chroma_upsampling: str = "bilinear") -> float:
         """ssimu2_score_against_reference_yuv against the reference of any set_reference* call."""
-        self._need_yuv()
         f = self._yuv_frame(frame, "frame")
+        up = self._chroma_args(chroma_upsampling, f)
+        self._need_yuv()
         self._check_ref_shape((f.height, f.width), "frame size")
         c = f.as_c()
-        return self._score(self._L.ssimu2_score_against_reference_yuv, ctypes.byref(c), int(rgb_depth))
+        return self._score(self._yuv_fn("score_against_reference_yuv"), ctypes.byref(c), int(rgb_depth), *up)
 
     # -- error maps of 16-bit, RGBA and YUV frames (include/ssimu2_hip_map.h, DESIGN.md section 15): the map library only
     def _need_maps(self):
@@ -615,23 +656,25 @@ class Ssimu2:
         row_bytes = (a.strides[0] if h > 1 else 4 * w) if row_bytes is None else row_bytes
         return self._map(self._L.ssimu2_error_map_against_reference_rgba8, h, w, _u8p(a), int(row_bytes))
 
-    def error_map_yuv(self, ref: YuvFrame, dist: YuvFrame, rgb_depth: int = 16):
+    def error_map_yuv(self, ref: YuvFrame, dist: YuvFrame, rgb_depth: int = 16, chroma_upsampling: str = "bilinear"):
         """ssimu2_error_map_yuv -> (score, map) of two YUV frames of one size, converted to codes of `rgb_depth` bits."""
-        self._need_maps()
         r, d = self._yuv_frame(ref, "ref"), self._yuv_frame(dist, "dist")
+        up = self._chroma_args(chroma_upsampling, r, d)
+        self._need_maps()
         if (r.height, r.width) != (d.height, d.width):
             raise ValueError("ref and dist must have the same shape")
         cr, cd = r.as_c(), d.as_c()
-        return self._map(self._L.ssimu2_error_map_yuv, r.height, r.width, ctypes.byref(cr), ctypes.byref(cd), r.width,
-                         r.height, int(rgb_depth))
+        return self._map(self._yuv_fn("error_map_yuv"), r.height, r.width, ctypes.byref(cr), ctypes.byref(cd), r.width,
+                         r.height, int(rgb_depth), *up)
 
-    def error_map_against_reference_yuv(self, frame: YuvFrame, rgb_depth: int = 16):
+    def error_map_against_reference_yuv(self, frame: YuvFrame, rgb_depth: int = 16, chroma_upsampling: str = "bilinear"):
         """ssimu2_error_map_against_reference_yuv -> (score, map) against the reference of any set_reference* call."""
-        self._need_maps()
         f = self._yuv_frame(frame, "frame")
+        up = self._chroma_args(chroma_upsampling, f)
+        self._need_maps()
         self._check_ref_shape((f.height, f.width), "frame size")
         c = f.as_c()
-        return self._map(self._L.ssimu2_error_map_against_reference_yuv, f.height, f.width, ctypes.byref(c), int(rgb_depth))
+        return self._map(self._yuv_fn("error_map_against_reference_yuv"), f.height, f.width, ctypes.byref(c), int(rgb_depth), *up)
 
     # -- device-resident entry points (pointers are raw device addresses) -------------------
     # The per-frame ones make their C call in their own body, not through _call / _score / _scores: a 512x512 score is

@@ -1,8 +1,9 @@
 """SSIMULACRA2 of an AVIF from the decoder's own Y, U and V planes, converted to RGB on the device with the exact colour
-matrix at full precision (include/ssimu2_hip_yuv.h).
+matrix at full precision (include/ssimu2_hip_yuv.h); a 4:2:0 or 4:2:2 file's chroma is upsampled
+there too, as libavif's built-in converter does it (include/ssimu2_hip_chroma.h, section 16).
 
     python -m oavif_amd.yuvscore REF.png|REF.avif DIST.avif [--rgb-depth N] [--blur fir|recursive|recursive_fma] [--compare]
-                                 [--map OUT.png|.pam|.pfm]
+                                 [--map OUT.png|.pam|.pfm] [--chroma-upsampling bilinear|nearest]
 
 prints the score of DIST against REF through the YUV path; `--map` also writes where DIST is damaged, the error map of
 that very score (ssimu2_error_map_against_reference_yuv, include/ssimu2_hip_map.h), in errmap's formats.  A PNG reference is taken as 8-bit RGB (alpha dropped, 16
@@ -46,6 +47,8 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--map", default=None, metavar="OUT",
                     help="also write the error map of the YUV-path score: OUT.pfm (float), .pam or .png (8-bit, "
                          "normalised to the maximum), as python -m oavif_amd.errmap writes it")
+    ap.add_argument("--chroma-upsampling", choices=("bilinear", "nearest"), default="bilinear",
+                    help="how the chroma of a 4:2:0 or 4:2:2 file is upsampled (default bilinear: libavif's automatic choice)")
     return ap
 
 
@@ -66,8 +69,8 @@ def frame_of(decoded) -> YuvFrame:
     not convert."""
     if decoded.has_alpha:
         raise ValueError("the image has an alpha plane: score it with python -m oavif_amd.alpha")
-    if decoded.format not in (_lib.YUV_444, _lib.YUV_400):
-        raise ValueError("subsampled chroma (4:2:0 / 4:2:2) is not converted on the device")
+    if decoded.format not in (_lib.YUV_444, _lib.YUV_422, _lib.YUV_420, _lib.YUV_400):
+        raise ValueError(f"pixel format {decoded.format} is not converted on the device")
     if decoded.matrix_coefficients not in MATRIX_COEFFICIENTS:
         raise ValueError(f"matrix coefficients {decoded.matrix_coefficients} are not converted on the device")
     return YuvFrame(decoded.planes, decoded.depth, decoded.format, decoded.full_range, decoded.matrix_coefficients)
@@ -78,23 +81,23 @@ def main(argv=None) -> int:
     from . import avif_bridge as ab, cli
     try:
         dist_data = open(a.dist, "rb").read()
-        with Ssimu2(a.device, blur=BLUR_MODES[a.blur], yuv=True, maps=a.map is not None) as s, \
+        with Ssimu2(a.device, blur=BLUR_MODES[a.blur], chroma=True) as s, \
                 ab.decode_yuv(dist_data) as dist:
             if a.ref.lower().endswith(".avif"):
                 with ab.decode_yuv(open(a.ref, "rb").read()) as ref:
                     if (ref.width, ref.height) != (dist.width, dist.height):
                         raise ValueError(f"{a.ref} is {ref.width}x{ref.height}, {a.dist} is {dist.width}x{dist.height}")
-                    s.set_reference_yuv(frame_of(ref), a.rgb_depth)
+                    s.set_reference_yuv(frame_of(ref), a.rgb_depth, a.chroma_upsampling)
             else:
                 rgb = cli.load_source(a.ref).rgb
                 if rgb.shape[:2] != (dist.height, dist.width):
                     raise ValueError(f"{a.ref} is {rgb.shape[1]}x{rgb.shape[0]}, {a.dist} is {dist.width}x{dist.height}")
                 s.set_reference(rgb)
             if a.map is None:
-                print(f"yuv {s.score_against_reference_yuv(frame_of(dist), a.rgb_depth):.6f}")
+                print(f"yuv {s.score_against_reference_yuv(frame_of(dist), a.rgb_depth, a.chroma_upsampling):.6f}")
             else:
                 from . import errmap
-                score, m = s.error_map_against_reference_yuv(frame_of(dist), a.rgb_depth)
+                score, m = s.error_map_against_reference_yuv(frame_of(dist), a.rgb_depth, a.chroma_upsampling)
                 data, peak = errmap.encode(m, os.path.splitext(a.map)[1].lower())
                 with open(a.map, "wb") as f:
                     f.write(data)
