@@ -4,8 +4,8 @@
 
    These functions live in liboavif_hip_chroma.so, which is liboavif_hip_map.so -- the same objects, the same kernels,
    every function of ssimu2_hip.h, oavif_tq.h, ssimu2_hip_ext.h, ssimu2_hip_yuv.h and ssimu2_hip_map.h -- plus the six
-   below.  The other five libraries have none of them, and the calls of ssimu2_hip_yuv.h and ssimu2_hip_map.h go on
-   refusing formats 2 and 3.
+   below.  Of the other libraries only liboavif_hip_yuva.so, built on this one, has them, and the calls of
+   ssimu2_hip_yuv.h and ssimu2_hip_map.h go on refusing formats 2 and 3.
 
    Definition (the library's own, exact; it extends ssimu2_hip_yuv.h's, whose constants and names are used here).
    A subsampled frame's planes 1 and 2 are cw x ch samples:

@@ -21,6 +21,9 @@ YUV_LIB_PATH = os.environ.get("OAVIF_AMD_YUV_LIB") or os.path.join(_HERE, "lib",
 MAP_LIB_PATH = os.environ.get("OAVIF_AMD_MAP_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_map.so")
 # the map library's objects plus the 4:2:2 / 4:2:0 YUV calls of include/ssimu2_hip_chroma.h (Ssimu2(..., chroma=True))
 CHROMA_LIB_PATH = os.environ.get("OAVIF_AMD_CHROMA_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_chroma.so")
+# the chroma library's objects plus the calls of include/ssimu2_hip_yuva.h that take YUV planes with an alpha plane
+# (Ssimu2(..., yuva=True))
+YUVA_LIB_PATH = os.environ.get("OAVIF_AMD_YUVA_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_yuva.so")
 
 OK = 0
 ERR_INVALID_ARG = -1
@@ -98,6 +101,12 @@ class YuvFrameC(ctypes.Structure):
     """ssimu2_yuv_frame (include/ssimu2_hip_yuv.h)."""
     _fields_ = [("planes", ctypes.c_void_p * 3), ("row_bytes", ctypes.c_uint32 * 3), ("depth", ctypes.c_uint32),
                 ("format", ctypes.c_uint32), ("full_range", ctypes.c_uint32), ("matrix_coefficients", ctypes.c_uint32)]
+
+
+class YuvaFrameC(ctypes.Structure):
+    """ssimu2_yuva_frame (include/ssimu2_hip_yuva.h)."""
+    _fields_ = [("yuv", YuvFrameC), ("alpha", ctypes.c_void_p), ("alpha_row_bytes", ctypes.c_uint32),
+                ("alpha_premultiplied", ctypes.c_uint32)]
 
 
 class TQSpecStats(ctypes.Structure):
@@ -220,12 +229,22 @@ CHROMA_FUNCTIONS = {   # include/ssimu2_hip_chroma.h: only liboavif_hip_chroma.s
     "ssimu2_error_map_against_reference_yuv_chroma": (_ci, [_vp, _P(YuvFrameC), _u32, _u32, _f32p, _f64p]),
 }
 
+YUVA_FUNCTIONS = {     # include/ssimu2_hip_yuva.h: only liboavif_hip_yuva.so has these
+    "ssimu2_composite_yuva": (_ci, [_vp, _P(YuvaFrameC), _u32, _u32, _u32, _u32, _u32, _u16p]),
+    "ssimu2_score_yuva": (_ci, [_vp, _P(YuvaFrameC), _P(YuvaFrameC), _u32, _u32, _u32, _u32, _u32, _f64p]),
+    "ssimu2_set_reference_yuva": (_ci, [_vp, _P(YuvaFrameC), _u32, _u32, _u32, _u32, _u32]),
+    "ssimu2_score_against_reference_yuva": (_ci, [_vp, _P(YuvaFrameC), _u32, _u32, _f64p]),
+    "ssimu2_error_map_yuva": (_ci, [_vp, _P(YuvaFrameC), _P(YuvaFrameC), _u32, _u32, _u32, _u32, _u32, _f32p, _f64p]),
+    "ssimu2_error_map_against_reference_yuva": (_ci, [_vp, _P(YuvaFrameC), _u32, _u32, _f32p, _f64p]),
+}
+
 EXPORTED_SYMBOLS = tuple(PUBLIC_FUNCTIONS)
 INSTR_SYMBOLS = tuple(HOOK_FUNCTIONS)
 EXT_SYMBOLS = tuple(EXT_FUNCTIONS)
 YUV_SYMBOLS = tuple(YUV_FUNCTIONS)
 MAP_SYMBOLS = tuple(MAP_FUNCTIONS)
 CHROMA_SYMBOLS = tuple(CHROMA_FUNCTIONS)
+YUVA_SYMBOLS = tuple(YUVA_FUNCTIONS)
 
 _lib = None
 _instr = None
@@ -233,6 +252,7 @@ _ext = None
 _yuv = None
 _map = None
 _chroma = None
+_yuva = None
 
 
 def lib() -> ctypes.CDLL:
@@ -283,6 +303,14 @@ def chroma_lib() -> ctypes.CDLL:
     return _chroma
 
 
+def yuva_lib() -> ctypes.CDLL:
+    """The alpha-plane build (include/ssimu2_hip_yuva.h): the chroma library plus the calls that take Y, U, V and A planes."""
+    global _yuva
+    if _yuva is None:
+        _yuva = _load(YUVA_LIB_PATH)
+    return _yuva
+
+
 def _load(path: str) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise ImportError(
@@ -298,7 +326,8 @@ def _load(path: str) -> ctypes.CDLL:
         except Exception:
             pass
     L = ctypes.CDLL(path)
-    for table in (PUBLIC_FUNCTIONS, HOOK_FUNCTIONS, EXT_FUNCTIONS, YUV_FUNCTIONS, MAP_FUNCTIONS, CHROMA_FUNCTIONS):
+    for table in (PUBLIC_FUNCTIONS, HOOK_FUNCTIONS, EXT_FUNCTIONS, YUV_FUNCTIONS, MAP_FUNCTIONS, CHROMA_FUNCTIONS,
+                  YUVA_FUNCTIONS):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name, None)   # a build older than a symbol lacks it (scripts/gpu_ab.py loads such builds)
             if fn is not None:

@@ -43,9 +43,9 @@ _RESULT_OK = 0
 # offsets into the public structs of libavif 1.x (x86-64); verified by _check_layout()
 _IMG_WIDTH, _IMG_HEIGHT, _IMG_DEPTH, _IMG_YUVFORMAT, _IMG_YUVRANGE = 0, 4, 8, 12, 16
 _IMG_YUVPLANES, _IMG_YUVROWBYTES, _IMG_OWNSYUV = 24, 48, 60   # uint8_t* [3], uint32_t [3], avifBool
-_IMG_ALPHAPLANE = 64
+_IMG_ALPHAPLANE, _IMG_ALPHAROWBYTES, _IMG_OWNSALPHA, _IMG_ALPHAPREMULTIPLIED = 64, 72, 76, 80   # uint8_t*, uint32_t, avifBool x 2
 _PIXEL_FORMAT_YUV400 = 4
-_PLANES_YUV = 1
+_PLANES_YUV, _PLANES_A = 1, 2
 _IMG_ICC = 88               # avifRWData {data, size}
 _IMG_CP, _IMG_TC, _IMG_MC = 104, 106, 108   # uint16_t each
 _RGB_SIZE = 64
@@ -178,6 +178,18 @@ def _check_layout(L) -> Optional[str]:
         planes, rows, owns = yuv()
         if not all(planes) or len(set(planes)) != 3 or rows != [24 * 2] * 3 or owns != 1 or _ptr(im, _IMG_ALPHAPLANE) != 0:
             return f"avifImage.yuvPlanes / yuvRowBytes ({planes}, {rows}, {owns}) are not where the 1.x layout puts them"
+        # alphaPlane / alphaRowBytes / imageOwnsAlphaPlane / alphaPremultiplied (decode_yuv reads three of them)
+        alpha = lambda: (_ptr(im, _IMG_ALPHAPLANE), _u32(im, _IMG_ALPHAROWBYTES), _u32(im, _IMG_OWNSALPHA),
+                         _u32(im, _IMG_ALPHAPREMULTIPLIED))
+        if alpha() != (0, 0, 0, 0):
+            return f"avifImage alpha fields {alpha()} of an image without alpha do not match the 1.x layout"
+        if L.avifImageAllocatePlanes(im, _PLANES_A) != _RESULT_OK:
+            return "avifImageAllocatePlanes (alpha) failed"
+        a_ptr, a_row, a_owns, a_pre = alpha()
+        # (a pointer read one field late would be the two words rowBytes | owns << 32)
+        if not a_ptr or a_ptr in planes or a_ptr == (24 * 2 | 1 << 32) or a_row != 24 * 2 or a_owns != 1 or a_pre != 0 \
+                or yuv() != (planes, rows, owns):
+            return f"avifImage.alphaPlane / alphaRowBytes ({a_ptr:#x}, {a_row}, {a_owns}, {a_pre}) are not where the 1.x layout puts them"
         icc = b"layout-check"
         if L.avifImageSetProfileICC(im, icc, len(icc)) != _RESULT_OK:
             return "avifImageSetProfileICC failed"
@@ -298,7 +310,10 @@ class EncoderSource:
     hoist of SURVEY.md 8f rank 4 taken one step further.  encode() only reads the image, so the probes of a
     speculative search may encode from one EncoderSource on several threads at once."""
 
-    def __init__(self, scaled: np.ndarray, out_depth: int, o, icc: Optional[bytes] = None):
+    def __init__(self, scaled: np.ndarray, out_depth: int, o, icc: Optional[bytes] = None,
+                 yuv_format: int = _PIXEL_FORMAT_YUV444):
+        """`yuv_format`: the avifPixelFormat of the image (1 = 4:4:4, the reference's; 2 = 4:2:2 and 3 = 4:2:0 for tests
+        and measurements of the subsampled scorer inputs)."""
         L = self._L = _lib()
         self._image = None
         if scaled.ndim != 3 or scaled.shape[2] not in (3, 4):
@@ -310,7 +325,9 @@ class EncoderSource:
         scaled = np.ascontiguousarray(scaled)
         h, w, ch = scaled.shape
         self.width, self.height, self.channels, self.depth = w, h, ch, out_depth
-        image = L.avifImageCreate(w, h, out_depth, _PIXEL_FORMAT_YUV444)
+        if yuv_format not in (1, 2, 3):
+            raise AvifBridgeError("ConvertFailed", f"yuv_format {yuv_format}")
+        image = L.avifImageCreate(w, h, out_depth, int(yuv_format))
         if not image:
             raise AvifBridgeError("OutOfMemory")
         try:
@@ -382,13 +399,14 @@ class EncoderSource:
         self.close()
 
 
-def encode(scaled: np.ndarray, out_depth: int, o, q: int, icc: Optional[bytes] = None) -> bytes:
+def encode(scaled: np.ndarray, out_depth: int, o, q: int, icc: Optional[bytes] = None,
+           yuv_format: int = _PIXEL_FORMAT_YUV444) -> bytes:
     """io.encodeAvifToBuffer (io.zig:544-636) as the reference runs it: image, conversion and encode in one
     call.  `scaled` = prescale_source(pixels, out_depth): (h, w, 3|4), uint8 for an 8-bit encode, uint16
     holding 10-bit values for a 10-bit one.  `o` carries the fields of AvifEncOptions that copyToEncoder reads
     (parse_args.zig:65-74) plus the CICP triple.  Callers that encode one source many times keep an
     EncoderSource instead."""
-    with EncoderSource(scaled, out_depth, o, icc) as src:
+    with EncoderSource(scaled, out_depth, o, icc, yuv_format) as src:
         return src.encode(o, q)
 
 
@@ -490,7 +508,9 @@ class DecodedYuv:
     open until then).  `planes`: (h, w) arrays, uint8 at depth 8 and uint16 above, rows yuvRowBytes apart -- three for
     4:4:4, one for 4:0:0, subsampled chroma planes at their own size; `format` is libavif's avifPixelFormat
     (1 = 4:4:4 ... 4 = 4:0:0), `full_range` its yuvRange, `matrix_coefficients` the CICP code.  `has_alpha`: the image
-    has an alpha plane too, which is not handed out: such frames go through decode_common."""
+    has an alpha plane too: `alpha` is its (h, w) view (the sample type of the planes, rows `alpha_row_bytes` apart;
+    None for an opaque image) and `alpha_premultiplied` the image's flag -- what include/ssimu2_hip_yuva.h's frame
+    takes (scorer.YuvFrame(..., alpha=, alpha_premultiplied=))."""
 
     def __init__(self, L, dec, img):
         self._L, self._dec = L, dec
@@ -510,10 +530,18 @@ class DecodedYuv:
             rows = np.ctypeslib.as_array((sample * (row // size * h)).from_address(ptr)).reshape(h, row // size)
             self.planes.append(rows[:, :w])
             self.row_bytes.append(row)
+        self.alpha, self.alpha_row_bytes = None, 0
+        self.alpha_premultiplied = _u32(img, _IMG_ALPHAPREMULTIPLIED) != 0
+        if self.has_alpha:
+            ptr, row = _ptr(img, _IMG_ALPHAPLANE), _u32(img, _IMG_ALPHAROWBYTES)
+            if row < self.width * size or row % size:
+                raise AvifBridgeError("DecodeImageFailed", f"alpha plane: pointer {ptr:#x}, rowBytes {row}")
+            rows = np.ctypeslib.as_array((sample * (row // size * self.height)).from_address(ptr)).reshape(self.height, row // size)
+            self.alpha, self.alpha_row_bytes = rows[:, :self.width], row
 
     def close(self) -> None:
         if getattr(self, "_dec", None) is not None:
-            self.planes = None
+            self.planes = self.alpha = None
             self._L.avifDecoderDestroy(self._dec)
             self._dec = None
 

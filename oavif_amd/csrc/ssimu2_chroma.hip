@@ -3,7 +3,8 @@
 //
 // A translation unit of its own over ssimu2_host.h, like the RGBA, YUV and map units: one kernel template, one Feed
 // constructor, one check and six functions.  Its object is linked with the map library's objects into
-// liboavif_hip_chroma.so; the other five libraries contain none of this, and their exports are what they were.
+// liboavif_hip_chroma.so (and liboavif_hip_yuva.so on top of it); the other five libraries contain none of this, and
+// their exports are what they were.
 //
 // A 4:2:2 or 4:2:0 frame is a YUV Feed (yuv_feed: the one yuv_constants) whose planes 1 and 2 carry their own size
 // (Plane::w, Plane::h), so that only cw x ch samples of each leave the caller's memory, and whose unpacking is
@@ -17,32 +18,8 @@ using namespace ssimu2h;
 
 namespace ssimu2 {
 
-// Sample `c` of a plane row of S-byte samples (2-byte aligned for S = 2).
-template <int S>
-__device__ __forceinline__ uint32_t sample_at(const uint8_t* row, uint32_t c) {
-    if (S == 1) return row[c];
-    uint16_t one;
-    __builtin_memcpy(&one, row + 2u * c, 2);
-    return one;
-}
-
-// N (2 or 4) adjacent samples of a plane row from `p` on, in one load of 2 bytes, one dword or two.
-template <int S, int N>
-__device__ __forceinline__ void samples_at(const uint8_t* p, uint32_t* out) {
-    if constexpr (S * N == 2) {
-        uint16_t two;
-        __builtin_memcpy(&two, p, 2);
-        out[0] = two & 0xFFu;
-        out[1] = two >> 8;
-    } else {
-        uint32_t v[S * N / 4];
-#pragma unroll
-        for (int k = 0; k < S * N / 4; ++k) __builtin_memcpy(&v[k], p + 4 * k, 4);
-#pragma unroll
-        for (int i = 0; i < N; ++i)
-            out[i] = S == 1 ? (v[0] >> (8 * i)) & 0xFFu : (v[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
-    }
-}
+// sample_at, samples_at (a plane row's samples in one load) and chroma_blend are ssimu2_yuv_pixel.h's, shared with the
+// alpha unit.
 
 // ---------------------------------------------------------------------------------------------
 // Planes of S-byte samples -- Y of w x h, U and V of cw x ch (cw = (w + 1) / 2; V: ch = (h + 1) / 2, 4:2:0; else
@@ -111,8 +88,8 @@ __global__ __launch_bounds__(256) void k_yuv_chroma_to_codes(const uint8_t* __re
                 const int lc = LC + (i >> 1), ln = BILINEAR ? ((i & 1) ? lc + 1 : lc - 1) : lc;
                 float Cb = cb[QC][lc], Cr = cr[QC][lc];
                 if (BILINEAR) {
-                    Cb = ((cb[QC][lc] * 0.5625f + cb[QC][ln] * 0.1875f) + cb[qn][lc] * 0.1875f) + cb[qn][ln] * 0.0625f;
-                    Cr = ((cr[QC][lc] * 0.5625f + cr[QC][ln] * 0.1875f) + cr[qn][lc] * 0.1875f) + cr[qn][ln] * 0.0625f;
+                    Cb = chroma_blend(cb[QC][lc], cb[QC][ln], cb[qn][lc], cb[qn][ln]);
+                    Cr = chroma_blend(cr[QC][lc], cr[QC][ln], cr[qn][lc], cr[qn][ln]);
                 }
                 yuv_codes(yuv_unorm(y, k.max_code, k.bias_y, k.range_y), Cb, Cr, k, code);
             };
@@ -159,18 +136,15 @@ using namespace ssimu2;
 
 namespace {
 
-// What the unpacking of a frame needs beyond the planes.  `yuv` comes first: a 4:4:4 or 4:0:0 frame's Feed::aux points
-// at it, for yuv_feed's own unpacking.
-struct ChromaAux {
-    YuvAux yuv;
-    bool vertical, bilinear;
-};
+// ChromaAux, what the unpacking of a frame needs beyond the planes, is ssimu2_host.h's.
 
 bool subsampled(uint32_t format) { return format == SSIMU2_YUV_422 || format == SSIMU2_YUV_420; }
 
+}  // namespace
+
 // Argument checks of one frame for a w x h call (the ctx is not null): check_yuv's, with formats 2 and 3 let through
 // and their chroma planes held to cw samples per row.
-int check_chroma(ssimu2_ctx* c, const ssimu2_yuv_frame* f, uint32_t w, uint32_t rgb_depth, uint32_t upsampling) {
+int ssimu2h::check_chroma(ssimu2_ctx* c, const ssimu2_yuv_frame* f, uint32_t w, uint32_t rgb_depth, uint32_t upsampling) {
     if (upsampling > SSIMU2_CHROMA_NEAREST) return c->fail(SSIMU2_ERR_INVALID_ARG, "chroma_upsampling must be 0 (bilinear) or 1 (nearest)");
     if (!f || !subsampled(f->format)) {
         if (f && f->format != SSIMU2_YUV_444 && f->format != SSIMU2_YUV_400)
@@ -192,6 +166,8 @@ int check_chroma(ssimu2_ctx* c, const ssimu2_yuv_frame* f, uint32_t w, uint32_t 
     return SSIMU2_OK;
 }
 
+namespace {
+
 // The planes in `stage` (plane_off, each with its own size) -> the tight u16 frame of codes `dst`.
 void convert(ssimu2_ctx* c, const Feed& f, uint32_t w, uint32_t h, void* dst) {
     const ChromaAux& a = *(const ChromaAux*)f.aux;
@@ -211,8 +187,12 @@ void convert(ssimu2_ctx* c, const Feed& f, uint32_t w, uint32_t h, void* dst) {
            f.plane[1].row_bytes, f.plane[2].row_bytes, w, h, a.yuv.k, (uint16_t*)dst);
 }
 
+}  // namespace
+
 // One frame of any of the four formats in host memory, for a w x h call.  `aux` outlives the call.
-Feed chroma_feed(const ssimu2_yuv_frame& f, uint32_t w, uint32_t h, uint32_t rgb_depth, uint32_t upsampling, ChromaAux* aux) {
+Feed ssimu2h::chroma_feed(const ssimu2_yuv_frame& f, uint32_t w, uint32_t h, uint32_t rgb_depth, uint32_t upsampling,
+                          ChromaAux* aux) {
+    aux->vertical = aux->bilinear = false;
     if (!subsampled(f.format)) return yuv_feed(f, rgb_depth, &aux->yuv);
     ssimu2_yuv_frame full = f;  // three planes and the constants, as of a 4:4:4 frame
     full.format = SSIMU2_YUV_444;
@@ -227,8 +207,6 @@ Feed chroma_feed(const ssimu2_yuv_frame& f, uint32_t w, uint32_t h, uint32_t rgb
     feed.aux = aux;
     return feed;
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -1,7 +1,7 @@
 // What a front end of the MI355X SSIMULACRA2 scorer may use of its host code: the interface between ssimu2_hip.hip
 // (which defines everything declared here but the front ends' own feed builders, marked below) and the translation
 // units that add an input form -- ssimu2_ext.hip (RGBA), ssimu2_yuv.hip (YUV), ssimu2_chroma.hip (4:2:2 and 4:2:0
-// YUV) -- or a call over those forms -- ssimu2_map.hip (error maps of 16-bit, RGBA and YUV frames).  Private to oavif_amd/csrc: nothing here is exported,
+// YUV), ssimu2_yuva.hip (YUV with an alpha plane) -- or a call over those forms -- ssimu2_map.hip (error maps of 16-bit, RGBA and YUV frames).  Private to oavif_amd/csrc: nothing here is exported,
 // and a caller sees include/*.h only.
 //
 // A front end turns a caller's frame into a Feed -- where its rows are, how they get onto the device, what kernel of
@@ -228,9 +228,10 @@ struct Plane {
     uint32_t w = 0, h = 0;  // its own size in pixels where it is not the frame's (subsampled chroma); 0 = the frame's
 };
 struct Feed {
-    // The caller's frame: one plane of interleaved pixels, or up to three planes of one sample per pixel (`unpack`
-    // makes the pixels of them); all `nplanes` of them of one layout (`ch`, `sample`) and in one place (`kind`)
-    Plane plane[3];
+    // The caller's frame: one plane of interleaved pixels, or up to four planes of one sample per pixel -- Y, or Y, U
+    // and V, then an alpha plane if there is one (`unpack` makes the pixels of them); all `nplanes` of them of one
+    // layout (`ch`, `sample`) and in one place (`kind`)
+    Plane plane[4];
     uint32_t nplanes;
     hipMemcpyKind kind;  // where they are: host memory, or an 8-bit frame already on the device
     uint32_t ch;         // samples per pixel there: 3, or 4 with the fourth skipped or composited away; 1 in a planar frame
@@ -317,5 +318,15 @@ struct YuvAux {
 };
 int check_yuv(ssimu2_ctx* c, const ssimu2_yuv_frame* f, uint32_t w, uint32_t rgb_depth);
 Feed yuv_feed(const ssimu2_yuv_frame& f, uint32_t rgb_depth, YuvAux* aux);
+// Subsampled YUV (defined in ssimu2_chroma.hip; in the libraries that link it): what the unpacking of a frame of any of
+// the four formats needs beyond the planes -- `yuv` comes first: a 4:4:4 or 4:0:0 frame's Feed::aux points at it, for
+// yuv_feed's own unpacking --, the argument checks of one such frame (the ctx is not null), and its Feed for a w x h
+// call, planes 1 and 2 with their own size.
+struct ChromaAux {
+    YuvAux yuv;
+    bool vertical, bilinear;  // 4:2:0; the bilinear blend (both false for a 4:4:4 or 4:0:0 frame)
+};
+int check_chroma(ssimu2_ctx* c, const ssimu2_yuv_frame* f, uint32_t w, uint32_t rgb_depth, uint32_t upsampling);
+Feed chroma_feed(const ssimu2_yuv_frame& f, uint32_t w, uint32_t h, uint32_t rgb_depth, uint32_t upsampling, ChromaAux* aux);
 
 }  // namespace ssimu2h

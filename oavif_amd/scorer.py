@@ -123,10 +123,12 @@ class YuvFrame:
     whose samples are not adjacent within a row is copied).  For the subsampled formats _lib.YUV_422 and _lib.YUV_420
     (include/ssimu2_hip_chroma.h, a chroma=True context) U and V are (ch, cw) with cw = (w + 1) // 2 and ch = h (4:2:2)
     or (h + 1) // 2 (4:2:0); `width` and `height` are plane 0's.  `full_range` and `matrix_coefficients` are the image's
-    yuvRange and CICP matrix code."""
+    yuvRange and CICP matrix code.  `alpha` (include/ssimu2_hip_yuva.h, a yuva=True context): the image's alpha plane, an
+    array of plane 0's shape and dtype whose rows may be any distance apart, straight and full range; None = opaque.
+    `alpha_premultiplied` is the image's flag, which the library refuses when it is set."""
 
     def __init__(self, planes, depth: int = 8, format: int = _lib.YUV_444, full_range: bool = True,
-                 matrix_coefficients: int = 6):
+                 matrix_coefficients: int = 6, alpha=None, alpha_premultiplied: bool = False):
         self.depth, self.format = int(depth), int(format)
         self.full_range, self.matrix_coefficients = int(full_range), int(matrix_coefficients)
         self.subsampled = self.format in (_lib.YUV_422, _lib.YUV_420)
@@ -152,6 +154,16 @@ class YuvFrame:
                 a = np.ascontiguousarray(a)
             self.planes.append(a)
         self.height, self.width = self.planes[0].shape
+        self.alpha, self.alpha_premultiplied = None, int(bool(alpha_premultiplied))
+        if alpha is not None:
+            a = np.asarray(alpha)
+            if a.dtype != dtype:
+                raise TypeError(f"the alpha plane of a {self.depth}-bit frame must be {np.dtype(dtype).name}, got {a.dtype}")
+            if a.ndim != 2 or a.shape != self.planes[0].shape:
+                raise ValueError(f"the alpha plane must be (h, w) like plane 0, got {a.shape}")
+            if a.strides[1] != a.itemsize or (a.shape[0] > 1 and a.strides[0] < a.shape[1] * a.itemsize):
+                a = np.ascontiguousarray(a)
+            self.alpha = a
 
     def as_c(self) -> "_lib.YuvFrameC":
         """The C struct; it points into self.planes, which must stay alive for the call."""
@@ -160,6 +172,17 @@ class YuvFrame:
             c.planes[k] = a.ctypes.data
             c.row_bytes[k] = a.strides[0] if a.shape[0] > 1 else a.shape[1] * a.itemsize
         c.depth, c.format, c.full_range, c.matrix_coefficients = self.depth, self.format, self.full_range, self.matrix_coefficients
+        return c
+
+    def as_yuva_c(self) -> "_lib.YuvaFrameC":
+        """ssimu2_yuva_frame; it points into self.planes and self.alpha, which must stay alive for the call."""
+        c = _lib.YuvaFrameC()
+        c.yuv = self.as_c()
+        if self.alpha is not None:
+            a = self.alpha
+            c.alpha = a.ctypes.data
+            c.alpha_row_bytes = a.strides[0] if a.shape[0] > 1 else a.shape[1] * a.itemsize
+        c.alpha_premultiplied = self.alpha_premultiplied
         return c
 
 
@@ -233,10 +256,11 @@ class Ssimu2:
     yuv = False        # bound to liboavif_hip_yuv.so (the YUV calls of include/ssimu2_hip_yuv.h, and the RGBA calls)
     maps = False       # bound to liboavif_hip_map.so (the error maps of include/ssimu2_hip_map.h, and the RGBA and YUV calls)
     chroma = False     # bound to liboavif_hip_chroma.so (4:2:2 / 4:2:0 frames, include/ssimu2_hip_chroma.h, and all of the above)
+    yuva = False       # bound to liboavif_hip_yuva.so (YUV frames with an alpha plane, include/ssimu2_hip_yuva.h, and all of the above)
 
     def __init__(self, device: int = 0, stream: int | None = None, instrumented: bool = False,
                  blur: int | None = None, service: str | None = None, extended: bool = False, yuv: bool = False,
-                 maps: bool = False, chroma: bool = False):
+                 maps: bool = False, chroma: bool = False, yuva: bool = False):
         """`service`: socket path of a running scoring service (oavif_amd.service): the context lives there, and this
         process makes no HIP call for it (OAVIF_SCORER_SOCKET set around ssimu2_ctx_create, then restored; None = the
         environment as it is).  `instrumented=True` binds liboavif_hip_instr.so (the hooks of
@@ -252,7 +276,14 @@ class Ssimu2:
         against-reference forms); that library has the RGBA and YUV calls too, so `extended=True` / `yuv=True` may be
         given with it; not together with `instrumented`.  `chroma=True` binds liboavif_hip_chroma.so: everything
         `maps=True` has, the YUV calls included, and YuvFrames of the subsampled formats 4:2:2 and 4:2:0 in every YUV
-        method (include/ssimu2_hip_chroma.h); not together with `instrumented`."""
+        method (include/ssimu2_hip_chroma.h); not together with `instrumented`.  `yuva=True` binds liboavif_hip_yuva.so:
+        everything `chroma=True` has, and the calls of include/ssimu2_hip_yuva.h that composite a YuvFrame with an alpha
+        plane over a background (composite_yuva, compute_ssimu2_yuva, set_reference_yuva, score_against_reference_yuva,
+        error_map_yuva_alpha, error_map_against_reference_yuva_alpha); not together with `instrumented`."""
+        if instrumented and yuva:
+            raise ValueError("instrumented=True and yuva=True are different libraries: choose one")
+        chroma = bool(chroma or yuva)
+        self.yuva = bool(yuva)
         if instrumented and chroma:
             raise ValueError("instrumented=True and chroma=True are different libraries: choose one")
         if instrumented and maps:
@@ -262,9 +293,10 @@ class Ssimu2:
         if instrumented and yuv:
             raise ValueError("instrumented=True and yuv=True are different libraries: choose one")
         self.chroma = bool(chroma)
-        self.instrumented, self.extended = bool(instrumented), bool(extended)
+        # a yuva context scores against RGBA references and beside RGBA frames: the RGBA methods come with it
+        self.instrumented, self.extended = bool(instrumented), bool(extended or yuva)
         self.yuv, self.maps = bool(yuv or chroma), bool(maps or chroma)
-        self._L = (_lib.instr_lib() if instrumented else _lib.chroma_lib() if chroma else _lib.map_lib() if maps
+        self._L = (_lib.instr_lib() if instrumented else _lib.yuva_lib() if yuva else _lib.chroma_lib() if chroma else _lib.map_lib() if maps
                    else _lib.yuv_lib() if yuv else _lib.ext_lib() if extended else _lib.lib())
         self._ctx = ctypes.c_void_p()
         self._holder = None
@@ -675,6 +707,75 @@ class Ssimu2:
         self._check_ref_shape((f.height, f.width), "frame size")
         c = f.as_c()
         return self._map(self._yuv_fn("error_map_against_reference_yuv"), f.height, f.width, ctypes.byref(c), int(rgb_depth), *up)
+
+    # -- YUV frames with an alpha plane (include/ssimu2_hip_yuva.h): the yuva library only --------
+    def _yuva_args(self, chroma_upsampling, *frames) -> int:
+        """The refusal of a context of another library, then the upsampling code."""
+        if not self.yuva:
+            raise Ssimu2Error(_lib.ERR_UNSUPPORTED, "YUV frames with an alpha plane need Ssimu2(..., yuva=True) "
+                                                    "(liboavif_hip_yuva.so)")
+        for k, f in enumerate(frames):
+            self._yuv_frame(f, "frame" if len(frames) == 1 else ("ref", "dist")[k])
+        try:
+            return self._CHROMA_UPSAMPLING[chroma_upsampling]
+        except (KeyError, TypeError):
+            raise ValueError(f"chroma_upsampling must be 'bilinear' or 'nearest', got {chroma_upsampling!r}") from None
+
+    def composite_yuva(self, frame: YuvFrame, background, rgb_depth: int = 16, chroma_upsampling: str = "bilinear") -> np.ndarray:
+        """ssimu2_composite_yuva: the (h, w, 3) uint16 composite codes n (0..65025) of `frame` -- its colour codes of
+        depth `rgb_depth` under its alpha plane over `background` ((r, g, b) or 0xRRGGBB): the frame as the scorer sees it."""
+        up = self._yuva_args(chroma_upsampling, frame)
+        bg = background_rgb(background)
+        out = np.empty((frame.height, frame.width, 3), np.uint16)
+        c = frame.as_yuva_c()
+        self._call(self._L.ssimu2_composite_yuva, ctypes.byref(c), frame.width, frame.height, int(rgb_depth), up, bg, _u16p(out))
+        return out
+
+    def compute_ssimu2_yuva(self, ref: YuvFrame, dist: YuvFrame, background, rgb_depth: int = 16,
+                            chroma_upsampling: str = "bilinear") -> float:
+        """ssimu2_score_yuva: two frames of one size, each with its own format, depth and alpha plane, both composited
+        over `background`."""
+        up = self._yuva_args(chroma_upsampling, ref, dist)
+        if (ref.height, ref.width) != (dist.height, dist.width):
+            raise ValueError("ref and dist must have the same shape")
+        cr, cd = ref.as_yuva_c(), dist.as_yuva_c()
+        return self._score(self._L.ssimu2_score_yuva, ctypes.byref(cr), ctypes.byref(cd), ref.width, ref.height,
+                           int(rgb_depth), up, background_rgb(background))
+
+    def set_reference_yuva(self, ref: YuvFrame, background, rgb_depth: int = 16, chroma_upsampling: str = "bilinear") -> None:
+        """ssimu2_set_reference_yuva; later frames with an alpha plane (and RGBA frames) are composited over the same
+        background."""
+        up = self._yuva_args(chroma_upsampling, ref)
+        c = ref.as_yuva_c()
+        self._call(self._L.ssimu2_set_reference_yuva, ctypes.byref(c), ref.width, ref.height, int(rgb_depth), up,
+                   background_rgb(background))
+        self._ref_shape = (ref.height, ref.width, 3)
+
+    def score_against_reference_yuva(self, frame: YuvFrame, rgb_depth: int = 16, chroma_upsampling: str = "bilinear") -> float:
+        """ssimu2_score_against_reference_yuva against the reference of set_reference_yuva or set_reference_rgba, over
+        its background."""
+        up = self._yuva_args(chroma_upsampling, frame)
+        self._check_ref_shape((frame.height, frame.width), "frame size")
+        c = frame.as_yuva_c()
+        return self._score(self._L.ssimu2_score_against_reference_yuva, ctypes.byref(c), int(rgb_depth), up)
+
+    def error_map_yuva_alpha(self, ref: YuvFrame, dist: YuvFrame, background, rgb_depth: int = 16,
+                             chroma_upsampling: str = "bilinear"):
+        """ssimu2_error_map_yuva -> (score, map) of two frames with alpha planes, both composited over `background`."""
+        up = self._yuva_args(chroma_upsampling, ref, dist)
+        if (ref.height, ref.width) != (dist.height, dist.width):
+            raise ValueError("ref and dist must have the same shape")
+        cr, cd = ref.as_yuva_c(), dist.as_yuva_c()
+        return self._map(self._L.ssimu2_error_map_yuva, ref.height, ref.width, ctypes.byref(cr), ctypes.byref(cd), ref.width,
+                         ref.height, int(rgb_depth), up, background_rgb(background))
+
+    def error_map_against_reference_yuva_alpha(self, frame: YuvFrame, rgb_depth: int = 16, chroma_upsampling: str = "bilinear"):
+        """ssimu2_error_map_against_reference_yuva -> (score, map) against the reference, over its background."""
+        up = self._yuva_args(chroma_upsampling, frame)
+        self._check_ref_shape((frame.height, frame.width), "frame size")
+        c = frame.as_yuva_c()
+        return self._map(self._L.ssimu2_error_map_against_reference_yuva, frame.height, frame.width, ctypes.byref(c),
+                         int(rgb_depth), up)
 
     # -- device-resident entry points (pointers are raw device addresses) -------------------
     # The per-frame ones make their C call in their own body, not through _call / _score / _scores: a 512x512 score is
