@@ -314,7 +314,8 @@ int ssimu2_score_against_reference_strided16(ssimu2_ctx* ctx, const uint16_t* pi
    Contract: n == 0 is SSIMU2_OK and touches nothing (no pointer is read, no state changes).  SSIMU2_ERR_INVALID_ARG:
    a null array, a null item, null out_scores, a zero dimension, item_stride_bytes < 3 * w * h, n > SSIMU2_MAX_BATCH
    (split the work), or a frame so large that n items exceed one launch's grid.  SSIMU2_ERR_UNSUPPORTED with the
-   context in SSIMU2_BLUR_RECURSIVE / _FMA (the message names ssimu2_ctx_set_blur; those modes score pair by pair).
+   context in SSIMU2_BLUR_RECURSIVE / _FMA (the message names ssimu2_ctx_set_blur; those modes score pair by pair
+   here: the calls that batch in them are ssimu2_hip_rbatch.h's, in a library of their own).
    SSIMU2_ERR_NO_REFERENCE for ..._against_reference without a reference.  SSIMU2_ERR_OOM when the batch's scratch
    cannot grow: the context stays usable, a smaller batch may fit.  Frames too small for any scale (below 8 x 8) score
    100.0 with zero averages.  A batch call leaves the blur mode, a cached reference (the pair form too: it has scratch

@@ -24,6 +24,9 @@ CHROMA_LIB_PATH = os.environ.get("OAVIF_AMD_CHROMA_LIB") or os.path.join(_HERE, 
 # the chroma library's objects plus the calls of include/ssimu2_hip_yuva.h that take YUV planes with an alpha plane
 # (Ssimu2(..., yuva=True))
 YUVA_LIB_PATH = os.environ.get("OAVIF_AMD_YUVA_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_yuva.so")
+# the YUVA library's objects plus the batch calls of include/ssimu2_hip_rbatch.h, which score in every blur mode
+# (Ssimu2(..., rbatch=True))
+RBATCH_LIB_PATH = os.environ.get("OAVIF_AMD_RBATCH_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_rbatch.so")
 
 OK = 0
 ERR_INVALID_ARG = -1
@@ -238,6 +241,13 @@ YUVA_FUNCTIONS = {     # include/ssimu2_hip_yuva.h: only liboavif_hip_yuva.so ha
     "ssimu2_error_map_against_reference_yuva": (_ci, [_vp, _P(YuvaFrameC), _u32, _u32, _f32p, _f64p]),
 }
 
+RBATCH_FUNCTIONS = {   # include/ssimu2_hip_rbatch.h: only liboavif_hip_rbatch.so has these
+    "ssimu2_rbatch_score_rgb8": (_ci, [_vp, _u8pp, _u8pp, _u32, _u32, _u32, _f64p]),
+    "ssimu2_rbatch_score_against_reference": (_ci, [_vp, _u8pp, _u32, _f64p]),
+    "ssimu2_rbatch_score_rgb8_device": (_ci, [_vp, _vp, _vp, _sz, _u32, _u32, _u32, _f64p]),
+    "ssimu2_rbatch_score_against_reference_device": (_ci, [_vp, _vp, _sz, _u32, _f64p]),
+}
+
 EXPORTED_SYMBOLS = tuple(PUBLIC_FUNCTIONS)
 INSTR_SYMBOLS = tuple(HOOK_FUNCTIONS)
 EXT_SYMBOLS = tuple(EXT_FUNCTIONS)
@@ -245,6 +255,7 @@ YUV_SYMBOLS = tuple(YUV_FUNCTIONS)
 MAP_SYMBOLS = tuple(MAP_FUNCTIONS)
 CHROMA_SYMBOLS = tuple(CHROMA_FUNCTIONS)
 YUVA_SYMBOLS = tuple(YUVA_FUNCTIONS)
+RBATCH_SYMBOLS = tuple(RBATCH_FUNCTIONS)
 
 _lib = None
 _instr = None
@@ -253,6 +264,7 @@ _yuv = None
 _map = None
 _chroma = None
 _yuva = None
+_rbatch = None
 
 
 def lib() -> ctypes.CDLL:
@@ -311,6 +323,14 @@ def yuva_lib() -> ctypes.CDLL:
     return _yuva
 
 
+def rbatch_lib() -> ctypes.CDLL:
+    """The batch build (include/ssimu2_hip_rbatch.h): the alpha-plane library plus the batch calls of every blur mode."""
+    global _rbatch
+    if _rbatch is None:
+        _rbatch = _load(RBATCH_LIB_PATH)
+    return _rbatch
+
+
 def _load(path: str) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise ImportError(
@@ -327,7 +347,7 @@ def _load(path: str) -> ctypes.CDLL:
             pass
     L = ctypes.CDLL(path)
     for table in (PUBLIC_FUNCTIONS, HOOK_FUNCTIONS, EXT_FUNCTIONS, YUV_FUNCTIONS, MAP_FUNCTIONS, CHROMA_FUNCTIONS,
-                  YUVA_FUNCTIONS):
+                  YUVA_FUNCTIONS, RBATCH_FUNCTIONS):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name, None)   # a build older than a symbol lacks it (scripts/gpu_ab.py loads such builds)
             if fn is not None:

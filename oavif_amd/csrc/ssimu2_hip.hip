@@ -496,42 +496,57 @@ int rg_ensure(ssimu2_ctx* c, const Pyramid& p) {
     return SSIMU2_OK;
 }
 
+// A recursive-mode plan of one w x h frame: every field that follows from the frame size (the pointers stay null), and
+// where its buffers lie -- the 21 planes of `planes` ([xa 3][xb 3][cache 6][hbuf 9], each with every scale packed, as
+// the context's rg.planes and a pair-form batch item have them) and the partial sums `part`.  One pair's workgroups of
+// the horizontal pass, of the vertical pass, and its doubles of partial sums are what it returns.
+struct RgCounts {
+    int hblocks, vblocks;
+    size_t part;
+};
+RgCounts rg_plan_geometry(const Pyramid& p, RgPlan* rp) {
+    memset(rp, 0, sizeof *rp);
+    rp->nscales = p.nscales;
+    RgCounts n{0, 0, 0};
+    for (int s = 0; s < p.nscales; ++s) {
+        rp->w[s] = p.w[s];
+        rp->h[s] = p.h[s];
+        rp->pitch[s] = rg_pitch(p.w[s]);
+        rp->vgroups[s] = (p.w[s] + RG_VW - 1) / RG_VW;
+        rp->hblk_end[s] = n.hblocks += 3 * ((p.h[s] + RG_HL - 1) / RG_HL);
+        rp->vblk_end[s] = n.vblocks += 3 * rp->vgroups[s];
+        n.part += (size_t)kStats * rp->vgroups[s];
+    }
+    rp->vjobs = n.vblocks;  // jobs of the persistent vertical pass: one channel of 64 columns, largest scale first
+    return n;
+}
+void rg_plan_buffers(const Pyramid& p, RgPlan* rp, float* xa, float* xb, float* cache, float* hbuf, double* part) {
+    for (int s = 0; s < p.nscales; ++s) {
+        const size_t off = rg_plane_off(p, s);
+        rp->xa[s] = xa + 3 * off;
+        rp->xb[s] = xb + 3 * off;
+        rp->cache[s] = cache + 6 * off;
+        rp->hbuf[s] = hbuf + 9 * off;
+        rp->part[s] = part;
+        part += (size_t)kStats * rp->vgroups[s];
+    }
+}
+
 // Plan of one frame's share of a recursive-mode score: `ref_frame` selects where the frame's XYB
 // planes go (xa, the reference's, or xb).
 void rg_build_plan(const ssimu2_ctx* c, const Pyramid& p, bool ref_frame, RgPlan* rp, int* hblocks, int* vblocks) {
-    memset(rp, 0, sizeof *rp);
+    const RgCounts n = rg_plan_geometry(p, rp);
     const size_t ntot = rg_plane_off(p, p.nscales);
     float* xa = c->rg.planes.as<float>();
     float* xb = xa + 3 * ntot;
     float* cache = xb + 3 * ntot;
     float* hbuf = cache + 6 * ntot;
-    rp->nscales = p.nscales;
-    int hb_ = 0, vb_ = 0;
-    size_t poff = 0;
-    for (int s = 0; s < p.nscales; ++s) {
-        const size_t off = rg_plane_off(p, s);
-        rp->w[s] = p.w[s];
-        rp->h[s] = p.h[s];
-        rp->pitch[s] = rg_pitch(p.w[s]);
-        hb_ += 3 * ((p.h[s] + RG_HL - 1) / RG_HL);
-        rp->vgroups[s] = (p.w[s] + RG_VW - 1) / RG_VW;
-        vb_ += 3 * rp->vgroups[s];
-        rp->hblk_end[s] = hb_;
-        rp->vblk_end[s] = vb_;
-        rp->xa[s] = xa + 3 * off;
-        rp->xb[s] = xb + 3 * off;
-        rp->xout[s] = (ref_frame ? xa : xb) + 3 * off;
-        rp->cache[s] = cache + 6 * off;
-        rp->hbuf[s] = hbuf + 9 * off;
-        rp->part[s] = c->rg.part.as<double>() + poff;
-        poff += (size_t)kStats * rp->vgroups[s];
-    }
+    rg_plan_buffers(p, rp, xa, xb, cache, hbuf, c->rg.part.as<double>());
+    for (int s = 0; s < p.nscales; ++s) rp->xout[s] = (ref_frame ? xa : xb) + 3 * rg_plane_off(p, s);
     rp->dump = hbuf + 9 * ntot;
-    // jobs of the persistent vertical pass: one channel of 64 columns, largest scale first
-    rp->vjobs = vb_;
     rp->q = c->d_rg_q;
-    *hblocks = hb_;
-    *vblocks = vb_;
+    *hblocks = n.hblocks;
+    *vblocks = n.vblocks;
 }
 
 // Instrumented builds (ssimu2_instr_rg_stop_after_scale): keep the raw planes of one scale for the
@@ -971,10 +986,11 @@ constexpr size_t kResultDoubles = kNumScales * kStats + 2;  // one item's block 
 
 // The opening of the four batch entry points, used as `if (rc || n == 0) return rc;`: a null context, an empty batch
 // (SSIMU2_OK, nothing else is looked at), then what every batch call refuses.
-int batch_open(ssimu2_ctx* c, uint32_t n, bool against_reference) {
+// `any_mode`: the calls of include/ssimu2_hip_rbatch.h, which batch in the recursive modes too (rbatch_open).
+int batch_open(ssimu2_ctx* c, uint32_t n, bool against_reference, bool any_mode = false) {
     if (!c) return SSIMU2_ERR_INVALID_ARG;
     if (n == 0) return SSIMU2_OK;
-    if (c->blur_mode != SSIMU2_BLUR_FIR)
+    if (!any_mode && c->blur_mode != SSIMU2_BLUR_FIR)
         return c->fail(SSIMU2_ERR_UNSUPPORTED, "batch scoring runs in SSIMU2_BLUR_FIR only: switch the context with "
                                                "ssimu2_ctx_set_blur, or score the pairs one by one");
     if (against_reference && !c->ref.have) return c->fail(SSIMU2_ERR_NO_REFERENCE, "no reference set");
@@ -1053,7 +1069,127 @@ int batch_stage(ssimu2_ctx* c, DevBuf& buf, const uint8_t* const* frames, uint32
     return SSIMU2_OK;
 }
 
+// ---- batches in the recursive modes (include/ssimu2_hip_rbatch.h) ------------
+// Floats behind the batch's last plane that no kernel writes and k_rg_h_batch may read.  rg_h_fetch is unconditional:
+// while a wave works on tile T it fetches tile T + AHEAD, and the last tile it works on is ntiles - 1 with ntiles =
+// ceil((w + 4) / 64).  64 * ntiles is a multiple of 64 below w + 68 <= pitch + 68, so at most pitch + 64; the farthest
+// column fetched is 64 * (ntiles - 1 + AHEAD) + 63 <= pitch + 64 * AHEAD + 63.  In the plane's last row, h - 1, that
+// is 64 * (AHEAD + 1) floats behind the plane's end at the most, and AHEAD is RG_H_AHEAD_REF = 2 in the reference's
+// pass, the larger of the two.  The last plane a wave reads of the last item (xb's third; xa's third in the
+// reference's pass) has that item's later planes and the dump row behind it in this layout; the slack covers it
+// wherever it lies.
+constexpr size_t kRgBatchTail = (size_t)RG_TW * (RG_H_AHEAD_REF + 1);
+
+// n items of w x h in SSIMU2_BLUR_RECURSIVE / _FMA: ONE k_pyramid_bands_xyb_batch, (pair form: ONE k_rg_h_batch<REF>
+// and ONE k_rg_v_emit_batch for the references,) ONE k_rg_h_batch, ONE k_rg_v_batch, ONE k_finalize_batch, one
+// synchronise.  Item i's planes are one block of the batch's own scratch -- pair form [xa 3][xb 3][cache 6][hbuf 9]
+// planes of every scale, against form [xb 3][hbuf 9] with xa and cache the context's cached reference (stride 0) --
+// each laid out inside as rg_build_plan lays the context's, so an item's jobs see the geometry of its single score.
+int rbatch_recursive(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dists, size_t stride0, uint32_t n,
+                     uint32_t w, uint32_t h, double* out_scores) {
+    const bool against_ref = d_refs == nullptr;
+    const Pyramid p = make_pyramid(w, h);
+    const size_t ntot = rg_plane_off(p, p.nscales);
+    const size_t item_planes = (against_ref ? 12 : 21) * ntot;  // floats between items
+    RgBatchPlan bp;
+    memset(&bp, 0, sizeof bp);
+    RgPlan& rp = bp.item;
+    const RgCounts one = rg_plan_geometry(p, &rp);
+    const long long hb = one.hblocks, vb = one.vblocks;
+    const size_t part_stride = one.part;
+    const int nframes = against_ref ? 1 : 2;
+    const long long bands = (long long)((w + PYR_BAND_W - 1) / PYR_BAND_W) * ((h + PYR_BAND_H - 1) / PYR_BAND_H);
+    if (hb * n > 0x7fffffffLL || vb * n > 0x7fffffffLL || bands * nframes * n > 0x7fffffffLL)
+        return c->fail(SSIMU2_ERR_INVALID_ARG, "batch too large for one launch: fewer items per call");
+    auto& b = c->batch;
+    const size_t dump_floats = p.nscales > 0 ? (size_t)rg_pitch(p.w[0]) + 16 : 16;
+    const size_t res_bytes = (size_t)n * kResultDoubles * sizeof(double);
+    int rc;
+    if ((rc = grow(c, b.rg_planes, ((size_t)n * item_planes + dump_floats + kRgBatchTail) * sizeof(float),
+                   "hipMalloc(recursive batch planes: 84 bytes per pixel, scale and item; 48 against a reference)")) ||
+        (rc = grow(c, b.rg_part, 16 + ((size_t)n * part_stride + 8) * sizeof(double), "hipMalloc(recursive batch partial sums)")))
+        return rc;
+    if (!fits(b.result, res_bytes)) c->batch_n = 0;  // as batch_run: regrowing takes the last batch's averages with it
+    if ((rc = grow(c, b.result, res_bytes, "hipHostMalloc(batch results)"))) return rc;
+
+    float* const base = b.rg_planes.as<float>();
+    float* const own_xa = base;                                     // pair form only
+    float* const xb = against_ref ? base : base + 3 * ntot;
+    float* const own_cache = xb + 3 * ntot;                         // pair form only
+    float* const hbuf = against_ref ? xb + 3 * ntot : own_cache + 6 * ntot;
+    // the cached reference: where rg_build_plan puts the context's xa and cache planes (read only here)
+    float* const ref_xa = against_ref ? c->rg.planes.as<float>() : own_xa;
+    float* const ref_cache = against_ref ? c->rg.planes.as<float>() + 6 * ntot : own_cache;
+    rg_plan_buffers(p, &rp, ref_xa, xb, ref_cache, hbuf, (double*)(b.rg_part.as<char>() + 16));
+    FinalizeArgs fa = finalize_args(p);
+    for (int s = 0; s < p.nscales; ++s) {
+        bp.hblk_end[s] = (int)(rp.hblk_end[s] * (long long)n);
+        bp.vblk_end[s] = (int)(rp.vblk_end[s] * (long long)n);
+        rp.emit[s] = against_ref ? nullptr : rp.cache[s];  // the pair form's k_rg_v_emit_batch writes the items' cache planes
+        fa.part[s] = rp.part[s];
+        fa.nblocks[s] = rp.vgroups[s];  // one partial sum per column group, as rg_enqueue_pass
+    }
+    rp.dump = base + (size_t)n * item_planes;
+    rp.q = b.rg_part.as<unsigned>();
+    bp.n_items = (int)n;
+    bp.vjobs = (int)(vb * n);
+    bp.items_fastest = against_ref;
+    bp.xa_stride = against_ref ? 0 : item_planes;
+    bp.cache_stride = against_ref ? 0 : item_planes;
+    bp.xb_stride = bp.hbuf_stride = item_planes;
+    bp.part_stride = part_stride;
+    if (p.nscales > 0) {  // a frame below 8 x 8 has no scale to score
+        const bool fma = c->blur_mode == SSIMU2_BLUR_RECURSIVE_FMA;
+        const uint8_t* frames[2] = {against_ref ? d_dists : d_refs, d_dists};
+        float* none[2] = {nullptr, nullptr};
+        PyrBatchArgs pb;
+        pb.a = pyramid_args(p, nframes, frames, none);
+        for (int f = 0; f < nframes; ++f) {
+            float* x = f == 0 && !against_ref ? own_xa : xb;
+            for (int l = 0; l < p.nscales; ++l) (l == 0 ? pb.a.xyb0[f] : pb.a.out[f][l - 1]) = x + 3 * rg_plane_off(p, l);
+        }
+        for (int l = 0; l < p.nscales; ++l) pb.a.opitch[l] = rp.pitch[l];
+        pb.a.zero4 = rp.q;
+        pb.in_stride = stride0;
+        pb.out_stride = item_planes;
+        launch(k_pyramid_bands_xyb_batch, dim3((unsigned)(bands * nframes * n)), dim3(PYR_THREADS), 0, c->stream, pb);
+        if (!against_ref) {
+            launch(fma ? k_rg_h_batch<true, true> : k_rg_h_batch<false, true>, dim3((unsigned)(hb * n)), dim3(128), 0, c->stream, bp);
+            launch(fma ? k_rg_v_emit_batch<true, 2> : k_rg_v_emit_batch<false, 2>, dim3((unsigned)(vb * n)), dim3(128), 0, c->stream, bp);
+        }
+        launch(fma ? k_rg_h_batch<true, false> : k_rg_h_batch<false, false>, dim3((unsigned)(hb * n)), dim3(192), 0, c->stream, bp);
+        const int cus = c->dev.compute_units > 0 ? (int)c->dev.compute_units : 256;  // one workgroup per CU, as k_rg_v
+        launch(fma ? k_rg_v_batch<true> : k_rg_v_batch<false>, dim3((unsigned)(vb * n < cus ? vb * n : cus)), dim3(512),
+               c->rg_v_pad, c->stream, bp);
+    }
+    launch(k_finalize_batch, dim3(n), dim3(1024), 0, c->stream, fa, part_stride, b.result.as<double>());
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->batch_n = n;
+    for (uint32_t i = 0; i < n; ++i) out_scores[i] = b.result.as<double>()[(size_t)i * kResultDoubles + 108];
+    return SSIMU2_OK;
+}
+
 }  // namespace
+
+int ssimu2h::rbatch_open(ssimu2_ctx* c, uint32_t n, bool against_reference) { return batch_open(c, n, against_reference, true); }
+
+int ssimu2h::rbatch_check_size(ssimu2_ctx* c, uint32_t w, uint32_t h) {
+    return c->blur_mode != SSIMU2_BLUR_FIR ? rg_check_size(c, w, h) : SSIMU2_OK;
+}
+
+int ssimu2h::rbatch_stage(ssimu2_ctx* c, bool ref, const uint8_t* const* frames, uint32_t n, size_t bytes, size_t stride,
+                          const uint8_t** d_frames) {
+    DevBuf& buf = ref ? c->batch.u8_ref : c->batch.u8_dist;
+    const int rc = batch_stage(c, buf, frames, n, bytes, stride);
+    *d_frames = buf.as<uint8_t>();
+    return rc;
+}
+
+int ssimu2h::rbatch_run(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dists, size_t stride0, uint32_t n, uint32_t w,
+                        uint32_t h, double* out_scores) {
+    return (c->blur_mode == SSIMU2_BLUR_FIR ? batch_run : rbatch_recursive)(c, d_refs, d_dists, stride0, n, w, h, out_scores);
+}
 
 extern "C" {
 

@@ -1,7 +1,8 @@
 // What a front end of the MI355X SSIMULACRA2 scorer may use of its host code: the interface between ssimu2_hip.hip
 // (which defines everything declared here but the front ends' own feed builders, marked below) and the translation
 // units that add an input form -- ssimu2_ext.hip (RGBA), ssimu2_yuv.hip (YUV), ssimu2_chroma.hip (4:2:2 and 4:2:0
-// YUV), ssimu2_yuva.hip (YUV with an alpha plane) -- or a call over those forms -- ssimu2_map.hip (error maps of 16-bit, RGBA and YUV frames).  Private to oavif_amd/csrc: nothing here is exported,
+// YUV), ssimu2_yuva.hip (YUV with an alpha plane) -- or a call over those forms -- ssimu2_map.hip (error maps of 16-bit, RGBA and YUV frames),
+// ssimu2_rbatch.hip (batches in every blur mode).  Private to oavif_amd/csrc: nothing here is exported,
 // and a caller sees include/*.h only.
 //
 // A front end turns a caller's frame into a Feed -- where its rows are, how they get onto the device, what kernel of
@@ -116,9 +117,12 @@ struct ssimu2_ctx {
     // batch: batch_run / batch_stage (ssimu2_score_batch_*), each buffer when too small; released by ssimu2_ctx_destroy
     // only.  Scratch of its own, so a batch leaves the single-score buffers and a cached reference alone: the staged
     // 8-bit frames of the host-pointer forms, the linear pyramids (scales 1..5) and partial sums of every item, and the
-    // page-locked result block k_finalize_batch writes (110 doubles per item)
+    // page-locked result block k_finalize_batch writes (110 doubles per item).  rg_planes / rg_part: rbatch_run, by
+    // the first batch in a recursive mode -- every item's planes, then one dump row; the job
+    // cursor's four words, then every item's partial sums
     struct {
         DevBuf u8_ref, u8_dist, lin_ref, lin_dist, part;
+        DevBuf rg_planes, rg_part;
         DevBuf result{nullptr, 0, true};
     } batch;
     uint32_t batch_n = 0;  // items of the last finished batch (ssimu2_last_batch_averages)
@@ -289,6 +293,22 @@ int map_against(ssimu2_ctx* c, const Feed& dist, float* out_map, double* out_sco
 // codes 257 u), with this launch: n pixels of interleaved RGB8 -> fp32 [3][n].  The kernel is ssimu2_map.hip's, which
 // sets the pointer when its library is loaded; null in a library without that unit, where nothing calls map_against.
 extern void (*map_lin0_of_u8)(ssimu2_ctx* c, const uint8_t* rgb8, const float* tab, size_t n, float* lin0);
+
+// ---- batches in every blur mode (include/ssimu2_hip_rbatch.h) ---------------
+// What ssimu2_rbatch.hip's four calls are made of.  rbatch_open: what every batch call refuses first, used as
+// `if (rc || n == 0) return rc;` -- a null context, an empty batch (SSIMU2_OK), a missing reference, too many items;
+// no blur mode is refused.  rbatch_check_size: the recursive modes' limit per item (nothing in FIR).  rbatch_stage: n
+// host frames of `bytes` bytes into the batch's own staging buffer of the reference or distorted side, `stride` bytes
+// apart, on the context stream; *d_frames is where they lie.  rbatch_run: n device-resident items of w x h, d_dists +
+// i * stride0 against d_refs + i * stride0 or (d_refs null) against the cached reference, in the context's blur mode
+// -- FIR: the batch of ssimu2_score_batch_*; recursive: one conversion, one launch per pass, one final reduction
+// whatever n is.  Blocking; fills the batch result block, so ssimu2_last_batch_averages serves it.
+int rbatch_open(ssimu2_ctx* c, uint32_t n, bool against_reference);
+int rbatch_check_size(ssimu2_ctx* c, uint32_t w, uint32_t h);
+int rbatch_stage(ssimu2_ctx* c, bool ref, const uint8_t* const* frames, uint32_t n, size_t bytes, size_t stride,
+                 const uint8_t** d_frames);
+int rbatch_run(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dists, size_t stride0, uint32_t n, uint32_t w,
+               uint32_t h, double* out_scores);
 
 // ---- what the front ends build their feeds with, for the units above them -------------------------
 // A tight frame of u16 samples of depth `bit_depth` in host memory, and the 16-bit calls' argument checks (the ctx is

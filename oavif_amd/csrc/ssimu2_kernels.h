@@ -469,6 +469,7 @@ __device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, flo
                     linear_to_xyb(PYR_LIN(j, i, 0), PYR_LIN(j, i, 1), PYR_LIN(j, i, 2), px[0][i], px[1][i], px[2][i]);
                 }
                 float* row = a.xyb0[f] + (size_t)(Y0 + j) * p0 + XB;
+                if constexpr (BATCH) row += out_off;
                 const uint32_t at = 16u * tx;
                 if (inside) {
 #pragma unroll
@@ -564,6 +565,18 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_bands_xyb(PyrBandArgs a
     __shared__ float s_tiles[PYR_BAND_LDS_FLOATS];
     if (blockIdx.x == 0 && threadIdx.x < 4 && a.zero4) a.zero4[threadIdx.x] = 0u;  // k_rg_v starts after this launch has ended
     pyramid_band<true>(a, (int)blockIdx.x, s_lut, s_tiles);
+}
+
+// The batch of the recursive modes (ssimu2_rbatch_*): PyrBatchArgs as k_pyramid_bands_batch takes them, out_stride
+// the floats between two items' plane sets (every level and the frames' own XYB planes lie in one set per item).
+__global__ __launch_bounds__(PYR_THREADS) void k_pyramid_bands_xyb_batch(PyrBatchArgs b) {
+    __shared__ float s_lut[256];
+    __shared__ float s_tiles[PYR_BAND_LDS_FLOATS];
+    if (blockIdx.x == 0 && threadIdx.x < 4 && b.a.zero4) b.a.zero4[threadIdx.x] = 0u;  // k_rg_v_batch starts after this launch has ended
+    const int per_item = b.a.bands_x * b.a.bands_y * b.a.nframes;
+    const int item = (int)blockIdx.x / per_item;
+    pyramid_band<true, 0, true>(b.a, (int)blockIdx.x - item * per_item, s_lut, s_tiles, nullptr, (size_t)item * b.in_stride,
+                                (size_t)item * b.out_stride);
 }
 
 // The 16-bit counterparts (CH = 3: tight or padded RGB rows; 4: RGBA rows, alpha dropped here).

@@ -78,6 +78,40 @@ struct RgPlan {
     unsigned* q;                  // four zeroed words; [2] is k_rg_v's job cursor, the others are unused
 };
 
+// ---- batch form: N pairs of one size in one launch per stage (ssimu2_rbatch_*) ----
+// `item` is the RgPlan of item 0; item i's buffers lie i * stride further on, and a stride of 0 is a buffer every
+// item shares: the reference's xa / cache planes in the against-reference form (the context's own), where the pair
+// form has them per item.  Every grid is ordered largest scale first ACROSS all items, as one score's is across its
+// scales.  An item keeps the jobs of its single score -- the same row groups, column groups, maps waves and partial
+// sums under (item, statistic, column group) -- so which workgroup runs a job never enters its arithmetic.
+struct RgBatchPlan {
+    RgPlan item;
+    int n_items;
+    int hblk_end[kNumScales];  // exclusive end of each scale's range in the k_rg_h_batch grid: n_items * item's
+    int vblk_end[kNumScales];  // ... in the k_rg_v_emit_batch grid = job numbers of k_rg_v_batch
+    int vjobs;                 // n_items * item.vjobs
+    // k_rg_v_batch: a scale's jobs are numbered (channel, column group) * n_items + item -- neighbouring jobs are the
+    // same columns of consecutive items, which all read the same columns of a shared reference -- instead of
+    // item * (3 * vgroups) + (channel, column group)
+    int items_fastest;
+    size_t xa_stride, xb_stride, cache_stride, hbuf_stride;  // floats between items' planes
+    size_t part_stride;                                      // doubles between items' partial sums
+};
+
+// job / workgroup `blk` of a scale with `per_item` of them per item -> (item, the item's own index); uniform
+__device__ __forceinline__ void rg_batch_split(const RgBatchPlan& bp, int blk, int per_item, bool items_fastest,
+                                               int& item, int& rest) {
+    if (items_fastest) {
+        rest = blk / bp.n_items;
+        item = blk - rest * bp.n_items;
+    } else {
+        item = blk / per_item;
+        rest = blk - item * per_item;
+    }
+    item = __builtin_amdgcn_readfirstlane(item);
+    rest = __builtin_amdgcn_readfirstlane(rest);
+}
+
 // ---- the recursion --------------------------------------------------------------------------------
 // one step (FastGaussian1D, scalar form):
 //   o_k = n2_k * (left + right) - prev2_k - d1_k * prev_k;   out = (o_1 + o_3) + o_5
@@ -167,7 +201,10 @@ struct RgLine {
     float cur[2][RG_HT];    // inputs of the current and the previous 16-column group (by parity)
 };
 
-template <int OPK>
+// BATCH, here and in the three templates below, changes nothing they do: it gives k_rg_h_batch instantiations of its
+// own.  With the helpers shared between the two kernels k_rg_h came out of the compiler with other registers and
+// another schedule (scripts/isa_ab.py), and it has to stay as measured.
+template <int OPK, bool BATCH = false>
 __device__ __forceinline__ void rg_h_fetch(const RgLine& L, rg_f4 (&ra)[RG_TR], rg_f4 (&rb)[RG_TR], int T) {
     // unconditional and all alike (countable by s_waitcnt vmcnt): a tile that reaches past the end
     // of a row reads on into the next row / plane of the same allocation -- every plane read here
@@ -188,7 +225,7 @@ __device__ __forceinline__ void rg_h_fetch(const RgLine& L, rg_f4 (&ra)[RG_TR], 
 // OPK: 0 = the plane itself, 1 = its square, 2 = the product of two planes (rounded to fp32 before
 // the blur, as published).  EDGE: the tile touches the row's first or last columns.
 // Segment S = output columns 64 S .. 64 S + 63 of the 20 rows, from the ring to the plane.
-template <bool EDGE>
+template <bool EDGE, bool BATCH = false>
 __device__ __forceinline__ void rg_h_store(const RgLine& L, const RgRing& tout, int S) {
     const int rr = threadIdx.x >> 4 & 3, cc = threadIdx.x & 15;
 #pragma unroll
@@ -215,7 +252,7 @@ __device__ __forceinline__ void rg_h_store(const RgLine& L, const RgRing& tout, 
 // at 0.85 of what a mixed stream reaches, more loads in flight only lengthen the queue.  So: 2 for the reference, 1 for a pass.
 constexpr int RG_H_AHEAD_REF = 2;
 constexpr int RG_H_AHEAD_PASS = 1;
-template <bool FMA, int OPK, bool EDGE, int AHEAD>
+template <bool FMA, int OPK, bool EDGE, int AHEAD, bool BATCH = false>
 __device__ __forceinline__ void rg_h_tile(RgLine& L, RgTile& tin, RgRing& tout, float* dump,
                                           rg_f4 (&ra)[RG_TR], rg_f4 (&rb)[RG_TR], int T) {
     const int rr = threadIdx.x >> 4 & 3, cc = threadIdx.x & 15;
@@ -232,7 +269,7 @@ __device__ __forceinline__ void rg_h_tile(RgLine& L, RgTile& tin, RgRing& tout, 
         }
         *reinterpret_cast<rg_f4*>(&tin[4 * i + rr][4 * cc]) = v;
     }
-    rg_h_fetch<OPK>(L, ra, rb, T + AHEAD);  // lands under the steps of this tile (and of the next, AHEAD = 2)
+    rg_h_fetch<OPK, BATCH>(L, ra, rb, T + AHEAD);  // lands under the steps of this tile (and of the next, AHEAD = 2)
     __builtin_amdgcn_wave_barrier();
     // 16 columns at a time; the LDS reads of the next 16 are issued before the steps of these 16
     // (an LDS read takes ~100+ cycles to land)
@@ -271,10 +308,10 @@ __device__ __forceinline__ void rg_h_tile(RgLine& L, RgTile& tin, RgRing& tout, 
     }
 #undef RG_H_READ
     __builtin_amdgcn_wave_barrier();
-    if (T > 0) rg_h_store<EDGE>(L, tout, T - 1);  // uniform; segment T - 1 is complete now
+    if (T > 0) rg_h_store<EDGE, BATCH>(L, tout, T - 1);  // uniform; segment T - 1 is complete now
 }
 
-template <bool FMA, int OPK, int AHEAD>
+template <bool FMA, int OPK, int AHEAD, bool BATCH = false>
 __device__ __forceinline__ void rg_h_line(RgLine& L, RgTile& tin, RgRing& tout, float* dump) {
     const int w = L.w;
     const int ntiles = (w + (RG_N - 1) + RG_TW - 1) / RG_TW;  // steps run to m = w + 3
@@ -285,37 +322,37 @@ __device__ __forceinline__ void rg_h_line(RgLine& L, RgTile& tin, RgRing& tout, 
     L.p1 = L.p2 = 0.0f;
     if constexpr (AHEAD == 1) {
         rg_f4 ra[RG_TR], rb[RG_TR];
-        rg_h_fetch<OPK>(L, ra, rb, 0);
-        rg_h_tile<FMA, OPK, true, 1>(L, tin, tout, dump, ra, rb, 0);
+        rg_h_fetch<OPK, BATCH>(L, ra, rb, 0);
+        rg_h_tile<FMA, OPK, true, 1, BATCH>(L, tin, tout, dump, ra, rb, 0);
         int T = 1;
 #pragma unroll 1
-        for (; T < nmain; ++T) rg_h_tile<FMA, OPK, false, 1>(L, tin, tout, dump, ra, rb, T);
+        for (; T < nmain; ++T) rg_h_tile<FMA, OPK, false, 1, BATCH>(L, tin, tout, dump, ra, rb, T);
 #pragma unroll 1
-        for (; T < ntiles; ++T) rg_h_tile<FMA, OPK, true, 1>(L, tin, tout, dump, ra, rb, T);
+        for (; T < ntiles; ++T) rg_h_tile<FMA, OPK, true, 1, BATCH>(L, tin, tout, dump, ra, rb, T);
     } else {
         // two register sets: tile T is staged from set T & 1, which is then refilled with tile T + 2
         rg_f4 ra0[RG_TR], rb0[RG_TR], ra1[RG_TR], rb1[RG_TR];
-        rg_h_fetch<OPK>(L, ra0, rb0, 0);
-        rg_h_fetch<OPK>(L, ra1, rb1, 1);
-        rg_h_tile<FMA, OPK, true, 2>(L, tin, tout, dump, ra0, rb0, 0);
+        rg_h_fetch<OPK, BATCH>(L, ra0, rb0, 0);
+        rg_h_fetch<OPK, BATCH>(L, ra1, rb1, 1);
+        rg_h_tile<FMA, OPK, true, 2, BATCH>(L, tin, tout, dump, ra0, rb0, 0);
         int T = 1;
 #pragma unroll 1
         for (; T + 1 < nmain; T += 2) {  // T odd here
-            rg_h_tile<FMA, OPK, false, 2>(L, tin, tout, dump, ra1, rb1, T);
-            rg_h_tile<FMA, OPK, false, 2>(L, tin, tout, dump, ra0, rb0, T + 1);
+            rg_h_tile<FMA, OPK, false, 2, BATCH>(L, tin, tout, dump, ra1, rb1, T);
+            rg_h_tile<FMA, OPK, false, 2, BATCH>(L, tin, tout, dump, ra0, rb0, T + 1);
         }
         if (T < nmain) {  // uniform
-            rg_h_tile<FMA, OPK, false, 2>(L, tin, tout, dump, ra1, rb1, T);
+            rg_h_tile<FMA, OPK, false, 2, BATCH>(L, tin, tout, dump, ra1, rb1, T);
             ++T;
         }
 #pragma unroll 1
         for (; T < ntiles; ++T) {
-            if (T & 1) rg_h_tile<FMA, OPK, true, 2>(L, tin, tout, dump, ra1, rb1, T);
-            else rg_h_tile<FMA, OPK, true, 2>(L, tin, tout, dump, ra0, rb0, T);
+            if (T & 1) rg_h_tile<FMA, OPK, true, 2, BATCH>(L, tin, tout, dump, ra1, rb1, T);
+            else rg_h_tile<FMA, OPK, true, 2, BATCH>(L, tin, tout, dump, ra0, rb0, T);
         }
     }
     __builtin_amdgcn_wave_barrier();
-    rg_h_store<true>(L, tout, ntiles - 1);  // the row's last columns (w - 1 <= 64 (ntiles - 1) + 59)
+    rg_h_store<true, BATCH>(L, tout, ntiles - 1);  // the row's last columns (w - 1 <= 64 (ntiles - 1) + 59)
 }
 
 // plane index among the 15 of a scale (5 * channel + {x, y, xx, yy, xy}) of plane `kind` of a pass
@@ -381,6 +418,54 @@ __global__ __launch_bounds__(REF ? 128 : 192) __attribute__((amdgpu_waves_per_eu
     else rg_h_line<FMA, 2, AHEAD>(L, s_in[NK - 1], s_o[NK - 1], s_dump);
 }
 
+// The horizontal pass of a batch (RgBatchPlan): scale s takes n_items * 3 * ceil(h_s / 20) consecutive workgroups,
+// item by item, each the workgroup of k_rg_h over that item's planes -- their offsets are formed on the scalar unit
+// from kernel arguments and the workgroup index -- and the unchanged rg_h_line runs on them.  A kernel of its own text,
+// not a shared body: k_rg_h compiled through one came out with other instructions (profiles/rbatch_isa_ab.txt is
+// taken with this form).
+template <bool FMA, bool REF>
+__global__ __launch_bounds__(REF ? 128 : 192) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_rg_h_batch(RgBatchPlan bp) {
+    constexpr int NK = REF ? 2 : 3;
+    __shared__ __attribute__((aligned(16))) RgTile s_in[NK];
+    __shared__ __attribute__((aligned(16))) RgRing s_o[NK];
+    __shared__ __attribute__((aligned(16))) float s_dump[RG_OW];
+    const RgPlan& p = bp.item;
+    int sc = 0, first = 0;
+#pragma unroll
+    for (int s = 0; s < kNumScales - 1; ++s)
+        if (s + 1 < p.nscales && (int)blockIdx.x >= bp.hblk_end[s]) {
+            sc = s + 1;
+            first = bp.hblk_end[s];
+        }
+    int item, blk;
+    rg_batch_split(bp, (int)blockIdx.x - first, 3 * ((p.h[sc] + RG_HL - 1) / RG_HL), false, item, blk);
+    const int ch = blk % 3, rgrp = blk / 3;
+    const int kind = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int w = p.w[sc], h = p.h[sc], pitch = p.pitch[sc];
+    const size_t n = (size_t)pitch * h;
+    RgLine L;
+    const int l16 = lane & 15;  // lane -> (DPP row, line, section), as in k_rg_h
+    const int sec = l16 < 15 ? l16 / 5 : 2;
+    L.line = (lane >> 4) * 5 + (l16 < 15 ? l16 - 5 * sec : 4);
+    L.holds_out = l16 >= 10 && l16 < 15;
+    L.n2 = c_k.rg_n2[sec];
+    L.d1 = c_k.rg_d1[sec];
+    L.w = w;
+#pragma unroll
+    for (int i = 0; i < RG_TR; ++i)
+        L.goff[i] = (uint32_t)min(rgrp * RG_HL + 4 * i + (lane >> 4), h - 1) * (uint32_t)pitch + 4u * (uint32_t)(lane & 15);
+    const float* xa = p.xa[sc] + (size_t)item * bp.xa_stride + ch * n;
+    const float* xb = REF ? xa : p.xb[sc] + (size_t)item * bp.xb_stride + ch * n;
+    L.gout = p.hbuf[sc] + (size_t)item * bp.hbuf_stride + (size_t)(ch * NK + kind) * n;
+    L.ga = kind == 2 ? xa : xb;  // REF: x, x*x.  pass: y, y*y, x*y
+    L.gb = xb;
+    constexpr int AHEAD = REF ? RG_H_AHEAD_REF : RG_H_AHEAD_PASS;
+    if (kind == 0) rg_h_line<FMA, 0, AHEAD, true>(L, s_in[0], s_o[0], s_dump);
+    else if (kind == 1) rg_h_line<FMA, 1, AHEAD, true>(L, s_in[1], s_o[1], s_dump);
+    else rg_h_line<FMA, 2, AHEAD, true>(L, s_in[NK - 1], s_o[NK - 1], s_dump);
+}
+
 // ---- vertical pass (+ maps) -----------------------------------------------------------------------
 // The recursion of one plane down this lane's column, PF batches of ten rows in a register queue
 // (three in flight under the one consumed).  Everything that counts in vmcnt is unconditional:
@@ -438,17 +523,20 @@ __device__ __forceinline__ void rg_v_column(const float* __restrict__ in, int pi
 // search) -- and, in instrumented builds, the three per-pass planes for the parity tests (NK = 3).
 // One wave per plane and 64 columns; grid = sum over scales of 3 channels x ceil(w / 64).
 // Stores are unconditional too: rows outside the image go to a dump row.
-template <bool FMA, int NK>
-__global__ __launch_bounds__(64 * NK) void k_rg_v_emit(RgPlan p) {
+// BATCH (k_rg_v_emit_batch, the pair form's reference side): scale s takes n_items * 3 * vgroups[s] workgroups, item by item.
+template <bool FMA, int NK, bool BATCH>
+__device__ __forceinline__ void rg_v_emit_body(const RgPlan& p, const RgBatchPlan* bp) {
     int sc = 0, first = 0;
 #pragma unroll
     for (int s = 0; s < kNumScales - 1; ++s)
-        if (s + 1 < p.nscales && (int)blockIdx.x >= p.vblk_end[s]) {
+        if (s + 1 < p.nscales && (int)blockIdx.x >= (BATCH ? bp->vblk_end[s] : p.vblk_end[s])) {
             sc = s + 1;
-            first = p.vblk_end[s];
+            first = BATCH ? bp->vblk_end[s] : p.vblk_end[s];
         }
     if (p.emit[sc] == nullptr) return;  // uniform (the instrumented builds' one-scale runs)
-    const int blk = (int)blockIdx.x - first;
+    int blk = (int)blockIdx.x - first;
+    int item = 0;
+    if constexpr (BATCH) rg_batch_split(*bp, blk, 3 * p.vgroups[sc], false, item, blk);
     const int ch = blk % 3, cg = blk / 3;
     const int kind = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int w = p.w[sc], h = p.h[sc], pitch = p.pitch[sc];
@@ -456,6 +544,10 @@ __global__ __launch_bounds__(64 * NK) void k_rg_v_emit(RgPlan p) {
     const int xc = min(cg * RG_VW + (int)(threadIdx.x & 63), w - 1);  // lanes right of the image shadow its last column
     const float* in = p.hbuf[sc] + (size_t)(ch * NK + kind) * n + xc;
     float* out = p.emit[sc] + (size_t)(ch * NK + kind) * n;
+    if constexpr (BATCH) {
+        in += (size_t)item * bp->hbuf_stride;
+        out += (size_t)item * bp->cache_stride;  // the batch emits into the items' cache planes
+    }
     float* dump = p.dump;
     rg_v_column<FMA>(in, pitch, h, [&](int b, const float (&o)[RG_VB]) {
 #pragma unroll
@@ -465,6 +557,16 @@ __global__ __launch_bounds__(64 * NK) void k_rg_v_emit(RgPlan p) {
             row[xc] = o[j];
         }
     });
+}
+
+template <bool FMA, int NK>
+__global__ __launch_bounds__(64 * NK) void k_rg_v_emit(RgPlan p) {
+    rg_v_emit_body<FMA, NK, false>(p, nullptr);
+}
+
+template <bool FMA, int NK>
+__global__ __launch_bounds__(64 * NK) void k_rg_v_emit_batch(RgBatchPlan bp) {
+    rg_v_emit_body<FMA, NK, true>(bp.item, &bp);
 }
 
 // Vertical pass of a pass's planes + maps.  Waves 0-2 recurse {y, y*y, x*y} into a double-buffered
@@ -498,8 +600,12 @@ struct RgMapArgs {
 // m->dens[scale] instead of summing, and no partial sums exist (s_part is never named, so it costs that instantiation
 // no LDS).  `m` is null in the score pass.  Both are the entry's kernel arguments, which no store of the kernel aliases
 // (__restrict__: their fields may stay in registers across the job loop's atomic and barriers).
-template <bool FMA, bool MAP>
-__device__ __forceinline__ void rg_v_body(const RgPlan& __restrict__ p, const RgMapArgs* __restrict__ m) {
+// BATCH (k_rg_v_batch): the jobs of every item, n_items * vjobs of them, scale s in n_items * 3 * vgroups[s] consecutive
+// job numbers (RgBatchPlan::items_fastest says how they are dealt inside a scale); the job's planes and partial sums
+// lie the item's strides behind item 0's.  Per item the jobs, waves and sums of the single score.
+template <bool FMA, bool MAP, bool BATCH = false>
+__device__ __forceinline__ void rg_v_body(const RgPlan& __restrict__ p, const RgMapArgs* __restrict__ m,
+                                          const RgBatchPlan* __restrict__ bp = nullptr) {
     constexpr int NK = 3;
     __shared__ float s_out[2][NK][RG_VB][RG_VW];
     __shared__ double s_part[RG_MAPS_WAVES][6];  // !MAP only
@@ -510,7 +616,7 @@ __device__ __forceinline__ void rg_v_body(const RgPlan& __restrict__ p, const Rg
     for (;;) {
         if (threadIdx.x == 0) {
             const int j = (int)atomicAdd(p.q + 2, 1u);
-            s_job = j < p.vjobs ? j : -1;
+            s_job = j < (BATCH ? bp->vjobs : p.vjobs) ? j : -1;
         }
         __syncthreads();
         const int job = __builtin_amdgcn_readfirstlane(s_job);
@@ -518,11 +624,13 @@ __device__ __forceinline__ void rg_v_body(const RgPlan& __restrict__ p, const Rg
         int sc = 0, first = 0;
 #pragma unroll
         for (int s = 0; s < kNumScales - 1; ++s)
-            if (s + 1 < p.nscales && job >= p.vblk_end[s]) {
+            if (s + 1 < p.nscales && job >= (BATCH ? bp->vblk_end[s] : p.vblk_end[s])) {
                 sc = s + 1;
-                first = p.vblk_end[s];
+                first = BATCH ? bp->vblk_end[s] : p.vblk_end[s];
             }
-        const int blk = job - first;
+        int blk = job - first;
+        int item = 0;
+        if constexpr (BATCH) rg_batch_split(*bp, blk, 3 * p.vgroups[sc], bp->items_fastest != 0, item, blk);
         const int ch = blk % 3, cg = blk / 3;
         const int w = p.w[sc], h = p.h[sc], pitch = p.pitch[sc];
         const size_t n = (size_t)pitch * h;
@@ -534,6 +642,7 @@ __device__ __forceinline__ void rg_v_body(const RgPlan& __restrict__ p, const Rg
         if (wave < NK) {
             const int kind = wave;
             const float* in = p.hbuf[sc] + (size_t)(ch * NK + kind) * n + xc;
+            if constexpr (BATCH) in += (size_t)item * bp->hbuf_stride;
             rg_v_column<FMA>(in, pitch, h, [&](int b, const float (&o)[RG_VB]) {
 #pragma unroll
                 for (int j = 0; j < RG_VB; ++j) s_out[b & 1][kind][j][lane] = o[j];
@@ -543,9 +652,14 @@ __device__ __forceinline__ void rg_v_body(const RgPlan& __restrict__ p, const Rg
             // maps: this wave's two rows of every batch; the same barriers as the recursion waves
             const int j0 = 2 * (wave - NK);
             const float* g_mu1 = p.cache[sc] + (size_t)(2 * ch) * n + xc;
+            if constexpr (BATCH) g_mu1 += (size_t)item * bp->cache_stride;
             const float* g_s11 = g_mu1 + n;
             const float* g_r1 = p.xa[sc] + (size_t)ch * n + xc;
             const float* g_r2 = p.xb[sc] + (size_t)ch * n + xc;
+            if constexpr (BATCH) {
+                g_r1 += (size_t)item * bp->xa_stride;
+                g_r2 += (size_t)item * bp->xb_stride;
+            }
             double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // !MAP
             float mc[6];  // MAP: coefficients of this channel's six terms
             float* dens = nullptr;
@@ -617,7 +731,9 @@ __device__ __forceinline__ void rg_v_body(const RgPlan& __restrict__ p, const Rg
                 double sum = s_part[0][k];
 #pragma unroll
                 for (int mw = 1; mw < RG_MAPS_WAVES; ++mw) sum += s_part[mw][k];
-                p.part[sc][(size_t)term_stat(ch, k) * p.vgroups[sc] + cg] = sum;
+                double* part = p.part[sc];
+                if constexpr (BATCH) part += (size_t)item * bp->part_stride;
+                part[(size_t)term_stat(ch, k) * p.vgroups[sc] + cg] = sum;
             }
         }
     }
@@ -626,6 +742,11 @@ __device__ __forceinline__ void rg_v_body(const RgPlan& __restrict__ p, const Rg
 template <bool FMA>
 __global__ __launch_bounds__(512) void k_rg_v(RgPlan p) {
     rg_v_body<FMA, false>(p, nullptr);
+}
+
+template <bool FMA>
+__global__ __launch_bounds__(512) void k_rg_v_batch(RgBatchPlan bp) {
+    rg_v_body<FMA, false, true>(bp.item, nullptr, &bp);
 }
 
 template <bool FMA>

@@ -1,12 +1,15 @@
 """Score a list of image pairs with the batch scorer.
 
-    python -m oavif_amd.scorepairs PAIRS.tsv OUT.csv [--batch B] [--device D]
+    python -m oavif_amd.scorepairs PAIRS.tsv OUT.csv [--batch B] [--device D] [--blur fir|recursive|recursive_fma]
 
 PAIRS.tsv holds one `ref<TAB>dist` path pair per line (PNG or PAM, through the project's own loaders; relative paths are
 taken from the list's directory; blank lines and lines starting with '#' are skipped).  Pairs are grouped by frame
 size, every group is scored with Ssimu2.score_batch in batches of at most B pairs (one launch set each), and OUT.csv
-gets one row per pair in input order: line, ref, dist, width, height, score.  8-bit RGB in SSIMU2_BLUR_FIR (what the
-batch calls score); 16-bit PNGs are truncated to 8 bits and alpha is dropped, as the search's reference is.
+gets one row per pair in input order: line, ref, dist, width, height, score.  8-bit RGB; 16-bit PNGs are truncated to
+8 bits and alpha is dropped, as the search's reference is.  --blur: the blur mode the pairs are scored in.  The default
+is fir, SSIMU2_BLUR_FIR on the product library, as the command always scored.  recursive and recursive_fma -- the
+published recursion -- bind the library of include/ssimu2_hip_rbatch.h, whose batches score in those modes with the
+bits of single scores.
 """
 from __future__ import annotations
 
@@ -18,6 +21,7 @@ from typing import Callable, List, Sequence, Tuple
 import numpy as np
 
 DEFAULT_BATCH = 64
+BLUR_MODES = ("fir", "recursive", "recursive_fma")   # --blur; the index is the SSIMU2_BLUR_* value
 
 
 class PairListError(Exception):
@@ -104,12 +108,30 @@ def write_csv(rows, f) -> None:
         wr.writerow([line, rp, dp, w, h, repr(score)])
 
 
+def make_scorer(device: int, blur: str):
+    """The scorer of a run that brings none: the product library in fir, as ever; in a recursive mode the library whose
+    batch calls score in it."""
+    from .scorer import Ssimu2
+    if blur == "fir":
+        return Ssimu2(device)
+    return Ssimu2(device, blur=BLUR_MODES.index(blur), rbatch=True)
+
+
+USAGE = "usage: python -m oavif_amd.scorepairs PAIRS.tsv OUT.csv [--batch B] [--device D] [--blur fir|recursive|recursive_fma]"
+
+
 def main(argv=None, scorer=None) -> int:
     args = list(sys.argv[1:] if argv is None else argv)
-    batch, device, pos = DEFAULT_BATCH, 0, []
+    batch, device, blur, pos = DEFAULT_BATCH, 0, "fir", []
     i = 0
     while i < len(args):
-        if args[i] in ("--batch", "--device"):
+        if args[i] == "--blur":
+            if i + 1 >= len(args) or args[i + 1] not in BLUR_MODES:
+                print(f"--blur needs one of {', '.join(BLUR_MODES)}", file=sys.stderr)
+                return 2
+            blur = args[i + 1]
+            i += 2
+        elif args[i] in ("--batch", "--device"):
             if i + 1 >= len(args) or not args[i + 1].lstrip("-").isdigit():
                 print(f"{args[i]} needs an integer", file=sys.stderr)
                 return 2
@@ -122,7 +144,7 @@ def main(argv=None, scorer=None) -> int:
             pos.append(args[i])
             i += 1
     if len(pos) != 2 or batch < 1:
-        print("usage: python -m oavif_amd.scorepairs PAIRS.tsv OUT.csv [--batch B] [--device D]", file=sys.stderr)
+        print(USAGE, file=sys.stderr)
         return 2
     from . import _lib
     batch = min(batch, _lib.MAX_BATCH)
@@ -133,8 +155,7 @@ def main(argv=None, scorer=None) -> int:
         return 1
     own = scorer is None
     if own:
-        from .scorer import Ssimu2
-        scorer = Ssimu2(device)
+        scorer = make_scorer(device, blur)
     try:
         rows = score_pairs(scorer, pairs, batch)
     except PairListError as e:

@@ -246,6 +246,13 @@ class _PinnedBuffer:
             pass
 
 
+# the batch calls of include/ssimu2_hip.h -> their counterparts of include/ssimu2_hip_rbatch.h (Ssimu2._batch_fn)
+_RBATCH_CALLS = {"ssimu2_score_batch_rgb8": "ssimu2_rbatch_score_rgb8",
+                 "ssimu2_score_batch_against_reference": "ssimu2_rbatch_score_against_reference",
+                 "ssimu2_score_batch_rgb8_device": "ssimu2_rbatch_score_rgb8_device",
+                 "ssimu2_score_batch_against_reference_device": "ssimu2_rbatch_score_against_reference_device"}
+
+
 class Ssimu2:
     """One scorer context = one HIP stream + device scratch (not re-entrant)."""
 
@@ -257,10 +264,11 @@ class Ssimu2:
     maps = False       # bound to liboavif_hip_map.so (the error maps of include/ssimu2_hip_map.h, and the RGBA and YUV calls)
     chroma = False     # bound to liboavif_hip_chroma.so (4:2:2 / 4:2:0 frames, include/ssimu2_hip_chroma.h, and all of the above)
     yuva = False       # bound to liboavif_hip_yuva.so (YUV frames with an alpha plane, include/ssimu2_hip_yuva.h, and all of the above)
+    rbatch = False     # bound to liboavif_hip_rbatch.so (batches in every blur mode, include/ssimu2_hip_rbatch.h, and all of the above)
 
     def __init__(self, device: int = 0, stream: int | None = None, instrumented: bool = False,
                  blur: int | None = None, service: str | None = None, extended: bool = False, yuv: bool = False,
-                 maps: bool = False, chroma: bool = False, yuva: bool = False):
+                 maps: bool = False, chroma: bool = False, yuva: bool = False, rbatch: bool = False):
         """`service`: socket path of a running scoring service (oavif_amd.service): the context lives there, and this
         process makes no HIP call for it (OAVIF_SCORER_SOCKET set around ssimu2_ctx_create, then restored; None = the
         environment as it is).  `instrumented=True` binds liboavif_hip_instr.so (the hooks of
@@ -279,7 +287,15 @@ class Ssimu2:
         method (include/ssimu2_hip_chroma.h); not together with `instrumented`.  `yuva=True` binds liboavif_hip_yuva.so:
         everything `chroma=True` has, and the calls of include/ssimu2_hip_yuva.h that composite a YuvFrame with an alpha
         plane over a background (composite_yuva, compute_ssimu2_yuva, set_reference_yuva, score_against_reference_yuva,
-        error_map_yuva_alpha, error_map_against_reference_yuva_alpha); not together with `instrumented`."""
+        error_map_yuva_alpha, error_map_against_reference_yuva_alpha); not together with `instrumented`.  `rbatch=True`
+        binds liboavif_hip_rbatch.so: everything `yuva=True` has, and score_batch, score_batch_against_reference and
+        their _device forms go through the calls of include/ssimu2_hip_rbatch.h, which batch in the context's blur
+        mode, the recursive ones included (without it they are SSIMU2_ERR_UNSUPPORTED there); not together with
+        `instrumented`."""
+        if instrumented and rbatch:
+            raise ValueError("instrumented=True and rbatch=True are different libraries: choose one")
+        self.rbatch = bool(rbatch)
+        yuva = bool(yuva or rbatch)
         if instrumented and yuva:
             raise ValueError("instrumented=True and yuva=True are different libraries: choose one")
         chroma = bool(chroma or yuva)
@@ -296,7 +312,7 @@ class Ssimu2:
         # a yuva context scores against RGBA references and beside RGBA frames: the RGBA methods come with it
         self.instrumented, self.extended = bool(instrumented), bool(extended or yuva)
         self.yuv, self.maps = bool(yuv or chroma), bool(maps or chroma)
-        self._L = (_lib.instr_lib() if instrumented else _lib.yuva_lib() if yuva else _lib.chroma_lib() if chroma else _lib.map_lib() if maps
+        self._L = (_lib.instr_lib() if instrumented else _lib.rbatch_lib() if rbatch else _lib.yuva_lib() if yuva else _lib.chroma_lib() if chroma else _lib.map_lib() if maps
                    else _lib.yuv_lib() if yuv else _lib.ext_lib() if extended else _lib.lib())
         self._ctx = ctypes.c_void_p()
         self._holder = None
@@ -822,9 +838,15 @@ class Ssimu2:
     def _ptr_array(frames):
         return (ctypes.POINTER(ctypes.c_uint8) * len(frames))(*[_u8p(f) for f in frames])
 
+    def _batch_fn(self, name: str):
+        """The batch call `name` of include/ssimu2_hip.h, or on an rbatch=True context its counterpart of
+        include/ssimu2_hip_rbatch.h (the same parameters; every blur mode)."""
+        return getattr(self._L, _RBATCH_CALLS[name] if self.rbatch else name)
+
     def score_batch(self, refs, dists) -> np.ndarray:
         """ssimu2_score_batch_rgb8: N pairs of one size in one launch set -> float64 scores in input order.
-        A cached reference is kept."""
+        A cached reference is kept.  FIR only, unless the context was made with rbatch=True (_batch_fn); so are the
+        three methods below."""
         refs, dists = self._check_batch(refs, "refs"), self._check_batch(dists, "dists")
         if len(refs) != len(dists):
             raise ValueError("refs and dists must hold the same number of frames")
@@ -833,7 +855,7 @@ class Ssimu2:
         if refs[0].shape != dists[0].shape:
             raise ValueError("refs and dists must have the same shape")
         h, w, _ = refs[0].shape
-        return self._scores(self._L.ssimu2_score_batch_rgb8, len(refs), self._ptr_array(refs), self._ptr_array(dists),
+        return self._scores(self._batch_fn("ssimu2_score_batch_rgb8"), len(refs), self._ptr_array(refs), self._ptr_array(dists),
                             len(refs), w, h)
 
     def score_batch_against_reference(self, dists) -> np.ndarray:
@@ -842,13 +864,13 @@ class Ssimu2:
         if not dists:
             return np.zeros(0, np.float64)
         self._check_ref_shape(dists[0].shape)
-        return self._scores(self._L.ssimu2_score_batch_against_reference, len(dists), self._ptr_array(dists), len(dists))
+        return self._scores(self._batch_fn("ssimu2_score_batch_against_reference"), len(dists), self._ptr_array(dists), len(dists))
 
     def score_batch_device(self, d_refs: int, d_dists: int, item_stride_bytes: int, n: int, w: int, h: int) -> np.ndarray:
         """ssimu2_score_batch_rgb8_device: item i at d_refs + i * item_stride_bytes / d_dists + i * item_stride_bytes."""
         out = np.zeros(int(n), np.float64)   # in its own body: see "device-resident entry points"
-        rc = self._L.ssimu2_score_batch_rgb8_device(self._ctx, ctypes.c_void_p(d_refs), ctypes.c_void_p(d_dists),
-                                                    int(item_stride_bytes), int(n), w, h, out.ctypes.data_as(_F64P))
+        rc = self._batch_fn("ssimu2_score_batch_rgb8_device")(self._ctx, ctypes.c_void_p(d_refs), ctypes.c_void_p(d_dists),
+                                                              int(item_stride_bytes), int(n), w, h, out.ctypes.data_as(_F64P))
         if rc != 0:
             self._raise(rc)
         return out
@@ -856,8 +878,8 @@ class Ssimu2:
     def score_batch_against_reference_device(self, d_dists: int, item_stride_bytes: int, n: int) -> np.ndarray:
         """ssimu2_score_batch_against_reference_device against the reference of set_reference / set_reference_device."""
         out = np.zeros(int(n), np.float64)
-        rc = self._L.ssimu2_score_batch_against_reference_device(self._ctx, ctypes.c_void_p(d_dists),
-                                                                 int(item_stride_bytes), int(n), out.ctypes.data_as(_F64P))
+        rc = self._batch_fn("ssimu2_score_batch_against_reference_device")(self._ctx, ctypes.c_void_p(d_dists), int(item_stride_bytes),
+                                                                           int(n), out.ctypes.data_as(_F64P))
         if rc != 0:
             self._raise(rc)
         return out
