@@ -27,6 +27,8 @@ YUVA_LIB_PATH = os.environ.get("OAVIF_AMD_YUVA_LIB") or os.path.join(_HERE, "lib
 # the YUVA library's objects plus the batch calls of include/ssimu2_hip_rbatch.h, which score in every blur mode
 # (Ssimu2(..., rbatch=True))
 RBATCH_LIB_PATH = os.environ.get("OAVIF_AMD_RBATCH_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_rbatch.so")
+# the rbatch library's objects plus the 16-bit and YUV batches of include/ssimu2_hip_hbatch.h (Ssimu2(..., hbatch=True))
+HBATCH_LIB_PATH = os.environ.get("OAVIF_AMD_HBATCH_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_hbatch.so")
 
 OK = 0
 ERR_INVALID_ARG = -1
@@ -131,7 +133,7 @@ CODEC_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32,
 _vp, _ci, _u32, _sz, _f64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_double
 _u8p, _u16p, _u32p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint16), ctypes.POINTER(ctypes.c_uint32)
 _f32p, _f64p, _cip, _szp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_f64), ctypes.POINTER(_ci), ctypes.POINTER(_sz)
-_vpp, _u8pp = ctypes.POINTER(_vp), ctypes.POINTER(_u8p)
+_vpp, _u8pp, _u16pp = ctypes.POINTER(_vp), ctypes.POINTER(_u8p), ctypes.POINTER(_u16p)
 _P = ctypes.POINTER
 
 PUBLIC_FUNCTIONS = {   # include/ssimu2_hip.h, then include/oavif_tq.h
@@ -248,6 +250,15 @@ RBATCH_FUNCTIONS = {   # include/ssimu2_hip_rbatch.h: only liboavif_hip_rbatch.s
     "ssimu2_rbatch_score_against_reference_device": (_ci, [_vp, _vp, _sz, _u32, _f64p]),
 }
 
+HBATCH_FUNCTIONS = {   # include/ssimu2_hip_hbatch.h: only liboavif_hip_hbatch.so has these
+    "ssimu2_hbatch_score_rgb16": (_ci, [_vp, _u16pp, _u16pp, _u32, _u32, _u32, _u32, _f64p]),
+    "ssimu2_hbatch_score_against_reference_rgb16": (_ci, [_vp, _u16pp, _u32, _u32, _f64p]),
+    "ssimu2_hbatch_score_rgb16_device": (_ci, [_vp, _vp, _vp, _sz, _u32, _u32, _u32, _u32, _f64p]),
+    "ssimu2_hbatch_score_against_reference_rgb16_device": (_ci, [_vp, _vp, _sz, _u32, _u32, _f64p]),
+    "ssimu2_hbatch_score_against_reference_yuv": (_ci, [_vp, _P(YuvFrameC), _u32, _u32, _u32, _f64p]),
+    "ssimu2_hbatch_convert_yuv": (_ci, [_vp, _P(YuvFrameC), _u32, _u32, _u32, _u32, _u32, _u16p]),
+}
+
 EXPORTED_SYMBOLS = tuple(PUBLIC_FUNCTIONS)
 INSTR_SYMBOLS = tuple(HOOK_FUNCTIONS)
 EXT_SYMBOLS = tuple(EXT_FUNCTIONS)
@@ -256,6 +267,7 @@ MAP_SYMBOLS = tuple(MAP_FUNCTIONS)
 CHROMA_SYMBOLS = tuple(CHROMA_FUNCTIONS)
 YUVA_SYMBOLS = tuple(YUVA_FUNCTIONS)
 RBATCH_SYMBOLS = tuple(RBATCH_FUNCTIONS)
+HBATCH_SYMBOLS = tuple(HBATCH_FUNCTIONS)
 
 _lib = None
 _instr = None
@@ -265,6 +277,7 @@ _map = None
 _chroma = None
 _yuva = None
 _rbatch = None
+_hbatch = None
 
 
 def lib() -> ctypes.CDLL:
@@ -331,6 +344,14 @@ def rbatch_lib() -> ctypes.CDLL:
     return _rbatch
 
 
+def hbatch_lib() -> ctypes.CDLL:
+    """The 16-bit batch build (include/ssimu2_hip_hbatch.h): the batch library plus the batches of 16-bit and YUV frames."""
+    global _hbatch
+    if _hbatch is None:
+        _hbatch = _load(HBATCH_LIB_PATH)
+    return _hbatch
+
+
 def _load(path: str) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise ImportError(
@@ -347,7 +368,7 @@ def _load(path: str) -> ctypes.CDLL:
             pass
     L = ctypes.CDLL(path)
     for table in (PUBLIC_FUNCTIONS, HOOK_FUNCTIONS, EXT_FUNCTIONS, YUV_FUNCTIONS, MAP_FUNCTIONS, CHROMA_FUNCTIONS,
-                  YUVA_FUNCTIONS, RBATCH_FUNCTIONS):
+                  YUVA_FUNCTIONS, RBATCH_FUNCTIONS, HBATCH_FUNCTIONS):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name, None)   # a build older than a symbol lacks it (scripts/gpu_ab.py loads such builds)
             if fn is not None:

@@ -1080,14 +1080,37 @@ int batch_stage(ssimu2_ctx* c, DevBuf& buf, const uint8_t* const* frames, uint32
 // wherever it lies.
 constexpr size_t kRgBatchTail = (size_t)RG_TW * (RG_H_AHEAD_REF + 1);
 
+// Where the frames of a recursive batch lie on the device: item i's reference at refs + i * stride0 (null: every item
+// against the cached reference), its distorted frame at dists + i * stride0.  s16 null: tight 8-bit RGB; else tight
+// 16-bit frames read as *s16 describes (pitch, channels, table, top code; its px is not looked at).
+struct BatchFrames {
+    const void *refs, *dists;
+    size_t stride0;
+    const Src16* s16;
+};
+
+long long rg_batch_bands(uint32_t w, uint32_t h) {
+    return (long long)((w + PYR_BAND_W - 1) / PYR_BAND_W) * ((h + PYR_BAND_H - 1) / PYR_BAND_H);
+}
+
+// What a recursive batch is refused for once its sizes are known, before anything is allocated or enqueued: a grid or a
+// job count of one of its launches beyond 2^31 - 1.  `one`: an item's counts; `bands`: an item's conversion workgroups.
+int rg_batch_check_launch(ssimu2_ctx* c, const RgCounts& one, long long bands, uint32_t n) {
+    if ((long long)one.hblocks * n > 0x7fffffffLL || (long long)one.vblocks * n > 0x7fffffffLL || bands * n > 0x7fffffffLL)
+        return c->fail(SSIMU2_ERR_INVALID_ARG, "batch too large for one launch: fewer items per call");
+    return SSIMU2_OK;
+}
+
 // n items of w x h in SSIMU2_BLUR_RECURSIVE / _FMA: ONE k_pyramid_bands_xyb_batch, (pair form: ONE k_rg_h_batch<REF>
 // and ONE k_rg_v_emit_batch for the references,) ONE k_rg_h_batch, ONE k_rg_v_batch, ONE k_finalize_batch, one
 // synchronise.  Item i's planes are one block of the batch's own scratch -- pair form [xa 3][xb 3][cache 6][hbuf 9]
 // planes of every scale, against form [xb 3][hbuf 9] with xa and cache the context's cached reference (stride 0) --
 // each laid out inside as rg_build_plan lays the context's, so an item's jobs see the geometry of its single score.
-int rbatch_recursive(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dists, size_t stride0, uint32_t n,
-                     uint32_t w, uint32_t h, double* out_scores) {
-    const bool against_ref = d_refs == nullptr;
+// Where the items' frames come from (`fr`): 8-bit bytes or 16-bit frames (ssimu2_hbatch_*), for
+// which the one conversion launch is k_pyramid_bands_xyb16_batch.  Nothing behind the conversion knows which it was.
+int rbatch_recursive(ssimu2_ctx* c, const BatchFrames& fr, uint32_t n, uint32_t w, uint32_t h, double* out_scores) {
+    const bool against_ref = fr.refs == nullptr;
+    const size_t stride0 = fr.stride0;
     const Pyramid p = make_pyramid(w, h);
     const size_t ntot = rg_plane_off(p, p.nscales);
     const size_t item_planes = (against_ref ? 12 : 21) * ntot;  // floats between items
@@ -1098,13 +1121,12 @@ int rbatch_recursive(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dist
     const long long hb = one.hblocks, vb = one.vblocks;
     const size_t part_stride = one.part;
     const int nframes = against_ref ? 1 : 2;
-    const long long bands = (long long)((w + PYR_BAND_W - 1) / PYR_BAND_W) * ((h + PYR_BAND_H - 1) / PYR_BAND_H);
-    if (hb * n > 0x7fffffffLL || vb * n > 0x7fffffffLL || bands * nframes * n > 0x7fffffffLL)
-        return c->fail(SSIMU2_ERR_INVALID_ARG, "batch too large for one launch: fewer items per call");
+    const long long bands = rg_batch_bands(w, h);
+    int rc;
+    if ((rc = rg_batch_check_launch(c, one, bands * nframes, n))) return rc;
     auto& b = c->batch;
     const size_t dump_floats = p.nscales > 0 ? (size_t)rg_pitch(p.w[0]) + 16 : 16;
     const size_t res_bytes = (size_t)n * kResultDoubles * sizeof(double);
-    int rc;
     if ((rc = grow(c, b.rg_planes, ((size_t)n * item_planes + dump_floats + kRgBatchTail) * sizeof(float),
                    "hipMalloc(recursive batch planes: 84 bytes per pixel, scale and item; 48 against a reference)")) ||
         (rc = grow(c, b.rg_part, 16 + ((size_t)n * part_stride + 8) * sizeof(double), "hipMalloc(recursive batch partial sums)")))
@@ -1140,7 +1162,8 @@ int rbatch_recursive(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dist
     bp.part_stride = part_stride;
     if (p.nscales > 0) {  // a frame below 8 x 8 has no scale to score
         const bool fma = c->blur_mode == SSIMU2_BLUR_RECURSIVE_FMA;
-        const uint8_t* frames[2] = {against_ref ? d_dists : d_refs, d_dists};
+        const uint8_t* const d_dists = (const uint8_t*)fr.dists;
+        const uint8_t* frames[2] = {against_ref ? d_dists : (const uint8_t*)fr.refs, d_dists};
         float* none[2] = {nullptr, nullptr};
         PyrBatchArgs pb;
         pb.a = pyramid_args(p, nframes, frames, none);
@@ -1152,7 +1175,15 @@ int rbatch_recursive(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dist
         pb.a.zero4 = rp.q;
         pb.in_stride = stride0;
         pb.out_stride = item_planes;
-        launch(k_pyramid_bands_xyb_batch, dim3((unsigned)(bands * nframes * n)), dim3(PYR_THREADS), 0, c->stream, pb);
+        if (fr.s16) {  // both sides are read as *fr.s16 says: its pitch, table and top code, from their own first byte
+            Src16 ref16 = *fr.s16, dist16 = *fr.s16;
+            ref16.px = fr.refs, dist16.px = fr.dists;
+            const Src16* src[2] = {against_ref ? &dist16 : &ref16, &dist16};
+            const PyrHbdArgs hbd = hbd_args(nframes, src, nullptr);
+            launch(k_pyramid_bands_xyb16_batch<3>, dim3((unsigned)(bands * nframes * n)), dim3(PYR_THREADS), 0, c->stream, pb, hbd);
+        } else {
+            launch(k_pyramid_bands_xyb_batch, dim3((unsigned)(bands * nframes * n)), dim3(PYR_THREADS), 0, c->stream, pb);
+        }
         if (!against_ref) {
             launch(fma ? k_rg_h_batch<true, true> : k_rg_h_batch<false, true>, dim3((unsigned)(hb * n)), dim3(128), 0, c->stream, bp);
             launch(fma ? k_rg_v_emit_batch<true, 2> : k_rg_v_emit_batch<false, 2>, dim3((unsigned)(vb * n)), dim3(128), 0, c->stream, bp);
@@ -1188,7 +1219,32 @@ int ssimu2h::rbatch_stage(ssimu2_ctx* c, bool ref, const uint8_t* const* frames,
 
 int ssimu2h::rbatch_run(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dists, size_t stride0, uint32_t n, uint32_t w,
                         uint32_t h, double* out_scores) {
-    return (c->blur_mode == SSIMU2_BLUR_FIR ? batch_run : rbatch_recursive)(c, d_refs, d_dists, stride0, n, w, h, out_scores);
+    if (c->blur_mode == SSIMU2_BLUR_FIR) return batch_run(c, d_refs, d_dists, stride0, n, w, h, out_scores);
+    return rbatch_recursive(c, {d_refs, d_dists, stride0, nullptr}, n, w, h, out_scores);
+}
+
+// ---- 16-bit and YUV batches (include/ssimu2_hip_hbatch.h) -------------------
+int ssimu2h::hbatch_buffer(ssimu2_ctx* c, int which, size_t bytes, uint8_t** d_buf) {
+    DevBuf& buf = which == 0 ? c->batch.h16_ref : which == 1 ? c->batch.h16_dist : c->batch.yuv_planes;
+    const int rc = grow(c, buf, bytes + 16, "hipMalloc(16-bit batch frames)");
+    *d_buf = buf.as<uint8_t>();
+    return rc;
+}
+
+int ssimu2h::hbatch_table(ssimu2_ctx* c, uint32_t depth, const float** tab) {
+    return device_table(c, 1u << depth, (1u << depth) - 1u, tab);
+}
+
+int ssimu2h::hbatch_run(ssimu2_ctx* c, const void* d_refs, const void* d_dists, size_t stride0, uint32_t n, uint32_t w,
+                        uint32_t h, const float* tab, uint32_t depth, double* out_scores) {
+    const Src16 tight{nullptr, w * 6u, 3u, tab, (1u << depth) - 1u};
+    return rbatch_recursive(c, {d_refs, d_dists, stride0, &tight}, n, w, h, out_scores);
+}
+
+int ssimu2h::hbatch_check_launch(ssimu2_ctx* c, uint32_t n, uint32_t w, uint32_t h, bool against_reference) {
+    RgPlan rp;
+    const RgCounts one = rg_plan_geometry(make_pyramid(w, h), &rp);
+    return rg_batch_check_launch(c, one, rg_batch_bands(w, h) * (against_reference ? 1 : 2), n);
 }
 
 extern "C" {

@@ -2,7 +2,7 @@
 // (which defines everything declared here but the front ends' own feed builders, marked below) and the translation
 // units that add an input form -- ssimu2_ext.hip (RGBA), ssimu2_yuv.hip (YUV), ssimu2_chroma.hip (4:2:2 and 4:2:0
 // YUV), ssimu2_yuva.hip (YUV with an alpha plane) -- or a call over those forms -- ssimu2_map.hip (error maps of 16-bit, RGBA and YUV frames),
-// ssimu2_rbatch.hip (batches in every blur mode).  Private to oavif_amd/csrc: nothing here is exported,
+// ssimu2_rbatch.hip (batches in every blur mode), ssimu2_hbatch.hip (16-bit and YUV batches).  Private to oavif_amd/csrc: nothing here is exported,
 // and a caller sees include/*.h only.
 //
 // A front end turns a caller's frame into a Feed -- where its rows are, how they get onto the device, what kernel of
@@ -119,10 +119,13 @@ struct ssimu2_ctx {
     // 8-bit frames of the host-pointer forms, the linear pyramids (scales 1..5) and partial sums of every item, and the
     // page-locked result block k_finalize_batch writes (110 doubles per item).  rg_planes / rg_part: rbatch_run, by
     // the first batch in a recursive mode -- every item's planes, then one dump row; the job
-    // cursor's four words, then every item's partial sums
+    // cursor's four words, then every item's partial sums.  h16_ref / h16_dist / yuv_planes: the calls of
+    // include/ssimu2_hip_hbatch.h -- the staged 16-bit frames of the host-pointer forms or the
+    // codes of a YUV batch, and the staged planes of a YUV batch
     struct {
         DevBuf u8_ref, u8_dist, lin_ref, lin_dist, part;
         DevBuf rg_planes, rg_part;
+        DevBuf h16_ref, h16_dist, yuv_planes;
         DevBuf result{nullptr, 0, true};
     } batch;
     uint32_t batch_n = 0;  // items of the last finished batch (ssimu2_last_batch_averages)
@@ -309,6 +312,21 @@ int rbatch_stage(ssimu2_ctx* c, bool ref, const uint8_t* const* frames, uint32_t
                  const uint8_t** d_frames);
 int rbatch_run(ssimu2_ctx* c, const uint8_t* d_refs, const uint8_t* d_dists, size_t stride0, uint32_t n, uint32_t w,
                uint32_t h, double* out_scores);
+
+// ---- 16-bit and YUV batches (include/ssimu2_hip_hbatch.h) -------------------
+// What ssimu2_hbatch.hip's calls are made of, beside rbatch_open and rbatch_check_size.  hbatch_buffer: one of the
+// batch group's three buffers of that unit -- 0: the references' 16-bit frames, 1: the distorted side's frames or the
+// codes of a YUV batch, 2: the staged planes of a YUV batch -- holding `bytes` bytes and 16 of slack.  hbatch_table:
+// the device table of `depth`, as a single 16-bit call reads it.  hbatch_run, recursive modes only: n items of tight
+// u16 RGB frames of w x h on the device, d_dists + i * stride0 against d_refs + i * stride0 or (d_refs null) against
+// the cached reference, read through `tab` with samples above 2^depth - 1 clamped; blocking, fills the batch result
+// block like rbatch_run.  hbatch_check_launch: the "fewer items per call" refusal hbatch_run would make; every form
+// makes it itself first, before it allocates (the depth's table, the staging buffers) or copies anything.
+int hbatch_buffer(ssimu2_ctx* c, int which, size_t bytes, uint8_t** d_buf);
+int hbatch_table(ssimu2_ctx* c, uint32_t depth, const float** tab);
+int hbatch_check_launch(ssimu2_ctx* c, uint32_t n, uint32_t w, uint32_t h, bool against_reference);
+int hbatch_run(ssimu2_ctx* c, const void* d_refs, const void* d_dists, size_t stride0, uint32_t n, uint32_t w, uint32_t h,
+               const float* tab, uint32_t depth, double* out_scores);
 
 // ---- what the front ends build their feeds with, for the units above them -------------------------
 // A tight frame of u16 samples of depth `bit_depth` in host memory, and the 16-bit calls' argument checks (the ctx is

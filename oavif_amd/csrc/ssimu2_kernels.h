@@ -16,6 +16,7 @@
 //                  scale, then their sum at full resolution
 //   k_pyramid_bands16, k_pyramid_bands_xyb16, k_march_lin, k_march_refblur_lin : 16-bit input
 //                  (ssimu2_*_rgb16 / _strided16)
+//   k_pyramid_bands_xyb16_batch : the 16-bit conversion of a whole batch (ssimu2_hbatch_*)
 //
 // Arithmetic contract: this translation unit is compiled with -ffp-contract=off;
 // every fused multiply-add is an explicit fmaf().  The sequence of IEEE operations per pixel
@@ -279,10 +280,12 @@ __device__ __forceinline__ void pyr_lds_level(const float* src, int sw, int sh, 
 // Linear values of one thread's 4 x 4 block of a 16-bit frame: per row 2 * CH contiguous dwords
 // (24 / 32 bytes, unaligned dword loads), all four rows in flight before the table gathers; at the
 // frame border clamped coordinates, one 16-bit load per sample.
-template <int CH>
+// BATCH (k_pyramid_bands_xyb16_batch): the frame lies `in_off` bytes behind hb.in[f] -- item i of a batch.
+template <int CH, bool BATCH = false>
 __device__ __forceinline__ void pyr_load16(const PyrHbdArgs& hb, int f, int w0, int h0, int X0, int Y0, bool inside,
-                                           float (&lin)[4][4][3]) {
+                                           float (&lin)[4][4][3], size_t in_off = 0) {
     const uint8_t* base = hb.in[f];
+    if constexpr (BATCH) base += in_off;
     const uint32_t pitch = hb.pitch[f], maxv = hb.maxv[f];
     const float* tab = hb.tab[f];
     uint32_t s[4][4][3];
@@ -395,7 +398,7 @@ __device__ __forceinline__ void pyramid_band(const PyrBandArgs& a, int band, flo
     float v2[3] = {0.f, 0.f, 0.f};  // this thread's level-2 output
     if (work) {
         float lin16[4][4][3];  // CH16: linear values of this thread's 4 x 4 pixels
-        if constexpr (CH16 != 0) pyr_load16<CH16>(*hb, f, w0, h0, X0, Y0, inside, lin16);
+        if constexpr (CH16 != 0) pyr_load16<CH16, BATCH>(*hb, f, w0, h0, X0, Y0, inside, lin16, in_off);
         // byte 3*i + c of a row = channel c of pixel i
 #define PYR_LIN(j, i, c) \
     (CH16 ? lin16[j][i][c] : lut[(raw[j][(3 * (i) + (c)) >> 2] >> (8 * ((3 * (i) + (c)) & 3))) & 255u])
@@ -594,6 +597,21 @@ __global__ __launch_bounds__(PYR_THREADS) void k_pyramid_bands_xyb16(PyrBandArgs
     if (blockIdx.x == 0 && threadIdx.x < 4 && a.zero4) a.zero4[threadIdx.x] = 0u;  // k_rg_v starts after this launch has ended
     __syncthreads();
     pyramid_band<true, CH>(a, (int)blockIdx.x, nullptr, s_tiles, &hb);
+}
+
+// The 16-bit batch of the recursive modes (ssimu2_hbatch_*): `b` as k_pyramid_bands_xyb_batch
+// takes it, in_stride the bytes between the 16-bit frames of consecutive items, and `hb` describes item 0's frames --
+// one pitch, table and top code for the whole batch.  Grid: [item][frame][band]; per frame the arithmetic of
+// k_pyramid_bands_xyb16, so an item's planes do not depend on the batch.
+template <int CH>
+__global__ __launch_bounds__(PYR_THREADS) void k_pyramid_bands_xyb16_batch(PyrBatchArgs b, PyrHbdArgs hb) {
+    __shared__ float s_tiles[PYR_BAND_LDS_FLOATS];
+    if (blockIdx.x == 0 && threadIdx.x < 4 && b.a.zero4) b.a.zero4[threadIdx.x] = 0u;  // k_rg_v_batch starts after this launch has ended
+    __syncthreads();
+    const int per_item = b.a.bands_x * b.a.bands_y * b.a.nframes;
+    const int item = (int)blockIdx.x / per_item;
+    pyramid_band<true, CH, true>(b.a, (int)blockIdx.x - item * per_item, nullptr, s_tiles, &hb, (size_t)item * b.in_stride,
+                                 (size_t)item * b.out_stride);
 }
 
 // ---- fused per-scale kernel, marching form, all scales in one launch ----------------------------

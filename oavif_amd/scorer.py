@@ -265,10 +265,12 @@ class Ssimu2:
     chroma = False     # bound to liboavif_hip_chroma.so (4:2:2 / 4:2:0 frames, include/ssimu2_hip_chroma.h, and all of the above)
     yuva = False       # bound to liboavif_hip_yuva.so (YUV frames with an alpha plane, include/ssimu2_hip_yuva.h, and all of the above)
     rbatch = False     # bound to liboavif_hip_rbatch.so (batches in every blur mode, include/ssimu2_hip_rbatch.h, and all of the above)
+    hbatch = False     # bound to liboavif_hip_hbatch.so (16-bit and YUV batches, include/ssimu2_hip_hbatch.h, and all of the above)
 
     def __init__(self, device: int = 0, stream: int | None = None, instrumented: bool = False,
                  blur: int | None = None, service: str | None = None, extended: bool = False, yuv: bool = False,
-                 maps: bool = False, chroma: bool = False, yuva: bool = False, rbatch: bool = False):
+                 maps: bool = False, chroma: bool = False, yuva: bool = False, rbatch: bool = False,
+                 hbatch: bool = False):
         """`service`: socket path of a running scoring service (oavif_amd.service): the context lives there, and this
         process makes no HIP call for it (OAVIF_SCORER_SOCKET set around ssimu2_ctx_create, then restored; None = the
         environment as it is).  `instrumented=True` binds liboavif_hip_instr.so (the hooks of
@@ -291,7 +293,14 @@ class Ssimu2:
         binds liboavif_hip_rbatch.so: everything `yuva=True` has, and score_batch, score_batch_against_reference and
         their _device forms go through the calls of include/ssimu2_hip_rbatch.h, which batch in the context's blur
         mode, the recursive ones included (without it they are SSIMU2_ERR_UNSUPPORTED there); not together with
-        `instrumented`."""
+        `instrumented`.  `hbatch=True` binds liboavif_hip_hbatch.so: everything `rbatch=True` has, and the batches of
+        16-bit and YUV frames of include/ssimu2_hip_hbatch.h, which run in the recursive blur modes (score_batch_hbd,
+        score_batch_against_reference_hbd, their _device forms, score_batch_against_reference_yuv, convert_yuv_batch);
+        not together with `instrumented`."""
+        if instrumented and hbatch:
+            raise ValueError("instrumented=True and hbatch=True are different libraries: choose one")
+        self.hbatch = bool(hbatch)
+        rbatch = bool(rbatch or hbatch)
         if instrumented and rbatch:
             raise ValueError("instrumented=True and rbatch=True are different libraries: choose one")
         self.rbatch = bool(rbatch)
@@ -312,7 +321,7 @@ class Ssimu2:
         # a yuva context scores against RGBA references and beside RGBA frames: the RGBA methods come with it
         self.instrumented, self.extended = bool(instrumented), bool(extended or yuva)
         self.yuv, self.maps = bool(yuv or chroma), bool(maps or chroma)
-        self._L = (_lib.instr_lib() if instrumented else _lib.rbatch_lib() if rbatch else _lib.yuva_lib() if yuva else _lib.chroma_lib() if chroma else _lib.map_lib() if maps
+        self._L = (_lib.instr_lib() if instrumented else _lib.hbatch_lib() if hbatch else _lib.rbatch_lib() if rbatch else _lib.yuva_lib() if yuva else _lib.chroma_lib() if chroma else _lib.map_lib() if maps
                    else _lib.yuv_lib() if yuv else _lib.ext_lib() if extended else _lib.lib())
         self._ctx = ctypes.c_void_p()
         self._holder = None
@@ -882,6 +891,100 @@ class Ssimu2:
                                                                            int(n), out.ctypes.data_as(_F64P))
         if rc != 0:
             self._raise(rc)
+        return out
+
+    # -- batches of 16-bit and YUV frames (include/ssimu2_hip_hbatch.h, DESIGN.md section 19): the hbatch library only --
+    def _need_hbatch(self):
+        if not self.hbatch:
+            raise Ssimu2Error(_lib.ERR_UNSUPPORTED, "batches of 16-bit and YUV frames need Ssimu2(..., hbatch=True) "
+                                                    "(liboavif_hip_hbatch.so)")
+
+    @staticmethod
+    def _check_batch16(frames, name: str):
+        """[N, h, w, 3] uint16 or a sequence of (h, w, 3) uint16 -> list of contiguous frames of one size."""
+        out = [_check_rgb16(f, f"{name}[{i}]") for i, f in enumerate(frames)]
+        if any(f.shape != out[0].shape for f in out):
+            raise ValueError(f"{name}: the frames of a batch must have one size")
+        return out
+
+    @staticmethod
+    def _ptr_array16(frames):
+        return (ctypes.POINTER(ctypes.c_uint16) * len(frames))(*[_u16p(f) for f in frames])
+
+    def score_batch_hbd(self, refs, dists, bit_depth: int) -> np.ndarray:
+        """ssimu2_hbatch_score_rgb16: N pairs of (h, w, 3) uint16 frames of `bit_depth` bits and one size in one launch
+        set -> float64 scores in input order, each with the bits of compute_ssimu2_hbd.  Recursive blur modes only.
+        A cached reference is kept."""
+        self._need_hbatch()
+        refs, dists = self._check_batch16(refs, "refs"), self._check_batch16(dists, "dists")
+        if len(refs) != len(dists):
+            raise ValueError("refs and dists must hold the same number of frames")
+        if not refs:
+            return np.zeros(0, np.float64)
+        if refs[0].shape != dists[0].shape:
+            raise ValueError("refs and dists must have the same shape")
+        h, w, _ = refs[0].shape
+        return self._scores(self._L.ssimu2_hbatch_score_rgb16, len(refs), self._ptr_array16(refs), self._ptr_array16(dists),
+                            len(refs), w, h, int(bit_depth))
+
+    def score_batch_against_reference_hbd(self, dists, bit_depth: int) -> np.ndarray:
+        """ssimu2_hbatch_score_against_reference_rgb16: N uint16 frames against the cached reference (kept), each with
+        the bits of score_against_reference_hbd."""
+        self._need_hbatch()
+        dists = self._check_batch16(dists, "dists")
+        if not dists:
+            return np.zeros(0, np.float64)
+        self._check_ref_shape(dists[0].shape)
+        return self._scores(self._L.ssimu2_hbatch_score_against_reference_rgb16, len(dists), self._ptr_array16(dists),
+                            len(dists), int(bit_depth))
+
+    def score_batch_hbd_device(self, d_refs: int, d_dists: int, item_stride_bytes: int, n: int, w: int, h: int,
+                               bit_depth: int) -> np.ndarray:
+        """ssimu2_hbatch_score_rgb16_device: item i at d_refs + i * item_stride_bytes / d_dists + i * item_stride_bytes
+        (tight uint16 frames; the stride even, any multiple of 2)."""
+        self._need_hbatch()
+        return self._scores(self._L.ssimu2_hbatch_score_rgb16_device, n, ctypes.c_void_p(d_refs), ctypes.c_void_p(d_dists),
+                            int(item_stride_bytes), int(n), int(w), int(h), int(bit_depth))
+
+    def score_batch_against_reference_hbd_device(self, d_dists: int, item_stride_bytes: int, n: int, bit_depth: int) -> np.ndarray:
+        """ssimu2_hbatch_score_against_reference_rgb16_device against the cached reference."""
+        self._need_hbatch()
+        return self._scores(self._L.ssimu2_hbatch_score_against_reference_rgb16_device, n, ctypes.c_void_p(d_dists),
+                            int(item_stride_bytes), int(n), int(bit_depth))
+
+    def _yuv_batch(self, frames, chroma_upsampling):
+        """-> (the frames, their C array, the upsampling code) of a YUV batch: YuvFrames of one size, none with an alpha
+        plane (refused: the C struct of a batch has no room for one, and dropping it would score another image)."""
+        self._need_hbatch()
+        frames = [self._yuv_frame(f, f"frames[{i}]") for i, f in enumerate(frames)]
+        for i, f in enumerate(frames):
+            if f.alpha is not None:
+                raise ValueError(f"frames[{i}] carries an alpha plane, which a YUV batch does not composite: score it "
+                                 "with score_against_reference_yuva")
+        up, = self._chroma_args(chroma_upsampling, *frames)
+        if any((f.height, f.width) != (frames[0].height, frames[0].width) for f in frames):
+            raise ValueError("frames: the frames of a batch must have one size")
+        arr = (_lib.YuvFrameC * max(len(frames), 1))(*[f.as_c() for f in frames])
+        return frames, arr, up
+
+    def score_batch_against_reference_yuv(self, frames, rgb_depth: int = 16, chroma_upsampling: str = "bilinear") -> np.ndarray:
+        """ssimu2_hbatch_score_against_reference_yuv: N YuvFrames of one size, depth, format, range and matrix (no alpha
+        plane) against the cached reference (kept), each with the bits of score_against_reference_yuv."""
+        frames, arr, up = self._yuv_batch(frames, chroma_upsampling)
+        if not frames:
+            return np.zeros(0, np.float64)
+        self._check_ref_shape((frames[0].height, frames[0].width), "frame size")
+        return self._scores(self._L.ssimu2_hbatch_score_against_reference_yuv, len(frames), arr, len(frames), int(rgb_depth), up)
+
+    def convert_yuv_batch(self, frames, rgb_depth: int = 16, chroma_upsampling: str = "bilinear") -> np.ndarray:
+        """ssimu2_hbatch_convert_yuv: the (n, h, w, 3) uint16 codes the scorer makes of the N frames of a YUV batch, item
+        i with the bits of convert_yuv(frames[i])."""
+        frames, arr, up = self._yuv_batch(frames, chroma_upsampling)
+        if not frames:
+            return np.zeros((0, 0, 0, 3), np.uint16)
+        h, w = frames[0].height, frames[0].width
+        out = np.empty((len(frames), h, w, 3), np.uint16)
+        self._call(self._L.ssimu2_hbatch_convert_yuv, arr, len(frames), w, h, int(rgb_depth), up, _u16p(out))
         return out
 
     def last_batch_averages(self, item: int):
