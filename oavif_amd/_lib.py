@@ -29,6 +29,9 @@ YUVA_LIB_PATH = os.environ.get("OAVIF_AMD_YUVA_LIB") or os.path.join(_HERE, "lib
 RBATCH_LIB_PATH = os.environ.get("OAVIF_AMD_RBATCH_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_rbatch.so")
 # the rbatch library's objects plus the 16-bit and YUV batches of include/ssimu2_hip_hbatch.h (Ssimu2(..., hbatch=True))
 HBATCH_LIB_PATH = os.environ.get("OAVIF_AMD_HBATCH_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_hbatch.so")
+# the hbatch library's objects plus the batches of RGBA and YUV-with-alpha frames of include/ssimu2_hip_abatch.h
+# (Ssimu2(..., abatch=True))
+ABATCH_LIB_PATH = os.environ.get("OAVIF_AMD_ABATCH_LIB") or os.path.join(_HERE, "lib", "liboavif_hip_abatch.so")
 
 OK = 0
 ERR_INVALID_ARG = -1
@@ -259,6 +262,14 @@ HBATCH_FUNCTIONS = {   # include/ssimu2_hip_hbatch.h: only liboavif_hip_hbatch.s
     "ssimu2_hbatch_convert_yuv": (_ci, [_vp, _P(YuvFrameC), _u32, _u32, _u32, _u32, _u32, _u16p]),
 }
 
+ABATCH_FUNCTIONS = {   # include/ssimu2_hip_abatch.h: only liboavif_hip_abatch.so has these
+    "ssimu2_abatch_score_against_reference_yuva": (_ci, [_vp, _P(YuvaFrameC), _u32, _u32, _u32, _f64p]),
+    "ssimu2_abatch_composite_yuva": (_ci, [_vp, _P(YuvaFrameC), _u32, _u32, _u32, _u32, _u32, _u32, _u16p]),
+    "ssimu2_abatch_score_against_reference_rgba8": (_ci, [_vp, _u8pp, _u32, _u32, _f64p]),
+    "ssimu2_abatch_score_rgba8": (_ci, [_vp, _u8pp, _u32, _u8pp, _u32, _u32, _u32, _u32, _u32, _f64p]),
+    "ssimu2_abatch_composite_rgba8": (_ci, [_vp, _u8pp, _u32, _u32, _u32, _u32, _u32, _u16p]),
+}
+
 EXPORTED_SYMBOLS = tuple(PUBLIC_FUNCTIONS)
 INSTR_SYMBOLS = tuple(HOOK_FUNCTIONS)
 EXT_SYMBOLS = tuple(EXT_FUNCTIONS)
@@ -268,6 +279,7 @@ CHROMA_SYMBOLS = tuple(CHROMA_FUNCTIONS)
 YUVA_SYMBOLS = tuple(YUVA_FUNCTIONS)
 RBATCH_SYMBOLS = tuple(RBATCH_FUNCTIONS)
 HBATCH_SYMBOLS = tuple(HBATCH_FUNCTIONS)
+ABATCH_SYMBOLS = tuple(ABATCH_FUNCTIONS)
 
 _lib = None
 _instr = None
@@ -278,6 +290,7 @@ _chroma = None
 _yuva = None
 _rbatch = None
 _hbatch = None
+_abatch = None
 
 
 def lib() -> ctypes.CDLL:
@@ -352,6 +365,15 @@ def hbatch_lib() -> ctypes.CDLL:
     return _hbatch
 
 
+def abatch_lib() -> ctypes.CDLL:
+    """The alpha batch build (include/ssimu2_hip_abatch.h): the 16-bit batch library plus the batches of RGBA and
+    YUV-with-alpha frames."""
+    global _abatch
+    if _abatch is None:
+        _abatch = _load(ABATCH_LIB_PATH)
+    return _abatch
+
+
 def _load(path: str) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise ImportError(
@@ -368,7 +390,7 @@ def _load(path: str) -> ctypes.CDLL:
             pass
     L = ctypes.CDLL(path)
     for table in (PUBLIC_FUNCTIONS, HOOK_FUNCTIONS, EXT_FUNCTIONS, YUV_FUNCTIONS, MAP_FUNCTIONS, CHROMA_FUNCTIONS,
-                  YUVA_FUNCTIONS, RBATCH_FUNCTIONS, HBATCH_FUNCTIONS):
+                  YUVA_FUNCTIONS, RBATCH_FUNCTIONS, HBATCH_FUNCTIONS, ABATCH_FUNCTIONS):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name, None)   # a build older than a symbol lacks it (scripts/gpu_ab.py loads such builds)
             if fn is not None:

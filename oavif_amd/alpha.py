@@ -181,6 +181,80 @@ def search_rgba(source_rgba, options, background, scorer: Ssimu2 | None = None, 
     return out
 
 
+def search_rgba_speculative_frames(scorer: Ssimu2, source_rgba, background, codec_frame, score_tgt: float = 80.0,
+                                   tolerance: float = 2.0, max_pass: int = 6, max_fanout: int = 4, first_wave_fanout: int = 1,
+                                   score_yuv: bool = True, rgb_depth: int = 8, chroma_upsampling: str = "bilinear"):
+    """The core of search_rgba_speculative, over any codec: codec_frame(q) -> (frame, avif size), where `frame` is what
+    avif_bridge.decode_yuv (`score_yuv`: `planes`, `depth`, `format`, `full_range`, `matrix_coefficients`, `alpha`,
+    `alpha_premultiplied`) or avif_bridge.decode_common (else: `channels`, `rows`, `pixels()`) leaves behind, with
+    `height`, `width` and `close()`.  The reference is set once, from `source_rgba` over `background`; the waves are
+    tq.speculative_frame_waves'; a wave of tq.MIN_BATCHED_WAVE or more frames of one kind is one
+    score_batch_against_reference_yuva (`score_yuv`) or score_batch_against_reference_rgba call on `scorer`, an
+    Ssimu2(..., abatch=True) in a recursive blur mode; a smaller or mixed wave goes through the single calls search_rgba
+    makes.  -> (TQResult, SpecStats, {q: avif size})."""
+    from . import tq
+    if not getattr(scorer, "abatch", False):
+        raise ValueError("search_rgba_speculative needs an Ssimu2(..., abatch=True) context: without the batch library "
+                         "every wave would be scored frame by frame (use search_rgba for that)")
+    if np.asarray(source_rgba).ndim != 3 or np.asarray(source_rgba).shape[2] != 4:
+        raise ValueError("search_rgba_speculative needs an (h, w, 4) RGBA source")
+    src = as_rgba(source_rgba)
+    scorer.set_reference_rgba(src, background)
+    how = (int(rgb_depth), chroma_upsampling)
+    least = tq.MIN_BATCHED_WAVE   # DESIGN.md section 20: the measurement gave no reason to raise it for frames with alpha
+
+    def kind(frame):
+        return (frame.depth, frame.format, int(frame.full_range), frame.matrix_coefficients, frame.alpha is None)
+
+    def rgba_of(frame):
+        return frame.pixels() if frame.channels == 4 else as_rgba(frame.pixels())   # no alpha plane left: opaque
+
+    def score_frames(frames):
+        if score_yuv:
+            if len(frames) >= least and all(kind(f) == kind(frames[0]) for f in frames):
+                return list(scorer.score_batch_against_reference_yuva([yuva_frame(f) for f in frames], *how))
+            return [scorer.score_against_reference_yuva(yuva_frame(f), *how) for f in frames]
+        if len(frames) >= least:
+            return list(scorer.score_batch_against_reference_rgba([rgba_of(f) for f in frames]))
+        return [scorer.score_against_reference_rgba(f.rows if f.channels == 4 else as_rgba(f.pixels())) for f in frames]
+
+    return tq.speculative_frame_waves(codec_frame, score_frames, src.shape[:2], score_tgt, tolerance, max_pass, max_fanout,
+                                      first_wave_fanout)
+
+
+def search_rgba_speculative(source_rgba, options, background, scorer: Ssimu2 | None = None, score_tgt: float | None = None,
+                            tolerance: float | None = None, max_pass: int | None = None, max_fanout: int = 4,
+                            first_wave_fanout: int = 1, score_yuv: bool = True, rgb_depth: int = 8,
+                            chroma_upsampling: str = "bilinear"):
+    """search_rgba with several probes in flight on ONE context: the encodes and decodes of a wave run on `max_fanout`
+    threads (one avif_bridge.EncoderSource, whose encode calls are independent), and a wave of tq.MIN_BATCHED_WAVE or
+    more frames is scored by one batch call of include/ssimu2_hip_abatch.h (search_rgba_speculative_frames).  `scorer`: an
+    Ssimu2(..., abatch=True) in a recursive blur mode; None = one in _lib.BLUR_RECURSIVE on device 0 for the duration of
+    the call.  An item of a batch has the bits of its single score and the speculative search equals the sequential one,
+    so with the same codec and blur mode q, num_pass, history and scores are search_rgba's.
+    -> (tq.TQResult, tq.SpecStats, {q: avif size})."""
+    from . import avif_bridge as ab
+    src = as_rgba(source_rgba) if np.asarray(source_rgba).ndim == 3 and np.asarray(source_rgba).shape[2] == 4 else None
+    if src is None:
+        raise ValueError("search_rgba_speculative needs an (h, w, 4) RGBA source")
+    depth = ab.output_depth(options.tenbit, False)
+    own = scorer is None
+    s = Ssimu2(0, blur=_lib.BLUR_RECURSIVE, abatch=True) if own else scorer
+    try:
+        with ab.EncoderSource(ab.prescale_source(src, depth), depth, options) as enc:
+            def codec_frame(q: int):
+                data = enc.encode(options, int(q))
+                return (ab.decode_yuv(data) if score_yuv else ab.decode_common(data)), len(data)
+
+            return search_rgba_speculative_frames(
+                s, src, background, codec_frame, options.score_tgt if score_tgt is None else score_tgt,
+                options.tolerance if tolerance is None else tolerance, options.max_pass if max_pass is None else max_pass,
+                max_fanout, first_wave_fanout, score_yuv, rgb_depth, chroma_upsampling)
+    finally:
+        if own:
+            s.close()
+
+
 def main(argv=None) -> int:
     a = parse_args(argv)
     if is_avif(a.ref) or is_avif(a.dist):

@@ -1,7 +1,7 @@
-"""Build the gfx950 shared libraries in-tree (oavif_amd/lib/liboavif_hip.so and its eight siblings).
+"""Build the gfx950 shared libraries in-tree (oavif_amd/lib/liboavif_hip.so and its nine siblings).
 
 Every source is compiled once, to an object under oavif_amd/lib/obj; the libraries are links of those objects
-(LIBRARIES, and MAP_LIBRARIES, CHROMA_LIBRARIES, YUVA_LIBRARIES, RBATCH_LIBRARIES and HBATCH_LIBRARIES beside it).  hipcc cross-compiles without a GPU; the built libraries are git-ignored.
+(LIBRARIES, and MAP_LIBRARIES, CHROMA_LIBRARIES, YUVA_LIBRARIES, RBATCH_LIBRARIES, HBATCH_LIBRARIES and ABATCH_LIBRARIES beside it).  hipcc cross-compiles without a GPU; the built libraries are git-ignored.
 """
 from __future__ import annotations
 
@@ -23,6 +23,7 @@ CHROMA_LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip_chroma.so")  # + include/s
 YUVA_LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip_yuva.so")      # + include/ssimu2_hip_yuva.h (YUV with an alpha plane, section 17)
 RBATCH_LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip_rbatch.so")  # + include/ssimu2_hip_rbatch.h (batches in every blur mode, section 18)
 HBATCH_LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip_hbatch.so")  # + include/ssimu2_hip_hbatch.h (16-bit and YUV batches, section 19)
+ABATCH_LIB_PATH = os.path.join(LIB_DIR, "liboavif_hip_abatch.so")  # + include/ssimu2_hip_abatch.h (RGBA and YUV-with-alpha batches, section 20)
 HOST_PATH = os.path.join(LIB_DIR, "oavif_host")   # csrc/oavif_host.c: main.zig's flow in C over the two public headers + libavif
 SERVICE_PATH = os.path.join(LIB_DIR, "oavif_scored")  # csrc/oavif_scored.cpp: the resident scoring service
 OBJ_DIR = os.path.join(LIB_DIR, "obj")  # one object per source, whichever libraries it is linked into
@@ -52,6 +53,9 @@ RBATCH_LIBRARIES = {RBATCH_LIB_PATH: RBATCH_SOURCES}
 # The ninth library, in a sixth table: the rbatch library's objects plus one unit over ssimu2_host.h (hbatch_units()).
 HBATCH_SOURCES = [*RBATCH_SOURCES, "ssimu2_hbatch.hip"]
 HBATCH_LIBRARIES = {HBATCH_LIB_PATH: HBATCH_SOURCES}
+# The tenth library, in a seventh table: the hbatch library's objects plus one unit over ssimu2_host.h (abatch_units()).
+ABATCH_SOURCES = [*HBATCH_SOURCES, "ssimu2_abatch.hip"]
+ABATCH_LIBRARIES = {ABATCH_LIB_PATH: ABATCH_SOURCES}
 MAX_COMPILES = 6  # compiles in flight; never the machine's CPU count
 _PROGRAMS = ("oavif_host.c", "oavif_scored.cpp")  # linked against the library, not into it
 # The flags that shape device code: the libraries' compile lines, the ISA tests and scripts/isa_ab.py all take them here.
@@ -111,8 +115,15 @@ def hbatch_units():
     return list(dict.fromkeys(s for sources in HBATCH_LIBRARIES.values() for s in sources if s not in have))
 
 
+def abatch_units():
+    """The sources of ABATCH_LIBRARIES that none of the other six tables has: compiled once each."""
+    have = {*compile_units(), *map_units(), *chroma_units(), *yuva_units(), *rbatch_units(), *hbatch_units()}
+    return list(dict.fromkeys(s for sources in ABATCH_LIBRARIES.values() for s in sources if s not in have))
+
+
 def libs_need_build() -> bool:
-    libs = (*LIBRARIES, *MAP_LIBRARIES, *CHROMA_LIBRARIES, *YUVA_LIBRARIES, *RBATCH_LIBRARIES, *HBATCH_LIBRARIES)
+    libs = (*LIBRARIES, *MAP_LIBRARIES, *CHROMA_LIBRARIES, *YUVA_LIBRARIES, *RBATCH_LIBRARIES, *HBATCH_LIBRARIES,
+            *ABATCH_LIBRARIES)
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
@@ -169,21 +180,21 @@ def _run_to(target: str, cmd, verbose: bool) -> None:
 
 
 def _build_libs(verbose: bool) -> None:
-    """Objects, then links: each unit of compile_units(), map_units(), chroma_units(), yuva_units(), rbatch_units() and
-    hbatch_units() to OBJ_DIR (MAX_COMPILES at a time), each library of the six tables from its own."""
+    """Objects, then links: each unit of compile_units(), map_units(), chroma_units(), yuva_units(), rbatch_units(),
+    hbatch_units() and abatch_units() to OBJ_DIR (MAX_COMPILES at a time), each library of the seven tables from its own."""
     os.makedirs(OBJ_DIR, exist_ok=True)
     flags = [*DEVICE_FLAGS, "-fPIC",
              "-fvisibility=hidden", "-fvisibility-inlines-hidden",  # exports = the headers' functions
              "-Wall", "-Wno-unused-function"]
     flags += os.environ.get("OAVIF_AMD_EXTRA_HIPCC_FLAGS", "").split()  # A/B builds of experiments
     hipcc = _hipcc()
-    obj = {s: os.path.join(OBJ_DIR, s + ".o") for s in (*compile_units(), *map_units(), *chroma_units(), *yuva_units(), *rbatch_units(), *hbatch_units())}
+    obj = {s: os.path.join(OBJ_DIR, s + ".o") for s in (*compile_units(), *map_units(), *chroma_units(), *yuva_units(), *rbatch_units(), *hbatch_units(), *abatch_units())}
     with concurrent.futures.ThreadPoolExecutor(MAX_COMPILES) as pool:
         jobs = [pool.submit(_run_to, o, [hipcc, *flags, "-c", os.path.join(CSRC, s)], verbose) for s, o in obj.items()]
     for job in jobs:
         job.result()  # the first failed compile raises here
     for target, sources in (*LIBRARIES.items(), *MAP_LIBRARIES.items(), *CHROMA_LIBRARIES.items(), *YUVA_LIBRARIES.items(),
-                            *RBATCH_LIBRARIES.items(), *HBATCH_LIBRARIES.items()):
+                            *RBATCH_LIBRARIES.items(), *HBATCH_LIBRARIES.items(), *ABATCH_LIBRARIES.items()):
         _run_to(target, [hipcc, *flags, "-shared", *(obj[s] for s in sources), "-lz"], verbose)  # -lz: png_ingest.cpp
 
 

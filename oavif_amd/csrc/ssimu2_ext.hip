@@ -10,6 +10,7 @@
 // recursive or finalize kernel knows about alpha.  To the host code an RGBA frame is one more Feed (rgba8 below): the
 // three shapes of a call -- score_pair, feed_reference, score_against -- are the product's.
 #include "../../include/ssimu2_hip_ext.h"
+#include "ssimu2_alpha_pixel.h"
 #include "ssimu2_host.h"
 
 using namespace ssimu2h;
@@ -22,8 +23,6 @@ namespace ssimu2 {
 // codes starts 6 * w * y bytes in, 2-byte aligned only); the last w % 4 pixels of a row go sample by sample.  Rows
 // beyond gridDim.y are taken in further rounds.  Pure integer arithmetic (n < 2^16), HBM-bound: 10 bytes per pixel.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t composite_code(uint32_t a, uint32_t c, uint32_t b) { return a * c + (255u - a) * b; }
-
 __global__ __launch_bounds__(256) void k_composite_rgba8(const uint8_t* __restrict__ src, uint32_t pitch, uint32_t w,
                                                          uint32_t h, uint32_t bg, uint16_t* __restrict__ dst) {
     const uint32_t x0 = (blockIdx.x * 256u + threadIdx.x) * 4u;
@@ -79,6 +78,11 @@ int ssimu2h::check_rgba(ssimu2_ctx* c, const void* a, const void* b, uint32_t ro
     return SSIMU2_OK;
 }
 
+// What an against-reference RGBA call answers to a reference that recorded no background.
+int ssimu2h::rgba_no_background(ssimu2_ctx* c) {
+    return c->fail(SSIMU2_ERR_INVALID_ARG, "the reference was not set by ssimu2_set_reference_rgba8: no background recorded");
+}
+
 namespace {
 
 // RGBA rows in `stage` composited over f.bg -> the tight u16 frame of codes `dst`.
@@ -129,8 +133,7 @@ int ssimu2_score_against_reference_rgba8(ssimu2_ctx* c, const uint8_t* pixels, u
     REMOTE_REFUSE(c, "ssimu2_score_against_reference_rgba8");
     const int rc = check_against(c, pixels && out_score);
     if (rc) return rc;
-    if (c->ref.bg < 0)
-        return c->fail(SSIMU2_ERR_INVALID_ARG, "the reference was not set by ssimu2_set_reference_rgba8: no background recorded");
+    if (c->ref.bg < 0) return rgba_no_background(c);
     if ((uint64_t)row_bytes < (uint64_t)c->ref.w * 4)
         return c->fail(SSIMU2_ERR_INVALID_ARG, "row_bytes smaller than one row of RGBA pixels");
     return score_against(c, rgba8_feed(pixels, row_bytes, (uint32_t)c->ref.bg), out_score);

@@ -1241,6 +1241,17 @@ int ssimu2h::hbatch_run(ssimu2_ctx* c, const void* d_refs, const void* d_dists, 
     return rbatch_recursive(c, {d_refs, d_dists, stride0, &tight}, n, w, h, out_scores);
 }
 
+// ---- RGBA and YUV-with-alpha batches (include/ssimu2_hip_abatch.h) ----------
+int ssimu2h::abatch_run(ssimu2_ctx* c, const void* d_refs, const void* d_dists, size_t stride0, uint32_t n, uint32_t w,
+                        uint32_t h, double* out_scores) {
+    constexpr uint32_t top = 65025;  // 255 * 255, the largest composite code
+    const float* tab;
+    const int rc = device_table(c, top + 1, top, &tab);
+    if (rc) return rc;
+    const Src16 tight{nullptr, w * 6u, 3u, tab, top};
+    return rbatch_recursive(c, {d_refs, d_dists, stride0, &tight}, n, w, h, out_scores);
+}
+
 int ssimu2h::hbatch_check_launch(ssimu2_ctx* c, uint32_t n, uint32_t w, uint32_t h, bool against_reference) {
     RgPlan rp;
     const RgCounts one = rg_plan_geometry(make_pyramid(w, h), &rp);

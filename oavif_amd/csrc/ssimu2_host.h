@@ -2,7 +2,8 @@
 // (which defines everything declared here but the front ends' own feed builders, marked below) and the translation
 // units that add an input form -- ssimu2_ext.hip (RGBA), ssimu2_yuv.hip (YUV), ssimu2_chroma.hip (4:2:2 and 4:2:0
 // YUV), ssimu2_yuva.hip (YUV with an alpha plane) -- or a call over those forms -- ssimu2_map.hip (error maps of 16-bit, RGBA and YUV frames),
-// ssimu2_rbatch.hip (batches in every blur mode), ssimu2_hbatch.hip (16-bit and YUV batches).  Private to oavif_amd/csrc: nothing here is exported,
+// ssimu2_rbatch.hip (batches in every blur mode), ssimu2_hbatch.hip (16-bit and YUV batches), ssimu2_abatch.hip (RGBA
+// and YUV-with-alpha batches).  Private to oavif_amd/csrc: nothing here is exported,
 // and a caller sees include/*.h only.
 //
 // A front end turns a caller's frame into a Feed -- where its rows are, how they get onto the device, what kernel of
@@ -54,7 +55,8 @@ struct DevBuf {
 
 }  // namespace ssimu2h
 
-struct ssimu2_yuv_frame;  // include/ssimu2_hip_yuv.h
+struct ssimu2_yuv_frame;   // include/ssimu2_hip_yuv.h
+struct ssimu2_yuva_frame;  // include/ssimu2_hip_yuva.h
 
 struct ssimu2_ctx {
     using DevBuf = ssimu2h::DevBuf;
@@ -121,7 +123,8 @@ struct ssimu2_ctx {
     // the first batch in a recursive mode -- every item's planes, then one dump row; the job
     // cursor's four words, then every item's partial sums.  h16_ref / h16_dist / yuv_planes: the calls of
     // include/ssimu2_hip_hbatch.h -- the staged 16-bit frames of the host-pointer forms or the
-    // codes of a YUV batch, and the staged planes of a YUV batch
+    // codes of a YUV batch, and the staged planes of a YUV batch.  The calls of include/ssimu2_hip_abatch.h (DESIGN.md
+    // section 20) add none: they stage planes and RGBA rows in yuv_planes and make their codes in h16_dist
     struct {
         DevBuf u8_ref, u8_dist, lin_ref, lin_dist, part;
         DevBuf rg_planes, rg_part;
@@ -328,6 +331,13 @@ int hbatch_check_launch(ssimu2_ctx* c, uint32_t n, uint32_t w, uint32_t h, bool 
 int hbatch_run(ssimu2_ctx* c, const void* d_refs, const void* d_dists, size_t stride0, uint32_t n, uint32_t w, uint32_t h,
                const float* tab, uint32_t depth, double* out_scores);
 
+// ---- RGBA and YUV-with-alpha batches (include/ssimu2_hip_abatch.h) ----------
+// What ssimu2_abatch.hip's calls add to the functions above.  abatch_run is hbatch_run for frames of composite codes:
+// the same rbatch_recursive, the items read through the context's composite table T (uploaded by the first call that
+// needs it, as a single RGBA call does) with codes above 65025 clamped.  hbatch_buffer's buffers serve these calls too.
+int abatch_run(ssimu2_ctx* c, const void* d_refs, const void* d_dists, size_t stride0, uint32_t n, uint32_t w, uint32_t h,
+               double* out_scores);
+
 // ---- what the front ends build their feeds with, for the units above them -------------------------
 // A tight frame of u16 samples of depth `bit_depth` in host memory, and the 16-bit calls' argument checks (the ctx is
 // not null).  Defined in ssimu2_hip.hip.
@@ -338,6 +348,7 @@ int check16(ssimu2_ctx* c, const void* px, uint32_t bit_depth);
 int check_rgba(ssimu2_ctx* c, const void* a, const void* b, uint32_t row_bytes_a, uint32_t row_bytes_b, uint32_t w,
                uint32_t h, uint32_t background_rgb);
 Feed rgba8_feed(const uint8_t* pixels, uint32_t row_bytes, uint32_t bg);
+int rgba_no_background(ssimu2_ctx* c);  // the refusal of an against-reference call whose reference recorded no background
 // YUV (defined in ssimu2_yuv.hip; in the libraries that link it): the constants of one conversion, formed on the host
 // in fp32 exactly as include/ssimu2_hip_yuv.h writes them; what a YUV Feed's unpacking needs beyond the planes
 // (Feed::aux, which outlives the call); the argument checks of one frame for a call of `w` columns (the ctx is not
@@ -366,5 +377,13 @@ struct ChromaAux {
 };
 int check_chroma(ssimu2_ctx* c, const ssimu2_yuv_frame* f, uint32_t w, uint32_t rgb_depth, uint32_t upsampling);
 Feed chroma_feed(const ssimu2_yuv_frame& f, uint32_t w, uint32_t h, uint32_t rgb_depth, uint32_t upsampling, ChromaAux* aux);
+
+// YUV with an alpha plane (defined in ssimu2_yuva.hip; in the libraries that link it): the argument checks of one such
+// frame for a call of `w` columns (the ctx is not null) -- check_chroma's, premultiplied alpha, the alpha plane's pitch
+// and alignment --, check_rgba's background rule on its own, and the refusal of an against-reference call whose
+// reference recorded no background.
+int check_yuva(ssimu2_ctx* c, const ssimu2_yuva_frame* f, uint32_t w, uint32_t rgb_depth, uint32_t upsampling);
+int check_background(ssimu2_ctx* c, uint32_t background_rgb);
+int no_background(ssimu2_ctx* c);
 
 }  // namespace ssimu2h

@@ -10,6 +10,7 @@
 // ssimu2_yuv_pixel.h composited over the background into the 65,026 codes the RGBA front end reads through its table T
 // (Feed::top = 65025, the context's alpha_tab).  The three shapes of a call and the two of a map are the scorer's.
 #include "../../include/ssimu2_hip_yuva.h"
+#include "ssimu2_alpha_pixel.h"
 #include "ssimu2_host.h"
 #include "ssimu2_yuv_pixel.h"
 
@@ -19,32 +20,6 @@
 using namespace ssimu2h;
 
 namespace ssimu2 {
-
-// The launch constants of one composite (formed on the host: yuva_constants).
-struct YuvaK {
-    uint32_t b[3];   // the background's 8-bit samples
-    uint32_t ma, mc; // 2^depth - 1, 2^rgb_depth - 1
-    uint32_t den;    // ma * mc: odd, below 2^28
-    uint64_t m;      // floor(2^64 / den)
-};
-
-// How n's division by den is taken.  DIV_NONE: depth 8 and rgb_depth 8, where n = a c + (255 - a) b exactly and nothing
-// is divided.  DIV_MULHI: q = umul64hi(x, floor(2^64 / den)) is floor(x / den) or one below it -- x M / 2^64 lies
-// below x / den by less than x / 2^64 < 2^-20 --, so one comparison of the remainder corrects it.  DIV_PLAIN: the
-// compiler's 64-bit division, kept for the measurement of DESIGN.md section 17 (OAVIF_YUVA_DIVISION=plain).
-enum { DIV_NONE = 0, DIV_MULHI = 1, DIV_PLAIN = 2 };
-
-// The composite code n of include/ssimu2_hip_yuva.h: alpha `a` (already at most ma), colour code `c`, background `b`.
-template <int DIV>
-__device__ __forceinline__ uint32_t yuva_code(uint32_t a, uint32_t c, uint32_t b, const YuvaK& k) {
-    if (DIV == DIV_NONE) return a * c + (255u - a) * b;
-    const uint64_t num = (uint64_t)(a * c) * 255u + (uint64_t)((k.ma - a) * b) * k.mc;  // a c < 2^28, (ma - a) b < 2^20
-    const uint64_t x = 255u * num + (k.den - 1u) / 2u;                                  // < 2^44
-    if (DIV == DIV_PLAIN) return (uint32_t)(x / k.den);
-    uint64_t q = __umul64hi(x, k.m);
-    if (x - q * k.den >= k.den) ++q;
-    return (uint32_t)q;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Planes of S-byte samples -- Y and A of w x h, U and V as SUB says -- rows `pitch` bytes apart at any alignment
@@ -164,22 +139,9 @@ __global__ __launch_bounds__(256) void k_yuva_to_codes(const uint8_t* __restrict
 
 using namespace ssimu2;
 
-namespace {
-
-constexpr uint32_t kCompositeTop = 65025;  // 255 * 255, the largest composite code: SSIMU2_ALPHA_CODES - 1
-
-// What the unpacking of a frame needs beyond the planes.  `chroma` comes first, as ChromaAux::yuv does.
-struct YuvaAux {
-    ChromaAux chroma;
-    YuvaK k;
-    int sub;  // k_yuva_to_codes' SUB
-    int div;  // ... and DIV
-    bool alpha;
-};
-
 // Argument checks of one frame for a w x h call (the ctx is not null): check_chroma's of the colour planes, then the
 // alpha plane's.
-int check_yuva(ssimu2_ctx* c, const ssimu2_yuva_frame* f, uint32_t w, uint32_t rgb_depth, uint32_t upsampling) {
+int ssimu2h::check_yuva(ssimu2_ctx* c, const ssimu2_yuva_frame* f, uint32_t w, uint32_t rgb_depth, uint32_t upsampling) {
     const int rc = check_chroma(c, f ? &f->yuv : nullptr, w, rgb_depth, upsampling);
     if (rc) return rc;
     if (f->alpha_premultiplied) return c->fail(SSIMU2_ERR_UNSUPPORTED, "premultiplied alpha is not supported: alpha_premultiplied must be 0");
@@ -193,10 +155,29 @@ int check_yuva(ssimu2_ctx* c, const ssimu2_yuva_frame* f, uint32_t w, uint32_t r
 }
 
 // check_rgba's background rule.
-int check_background(ssimu2_ctx* c, uint32_t background_rgb) {
+int ssimu2h::check_background(ssimu2_ctx* c, uint32_t background_rgb) {
     if (background_rgb > 0xFFFFFFu) return c->fail(SSIMU2_ERR_INVALID_ARG, "background_rgb is 0xRRGGBB: the upper byte must be 0");
     return SSIMU2_OK;
 }
+
+// What an against-reference call answers to a reference that recorded no background.
+int ssimu2h::no_background(ssimu2_ctx* c) {
+    return c->fail(SSIMU2_ERR_INVALID_ARG,
+                   "the reference was not set by ssimu2_set_reference_yuva or ssimu2_set_reference_rgba8: no background recorded");
+}
+
+namespace {
+
+constexpr uint32_t kCompositeTop = 65025;  // 255 * 255, the largest composite code: SSIMU2_ALPHA_CODES - 1
+
+// What the unpacking of a frame needs beyond the planes.  `chroma` comes first, as ChromaAux::yuv does.
+struct YuvaAux {
+    ChromaAux chroma;
+    YuvaK k;
+    int sub;  // k_yuva_to_codes' SUB
+    int div;  // ... and DIV
+    bool alpha;
+};
 
 // The planes in `stage` (plane_off, each with its own size; the alpha plane last) -> the tight u16 frame of composite
 // codes `dst`.
@@ -228,17 +209,6 @@ void composite(ssimu2_ctx* c, const Feed& f, uint32_t w, uint32_t h, void* dst) 
            h, a.chroma.yuv.k, a.k, (uint16_t*)dst);
 }
 
-// The header's integers for one call.
-YuvaK yuva_constants(uint32_t depth, uint32_t rgb_depth, uint32_t bg) {
-    YuvaK k;
-    k.b[0] = (bg >> 16) & 0xFFu, k.b[1] = (bg >> 8) & 0xFFu, k.b[2] = bg & 0xFFu;
-    k.ma = (1u << depth) - 1u;
-    k.mc = (1u << rgb_depth) - 1u;
-    k.den = k.ma * k.mc;
-    k.m = ~(uint64_t)0 / k.den;  // den is odd and above 1, so it does not divide 2^64: floor((2^64 - 1) / den) is floor(2^64 / den)
-    return k;
-}
-
 // One frame in host memory composited over `bg`, for a w x h call.  `aux` outlives the call.
 Feed yuva_feed(const ssimu2_yuva_frame& f, uint32_t w, uint32_t h, uint32_t rgb_depth, uint32_t upsampling, uint32_t bg,
                YuvaAux* aux) {
@@ -248,7 +218,7 @@ Feed yuva_feed(const ssimu2_yuva_frame& f, uint32_t w, uint32_t h, uint32_t rgb_
     // OAVIF_YUVA_DIVISION = mulhi | plain forces one form of the division, for the measurement of DESIGN.md section 17 and
     // the test that all three give the same codes; unset, the rule is: none at 8 and 8, else mulhi
     const char* const how = getenv("OAVIF_YUVA_DIVISION");
-    aux->div = f.yuv.depth == 8 && rgb_depth == 8 ? DIV_NONE : DIV_MULHI;
+    aux->div = yuva_division(f.yuv.depth, rgb_depth);
     if (how && !strcmp(how, "mulhi")) aux->div = DIV_MULHI;
     if (how && !strcmp(how, "plain")) aux->div = DIV_PLAIN;
     aux->alpha = f.alpha != nullptr;
@@ -258,11 +228,6 @@ Feed yuva_feed(const ssimu2_yuva_frame& f, uint32_t w, uint32_t h, uint32_t rgb_
     feed.unpack = composite;
     feed.aux = aux;
     return feed;
-}
-
-int no_background(ssimu2_ctx* c) {
-    return c->fail(SSIMU2_ERR_INVALID_ARG,
-                   "the reference was not set by ssimu2_set_reference_yuva or ssimu2_set_reference_rgba8: no background recorded");
 }
 
 }  // namespace

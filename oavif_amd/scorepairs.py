@@ -1,6 +1,7 @@
 """Score a list of image pairs with the batch scorer.
 
     python -m oavif_amd.scorepairs PAIRS.tsv OUT.csv [--batch B] [--device D] [--blur fir|recursive|recursive_fma]
+                                   [--background RRGGBB]
 
 PAIRS.tsv holds one `ref<TAB>dist` path pair per line (PNG or PAM, through the project's own loaders; relative paths are
 taken from the list's directory; blank lines and lines starting with '#' are skipped).  Pairs are grouped by frame
@@ -9,7 +10,10 @@ gets one row per pair in input order: line, ref, dist, width, height, score.  8-
 8 bits and alpha is dropped, as the search's reference is.  --blur: the blur mode the pairs are scored in.  The default
 is fir, SSIMU2_BLUR_FIR on the product library, as the command always scored.  recursive and recursive_fma -- the
 published recursion -- bind the library of include/ssimu2_hip_rbatch.h, whose batches score in those modes with the
-bits of single scores.
+bits of single scores.  --background RRGGBB (six hex digits; a recursive --blur only): alpha is
+not dropped -- every frame is taken as RGBA (one without an alpha channel counts as opaque), both sides of a pair are
+composited over that colour on the device and the batches go through Ssimu2.score_batch_rgba, the library of
+include/ssimu2_hip_abatch.h.  Without it nothing changes.
 """
 from __future__ import annotations
 
@@ -49,6 +53,31 @@ def load_rgb8(path: str) -> np.ndarray:
     return to_rgb8(arr)
 
 
+def load_rgba8(path: str) -> np.ndarray:
+    """A PNG or PAM file as an (h, w, 4) uint8 frame with straight alpha: gray replicated, 16 bits >> 8, a file without
+    an alpha channel opaque."""
+    ext = os.path.splitext(path)[1].lower()
+    data = open(path, "rb").read()
+    if ext == ".pam":
+        from .pam import load_pam
+        raster, w, h, ch = load_pam(data)
+        arr = np.frombuffer(raster, np.uint8).reshape(h, w, ch)
+    elif ext == ".png":
+        from .png import load_png
+        arr, _ch, _hbd, _icc = load_png(data)
+    else:
+        raise ValueError(f"unsupported image format {ext or path!r} (PNG or PAM)")
+    from .cli import to_rgb8
+    arr = np.asarray(arr)
+    if arr.dtype == np.uint16:
+        arr = (arr >> 8).astype(np.uint8)
+    if arr.ndim == 2:
+        arr = arr[:, :, None]
+    has_alpha = arr.shape[2] in (2, 4)
+    alpha = arr[:, :, -1] if has_alpha else np.full(arr.shape[:2], 255, np.uint8)
+    return np.ascontiguousarray(np.dstack([to_rgb8(arr), alpha]))
+
+
 def parse_pairs(text: str, base_dir: str = "") -> List[Tuple[int, str, str]]:
     """-> [(line number, ref path, dist path)] of a pair list."""
     out = []
@@ -64,8 +93,9 @@ def parse_pairs(text: str, base_dir: str = "") -> List[Tuple[int, str, str]]:
 
 
 def score_pairs(scorer, pairs: Sequence[Tuple[int, str, str]], batch: int = DEFAULT_BATCH,
-                load: Callable[[str], np.ndarray] = load_rgb8):
-    """Score `pairs` ([(line, ref path, dist path)]) with `scorer.score_batch(refs, dists)`: pairs grouped by frame
+                load: Callable[[str], np.ndarray] = load_rgb8, background: int | None = None):
+    """Score `pairs` ([(line, ref path, dist path)]) with `scorer.score_batch(refs, dists)` -- with a `background`
+    (0xRRGGBB; `load` then yields RGBA frames) `scorer.score_batch_rgba(refs, dists, background)` --: pairs grouped by frame
     size in order of first appearance, each group in batches of at most `batch`, frames loaded one batch at a time.
     -> [(line, ref, dist, w, h, score)] in input order.  A file that is missing or unreadable, or a pair whose frames
     differ in size, raises PairListError with the pair's line before anything is scored."""
@@ -93,7 +123,7 @@ def score_pairs(scorer, pairs: Sequence[Tuple[int, str, str]], batch: int = DEFA
             chunk = members[at:at + batch]
             refs = [load(pairs[i][1]) for i in chunk]
             dists = [load(pairs[i][2]) for i in chunk]
-            got = scorer.score_batch(refs, dists)
+            got = scorer.score_batch(refs, dists) if background is None else scorer.score_batch_rgba(refs, dists, background)
             if len(got) != len(chunk):
                 raise RuntimeError("score_batch returned the wrong number of scores")
             for i, s in zip(chunk, got):
@@ -108,21 +138,24 @@ def write_csv(rows, f) -> None:
         wr.writerow([line, rp, dp, w, h, repr(score)])
 
 
-def make_scorer(device: int, blur: str):
+def make_scorer(device: int, blur: str, background: int | None = None):
     """The scorer of a run that brings none: the product library in fir, as ever; in a recursive mode the library whose
-    batch calls score in it."""
+    batch calls score in it; with a background the one whose batches composite RGBA frames."""
     from .scorer import Ssimu2
+    if background is not None:
+        return Ssimu2(device, blur=BLUR_MODES.index(blur), abatch=True)
     if blur == "fir":
         return Ssimu2(device)
     return Ssimu2(device, blur=BLUR_MODES.index(blur), rbatch=True)
 
 
-USAGE = "usage: python -m oavif_amd.scorepairs PAIRS.tsv OUT.csv [--batch B] [--device D] [--blur fir|recursive|recursive_fma]"
+USAGE = ("usage: python -m oavif_amd.scorepairs PAIRS.tsv OUT.csv [--batch B] [--device D] [--blur fir|recursive|recursive_fma] "
+         "[--background RRGGBB]")
 
 
 def main(argv=None, scorer=None) -> int:
     args = list(sys.argv[1:] if argv is None else argv)
-    batch, device, blur, pos = DEFAULT_BATCH, 0, "fir", []
+    batch, device, blur, background, pos = DEFAULT_BATCH, 0, "fir", None, []
     i = 0
     while i < len(args):
         if args[i] == "--blur":
@@ -130,6 +163,13 @@ def main(argv=None, scorer=None) -> int:
                 print(f"--blur needs one of {', '.join(BLUR_MODES)}", file=sys.stderr)
                 return 2
             blur = args[i + 1]
+            i += 2
+        elif args[i] == "--background":
+            text = args[i + 1] if i + 1 < len(args) else ""
+            if len(text) != 6 or any(ch not in "0123456789abcdefABCDEF" for ch in text):
+                print("--background needs six hex digits RRGGBB", file=sys.stderr)
+                return 2
+            background = int(text, 16)
             i += 2
         elif args[i] in ("--batch", "--device"):
             if i + 1 >= len(args) or not args[i + 1].lstrip("-").isdigit():
@@ -146,6 +186,9 @@ def main(argv=None, scorer=None) -> int:
     if len(pos) != 2 or batch < 1:
         print(USAGE, file=sys.stderr)
         return 2
+    if background is not None and blur == "fir":
+        print("--background needs --blur recursive or recursive_fma: batches of RGBA frames run in those modes", file=sys.stderr)
+        return 2
     from . import _lib
     batch = min(batch, _lib.MAX_BATCH)
     try:
@@ -155,9 +198,10 @@ def main(argv=None, scorer=None) -> int:
         return 1
     own = scorer is None
     if own:
-        scorer = make_scorer(device, blur)
+        scorer = make_scorer(device, blur) if background is None else make_scorer(device, blur, background)
     try:
-        rows = score_pairs(scorer, pairs, batch)
+        rows = (score_pairs(scorer, pairs, batch) if background is None
+                else score_pairs(scorer, pairs, batch, load_rgba8, background))
     except PairListError as e:
         print(f"{pos[0]}: {e}", file=sys.stderr)
         return 1

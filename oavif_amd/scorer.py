@@ -266,11 +266,12 @@ class Ssimu2:
     yuva = False       # bound to liboavif_hip_yuva.so (YUV frames with an alpha plane, include/ssimu2_hip_yuva.h, and all of the above)
     rbatch = False     # bound to liboavif_hip_rbatch.so (batches in every blur mode, include/ssimu2_hip_rbatch.h, and all of the above)
     hbatch = False     # bound to liboavif_hip_hbatch.so (16-bit and YUV batches, include/ssimu2_hip_hbatch.h, and all of the above)
+    abatch = False     # bound to liboavif_hip_abatch.so (RGBA and YUV-with-alpha batches, include/ssimu2_hip_abatch.h, and all of the above)
 
     def __init__(self, device: int = 0, stream: int | None = None, instrumented: bool = False,
                  blur: int | None = None, service: str | None = None, extended: bool = False, yuv: bool = False,
                  maps: bool = False, chroma: bool = False, yuva: bool = False, rbatch: bool = False,
-                 hbatch: bool = False):
+                 hbatch: bool = False, abatch: bool = False):
         """`service`: socket path of a running scoring service (oavif_amd.service): the context lives there, and this
         process makes no HIP call for it (OAVIF_SCORER_SOCKET set around ssimu2_ctx_create, then restored; None = the
         environment as it is).  `instrumented=True` binds liboavif_hip_instr.so (the hooks of
@@ -296,7 +297,14 @@ class Ssimu2:
         `instrumented`.  `hbatch=True` binds liboavif_hip_hbatch.so: everything `rbatch=True` has, and the batches of
         16-bit and YUV frames of include/ssimu2_hip_hbatch.h, which run in the recursive blur modes (score_batch_hbd,
         score_batch_against_reference_hbd, their _device forms, score_batch_against_reference_yuv, convert_yuv_batch);
-        not together with `instrumented`."""
+        not together with `instrumented`.  `abatch=True` binds liboavif_hip_abatch.so: everything `hbatch=True` has, and
+        the batches of frames with transparency of include/ssimu2_hip_abatch.h, which run in the recursive blur modes
+        (score_batch_against_reference_yuva, composite_yuva_batch, score_batch_against_reference_rgba, score_batch_rgba,
+        composite_rgba_batch); not together with `instrumented`."""
+        if instrumented and abatch:
+            raise ValueError("instrumented=True and abatch=True are different libraries: choose one")
+        self.abatch = bool(abatch)
+        hbatch = bool(hbatch or abatch)
         if instrumented and hbatch:
             raise ValueError("instrumented=True and hbatch=True are different libraries: choose one")
         self.hbatch = bool(hbatch)
@@ -321,7 +329,7 @@ class Ssimu2:
         # a yuva context scores against RGBA references and beside RGBA frames: the RGBA methods come with it
         self.instrumented, self.extended = bool(instrumented), bool(extended or yuva)
         self.yuv, self.maps = bool(yuv or chroma), bool(maps or chroma)
-        self._L = (_lib.instr_lib() if instrumented else _lib.hbatch_lib() if hbatch else _lib.rbatch_lib() if rbatch else _lib.yuva_lib() if yuva else _lib.chroma_lib() if chroma else _lib.map_lib() if maps
+        self._L = (_lib.instr_lib() if instrumented else _lib.abatch_lib() if abatch else _lib.hbatch_lib() if hbatch else _lib.rbatch_lib() if rbatch else _lib.yuva_lib() if yuva else _lib.chroma_lib() if chroma else _lib.map_lib() if maps
                    else _lib.yuv_lib() if yuv else _lib.ext_lib() if extended else _lib.lib())
         self._ctx = ctypes.c_void_p()
         self._holder = None
@@ -985,6 +993,102 @@ class Ssimu2:
         h, w = frames[0].height, frames[0].width
         out = np.empty((len(frames), h, w, 3), np.uint16)
         self._call(self._L.ssimu2_hbatch_convert_yuv, arr, len(frames), w, h, int(rgb_depth), up, _u16p(out))
+        return out
+
+    # -- batches of RGBA and YUV-with-alpha frames (include/ssimu2_hip_abatch.h): the abatch library only --
+    def _need_abatch(self):
+        if not self.abatch:
+            raise Ssimu2Error(_lib.ERR_UNSUPPORTED, "batches of RGBA and YUV-with-alpha frames need Ssimu2(..., abatch=True) "
+                                                    "(liboavif_hip_abatch.so)")
+
+    def _yuva_batch(self, frames, chroma_upsampling):
+        """-> (the frames, their C array, the upsampling code) of a YUVA batch: YuvFrames of one size, with or without
+        an alpha plane (the library refuses a batch that mixes the two)."""
+        self._need_abatch()
+        frames = [self._yuv_frame(f, f"frames[{i}]") for i, f in enumerate(frames)]
+        up = self._yuva_args(chroma_upsampling)
+        if any((f.height, f.width) != (frames[0].height, frames[0].width) for f in frames):
+            raise ValueError("frames: the frames of a batch must have one size")
+        arr = (_lib.YuvaFrameC * max(len(frames), 1))(*[f.as_yuva_c() for f in frames])
+        return frames, arr, up
+
+    def score_batch_against_reference_yuva(self, frames, rgb_depth: int = 16, chroma_upsampling: str = "bilinear") -> np.ndarray:
+        """ssimu2_abatch_score_against_reference_yuva: N YuvFrames of one size, depth, format, range and matrix, all with
+        or all without an alpha plane, each composited over the reference's background and scored against the cached
+        reference (kept), each with the bits of score_against_reference_yuva.  Recursive blur modes only."""
+        frames, arr, up = self._yuva_batch(frames, chroma_upsampling)
+        if not frames:
+            return np.zeros(0, np.float64)
+        self._check_ref_shape((frames[0].height, frames[0].width), "frame size")
+        return self._scores(self._L.ssimu2_abatch_score_against_reference_yuva, len(frames), arr, len(frames), int(rgb_depth), up)
+
+    def composite_yuva_batch(self, frames, background, rgb_depth: int = 16, chroma_upsampling: str = "bilinear") -> np.ndarray:
+        """ssimu2_abatch_composite_yuva: the (n, h, w, 3) uint16 composite codes of the N frames of a YUVA batch over
+        `background`, item i with the bits of composite_yuva(frames[i], background)."""
+        frames, arr, up = self._yuva_batch(frames, chroma_upsampling)
+        bg = background_rgb(background)
+        if not frames:
+            return np.zeros((0, 0, 0, 3), np.uint16)
+        h, w = frames[0].height, frames[0].width
+        out = np.empty((len(frames), h, w, 3), np.uint16)
+        self._call(self._L.ssimu2_abatch_composite_yuva, arr, len(frames), w, h, int(rgb_depth), up, bg, _u16p(out))
+        return out
+
+    @staticmethod
+    def _rgba_batch(frames, name: str):
+        """[N, h, w, 4] uint8 or a sequence of (h, w, 4) uint8 frames or views of one size -> (the frames, their pointer
+        array, the one row_bytes of all).  Views whose rows lie one distance apart go through as they are; if the
+        distances differ every frame is made tight."""
+        out = [_check_rgba8(f, f"{name}[{i}]") for i, f in enumerate(frames)]
+        if any(f.shape != out[0].shape for f in out):
+            raise ValueError(f"{name}: the frames of a batch must have one size")
+        if not out:
+            return out, None, 0
+        h, w, _ = out[0].shape
+        pitches = {f.strides[0] if h > 1 else 4 * w for f in out}
+        if len(pitches) > 1:
+            out = [np.ascontiguousarray(f) for f in out]
+            pitches = {4 * w}
+        return out, (ctypes.POINTER(ctypes.c_uint8) * len(out))(*[_u8p(f) for f in out]), pitches.pop()
+
+    def score_batch_against_reference_rgba(self, frames) -> np.ndarray:
+        """ssimu2_abatch_score_against_reference_rgba8: N (h, w, 4) uint8 frames (rows may be padded), each composited
+        over the reference's background and scored against the cached reference (kept), each with the bits of
+        score_against_reference_rgba.  Recursive blur modes only."""
+        self._need_abatch()
+        frames, arr, row_bytes = self._rgba_batch(frames, "frames")
+        if not frames:
+            return np.zeros(0, np.float64)
+        self._check_ref_shape(frames[0].shape[:2], "frame size")
+        return self._scores(self._L.ssimu2_abatch_score_against_reference_rgba8, len(frames), arr, row_bytes, len(frames))
+
+    def score_batch_rgba(self, refs, dists, background) -> np.ndarray:
+        """ssimu2_abatch_score_rgba8: N pairs of (h, w, 4) uint8 frames of one size, both sides composited over
+        `background`, each with the bits of compute_ssimu2_rgba.  Recursive blur modes only."""
+        self._need_abatch()
+        refs, rarr, rrow = self._rgba_batch(refs, "refs")
+        dists, darr, drow = self._rgba_batch(dists, "dists")
+        bg = background_rgb(background)
+        if len(refs) != len(dists):
+            raise ValueError("refs and dists must hold the same number of frames")
+        if not refs:
+            return np.zeros(0, np.float64)
+        if refs[0].shape != dists[0].shape:
+            raise ValueError("refs and dists must have the same shape")
+        h, w, _ = refs[0].shape
+        return self._scores(self._L.ssimu2_abatch_score_rgba8, len(refs), rarr, rrow, darr, drow, len(refs), w, h, bg)
+
+    def composite_rgba_batch(self, frames, background) -> np.ndarray:
+        """ssimu2_abatch_composite_rgba8: the (n, h, w, 3) uint16 composite codes of N RGBA frames over `background`, item
+        i with the bits of composite_rgba(frames[i], background)."""
+        self._need_abatch()
+        frames, arr, row_bytes = self._rgba_batch(frames, "frames")
+        bg = background_rgb(background)
+        if not frames:
+            return np.zeros((0, 0, 0, 3), np.uint16)
+        h, w, _ = frames[0].shape
+        out = np.empty((len(frames), h, w, 3), np.uint16)
+        self._call(self._L.ssimu2_abatch_composite_rgba8, arr, row_bytes, len(frames), w, h, bg, _u16p(out))
         return out
 
     def last_batch_averages(self, item: int):

@@ -249,47 +249,17 @@ def search_hip_frames(scorer: Ssimu2, ref_rgb: np.ndarray, codec_frame, score_tg
 MIN_BATCHED_WAVE = 2
 
 
-def search_speculative_hip_frames(scorer: Ssimu2, ref_rgb: np.ndarray, codec_frame, score_tgt: float = 80.0,
-                                  tolerance: float = 2.0, max_pass: int = 6, max_fanout: int = 4,
-                                  first_wave_fanout: int = 1, ref_bit_depth: int | None = None):
-    """search_hip_frames with several probes in flight on ONE context (an Ssimu2(..., hbatch=True) in a recursive blur
-    mode): the codec_frame(q) calls of a wave -- the CPU encode and decode -- run on `max_fanout` threads, and a wave
-    of MIN_BATCHED_WAVE or more YUV frames (the decoder's own planes, all of one kind) is scored by one
-    score_batch_against_reference_yuv call, rgb_depth 16.  A smaller wave, and frames that are not YUV planes, go through
-    the single calls search_hip_frames uses.  Every frame is closed here.  An item of a batch has the bits of its
-    single score and the speculative search equals the sequential one, so q, num_pass, history and scores are
-    search_hip_frames' with the same codec.  A scorer made without hbatch=True is refused here (ValueError): it would
-    score every wave frame by frame and lose what the function is for.  -> (TQResult, SpecStats, {q: avif size})."""
+def speculative_frame_waves(codec_frame, score_frames, size_hw, score_tgt: float, tolerance: float, max_pass: int,
+                            max_fanout: int, first_wave_fanout: int):
+    """The wave logic of the speculative searches that score decoded frames on ONE context: the codec_frame(q) ->
+    (frame, avif size) calls of a wave -- the CPU encode and decode -- run on `max_fanout` threads, every job is waited
+    for, the frames (each `height` x `width` = size_hw, else ValueError) go to score_frames(frames) -> their scores in
+    order, and every frame handed over is closed, also when a job or the scoring raises (the first job's exception is
+    raised then).  What a wave of how many frames of which kind costs -- one batch call or single calls -- is
+    score_frames' own.  -> (TQResult, SpecStats, {q: avif size})."""
     from concurrent.futures import ThreadPoolExecutor
-    from .scorer import YuvFrame
-    if not getattr(scorer, "hbatch", False):
-        raise ValueError("search_speculative_hip_frames needs an Ssimu2(..., hbatch=True) context: without the batch "
-                         "library every wave would be scored frame by frame (use search_hip_frames for that)")
-    if ref_bit_depth is None:
-        if np.asarray(ref_rgb).dtype == np.uint16:
-            raise ValueError("a uint16 ref_rgb needs ref_bit_depth")
-        ref = np.ascontiguousarray(ref_rgb, dtype=np.uint8)
-        scorer.set_reference(ref)
-    else:
-        ref = np.asarray(ref_rgb)
-        scorer.set_reference_hbd(ref, int(ref_bit_depth))
     fan = max(1, min(int(max_fanout), _lib.TQ_MAX_FANOUT))
     sizes: dict = {}
-
-    def yuv_of(frame):
-        return YuvFrame(frame.planes, frame.depth, frame.format, frame.full_range, frame.matrix_coefficients)
-
-    def single(frame) -> float:
-        depth = getattr(frame, "rgb_depth", 8)
-        if hasattr(frame, "matrix_coefficients"):
-            return scorer.score_against_reference_yuv(yuv_of(frame), 16)
-        if depth > 8:
-            return scorer.score_decoded_against_reference_hbd(frame.rows.reshape(-1), frame.row_bytes, frame.channels, depth)
-        return scorer.score_decoded_against_reference(frame.rows.reshape(-1), frame.row_bytes, frame.channels)
-
-    def kind(frame):
-        return (frame.depth, frame.format, int(frame.full_range), frame.matrix_coefficients)
-
     with ThreadPoolExecutor(max_workers=fan) as pool:
         def wave(qs):
             jobs = [pool.submit(codec_frame, int(q)) for q in qs]
@@ -306,12 +276,9 @@ def search_speculative_hip_frames(scorer: Ssimu2, ref_rgb: np.ndarray, codec_fra
                 if failed is not None:
                     raise failed
                 for frame in frames:
-                    if (frame.height, frame.width) != ref.shape[:2]:
-                        raise ValueError(f"codec returned {frame.width}x{frame.height}, expected {ref.shape[1]}x{ref.shape[0]}")
-                yuv = [f for f in frames if hasattr(f, "matrix_coefficients")]
-                if len(yuv) == len(frames) >= MIN_BATCHED_WAVE and all(kind(f) == kind(yuv[0]) for f in yuv):
-                    return list(scorer.score_batch_against_reference_yuv([yuv_of(f) for f in frames], 16))
-                return [single(f) for f in frames]
+                    if (frame.height, frame.width) != tuple(size_hw):
+                        raise ValueError(f"codec returned {frame.width}x{frame.height}, expected {size_hw[1]}x{size_hw[0]}")
+                return [float(x) for x in score_frames(frames)]
             finally:
                 for frame in frames:
                     frame.close()
@@ -320,6 +287,55 @@ def search_speculative_hip_frames(scorer: Ssimu2, ref_rgb: np.ndarray, codec_fra
                                                      min(max(int(first_wave_fanout), 0), fan))
     res.last_avif_size = sizes.get(res.buf_q, 0)
     return res, stats, sizes
+
+
+def search_speculative_hip_frames(scorer: Ssimu2, ref_rgb: np.ndarray, codec_frame, score_tgt: float = 80.0,
+                                  tolerance: float = 2.0, max_pass: int = 6, max_fanout: int = 4,
+                                  first_wave_fanout: int = 1, ref_bit_depth: int | None = None):
+    """search_hip_frames with several probes in flight on ONE context (an Ssimu2(..., hbatch=True) in a recursive blur
+    mode): the codec_frame(q) calls of a wave -- the CPU encode and decode -- run on `max_fanout` threads, and a wave
+    of MIN_BATCHED_WAVE or more YUV frames (the decoder's own planes, all of one kind) is scored by one
+    score_batch_against_reference_yuv call, rgb_depth 16.  A smaller wave, and frames that are not YUV planes, go through
+    the single calls search_hip_frames uses.  Every frame is closed here (speculative_frame_waves).  An item of a batch
+    has the bits of its single score and the speculative search equals the sequential one, so q, num_pass, history and
+    scores are search_hip_frames' with the same codec.  A scorer made without hbatch=True is refused here (ValueError):
+    it would score every wave frame by frame and lose what the function is for.
+    -> (TQResult, SpecStats, {q: avif size})."""
+    from .scorer import YuvFrame
+    if not getattr(scorer, "hbatch", False):
+        raise ValueError("search_speculative_hip_frames needs an Ssimu2(..., hbatch=True) context: without the batch "
+                         "library every wave would be scored frame by frame (use search_hip_frames for that)")
+    if ref_bit_depth is None:
+        if np.asarray(ref_rgb).dtype == np.uint16:
+            raise ValueError("a uint16 ref_rgb needs ref_bit_depth")
+        ref = np.ascontiguousarray(ref_rgb, dtype=np.uint8)
+        scorer.set_reference(ref)
+    else:
+        ref = np.asarray(ref_rgb)
+        scorer.set_reference_hbd(ref, int(ref_bit_depth))
+
+    def yuv_of(frame):
+        return YuvFrame(frame.planes, frame.depth, frame.format, frame.full_range, frame.matrix_coefficients)
+
+    def single(frame) -> float:
+        depth = getattr(frame, "rgb_depth", 8)
+        if hasattr(frame, "matrix_coefficients"):
+            return scorer.score_against_reference_yuv(yuv_of(frame), 16)
+        if depth > 8:
+            return scorer.score_decoded_against_reference_hbd(frame.rows.reshape(-1), frame.row_bytes, frame.channels, depth)
+        return scorer.score_decoded_against_reference(frame.rows.reshape(-1), frame.row_bytes, frame.channels)
+
+    def kind(frame):
+        return (frame.depth, frame.format, int(frame.full_range), frame.matrix_coefficients)
+
+    def score_frames(frames):
+        yuv = [f for f in frames if hasattr(f, "matrix_coefficients")]
+        if len(yuv) == len(frames) >= MIN_BATCHED_WAVE and all(kind(f) == kind(yuv[0]) for f in yuv):
+            return list(scorer.score_batch_against_reference_yuv([yuv_of(f) for f in frames], 16))
+        return [single(f) for f in frames]
+
+    return speculative_frame_waves(codec_frame, score_frames, ref.shape[:2], score_tgt, tolerance, max_pass, max_fanout,
+                                   first_wave_fanout)
 
 
 def prescale(src: np.ndarray, out_depth: int) -> np.ndarray:

@@ -24,7 +24,7 @@ sys.path.insert(0, ROOT)
 from oavif_amd.build import DEVICE_FLAGS, _hipcc  # noqa: E402
 
 UNITS = ("ssimu2_hip.hip", "ssimu2_instrument.hip", "ssimu2_ext.hip", "ssimu2_yuv.hip", "ssimu2_map.hip",
-         "ssimu2_chroma.hip", "ssimu2_yuva.hip", "ssimu2_rbatch.hip", "ssimu2_hbatch.hip")
+         "ssimu2_chroma.hip", "ssimu2_yuva.hip", "ssimu2_rbatch.hip", "ssimu2_hbatch.hip", "ssimu2_abatch.hip")
 DIRS = ("oavif_amd/csrc", "include")
 MAX_COMPILES = 6
 
